@@ -300,7 +300,15 @@ def parse():
                     help="N > 1: skip the `multi` block (BASELINE's 8-GPU configurations K3 and K4 after the headline)")
     ap.add_argument("--allow-sync-exchange", action="store_true",
                     help="N > 1 on RCCL: accept a run whose asynchronous exchange fell back to the synchronous path (default: exit 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's image: the fp32 storage buffer, or the RGBA8 "
+                         "image of an rgba8 exchange; Mandelbrot: also its iteration counts) as DIR/<name>.npy, at most 64 MB: a fixed, "
+                         "seeded sample of pixels (DIR/pixel_index.npy) when the whole arrays are larger")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup is not None and a.warmup < 0:
+        ap.error("--warmup must not be negative")
     # the `multi` block: N > 1 from the plain command — the default headline with nothing overridden
     a.multi = [] if (a.no_multi or a.config or a.workload or a.spp or a.width or a.height or a.gpus < 2) else ["K3", "K4"]
     if a.config and a.workload and WORKLOAD_ALIAS[a.workload] != a.config:
@@ -358,6 +366,31 @@ def spawn_ranks(args):
         sys.exit(f"bench.py --gpus {args.gpus}: expected one JSON line from rank 0, got {len(lines)}")
     print(lines[0], flush=True)
     return 0
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs stays under 64 MB: whole arrays up to this size, a sample of pixels above it
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes `arrays` (name -> torch tensor whose first two dimensions are the image's rows and columns) as
+    out_dir/<name>.npy, floating point as float32 and integers as float64 (exact).  When the whole arrays would exceed DUMP_BYTES,
+    every array is reduced to the same fixed, seeded sample of pixels, whose row-major indices go to out_dir/pixel_index.npy
+    (float64): the sample depends on the image size alone, so two runs of one configuration dump the same pixels."""
+    import numpy as np
+    import torch
+    H, W = next(iter(arrays.values())).shape[:2]
+    dtypes = {k: torch.float32 if t.is_floating_point() else torch.float64 for k, t in arrays.items()}
+    per_pixel = sum(t[0, 0].numel() * dtypes[k].itemsize for k, t in arrays.items())
+    os.makedirs(out_dir, exist_ok=True)
+    index = None
+    if H * W * per_pixel > DUMP_BYTES:
+        index = np.unique(np.random.default_rng(DUMP_SEED).integers(0, H * W, DUMP_BYTES // (per_pixel + 8)))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), index.astype(np.float64))
+    for k, t in arrays.items():
+        if index is not None:
+            t = t.reshape(H * W, *t.shape[2:])[torch.from_numpy(index).to(t.device)]
+        np.save(os.path.join(out_dir, f"{k}.npy"), t.to(dtypes[k]).cpu().numpy())
 
 
 class Job:
@@ -704,8 +737,12 @@ def main():
     cfg = CONFIGS[cfg_name]
     is_pt = cfg["kind"] == "pt"
     exchange = args.exchange or ("rgba8" if cfg_name == "K3" else "f32")
-    m = measure(job, cfg_name, args.steps, args.warmup, rank, n, args, exchange=exchange, verify=args.verify)
+    m = measure(job, cfg_name, args.steps, args.warmup, rank, n, args, exchange=exchange, verify=args.verify,
+                keep_image=bool(args.dump_outputs))
     W, H, p = m["W"], m["H"], m["p"]
+    if args.dump_outputs and rank == 0:      # before anything below renders into the last step's buffer again
+        dump_outputs(args.dump_outputs, {"image": m["image"][:H],
+                                         **({"iters": m["image_iters"][:H]} if m["image_iters"] is not None else {})})
     rows_local, narrow, rgba8 = m["rows_local"], m["narrow"], m["rgba8"]
     dt, kernel_ms, gather_ms, gather_bytes = m["dt"], m["kernel_ms"], m["gather_ms"], m["gather_bytes"]
     local_units, value, tile = m["local_units"], m["value"], m["tile"]

@@ -155,6 +155,36 @@ def test_what_the_plain_command_measures(monkeypatch):
         _parse(monkeypatch, "--config", "K1", "--workload", "pathtrace")
     with pytest.raises(SystemExit):
         _parse(monkeypatch, "--math", "carefull")
+    a = _parse(monkeypatch, "--config", "K3", "--steps", "1", "--warmup", "0")
+    assert (a.steps, a.warmup) == (1, 0)                      # --steps is the number of timed steps, whatever the configuration
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            _parse(monkeypatch, *bad)
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: whole arrays, floating point as float32 and integers as float64, while they fit under the cap; above it the
+    same seeded sample of pixels from every array (pixel_index.npy), within the cap and identical from call to call."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(1)
+    img = torch.from_numpy(rng.random((30, 40, 4), dtype=np.float32))
+    it = torch.from_numpy(rng.integers(0, 50000, (30, 40), dtype=np.int32))
+    bench.dump_outputs(str(tmp_path / "whole"), {"image": img, "iters": it})
+    assert sorted(os.listdir(tmp_path / "whole")) == ["image.npy", "iters.npy"]
+    a, b = np.load(tmp_path / "whole" / "image.npy"), np.load(tmp_path / "whole" / "iters.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img.numpy()) and b.dtype == np.float64 and np.array_equal(b, it.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 6000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"image": img, "iters": it})
+    files = {f: np.load(tmp_path / "s1" / f) for f in ("image.npy", "iters.npy", "pixel_index.npy")}
+    assert sum(v.nbytes for v in files.values()) <= 6000
+    idx = files["pixel_index.npy"].astype(np.int64)
+    assert files["pixel_index.npy"].dtype == np.float64 and len(idx) > 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(files["image.npy"], img.numpy().reshape(-1, 4)[idx])
+    assert np.array_equal(files["iters.npy"], it.numpy().reshape(-1)[idx])
+    for f, v in files.items():
+        assert np.array_equal(np.load(tmp_path / "s2" / f), v)
 
 
 def test_app_command_lines_follow_the_reference_surface():

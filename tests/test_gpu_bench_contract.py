@@ -73,6 +73,30 @@ def test_other_workloads(workload, unit):
         assert r["executed_source"] is None or "not quoted" in r["executed_source"]
 
 
+def test_dump_outputs_are_what_the_last_timed_step_computed(ctx, B, tmp_path):
+    """--dump-outputs: K2 at reduced spp (the whole storage buffer, 8.6 MB) is the same from run to run and equals the same request
+    through the C ABI; K1 is above the 64 MB cap (153 MB): a seeded pixel sample of its storage buffer and iteration counts, equal to
+    the same pixels of the C ABI's render."""
+    import numpy as np
+    base = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-end-to-end"]
+    for d in ("a", "b"):
+        run_bench(base + ["--spp", "20", "--dump-outputs", str(tmp_path / d)])
+    assert sorted(os.listdir(tmp_path / "a")) == ["image.npy"]
+    a, b = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "b" / "image.npy")
+    assert a.dtype == np.float32 and a.shape == (600, 900, 4)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    ref = ctx.pathtrace(B.pathtrace_params(900, 600, 20, math_mode=B.PT_MATH_FAST))
+    assert np.array_equal(a.view(np.uint32), np.ascontiguousarray(ref, np.float32).view(np.uint32))
+    run_bench(base + ["--config", "K1", "--dump-outputs", str(tmp_path / "k1")])
+    files = {f: np.load(tmp_path / "k1" / f) for f in ("image.npy", "iters.npy", "pixel_index.npy")}
+    assert sorted(os.listdir(tmp_path / "k1")) == sorted(files)
+    assert sum(os.path.getsize(tmp_path / "k1" / f) for f in files) <= 64_000_000
+    idx = files["pixel_index.npy"].astype(np.int64)
+    rgba, iters = ctx.mandelbrot(B.mandelbrot_params(3200, 2400, max_iter=1000))
+    assert np.array_equal(files["image.npy"].view(np.uint32), np.ascontiguousarray(rgba, np.float32).reshape(-1, 4)[idx].view(np.uint32))
+    assert np.array_equal(files["iters.npy"], iters.reshape(-1)[idx].astype(np.float64))
+
+
 def test_two_rank_rehearsal_is_bit_identical_to_one_gpu():
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", "29533"]

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE
+from conftest import GOLDEN
 
 
 @pytest.fixture(scope="module")
@@ -212,16 +212,19 @@ def test_pathtrace_statistics_match_the_reference_image(O):
     assert np.all(np.abs(mine.mean(axis=(0, 1)) - blocks.mean(axis=(0, 1))) < 9.0)
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE), reason="reference checkout absent (GPU box)")
 def test_reference_lodepng_reencodes_its_own_artefact(O):
     """oracle/_ref (the reference's lodepng compiled where it lies): encode(decode(imageForReadme.png)) is the
-    file itself, byte for byte — pins the PNG stage of the output contract."""
+    file itself, byte for byte — pins the PNG stage of the output contract.  The file's decoded pixels
+    (readme_image_rgb.npz) and its SHA-256 and length (readme_image_png.sha256) are the committed fixtures."""
+    import hashlib
     if O.ref_lodepng() is None:
         pytest.skip("oracle/_ref not built")
-    data = open(os.path.join(REFERENCE, "imageForReadme.png"), "rb").read()
-    img = O.ref_png_decode(data)
-    assert img.shape == (600, 900, 4) and np.all(img[..., 3] == 255)
-    assert O.ref_png_encode(img, 900, 600) == data
+    rgb = np.load(os.path.join(GOLDEN, "readme_image_rgb.npz"))["rgb"]
+    img = np.ascontiguousarray(np.concatenate([rgb, np.full((600, 900, 1), 255, np.uint8)], -1))
+    data = O.ref_png_encode(img, 900, 600)
+    assert len(data) == 1057515
+    assert hashlib.sha256(data).hexdigest() == open(os.path.join(GOLDEN, "readme_image_png.sha256")).read().split()[0]
+    assert np.array_equal(O.ref_png_decode(data), img)
 
 
 def test_oracle_reproduces_the_reference_image_per_pixel(O):
