@@ -89,7 +89,21 @@ int mc_context_measure_clock(mc_context* ctx, double* sclk_mhz);
 
 /* ---- Mandelbrot: replaces shaders/mandelbrot.comp:21-60 + the dispatch recorded in
  *      MandelbrotApp::createCommandBuffer (src/mandelbrotApp.h:137-147) ----------------------------- */
-enum { MC_PRECISION_F32 = 0, MC_PRECISION_DS = 1 /* two-float, emulateDouble.h.glsl:59-139 */ };
+enum { MC_PRECISION_F32 = 0, MC_PRECISION_DS = 1 /* two-float, emulateDouble.h.glsl:59-139 */,
+       MC_PRECISION_F64 = 2 /* native IEEE double (emulateDouble.h.glsl:13, USE_NATIVE_FP64) */ };
+/* MC_PRECISION_F64, exactly (what tests/mandel_f64_ref.py restates):
+ *  - view: the same words as MC_PRECISION_DS, read as doubles: centre_x = (double)centre_x_hi + (double)centre_x_lo, and the same for
+ *    centre_y, scale_x and scale_y.  With hi = (float)d, lo = (float)(d - hi) that sum is exact, so a view means the same thing in DS
+ *    and F64 and no new packing exists.  The centre carries about 48 significant bits: that only shifts the view by less than
+ *    2^-48 |centre|; the pixel grid itself (the scale, the per-pixel offsets below) is computed in full double.
+ *  - per-pixel c, IEEE double, no contraction: x = (double)gx / (double)W, c.x = centre_x + (x - 0.5) * scale_x; the same for y with
+ *    gy, H, centre_y, scale_y.
+ *  - loop (mandelbrot.comp:40-46 in double, source order), z = 0, sx = sy = 0, n = 0; for i in [0, M):
+ *      nzx = (sx - sy) + c.x;  nzy = ((2 * zx) * zy) + c.y;  zx = nzx;  zy = nzy;  sx = zx * zx;  sy = zy * zy;
+ *      if (sx + sy > 2.0) break;  n++
+ *    n is the number of iterations that did not escape, in [0, M].
+ *  - colour: the fp32 table of mc_mandelbrot_colour_lut (t = n / M in fp32), so the RGBA f32, RGBA8 and PNG outputs are the same
+ *    functions of n as for the other two precisions. */
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1 /* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */
@@ -101,7 +115,7 @@ typedef struct mc_mandelbrot_params {
     uint32_t max_iter;        /* M (mandelbrot.comp:40); reference 128                                   */
     uint32_t precision;       /* MC_PRECISION_*                                                         */
     /* c = centre + (uv - 0.5) * scale (mandelbrot.comp:38); reference centre (-0.445, 0), scale 2.34   */
-    /* on both axes.  *_lo are the low words for MC_PRECISION_DS (hi=(float)d, lo=(float)(d-hi)).       */
+    /* on both axes.  *_lo are the low words for MC_PRECISION_DS and _F64 (hi=(float)d, lo=(float)(d-hi)). */
     float centre_x_hi, centre_x_lo, centre_y_hi, centre_y_lo;
     float scale_x_hi, scale_x_lo, scale_y_hi, scale_y_lo;
     float k_color[4];         /* push constant kColor (mandelbrotApp.h:139); reference {0.1,0.7,0.6,0}   */

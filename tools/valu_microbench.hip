@@ -3,6 +3,8 @@
 //   valu_microbench mix       how the issue classes combine; instructions under EXEC = 0 (profiles/r03_valu_microbench3.txt)
 //   valu_microbench among     a transcendental among other instructions (profiles/r03_valu_microbench7.txt)
 //   valu_microbench opcodes   every transcendental opcode, f32 and f16, alone and in a mix (profiles/r04_valu_microbench8.txt)
+//   valu_microbench fp64      the fp64 rows of "classes": v_add/mul/fma_f64, v_cmp_gt_f64 — the issue cost and the fp64 peak of the
+//                             MC_PRECISION_F64 Mandelbrot kernel (profiles/f64_valu_microbench.txt)
 // These are the measurements the path tracer's design rests on: add / mul / fmac / mov / logic issue in ~2.3 cycles
 // per wave64 instruction per SIMD, compare / select / min / max / convert / three-operand integer in ~4.2 alone but ~2.4 in a mix,
 // transcendentals in ~8.2 wherever they stand.  Each mode is the former file's code, unchanged, in a namespace of its own.
@@ -129,21 +131,29 @@ KERNELU32(k_cndmask, BODY_CNDMASK)
 KERNELU32(k_and, BODY1("v_and_b32"))
 KERNEL32(k_fmac, BODY1("v_fmac_f32"))
 KERNEL32(k_sub, BODY1("v_sub_f32"))
+// fp64 rows: the same 8 chains x 2 on register pairs (the "v" constraint of a double is a VGPR pair)
+#define KERNELF64(NAME, BODY)                                                    \
+    __global__ void __launch_bounds__(256) NAME(float* out, float seed) {        \
+        double a0 = seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3;                 \
+        double a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;               \
+        double b = a0 * 0.5 + 1.0;                                               \
+        for (int i = 0; i < kIters; i++) { BODY; }                               \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7); \
+    }
+KERNELF64(k_add64, BODY1("v_add_f64"))
+KERNELF64(k_mul64, BODY1("v_mul_f64"))
+KERNELF64(k_fma64, BODY_FMA("v_fma_f64"))
+KERNELF64(k_cmp64, BODY_CMP("v_cmp_gt_f64"))
 
 struct Entry {
     const char* name;
     void (*fn)(float*, float);
-    int flops_per_lane;   // fp32 flops per lane per instruction (0 for non-fp)
+    int flops_per_lane;   // flops per lane per instruction (0 for non-fp): fp32, or fp64 for the *_f64 rows
 };
 
+static int run_entries(const std::vector<Entry>& es);
+
 static int run() {
-    CHECK(hipSetDevice(0));
-    hipDeviceProp_t prop;
-    CHECK(hipGetDeviceProperties(&prop, 0));
-    const int cus = prop.multiProcessorCount;
-    printf("device %s  CUs %d  clock %d kHz\n", prop.name, cus, prop.clockRate);
-    float* out;
-    CHECK(hipMalloc(&out, sizeof(float) * 256 * cus * 64));
     std::vector<Entry> es = {
         {"v_add_f32", k_add, 1},     {"v_mul_f32", k_mul, 1},       {"v_fma_f32", k_fma, 2},     {"v_max_f32", k_max, 1},
         {"v_cmp_gt_f32", k_cmp, 0},  {"v_pk_add_f32", k_pk_add, 2}, {"v_pk_mul_f32", k_pk_mul, 2}, {"v_pk_fma_f32", k_pk_fma, 4},
@@ -153,6 +163,22 @@ static int run() {
         {"v_mov_b32", k_mov, 0},     {"v_cndmask_b32", k_cndmask, 0}, {"v_and_b32", k_and, 0},   {"v_fmac_f32", k_fmac, 2},
         {"v_sub_f32", k_sub, 1},
     };
+    return run_entries(es);
+}
+
+static int run_fp64() {
+    return run_entries({{"v_add_f64", k_add64, 1}, {"v_mul_f64", k_mul64, 1}, {"v_fma_f64", k_fma64, 2}, {"v_cmp_gt_f64", k_cmp64, 0},
+                        {"v_add_f32", k_add, 1}});   // the fp32 row again, same run, for the ratio
+}
+
+static int run_entries(const std::vector<Entry>& es) {
+    CHECK(hipSetDevice(0));
+    hipDeviceProp_t prop;
+    CHECK(hipGetDeviceProperties(&prop, 0));
+    const int cus = prop.multiProcessorCount;
+    printf("device %s  CUs %d  clock %d kHz\n", prop.name, cus, prop.clockRate);
+    float* out;
+    CHECK(hipMalloc(&out, sizeof(float) * 256 * cus * 64));
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
@@ -190,6 +216,7 @@ static int run() {
 #undef KERNEL32
 #undef KERNEL64
 #undef KERNELU32
+#undef KERNELF64
 #undef BODY_CNDMASK
 
 // ======================================================================================================================
@@ -505,6 +532,7 @@ int main(int argc, char** argv) {
     if (m == "mix") return mix::run();
     if (m == "among") return among::run();
     if (m == "opcodes") return opcodes::run();
-    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes\n");
+    if (m == "fp64") return classes::run_fp64();
+    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes | fp64\n");
     return 2;
 }

@@ -16,7 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mc_compute.h")
 
 MC_OK = 0
 ABI_VERSION = 3   # MC_ABI_VERSION of include/mc_compute.h this binding is written against
-PRECISION_F32, PRECISION_DS = 0, 1
+PRECISION_F32, PRECISION_DS, PRECISION_F64 = 0, 1, 2
 PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format

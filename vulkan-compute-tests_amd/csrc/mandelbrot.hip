@@ -1,7 +1,8 @@
 // Mandelbrot escape-time kernels for gfx950 (MI355X).
 //
 // Replaces shaders/mandelbrot.comp:21-60 (fp32) and adds the two-float deep-zoom variant composed
-// from the reference's ds_* primitives (shaders/emulateDouble.h.glsl:59-139).
+// from the reference's ds_* primitives (shaders/emulateDouble.h.glsl:59-139), and the
+// native fp64 variant the reference's USE_NATIVE_FP64 switch stands for (emulateDouble.h.glsl:13).
 //
 // Design (MI355X-first, not a translation of the 32x32 Vulkan workgroup):
 //  * one work-item per pixel; a wave64 owns an 8x8 pixel tile (coherent trip counts, and every
@@ -39,7 +40,8 @@ struct MandelArgs {
     uint16_t* __restrict__ out_iters16; // the same plane as 16-bit counts (MC_MANDEL_ITERS_U16, max_iter <= 65535), may be null
     const float4* __restrict__ lut;     // max_iter+1 entries (null when out_rgba is null)
     // c = centre + (uv - 0.5) * scale per column / per row, evaluated once on the host with the shader's fp32
-    // operation sequence (mandelbrot.comp:30-31,38): fp32 [cx[W] | cy[H]], two-float [cx(hi,lo)[W] | cy(hi,lo)[H]].
+    // operation sequence (mandelbrot.comp:30-31,38): fp32 [cx[W] | cy[H]], two-float [cx(hi,lo)[W] | cy(hi,lo)[H]],
+    // fp64 double [cx[W] | cy[H]] (read through a double pointer).
     // Replaces two IEEE divisions (~50 instructions) per pixel; exterior tiles only run a handful of iterations.
     const float* __restrict__ c_tab;
 };
@@ -139,6 +141,39 @@ struct StateDS {
         sx = ds_sqr(zx); sy = ds_sqr(zy);
         return ds_greater(ds_add(sx, sy), ds_set(2.0f));
     }
+};
+
+// Native IEEE double (MC_PRECISION_F64; the exact contract is in include/mc_compute.h).  The loop of StateF32<false> in
+// double: 5 v_add_f64 (2*zx is an add) + 3 v_mul_f64 per iteration, no contraction (-ffp-contract=off).  fp64 denormals
+// stay enabled (the gfx9 default; the kernel descriptor's FLOAT_DENORM_MODE_16_64 is 3), so orbits that pass near 0
+// round as IEEE does.
+struct StateF64 {
+    double cx, cy, zx, zy, sx, sy;   // sx = zx*zx, sy = zy*zy of the current z
+    __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const MandelArgs& a) {
+        const double* tab = reinterpret_cast<const double*>(a.c_tab);
+        cx = tab[gx];
+        cy = tab[a.W + gy];
+        zx = zy = sx = sy = 0.0;
+    }
+    __device__ __forceinline__ double advance() {
+        double nzx = (sx - sy) + cx;
+        double nzy = ((2.0 * zx) * zy) + cy;
+        zx = nzx; zy = nzy;
+        sx = zx * zx; sy = zy * zy;
+        return sx + sy;
+    }
+    __device__ __forceinline__ bool step() { return advance() > 2.0; }
+    __device__ __forceinline__ bool same_z(const StateF64& o) const { return zx == o.zx && zy == o.zy; }
+    static constexpr uint32_t kCycleCheckBlocks = 1;   // every block (8 iterations), as fp32: 2 v_cmp_f64 against ~66 VALU ops
+    // StateF32's filter on the HIGH word of |z|^2 (>= 0, or NaN): every value >= 2.0 (and inf, and any NaN) has a high word
+    // >= 0x40000000, every value < 2.0 one <= 0x3fffffff.  So the OR of a block's high words exceeds 0x3fffffff whenever one of
+    // them escaped (no false negatives); the only false positives are magnitudes of exactly 2.0.  The compiler ORs the whole
+    // 64-bit words (6 v_or3_b32 / v_or_b32 per 8 iterations) and compares once.
+    static constexpr bool kHasFastBlock = true;
+    using Acc = uint32_t;
+    __device__ __forceinline__ Acc acc_init() const { return 0u; }
+    __device__ __forceinline__ void advance_fast(Acc& acc) { acc |= (uint32_t)((uint64_t)__double_as_longlong(advance()) >> 32); }
+    static __device__ __forceinline__ bool needs_exact(Acc or_of_high_words) { return or_of_high_words > 0x3fffffffu; }
 };
 
 // Runs the escape-time loop for the 64 pixels of a wave.  Returns n in [0,max_iter] per lane:
@@ -272,7 +307,8 @@ static int ensure_lut(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_
 }
 
 // Per-column / per-row c tables.  x = float(gx)/float(W) (mandelbrot.comp:30), c.x = centre.x + (x - 0.5)*scale.x (:38) in
-// fp32 source order; the two-float variant composes ds_add(centre, ds_mul(ds_set(x - 0.5), scale)).
+// fp32 source order; the two-float variant composes ds_add(centre, ds_mul(ds_set(x - 0.5), scale)); the fp64
+// variant computes x = double(gx)/double(W), c.x = (hi + lo) + (x - 0.5)*(scale hi + lo) in double (include/mc_compute.h).
 // Host and device execute the same IEEE operations (no contraction), so the tables hold exactly the values the
 // kernel used to compute per pixel.  Cached in the context, keyed by (W, H, precision, view).
 static int ensure_c_table(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_t s) {
@@ -282,9 +318,18 @@ static int ensure_c_table(mc_context* ctx, const mc_mandelbrot_params* p, hipStr
         std::memcmp(ctx->ctab_key.data(), key.data(), key.size() * sizeof(float)) == 0)
         return MC_OK;
     const uint32_t W = p->width, H = p->height;
-    const bool ds = p->precision == MC_PRECISION_DS;
-    std::vector<float> tab(((size_t)W + H) * (ds ? 2 : 1));
+    const bool ds = p->precision == MC_PRECISION_DS, f64 = p->precision == MC_PRECISION_F64;
+    std::vector<float> tab(((size_t)W + H) * (ds || f64 ? 2 : 1));
     for (uint32_t g = 0; g < W + H; g++) {
+        if (f64) {
+            const bool is_x = g < W;
+            const double u = is_x ? (double)g / (double)W : (double)(g - W) / (double)H;
+            const double c = is_x ? (double)p->centre_x_hi + (double)p->centre_x_lo : (double)p->centre_y_hi + (double)p->centre_y_lo;
+            const double sc = is_x ? (double)p->scale_x_hi + (double)p->scale_x_lo : (double)p->scale_y_hi + (double)p->scale_y_lo;
+            const double v = c + (u - 0.5) * sc;
+            std::memcpy(&tab[2 * (size_t)g], &v, sizeof v);
+            continue;
+        }
         const bool is_x = g < W;
         const float u = is_x ? (float)g / (float)W : (float)(g - W) / (float)H;
         const float c_hi = is_x ? p->centre_x_hi : p->centre_y_hi, c_lo = is_x ? p->centre_x_lo : p->centre_y_lo;
@@ -320,7 +365,8 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (!ctx || !p || (!d_rgba && !d_iters)) return MC_ERR_INVALID_ARGUMENT;
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
-    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS) return MC_ERR_INVALID_ARGUMENT;
+    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64)
+        return MC_ERR_INVALID_ARGUMENT;
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);
@@ -351,6 +397,8 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     }
     if (p->precision == MC_PRECISION_DS) {
         hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
+    } else if (p->precision == MC_PRECISION_F64) {
+        hipLaunchKernelGGL((mandelbrot_kernel<StateF64, 8>), grid, block, 0, s, a);
     } else if (p->flags & MC_MANDEL_FMA) {
         hipLaunchKernelGGL((mandelbrot_kernel<StateF32<true>, 8>), grid, block, 0, s, a);
     } else {

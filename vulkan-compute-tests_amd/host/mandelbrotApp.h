@@ -28,7 +28,7 @@ struct MandelbrotApp : public ComputeApp {
         split(sx, params.scale_x_hi, params.scale_x_lo);
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
-    void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / MC_PRECISION_DS
+    void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
 
     virtual void preRun() override {
         if (!quiet) { printf(" * before createBuffer()\n"); fflush(stdout); }
