@@ -2,10 +2,9 @@
 """Fork census of the FAST path tracer kernels: which approximation of fast math carries how many of the samples
 that take another path than the reference arithmetic's, on the box scenes of tests/test_gpu_scenes.py (1 .. 8 spheres).
 
-For each library given — the shipped one and `make exp` builds with ONE fast-math shortcut switched off (MC_PT_FAST_*), the hardware
-seeds replaced by correctly rounded operations (MC_PT_FAST_IEEE), the hardware sine / cosine by the strict pair
-(MC_PT_FAST_ACCURATE_SINCOS), contraction off (MC_PT_FAST_CONTRACT=0/1), directions re-normalised (MC_PT_FAST_RENORMALISE) — every
-scene is rendered at the size the bound is asserted at (300 x 200, 500 spp) and compared with the CPU oracle evaluated with libm:
+For each library given — the shipped one, the contraction variants of `make variants` (MC_PT_FAST_CONTRACT=0/1) or any `make exp`
+build — and each run-time mode of --modes, every scene is rendered at the size the bound is asserted at (300 x 200, 500 spp) and
+compared with the CPU oracle evaluated with libm:
     rmse, p99.9 = the bound's two statistics (8-bit units; <= 0.5 / <= 4);   far = share of pixels further than 4;
     forked     = share of pixels whose largest channel difference exceeds 0.5 (a pixel that visibly took another sample);
     mean +- se = mean difference over the image and its standard error (per-pixel means as the sample);

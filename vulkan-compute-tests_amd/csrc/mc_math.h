@@ -61,9 +61,6 @@ __device__ __forceinline__ float rcp_short(float b) {
 // 1 step on 1/s from y": exactly these two patterns per binade pair) — those two get their ulp added by an integer test on x's bits.
 // Established like the other short forms: EVERY fp32 pattern of the window compared with the IEEE expansion on the device
 // (tests/test_gpu_parity.py::test_short_forms_exhaustive, fn 5; profiles/r04_exact_rsqrt_one_trans.txt).
-#ifndef MC_MATH_RSQRT_ONE_TRANS
-#define MC_MATH_RSQRT_ONE_TRANS 1
-#endif
 __device__ __forceinline__ float rsqrt_short(float x) {
     const float y = __builtin_amdgcn_rsqf(x);
     const float g = x * y;
@@ -89,52 +86,13 @@ __device__ __forceinline__ float div_step(float a, float s, float y) {
     return __builtin_fmaf(r, y, q0);
 }
 
-// Fork census (tools/fork_census.py; measurement builds only, `make exp EXP_FLAGS=-D...=1`): the fast mode's hardware seeds replaced by
-// the correctly rounded operations (MC_PT_FAST_IEEE: v_rcp / v_rsq / v_sqrt -> IEEE divide, sqrt, 1/sqrt) or its hardware sine / cosine
-// by the strict mode's Cody-Waite + cephes pair (MC_PT_FAST_ACCURATE_SINCOS), everything else of fast math left as it is — which
-// approximation carries how many of the forked samples (profiles/r05_fork_census.txt).
-#ifndef MC_PT_FAST_IEEE
-#define MC_PT_FAST_IEEE 0
-#endif
-#ifndef MC_PT_FAST_ACCURATE_SINCOS
-#define MC_PT_FAST_ACCURATE_SINCOS 0
-#endif
-// The careful tier (Fast == 2; MC_PT_FAST_SHORT = 1 gives the fast tier the same forms, for the census): the short forms of the strict
-// mode (correct rounding enumerated over every fp32 pattern of their windows, see sqrt_short / rcp_short / div_step / rsqrt_short below)
-// without the strict mode's window tests: outside the windows (denormal, infinite, NaN arguments — no finite path produces one) the
-// result is merely inaccurate, and the one argument a path does produce there, an exact zero under a square root, is selected per lane.
-#ifndef MC_PT_FAST_SHORT
-#define MC_PT_FAST_SHORT 0
-#endif
-#ifdef MC_EXPERIMENT_NO_TRANS
-// MEASUREMENT BUILD ONLY (make exp EXP_FLAGS=-DMC_EXPERIMENT_NO_TRANS; profiled with round 4's tools/pmc_libs.sh, since removed: profiles/r04_no_trans_pmc.txt): the fast kernels' hardware transcendentals
-// replaced by ordinary-instruction approximations (bit-pattern seeds + two Newton steps; a parabola pair for sin / cos) good to ~1e-3 —
-// the paths stay statistically the same, the image is NOT the product's.  Answers one question: what does the SIMD pay per VALU
-// instruction when no transcendental is in the stream (profiles/r04_no_trans_pmc.txt)?
-__device__ __forceinline__ float nt_rcp(float x) {
-    const float ax = __builtin_fabsf(x);
-    float r = as_float(0x7EF311C7u - as_uint(ax));
-    r = r * (2.0f - ax * r); r = r * (2.0f - ax * r);
-    return __builtin_copysignf(r, x);
-}
-__device__ __forceinline__ float nt_rsq(float x) {
-    float r = as_float(0x5F375A86u - (as_uint(x) >> 1));
-    const float h = 0.5f * x;
-    r = r * (1.5f - h * r * r); r = r * (1.5f - h * r * r);
-    return r;
-}
-__device__ __forceinline__ float nt_sin_rev(float u) {      // sin(2 pi u), u in revolutions
-    const float x = u - __builtin_rintf(u);                 // [-0.5, 0.5]
-    const float y = 8.0f * x * (1.0f - 2.0f * __builtin_fabsf(x));
-    return y * (0.775f + 0.225f * __builtin_fabsf(y));
-}
-#endif
+// The careful tier (Fast == 2): the short forms of the strict mode (correct rounding enumerated over every fp32 pattern of their
+// windows, see sqrt_short / rcp_short / div_step / rsqrt_short above) without the strict mode's window tests: outside the windows
+// (denormal, infinite, NaN arguments — no finite path produces one) the result is merely inaccurate, and the one argument a path does
+// produce there, an exact zero under a square root, is selected per lane.
 template <int Fast> __device__ __forceinline__ float fdiv(float a, float b) {
-#ifdef MC_EXPERIMENT_NO_TRANS
-    if (Fast) return a * nt_rcp(b);
-#endif
-    if (Fast == 2 || (Fast && MC_PT_FAST_SHORT)) return div_step(a, b, rcp_short(b));
-    if (Fast && !MC_PT_FAST_IEEE) return a * __builtin_amdgcn_rcpf(b);
+    if (Fast == 2) return div_step(a, b, rcp_short(b));
+    if (Fast) return a * __builtin_amdgcn_rcpf(b);
     return ieee_div(a, b);
 }
 // (a0, a1, a2) / s.  Strict: the short division inside its window (wave-wide test), the compiler's IEEE expansion outside.
@@ -156,35 +114,20 @@ template <int Fast, bool HaveY> __device__ __forceinline__ void div3(float& a0, 
     a0 = fdiv<Fast>(a0, s); a1 = fdiv<Fast>(a1, s); a2 = fdiv<Fast>(a2, s);
 }
 template <int Fast> __device__ __forceinline__ float fsqrt(float a) {
-#ifdef MC_EXPERIMENT_NO_TRANS
-    if (Fast) return a * nt_rsq(a);
-#endif
-    // Careful tier (and the MC_PT_FAST_SHORT experiment): the strict mode's short form WITHOUT its window test.  Outside the window it is
-    // merely inaccurate, with two exceptions stated here: -0 maps to +0 (the reference keeps -0; no decision downstream
-    // reads the sign of a zero root), and a DENORMAL argument gives NaN (rsq = inf, inf - inf) — in the intersectors a sphere whose
-    // discriminant is a denormal then fails every comparison and is a miss where the reference reports a grazing hit.  A discriminant
-    // below 2^-126 at scene scale (radii 0.2 - 1e5, |b| >= 1e-4) does not occur: 254 566 fuzzed scenes, 0 non-finite pixels.
-    if (Fast == 2 || (Fast && MC_PT_FAST_SHORT)) { const float r = sqrt_short(a); return a == 0.0f ? 0.0f : r; }
-    if (Fast && !MC_PT_FAST_IEEE) return __builtin_amdgcn_sqrtf(a);
-    if (Fast) return ieee_sqrt(a);
-#ifdef MC_EXPERIMENT_NO_WINDOW_GUARD   // measurement only: what the per-call window tests cost (NOT exact outside the window)
-    return sqrt_short(a);
-#endif
+    // Careful tier: the strict mode's short form WITHOUT its window test.  Outside the window it is merely inaccurate, with two
+    // exceptions stated here: -0 maps to +0 (the reference keeps -0; no decision downstream reads the sign of a zero root),
+    // and a DENORMAL argument gives NaN (rsq = inf, inf - inf) — in the intersectors a sphere whose discriminant is a denormal then
+    // fails every comparison and is a miss where the reference reports a grazing hit.  A discriminant below 2^-126 at scene scale
+    // (radii 0.2 - 1e5, |b| >= 1e-4) does not occur: 254 566 fuzzed scenes, 0 non-finite pixels.
+    if (Fast == 2) { const float r = sqrt_short(a); return a == 0.0f ? 0.0f : r; }
+    if (Fast) return __builtin_amdgcn_sqrtf(a);
     if (__builtin_expect(wave_all(in_short_window(a)), 1)) return sqrt_short(a);
     return ieee_sqrt(a);
 }
 template <int Fast> __device__ __forceinline__ float inversesqrt(float a) {
-#ifdef MC_EXPERIMENT_NO_TRANS
-    if (Fast) return nt_rsq(a);
-#endif
-    if (Fast == 2 || (Fast && MC_PT_FAST_SHORT)) return rsqrt_short(a);
-    if (Fast && !MC_PT_FAST_IEEE) return __builtin_amdgcn_rsqf(a);
-    if (Fast) return ieee_div(1.0f, ieee_sqrt(a));
-#ifdef MC_EXPERIMENT_NO_WINDOW_GUARD
-    return rsqrt_short(a);
-#endif
-    if (__builtin_expect(wave_all(in_short_window(a)), 1))
-        return MC_MATH_RSQRT_ONE_TRANS ? rsqrt_short(a) : rcp_short(sqrt_short(a));   // (sqrt in [2^-50, 2^50): inside rcp_short's window)
+    if (Fast == 2) return rsqrt_short(a);
+    if (Fast) return __builtin_amdgcn_rsqf(a);
+    if (__builtin_expect(wave_all(in_short_window(a)), 1)) return rsqrt_short(a);
     return ieee_div(1.0f, ieee_sqrt(a));
 }
 
@@ -238,12 +181,7 @@ __device__ __forceinline__ void mc_sincos(float x, float& s, float& c) {
 // sin/cos of angle = two_pi_f32 * u where `angle` is the already-rounded fp32 product the shader
 // computes (pathTracer.comp:412,426) and `u` the random number it came from.
 template <int Fast> __device__ __forceinline__ void sincos_angle(float angle, float u, float& s, float& c) {
-#ifdef MC_EXPERIMENT_NO_TRANS
-    if (Fast) { s = nt_sin_rev(u); c = nt_sin_rev(u + 0.25f); return; }
-#endif
-    if (Fast && MC_PT_FAST_ACCURATE_SINCOS) {   // (census build; a caller of the fast form may pass angle = 0: formed here)
-        mc_sincos(6.283185307179586f * u, s, c);
-    } else if (Fast) {
+    if (Fast) {
         // v_sin_f32 / v_cos_f32 take revolutions: sin(2*pi*u).  u in [0,1].
         s = __builtin_amdgcn_sinf(u);
         c = __builtin_amdgcn_cosf(u);

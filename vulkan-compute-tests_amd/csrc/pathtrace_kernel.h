@@ -36,15 +36,6 @@
 #include "ds_arith.h"
 #include "mc_math.h"
 
-// Fork census only (tools/fork_census.py, profiles/r05_fork_census.txt): the sampled / refracted directions re-normalised as the
-// reference does (:413, :428, :441); the root form of the shadow test although the spheres are disjoint
-#ifndef MC_PT_FAST_RENORMALISE
-#define MC_PT_FAST_RENORMALISE 0
-#endif
-#ifndef MC_PT_FAST_NO_DISJOINT
-#define MC_PT_FAST_NO_DISJOINT 0
-#endif
-
 namespace mc {
 namespace pt {
 
@@ -150,7 +141,7 @@ template <int Fast> __device__ __forceinline__ v3 tangent_u(v3 w) {
 // :413 and :428).  Strict: the literal normalize.  Fast (toleranced): the vector is already of unit length to within the
 // accuracy of v_sin/v_cos/v_sqrt (~1e-6), which is what the rescaling would remove; it is used as it is.
 template <int Fast, bool UnitBasis> __device__ __forceinline__ v3 normalize_unit_combination(v3 a) {
-    if constexpr (Fast == 1 && UnitBasis && !MC_PT_FAST_RENORMALISE) return a;
+    if constexpr (Fast == 1 && UnitBasis) return a;
     else return normalize<Fast>(a);   // (the careful tier re-normalises as the reference does: profiles/r05_fork_bias_identities.txt)
 }
 // reflect(I,N) = I - 2*dot(N,I)*N
@@ -208,31 +199,6 @@ static __device__ unsigned long long g_region_lanes[32];
 //   2 = everywhere.  The strict translation unit is built -ffp-contract=off and never defines MC_PT_DECISION_FP.
 #ifndef MC_PT_DECISION_FP
 #define MC_PT_DECISION_FP
-#endif
-#ifndef MC_PT_FAST_PLANES_ONE_RCP   // fast math: one division for the three slab tests (intersect_slab)
-#define MC_PT_FAST_PLANES_ONE_RCP 1
-#endif
-// Fast-math forms that can be switched off one by one for A/B measurements (`make exp EXP_NAME=x EXP_FLAGS=-D<macro>=0`; tools/fork_census.py and tools/fast_tolerance_k2.py take such libraries):
-#ifndef MC_PT_FAST_TANGENT_ONE_RSQ      // light sample: sin_a / |tangent| as one A * rsq(A * B)
-#define MC_PT_FAST_TANGENT_ONE_RSQ 1
-#endif
-#ifndef MC_PT_FAST_PLANE_ID_FROM_SIGN   // slab winner's id from constant selects and the sign of its d_a
-#define MC_PT_FAST_PLANE_ID_FROM_SIGN 1
-#endif
-#ifndef MC_PT_FAST_FRAME_NO_CROSS       // light sample: a t1 + b t2 + c sw without the cross product
-#define MC_PT_FAST_FRAME_NO_CROSS 1
-#endif
-#ifndef MC_PT_FAST_LIGHT_DET_ONLY       // shadow_visible_disjoint: the light's own root test is det >= 0
-#define MC_PT_FAST_LIGHT_DET_ONLY 1
-#endif
-#ifndef MC_PT_FAST_COLOUR_OVER_P        // pool kernel: colour / p as a record row
-#define MC_PT_FAST_COLOUR_OVER_P 1
-#endif
-#ifndef MC_PT_FAST_OCC_MINUS_R2         // pool kernel: |c - x|^2 - r^2 formed once per bounce
-#define MC_PT_FAST_OCC_MINUS_R2 1
-#endif
-#ifndef MC_PT_GENERIC_PREFETCH          // generic kernel reading the scene from memory: next sphere record fetched ahead
-#define MC_PT_GENERIC_PREFETCH 1
 #endif
 
 constexpr float kEps = 1e-4f, kTriEps = 1e-7f, kInf = 1e20f;   // pathTracer.comp:103-105
@@ -350,7 +316,7 @@ __device__ __forceinline__ int intersect_slab_impl(const HotSlabN<NS>& h, v3 o, 
     static_assert(HaveOc || !OccR2, "the r^2-reduced squared lengths come from the caller");
     float t = h.inf;
     int id = -1;
-    if (Fast && MC_PT_FAST_PLANES_ONE_RCP && !shadow_skip_planes) {
+    if (Fast && !shadow_skip_planes) {
         // Fast math: the nearest of the three facing planes is found BEFORE dividing — (W_a - o_a) / d_a < (W_b - o_b) / d_b is
         // compared as |W_a - o_a| |d_b| < |W_b - o_b| |d_a| (numerator and denominator of a facing plane have the same sign) —
         // and only the winner is divided: one v_rcp_f32 (8 issue cycles, profiles/r03_valu_microbench3.txt) instead of three,
@@ -358,23 +324,22 @@ __device__ __forceinline__ int intersect_slab_impl(const HotSlabN<NS>& h, v3 o, 
         // (|d_a| <= 1e-7, :119) loses every comparison against a real candidate; decisions differ from the reference's only
         // at ties of two planes' parameters (the edges of the box).
         float num[3], den[3];
-        int pid[3];
 #pragma unroll
         for (int a = 0; a < 3; a++) {
             const float da = comp(d, a), oa = comp(o, a);
             const bool pos = da > 0.0f;
-            num[a] = (pos ? h.W_pos[a] : h.W_negm[a]) - oa; den[a] = da; pid[a] = pos ? 2 * a + 1 : 2 * a;
+            num[a] = (pos ? h.W_pos[a] : h.W_negm[a]) - oa; den[a] = da;
         }
         float bn = num[0], bd = den[0];
-        int bid = MC_PT_FAST_PLANE_ID_FROM_SIGN ? 1 : pid[0];
+        int bid = 1;
 #pragma unroll
         for (int a = 1; a < 3; a++) {
             const bool nearer = __builtin_fabsf(num[a]) * __builtin_fabsf(bd) < __builtin_fabsf(bn) * __builtin_fabsf(den[a]);
-            bn = nearer ? num[a] : bn; bd = nearer ? den[a] : bd; bid = nearer ? (MC_PT_FAST_PLANE_ID_FROM_SIGN ? 2 * a + 1 : pid[a]) : bid;
+            bn = nearer ? num[a] : bn; bd = nearer ? den[a] : bd; bid = nearer ? 2 * a + 1 : bid;
         }
         // (the winner's id 2a + (d_a > 0): the odd id of its axis, less the sign bit of its d_a — two selects of constants and two
         // integer operations instead of three selects, two ORs and two selects of the ids)
-        if (MC_PT_FAST_PLANE_ID_FROM_SIGN) bid ^= (int)(dm::as_uint(bd) >> 31);
+        bid ^= (int)(dm::as_uint(bd) >> 31);
         const float dd = dm::fdiv<Fast>(bn, bd);
         if constexpr (Closed) { t = dd; id = bid; }
         else if (__builtin_fabsf(bd) > h.tri_eps && dd < t) { t = dd; id = bid; }
@@ -487,7 +452,7 @@ __device__ __forceinline__ bool shadow_visible_disjoint(const HotSlabN<NS>& h, v
         const float det = OccR2 ? b[i] * b[i] - occ[i] : (b[i] * b[i] - occ[i]) + h.r2[i];
         // (the ray is aimed INTO the light's cone, :408-:413: its line meets the light by construction and the root :319-:327 keep lies
         // ahead — only det >= 0 is tested for it: the rim of the cone, where rounding decides, and a NaN direction, which must not pass)
-        if (MC_PT_FAST_LIGHT_DET_ONLY && i == li) { hit[i] = det >= 0.0f; continue; }
+        if (i == li) { hit[i] = det >= 0.0f; continue; }
         const float e = b[i] - h.eps;
         hit[i] = !(det < 0.0f) && (e > 0.0f || det > e * e);
     }
@@ -566,7 +531,7 @@ __device__ __forceinline__ int intersect(const SceneArgs& sc, const float* __res
     // tested, so its latency hides behind the ~15 instructions of a sphere test instead of stalling the wave at the top of every
     // iteration: 5-11 % at 1500 spheres.  (Measured the other way for the LDS copy — 5-10 % SLOWER at 64 and 512 spheres: its
     // broadcast reads are short enough already — so only here.)  Same values, same order.
-    constexpr bool Prefetch = NP == -2 && MC_PT_GENERIC_PREFETCH;
+    constexpr bool Prefetch = NP == -2;
     float4 nxt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (Prefetch && ns > 0) nxt = *reinterpret_cast<const float4*>(obj + 12 * np);
 #pragma unroll
@@ -642,7 +607,7 @@ template <int Fast> __device__ __forceinline__ v3 camera_ray(const PTArgs& a, ui
 template <int Fast> __device__ __forceinline__ v3 light_sample_direction(v3 xc, float xcc, float lr2, v3 rnd, float& cos_a_max) {
     const float inv_len = dm::inversesqrt<Fast>(xcc);
     v3 sw = xc * inv_len;                                     // :409 normalize(xc)
-    if constexpr (Fast && MC_PT_FAST_TANGENT_ONE_RSQ) {
+    if constexpr (Fast) {
         // The tangents are left UNNORMALISED — t1 = cross(axis, sw) (tangent_u before its scaling), t2 = cross(sw, t1), both of
         // length k = sqrt(q^2 + sw.z^2) — and sin_a / k is formed as one factor: sqrt(A / B) = A * rsq(A * B) with A = sin_a^2 =
         // 1 - cos_a^2, B = k^2: one transcendental where 1 / k and sin_a took two (each ~12 issue cycles among other instructions,
@@ -650,44 +615,35 @@ template <int Fast> __device__ __forceinline__ v3 light_sample_direction(v3 xc, 
         const bool sel = __builtin_fabsf(sw.x) > 0.1f;
         const float q = sel ? sw.x : sw.y;
         const float B = __builtin_fmaf(q, q, sw.z * sw.z);
-        cos_a_max = dm::fsqrt<Fast>(1.0f - lr2 * (inv_len * inv_len));        // :410
+        cos_a_max = dm::fsqrt<Fast>(1.0f - lr2 * (inv_len * inv_len));        // :410 (1 / |xc|^2 as (1 / |xc|)^2: no v_rcp_f32)
         const float cos_a = (1.0f - rnd.x) + rnd.x * cos_a_max;               // :411
         const float A = __builtin_fmaxf(1.0f - cos_a * cos_a, 1e-30f);
         const float g = A * dm::inversesqrt<Fast>(A * B);
         float sphi, cphi;
         dm::sincos_angle<Fast>(0.0f, rnd.y, sphi, cphi);                      // :412
-        if (MC_PT_FAST_FRAME_NO_CROSS) {
-            // t1 = (z, 0, -x) or (0, -z, y) has a zero component and t2 = cross(sw, t1) = (-xy, B, -yz) or (B, -xy, -xz) carries B
-            // itself, so a t1 + b t2 + c sw needs no cross product: with m = the axis component (y or x), q the other one,
-            // cm = c - b m and sa = +-a:  special component = b B + c m,  the other two = sa z + q cm  and  -sa q + z cm.
-            const float a = cphi * g, b = sphi * g, c = cos_a;
-            const float m = sel ? sw.y : sw.x;
-            const float cm = __builtin_fmaf(-b, m, c);
-            const float sp = __builtin_fmaf(b, B, c * m);
-            const float sa = sel ? a : -a;
-            const float first = __builtin_fmaf(sa, sw.z, q * cm), lz = __builtin_fmaf(-sa, q, sw.z * cm);
-            const v3 lv{sel ? first : sp, sel ? sp : first, lz};              // :413
-            if constexpr (Fast == 2 || MC_PT_FAST_RENORMALISE != 0) return normalize<Fast>(lv);
-            return lv;
-        }
-        const v3 t1{sel ? sw.z : 0.0f, sel ? 0.0f : -sw.z, sel ? -q : q};
-        const v3 t2 = cross(sw, t1);
-        const v3 lv = (t1 * (cphi * g) + t2 * (sphi * g)) + sw * cos_a;       // :413
-        if constexpr (Fast == 2 || MC_PT_FAST_RENORMALISE != 0) return normalize<Fast>(lv);
+        // t1 = (z, 0, -x) or (0, -z, y) has a zero component and t2 = cross(sw, t1) = (-xy, B, -yz) or (B, -xy, -xz) carries B
+        // itself, so a t1 + b t2 + c sw needs no cross product: with m = the axis component (y or x), q the other one,
+        // cm = c - b m and sa = +-a:  special component = b B + c m,  the other two = sa z + q cm  and  -sa q + z cm.
+        const float a = cphi * g, b = sphi * g, c = cos_a;
+        const float m = sel ? sw.y : sw.x;
+        const float cm = __builtin_fmaf(-b, m, c);
+        const float sp = __builtin_fmaf(b, B, c * m);
+        const float sa = sel ? a : -a;
+        const float first = __builtin_fmaf(sa, sw.z, q * cm), lz = __builtin_fmaf(-sa, q, sw.z * cm);
+        const v3 lv{sel ? first : sp, sel ? sp : first, lz};                  // :413
+        if constexpr (Fast == 2) return normalize<Fast>(lv);
         return lv;
+    } else {
+        v3 su = tangent_u<Fast>(sw);
+        v3 sv = cross(sw, su);
+        cos_a_max = dm::fsqrt<Fast>(1.0f - dm::fdiv<Fast>(lr2, xcc));        // :410
+        float cos_a = (1.0f - rnd.x) + rnd.x * cos_a_max;         // :411
+        float sin_a = dm::fsqrt<Fast>(1.0f - cos_a * cos_a);
+        float phi = (2.0f * kPi) * rnd.y;                         // :412
+        float sphi, cphi;
+        dm::sincos_angle<Fast>(phi, rnd.y, sphi, cphi);
+        return normalize<Fast>(((su * cphi) * sin_a + (sv * sphi) * sin_a) + sw * cos_a);   // :413
     }
-    v3 su = tangent_u<Fast>(sw);
-    v3 sv = cross(sw, su);
-    // :410; fast: 1 / |xc|^2 is the square of the 1 / |xc| above (one multiply instead of a v_rcp_f32)
-    cos_a_max = dm::fsqrt<Fast>(1.0f - (Fast ? lr2 * (inv_len * inv_len) : dm::fdiv<Fast>(lr2, xcc)));
-    float cos_a = (1.0f - rnd.x) + rnd.x * cos_a_max;         // :411
-    float sin_a = dm::fsqrt<Fast>(1.0f - cos_a * cos_a);
-    float phi = (2.0f * kPi) * rnd.y;                         // :412
-    float sphi, cphi;
-    dm::sincos_angle<Fast>(phi, rnd.y, sphi, cphi);
-    // fast: the two scalar factors of a tangent are multiplied first (u*(c*s) for (u*c)*s: one product less per component)
-    return Fast ? normalize_unit_combination<Fast, true>((su * (cphi * sin_a) + sv * (sphi * sin_a)) + sw * cos_a)
-                : normalize_unit_combination<Fast, true>(((su * cphi) * sin_a + (sv * sphi) * sin_a) + sw * cos_a);   // :413
 }
 // Cosine-weighted bounce around w = nl (:426-:428).  Unit: w is of unit length (slab kernels: +-1 axis normals, normalised sphere
 // normals); a generic scene's plane normal is used as given, and there :428's normalize is not an identity.
@@ -751,7 +707,7 @@ template <int Fast> __device__ __forceinline__ v3 specular_bounce_fast(int mat, 
     // Careful tier: ONE direction is formed for all three outcomes, so the re-normalisation applies to all of them — the refracted ray,
     // which the reference normalises (:441), and the two reflections (:433, :446), which it leaves as reflect() returns them (unit to
     // within a rounding for unit rd and n: the extra normalize moves them by an ulp or so, inside the tier's tolerance).
-    if constexpr (Fast == 2 || MC_PT_FAST_RENORMALISE != 0) return normalize<Fast>(out);
+    if constexpr (Fast == 2) return normalize<Fast>(out);
     return out;
 }
 
@@ -912,7 +868,7 @@ __device__ __forceinline__ v3 trace_sample(const PTArgs& a, const float* __restr
                 bool reached;                                             // :420 shadow ray: is the nearest hit sphere i?
                 if constexpr (Slab) {
                     // (closed-box kernel, disjoint spheres — a uniform scene fact: the root-free test of the sample-pool kernel)
-                    if (Box && sc.spheres_disjoint != 0u && !MC_PT_FAST_NO_DISJOINT) reached = shadow_visible_disjoint<false>(hot, l, i, xoc, occ);
+                    if (Box && sc.spheres_disjoint != 0u) reached = shadow_visible_disjoint<false>(hot, l, i, xoc, occ);
                     else if (Box || sc.nee_skip_planes != 0u) reached = shadow_reaches_sphere<Fast>(hot, x, l, i, xc, occ);
                     else reached = intersect_slab<Fast>(hot, x, l, tne, false) == np + i;
                 } else {
@@ -968,7 +924,6 @@ template <int S> struct WaveTile;
 template <> struct WaveTile<1> { static constexpr uint32_t w = 8, h = 8; };
 template <> struct WaveTile<4> { static constexpr uint32_t w = 4, h = 4; };
 template <> struct WaveTile<16> { static constexpr uint32_t w = 2, h = 2; };
-template <> struct WaveTile<64> { static constexpr uint32_t w = 1, h = 1; };
 
 // Pixels covered by one 256-thread block (2 x 2 wave tiles).
 template <int S> constexpr uint32_t block_w() { return 2u * WaveTile<S>::w; }

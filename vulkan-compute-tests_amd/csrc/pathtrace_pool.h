@@ -36,25 +36,6 @@
 #include <type_traits>
 #include "pathtrace_kernel.h"
 
-#ifndef MC_PT_POOL_WAVES
-#define MC_PT_POOL_WAVES 7   // waves per SIMD the register budget is set for (72 VGPRs; 6: 18.29 ms, 7: 18.11, 8: 18.68 at K2)
-#endif
-#ifndef MC_PT_POOL_STRICT_WAVES
-#define MC_PT_POOL_STRICT_WAVES 6   // strict kernel: 80 VGPRs (three values spilled, none reloaded inside an iteration), 6 blocks of 26 KB per CU
-#endif
-#ifndef MC_PT_POOL_KEEP_VALID   // the pixel's validity kept across the loop (a lane mask) instead of re-derived per batch
-#define MC_PT_POOL_KEEP_VALID 1
-#endif
-#ifndef MC_PT_POOL_LANE_REGS   // the refill's lane / sub kept in registers (two instructions an iteration less; both kernels have the room)
-#define MC_PT_POOL_LANE_REGS 1
-#endif
-#ifndef MC_PT_POOL_HOT_W
-#define MC_PT_POOL_HOT_W true
-#endif
-#ifndef MC_PT_POOL_HOT_VGPR
-#define MC_PT_POOL_HOT_VGPR false
-#endif
-
 namespace mc {
 namespace pt {
 
@@ -65,17 +46,16 @@ constexpr uint32_t kPoolStashFloats = 128u * kPoolEntryFloats;     // per wave: 
 // Strict: the result ring holds this many batches per pixel (3 planes x, y, z).  Three for the reference's scene: with the 23 + 3 KB of a
 // block six blocks fit a CU's 160 KB, and 6 waves per SIMD with a 3-batch ring beat 5 waves with a 4-batch ring (32.7 against 33.1 ms at K2;
 // 2 batches stall the production: 34.3; profiles/r04_strict_occupancy.txt).  Scenes with more spheres run at 4 waves per SIMD: 4 batches.
-#ifndef MC_PT_POOL_RESULT_BATCHES
-#define MC_PT_POOL_RESULT_BATCHES 0   // 0: automatic (by sphere count)
-#endif
-template <int NS> constexpr uint32_t pool_result_batches() { return MC_PT_POOL_RESULT_BATCHES ? MC_PT_POOL_RESULT_BATCHES : (NS <= 3 ? 3u : 4u); }
+template <int NS> constexpr uint32_t pool_result_batches() { return NS <= 3 ? 3u : 4u; }
 template <int NS> constexpr uint32_t pool_result_floats() { return 64u * pool_result_batches<NS>() * 3u; }   // per wave: 64/S pixels x batches x S samples x 3
 template <int Fast, int NS> constexpr uint32_t pool_wave_lds_floats() { return kPoolStashFloats + (Fast ? 0u : pool_result_floats<NS>()); }
 template <int Fast, int NS> constexpr size_t pool_block_lds_bytes() { return (pool_record_floats<NS>() + 4u * pool_wave_lds_floats<Fast, NS>()) * sizeof(float); }
 // Waves per SIMD the register budget is set for: 7 / 6 for the reference's three spheres (72 / 80 VGPRs); every further sphere
 // keeps five more values live across a bounce (c_i - x, |c_i - x|^2 and its r^2-reduced form), so the budget widens with the count.
 template <int Fast, int NS> constexpr int pool_waves() {
-    return Fast ? (NS <= 3 ? MC_PT_POOL_WAVES : NS <= 5 ? 6 : NS <= 6 ? 5 : 4) : (NS <= 3 ? MC_PT_POOL_STRICT_WAVES : NS <= 6 ? 4 : 3);
+    constexpr int kFast3 = 7;     // 72 VGPRs (6: 18.29 ms, 7: 18.11, 8: 18.68 at K2)
+    constexpr int kStrict3 = 6;   // 80 VGPRs (three values spilled, none reloaded inside an iteration), 6 blocks of 26 KB per CU
+    return Fast ? (NS <= 3 ? kFast3 : NS <= 5 ? 6 : NS <= 6 ? 5 : 4) : (NS <= 3 ? kStrict3 : NS <= 6 ? 4 : 3);
 }
 
 // Disjoint (fast math): the host proved the spheres pairwise disjoint — shadow rays are decided without square roots
@@ -109,20 +89,20 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     // (fast tier only.  The careful tier keeps the reference's order (b^2 - |c - x|^2) + r^2: of the identities of exact arithmetic fast
     // math does not execute, this one and the un-normalised directions are the two whose forked samples do not balance — more of them
     // lose radiance than gain it; with both in the reference's form gains and losses cancel: profiles/r05_fork_bias_identities.txt)
-    constexpr bool kOccR2 = Fast == 1 && MC_PT_FAST_OCC_MINUS_R2;
+    constexpr bool kOccR2 = Fast == 1;
     constexpr uint32_t TW = WaveTile<S>::w, TH = WaveTile<S>::h, Ring = 2u * (uint32_t)S, RRing = pool_result_batches<NS>() * (uint32_t)S;
     HotSlabN<NS> hot;
-    hot.template load<MC_PT_POOL_HOT_VGPR, MC_PT_POOL_HOT_W>(a.scene);   // (uniform operands: this kernel has no vector registers to spare for copies)
+    hot.template load<false, true>(a.scene);   // (uniform operands but W_pos: this kernel has no vector registers to spare for copies)
     // A lane's pixel (pix = lane / S of the wave tile) and slot of a batch (sub = lane % S) never change.  What derives from them
     // and is needed only now and then — the stash base, the tile row, the validity — is derived afresh from an opaque copy of
     // the thread id where it is used, so that it does not occupy registers across the bounce loop (80 VGPRs = 6 waves per SIMD).
     struct Lane { uint32_t lane, pix, sub, ty; bool valid; };
     auto my_lane = [&](bool with_row) {
         uint32_t tid = threadIdx.x;
-        // (LANE_REGS: the refill's lane and sub stay in registers — the fast and careful kernels have the room.  The strict kernel at its
-        //  80-register budget has not: kept "in registers" they were spilled, and the lanes-below-me mask was reloaded from scratch in
-        //  the stash pick-up of nearly every iteration; there they are re-derived from the thread index, two instructions.)
-        if (!(MC_PT_POOL_LANE_REGS && Fast != 0 && !with_row)) asm volatile("" : "+v"(tid));
+        // (The refill's lane and sub stay in registers — two instructions an iteration less; the fast and careful kernels have the room.
+        //  The strict kernel at its 80-register budget has not: kept "in registers" they were spilled, and the lanes-below-me mask was
+        //  reloaded from scratch in the stash pick-up of nearly every iteration; there they are re-derived from the thread index.)
+        if (Fast == 0 || with_row) asm volatile("" : "+v"(tid));
         Lane q;
         q.lane = tid & 63u; q.pix = q.lane / (uint32_t)S; q.sub = q.lane % (uint32_t)S;
         const uint32_t wave = tid >> 6;
@@ -136,7 +116,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     };
     // my pixel's coordinates (:349) stay: the RNG key of every bounce needs them; so does the base of its stash
     uint32_t gx, gy;
-    bool pixel_valid;         // my pixel lies in the image and in the tile (:348)
+    bool pixel_valid;         // my pixel lies in the image and in the tile (:348); kept as a lane mask, not re-derived per batch
     float* const gstash = lds_dyn + kPoolRecordFloats + (threadIdx.x >> 6) * pool_wave_lds_floats<Fast, NS>() +
                           ((threadIdx.x & 63u) / (uint32_t)S) * (Ring * kPoolEntryFloats);
     // strict: my pixel's result ring [3][RRing] (x, y, z planes) behind the wave's stash
@@ -235,7 +215,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
             // one more batch when a pixel wants more rays than it has — and every pixel's ring has room for S more
             if (want) {
                 MC_REGION(2);    // a batch of camera rays
-                const Lane g = my_lane(MC_PT_POOL_KEEP_VALID ? false : true);
+                const Lane g = my_lane(false);
                 const uint32_t samp = a.sample_begin + batch * (uint32_t)S + g.sub;
                 // (strict: the pixel coordinates as fresh values — otherwise float(gy) of :359 is hoisted out of the loop, and at this
                 //  kernel's register budget "out of the loop" meant spilled and reloaded from scratch at the end of every iteration)
@@ -252,7 +232,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 int cid = intersect_slab<Fast, (Fast != 0), kOccR2, 22>(hot, a.lc, crd, ct, false, occ0, oc0);
                 // nothing to trace: a pixel outside the tile, a sample beyond the range; a camera ray that misses everything (:369)
                 // gathers nothing either
-                if (!((MC_PT_POOL_KEEP_VALID ? pixel_valid : g.valid) && samp < a.sample_end)) cid = -1;
+                if (!(pixel_valid && samp < a.sample_end)) cid = -1;
                 if constexpr (!Fast) {   // such a sample's result is a zero (adding +0 changes no bit of the sum)
                     const uint32_t slot = (batch * (uint32_t)S + g.sub) % RRing;
                     if (cid < 0) { gres[slot] = 0.0f; gres[RRing + slot] = 0.0f; gres[2u * RRing + slot] = 0.0f; }
@@ -296,13 +276,12 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 for (int i = 0; i < NS; i++) { xcc[i] = occ[i]; if constexpr (kOccR2) occ[i] = occ[i] - hot.r2[i]; }
                 const float4* obj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);   // per-lane fetch
                 // (fast: past depth 5 the colour row is the one already divided by the roulette probability)
-                const float4 o0 = obj[0], o1 = obj[(Fast && MC_PT_FAST_COLOUR_OVER_P && key > krr) ? 3 : 1];
+                const float4 o0 = obj[0], o1 = obj[(Fast && key > krr) ? 3 : 1];
                 const bool is_sphere = id >= 6;
                 v3 geo{o0.x, o0.y, o0.z};
                 v3 col{o1.x, o1.y, o1.z};
                 const uint32_t mbits = dm::as_uint(o1.w);
                 const int mat = (int)(mbits & 255u);                              // :378/:384
-                const float p = o0.w;                                             // :394 (fast: its reciprocal)
 #ifdef MC_PT_REGION_STATS
                 if (is_sphere) MC_REGION(5);    // sphere normal
 #endif
@@ -323,8 +302,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 }
                 accmat = accmat * col;                                            // :392
                 const v3 rnd{rx, ry, 0.0f};                                       // :393 (drawn at the end of the previous bounce)
-                if constexpr (Fast) { if (!MC_PT_FAST_COLOUR_OVER_P) accmat = accmat * (key > krr ? p : 1.0f); }   // :395, :397 (:396 was decided there too)
-                else if (key > krr) accmat = divs_recip<Fast>(accmat, p, obj[2].w);
+                // :395, :397 (:396 was decided there too).  Strict: accmat / p, p = o0.w (:394).  Fast: o1 is the colour row divided by p
+                if constexpr (!Fast) { if (key > krr) accmat = divs_recip<Fast>(accmat, o0.w, obj[2].w); }
                 bool go = true;
                 {
                 ro = x;                                                           // :429, :434, :447
@@ -439,7 +418,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
 template <int Fast, int S, int NS> inline int launch_pool_one(const PTArgs& a, uint32_t tile_rows, hipStream_t s) {
     dim3 grid((a.W + block_w<S>() - 1u) / block_w<S>(), (tile_rows + block_h<S>() - 1u) / block_h<S>());
     constexpr size_t lds = pool_block_lds_bytes<Fast, NS>();
-    if (Fast && (!a.scene.spheres_disjoint || MC_PT_FAST_NO_DISJOINT)) hipLaunchKernelGGL((pathtrace_pool_kernel<Fast, S, NS, false>), grid, dim3(256), lds, s, a);
+    if (Fast && !a.scene.spheres_disjoint) hipLaunchKernelGGL((pathtrace_pool_kernel<Fast, S, NS, false>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((pathtrace_pool_kernel<Fast, S, NS, true>), grid, dim3(256), lds, s, a);
     return MC_OK;
 }
