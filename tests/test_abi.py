@@ -392,6 +392,64 @@ def test_fast_math_guard_classification_and_kernel_query(B, O):
         B.pathtrace_select_kernel(q)
 
 
+def _lattice_of_spheres(n):
+    """n small diffuse spheres on a 16^3 lattice inside the reference room (0.25 apart, r = 0.02), the first one a light."""
+    g = np.arange(16, dtype=np.float32) * np.float32(0.25) - np.float32(1.9)
+    s = np.zeros((n, 12), np.float32)
+    s[:, 0:3] = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)[:n]
+    s[:, 3] = 0.02; s[:, 8:11] = 0.5; s[:, 11] = 1.0; s[0, 4:7] = 20.0
+    return s
+
+
+def test_kernel_choice_decision_table(B):
+    """mc_pathtrace_select_kernel over a table of requests at K2 (900 x 600 x 500) — the choice the host makes from the request and
+    the scene alone: (kernel, lanes per pixel, math mode that runs, launches)."""
+    P, S = B.default_scene()
+    P, S = np.float32(P).reshape(6, 12), np.float32(S).reshape(-1, 12)
+    GEN, SLAB, BOX, POOL, MEM = (B.PT_KERNEL_GENERIC, B.PT_KERNEL_SLAB, B.PT_KERNEL_BOX, B.PT_KERNEL_POOL,
+                                 B.PT_KERNEL_GENERIC_MEMORY)
+    STRICT, FAST, CAREFUL = B.PT_MATH_STRICT, B.PT_MATH_FAST, B.PT_MATH_FAST_CAREFUL
+    glass_wall = P.copy(); glass_wall[4, 11] = 3.0
+    tilt = P.copy(); tilt[2, :3] = (0.0, 0.99, 0.14)                                  # a generic scene of 9 objects
+    five = np.concatenate([S, S[:2] + np.float32([0, 0, 2.2] + [0] * 9)])
+    enclosed = (np.float32(ENCLOSED_LIGHT_PLANES), np.float32(ENCLOSED_LIGHT_SPHERES))
+    table = [   # (request, scene or None for the reference scene, expected)
+        (dict(math_mode=STRICT), None, (POOL, 16, STRICT, 1)),
+        (dict(math_mode=FAST), None, (POOL, 16, FAST, 1)),
+        (dict(math_mode=CAREFUL), None, (POOL, 16, CAREFUL, 1)),
+        (dict(math_mode=FAST, flags=B.PT_NO_POOL_KERNEL), None, (BOX, 16, FAST, 2)),          # 500 = 31 x 16 + 4
+        (dict(math_mode=STRICT, flags=B.PT_NO_POOL_KERNEL), None, (SLAB, 16, STRICT, 2)),
+        (dict(math_mode=FAST, flags=B.PT_NO_BOX_KERNEL), None, (SLAB, 16, FAST, 2)),
+        (dict(math_mode=FAST, flags=B.PT_GENERIC_KERNEL), None, (GEN, 16, FAST, 2)),
+        (dict(math_mode=FAST, flags=B.pt_force_s(4)), None, (BOX, 4, FAST, 1)),
+        (dict(math_mode=FAST, row_begin=1), None, (BOX, 16, FAST, 2)),                        # wave tiles unaligned: not the pool
+        (dict(math_mode=STRICT, row_begin=1), None, (POOL, 16, STRICT, 1)),                   # (strict adds in sample order)
+        (dict(math_mode=FAST, max_depth=0), None, (BOX, 16, FAST, 2)),
+        (dict(math_mode=FAST, max_depth=65), None, (SLAB, 16, FAST, 2)),                      # no emit_skip_ok, so no box
+        (dict(math_mode=FAST, flags=B.PT_NO_FAST_GUARD), (glass_wall, S), (SLAB, 16, FAST, 2)),
+        (dict(math_mode=STRICT), (glass_wall, S), (SLAB, 16, STRICT, 2)),
+        (dict(math_mode=STRICT, flags=B.pt_precision(1), sample_end=499), None, (GEN, 16, STRICT, 1)),
+        (dict(math_mode=FAST, flags=B.pt_precision(2), sample_begin=3, sample_end=13), None, (GEN, 1, FAST, 1)),
+        (dict(math_mode=STRICT, flags=B.pt_precision(3) | B.pt_force_s(4), sample_end=17), None, (GEN, 16, STRICT, 1)),
+        (dict(math_mode=FAST), (P, _lattice_of_spheres(700)), (GEN, 16, CAREFUL, 2)),
+        (dict(math_mode=FAST), (P, _lattice_of_spheres(3500)), (MEM, 16, CAREFUL, 2)),
+        (dict(math_mode=FAST, flags=B.PT_SCENE_IN_LDS), (tilt, S), (GEN, 16, FAST, 2)),
+        (dict(math_mode=FAST, flags=B.PT_SCENE_IN_MEMORY), (tilt, S), (MEM, 16, FAST, 2)),
+        (dict(math_mode=FAST), enclosed, (POOL, 16, STRICT, 1)),
+        (dict(math_mode=FAST), (P, five), (POOL, 16, CAREFUL, 1)),
+        (dict(math_mode=FAST, flags=B.PT_NO_FAST_GUARD), (P, five), (POOL, 16, FAST, 1)),
+    ]
+    for kw, scene, want in table:
+        k = B.pathtrace_select_kernel(B.pathtrace_params(900, 600, 500, **kw), *(scene or (P, S)))
+        assert (k.kernel, k.lanes_per_pixel, k.math_mode, k.launches) == want, (kw, want)
+    # beyond the LDS-resident scene store: refused when forced into LDS or given an extended-precision sphere test
+    big = _lattice_of_spheres(3500)
+    for flags in (B.PT_SCENE_IN_LDS, B.pt_precision(1)):
+        with pytest.raises(B.McError, match="exceeds the LDS-resident scene store") as e:
+            B.pathtrace_select_kernel(B.pathtrace_params(900, 600, 500, flags=flags), P, big)
+        assert e.value.status == 5   # MC_ERR_UNSUPPORTED
+
+
 def test_apps_reject_values_they_do_not_know(B, tmp_path):
     """VERDICT r5 item 4 (host/main.cpp): `--math` takes strict | fast | careful — anything else (a typo, a mode of another tool) ends the
     run with EXIT_FAILURE before a device is touched, instead of silently rendering strict; the same for --precision,

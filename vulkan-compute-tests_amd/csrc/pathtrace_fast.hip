@@ -25,14 +25,7 @@
 #include "pathtrace_kernel.h"
 #include "pathtrace_pool.h"
 
-namespace mc {
-namespace pt {
-int launch_fast(const PTArgs& a, int variant, int S, int prec, uint32_t tile_rows, hipStream_t s) {
-    if (variant == 4) return launch_pool<1>(a, S, tile_rows, s);
-    return launch_impl<1>(a, variant, S, prec, tile_rows, s);
-}
-}  // namespace pt
-}  // namespace mc
+template int mc::pt::launch_tier<1>(const mc::pt::PTArgs&, int, int, int, uint32_t, hipStream_t);
 
 #ifdef MC_PT_REGION_STATS
 // Diagnostic build (make stats): read and reset the per-region execution / active-lane counters — of all three tiers' kernels.

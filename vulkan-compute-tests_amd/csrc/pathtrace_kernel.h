@@ -31,6 +31,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 #include "mc_internal.h"
 #include "ds_arith.h"
@@ -1022,15 +1024,11 @@ __global__ void __launch_bounds__(256, (rounds_waves<Fast, Slab, NS>())) pathtra
     if (valid && j == 0) a.out[idx] = acc;
 }
 
-// Launch helpers implemented once per math mode (pathtrace_fast.hip / pathtrace_strict.hip).
-// variant: 0 = generic (run-time object counts), 1 = slab-specialised 6 planes + 3 spheres.
-// prec: 0 = fp32 sphere test (the reference's default build); 1/2/3 = native fp64 / DS / DF64 branch (generic kernel,
-// S in {1,16} only).
-// variant 4 = the sample-pool kernels (pathtrace_pool.h; closed-box slab scenes), variant 5 = generic, scene read from memory.
-// variant 3 = the closed-box fast kernel (slab scenes with SceneArgs::box_ok, fast math only).
-int launch_fast(const PTArgs& a, int variant, int S, int prec, uint32_t tile_rows, hipStream_t s);
-int launch_careful(const PTArgs& a, int variant, int S, int prec, uint32_t tile_rows, hipStream_t s);   // pathtrace_careful.hip: tier 2
-int launch_strict(const PTArgs& a, int variant, int S, int prec, uint32_t tile_rows, hipStream_t s);
+// The launcher of one tier, Fast = the MC_PT_MATH_* value that runs (0 strict, 1 fast, 2 careful): defined in pathtrace_pool.h and
+// instantiated once by the tier's own translation unit (pathtrace_strict.hip / pathtrace_fast.hip / pathtrace_careful.hip), so that the
+// kernels are compiled under that unit's floating-point settings.  kernel: MC_PT_KERNEL_*, chosen on the host (pathtrace.hip).
+// prec: 0 = fp32 sphere test (the reference's default build); 1/2/3 = native fp64 / DS / DF64 branch (generic kernel, S in {1,16} only).
+template <int Fast> int launch_tier(const PTArgs& a, int kernel, int S, int prec, uint32_t tile_rows, hipStream_t s);
 
 inline size_t scene_lds_bytes(const PTArgs& a) {
     return ((size_t)(a.scene.n_planes + a.scene.n_spheres) * 12u + a.scene.n_emissive) * sizeof(float);
@@ -1057,57 +1055,22 @@ inline int launch_one(const PTArgs& a, uint32_t tile_rows, hipStream_t s) {
     return MC_OK;
 }
 
-// The slab kernels (6 axis-aligned planes + NS spheres, NS = 1 .. kMaxSlabSpheres: one instantiation per count, the sphere loops
-// unrolled over VGPR-resident centres) at width S.
-template <int Fast, bool Box, int NS>
-inline int launch_slab_width(const PTArgs& a, int S, uint32_t tile_rows, hipStream_t s) {
-    if (S == 1) return launch_one<Fast, 6, NS, true, 1, 0, Box>(a, tile_rows, s);
-    if (S == 4) return launch_one<Fast, 6, NS, true, 4, 0, Box>(a, tile_rows, s);
-    if (S == 16) return launch_one<Fast, 6, NS, true, 16, 0, Box>(a, tile_rows, s);
-    return MC_ERR_INVALID_ARGUMENT;
+// Run-time value -> compile-time constant: f(std::integral_constant<int, V>{}) for the V of Vs equal to v; any other value is refused.
+template <int... Vs, class F> inline int dispatch(int v, F&& f) {
+    int rc = MC_ERR_INVALID_ARGUMENT;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
 }
+// ... over the sphere counts of the slab scenes, 1 .. kMaxSlabSpheres: one instantiation per count, the sphere loops unrolled
+template <class F, int... I> inline int dispatch_seq(int v, F&& f, std::integer_sequence<int, I...>) { return dispatch<(I + 1)...>(v, f); }
+template <class F> inline int dispatch_spheres(uint32_t n, F&& f) { return dispatch_seq((int)n, f, std::make_integer_sequence<int, kMaxSlabSpheres>{}); }
+
+// The slab kernels (6 axis-aligned planes + NS spheres, the centres VGPR-resident) at width S.
 template <int Fast, bool Box>
 inline int launch_slab(const PTArgs& a, int S, uint32_t tile_rows, hipStream_t s) {
-    switch (a.scene.n_spheres) {
-        case 1: return launch_slab_width<Fast, Box, 1>(a, S, tile_rows, s);
-        case 2: return launch_slab_width<Fast, Box, 2>(a, S, tile_rows, s);
-        case 3: return launch_slab_width<Fast, Box, 3>(a, S, tile_rows, s);
-        case 4: return launch_slab_width<Fast, Box, 4>(a, S, tile_rows, s);
-        case 5: return launch_slab_width<Fast, Box, 5>(a, S, tile_rows, s);
-        case 6: return launch_slab_width<Fast, Box, 6>(a, S, tile_rows, s);
-        case 7: return launch_slab_width<Fast, Box, 7>(a, S, tile_rows, s);
-        case 8: return launch_slab_width<Fast, Box, 8>(a, S, tile_rows, s);
-        default: return MC_ERR_INVALID_ARGUMENT;
-    }
-}
-
-template <int Fast>
-inline int launch_impl(const PTArgs& a, int variant, int S, int prec, uint32_t tile_rows, hipStream_t s) {
-    if (prec == 0) {
-        if constexpr (Fast) {
-            if (variant == 3) return launch_slab<Fast, true>(a, S, tile_rows, s);
-        }
-        if (variant == 3) return MC_ERR_INVALID_ARGUMENT;
-        if (variant == 1) {
-            return launch_slab<Fast, false>(a, S, tile_rows, s);
-        } else if (variant == 5) {   // generic, scene read from memory
-            if (S == 1) return launch_one<Fast, -2, -2, false, 1, 0>(a, tile_rows, s);
-            if (S == 4) return launch_one<Fast, -2, -2, false, 4, 0>(a, tile_rows, s);
-            if (S == 16) return launch_one<Fast, -2, -2, false, 16, 0>(a, tile_rows, s);
-        } else {
-            if (S == 1) return launch_one<Fast, -1, -1, false, 1, 0>(a, tile_rows, s);
-            if (S == 4) return launch_one<Fast, -1, -1, false, 4, 0>(a, tile_rows, s);
-            if (S == 16) return launch_one<Fast, -1, -1, false, 16, 0>(a, tile_rows, s);
-        }
-        return MC_ERR_INVALID_ARGUMENT;
-    }
-    if (S != 1 && S != 16) return MC_ERR_INVALID_ARGUMENT;
-    switch (prec) {
-        case 1: return S == 1 ? launch_one<Fast, -1, -1, false, 1, 1>(a, tile_rows, s) : launch_one<Fast, -1, -1, false, 16, 1>(a, tile_rows, s);
-        case 2: return S == 1 ? launch_one<Fast, -1, -1, false, 1, 2>(a, tile_rows, s) : launch_one<Fast, -1, -1, false, 16, 2>(a, tile_rows, s);
-        case 3: return S == 1 ? launch_one<Fast, -1, -1, false, 1, 3>(a, tile_rows, s) : launch_one<Fast, -1, -1, false, 16, 3>(a, tile_rows, s);
-        default: return MC_ERR_INVALID_ARGUMENT;
-    }
+    return dispatch_spheres(a.scene.n_spheres, [&](auto NS) {
+        return dispatch<1, 4, 16>(S, [&](auto W) { return launch_one<Fast, 6, NS, true, W, 0, Box>(a, tile_rows, s); });
+    });
 }
 
 }  // namespace pt

@@ -422,20 +422,27 @@ template <int Fast, int S, int NS> inline int launch_pool_one(const PTArgs& a, u
     else hipLaunchKernelGGL((pathtrace_pool_kernel<Fast, S, NS, true>), grid, dim3(256), lds, s, a);
     return MC_OK;
 }
-// variant 4 of launch_fast / launch_strict: 16 lanes per pixel and batch (the host never passes anything else); one instantiation
-// per sphere count 1 .. kMaxSlabSpheres
+// MC_PT_KERNEL_POOL: 16 lanes per pixel and batch (the host never passes anything else); one instantiation per sphere count
 template <int Fast> inline int launch_pool(const PTArgs& a, int S, uint32_t tile_rows, hipStream_t s) {
     if (S != 16) return MC_ERR_INVALID_ARGUMENT;
-    switch (a.scene.n_spheres) {
-        case 1: return launch_pool_one<Fast, 16, 1>(a, tile_rows, s);
-        case 2: return launch_pool_one<Fast, 16, 2>(a, tile_rows, s);
-        case 3: return launch_pool_one<Fast, 16, 3>(a, tile_rows, s);
-        case 4: return launch_pool_one<Fast, 16, 4>(a, tile_rows, s);
-        case 5: return launch_pool_one<Fast, 16, 5>(a, tile_rows, s);
-        case 6: return launch_pool_one<Fast, 16, 6>(a, tile_rows, s);
-        case 7: return launch_pool_one<Fast, 16, 7>(a, tile_rows, s);
-        case 8: return launch_pool_one<Fast, 16, 8>(a, tile_rows, s);
-        default: return MC_ERR_INVALID_ARGUMENT;
+    return dispatch_spheres(a.scene.n_spheres, [&](auto NS) { return launch_pool_one<Fast, 16, NS>(a, tile_rows, s); });
+}
+
+// One tier's launcher (declared in pathtrace_kernel.h; instantiated by pathtrace_strict.hip / pathtrace_fast.hip / pathtrace_careful.hip).
+template <int Fast> int launch_tier(const PTArgs& a, int kernel, int S, int prec, uint32_t tile_rows, hipStream_t s) {
+    if (kernel == MC_PT_KERNEL_POOL) return launch_pool<Fast>(a, S, tile_rows, s);
+    if (prec != 0)   // the extended-precision sphere tests: generic kernel, S = 1 or 16
+        return dispatch<1, 2, 3>(prec, [&](auto P) {
+            return dispatch<1, 16>(S, [&](auto W) { return launch_one<Fast, -1, -1, false, W, P>(a, tile_rows, s); });
+        });
+    switch (kernel) {
+        case MC_PT_KERNEL_BOX:   // (fast math only)
+            if constexpr (Fast != 0) return launch_slab<Fast, true>(a, S, tile_rows, s);
+            return MC_ERR_INVALID_ARGUMENT;
+        case MC_PT_KERNEL_SLAB: return launch_slab<Fast, false>(a, S, tile_rows, s);
+        case MC_PT_KERNEL_GENERIC_MEMORY:
+            return dispatch<1, 4, 16>(S, [&](auto W) { return launch_one<Fast, -2, -2, false, W, 0>(a, tile_rows, s); });
+        default: return dispatch<1, 4, 16>(S, [&](auto W) { return launch_one<Fast, -1, -1, false, W, 0>(a, tile_rows, s); });
     }
 }
 
