@@ -78,8 +78,9 @@ int mc_host_free(void* ptr);
 
 /* Device time of the LAST blocking host-buffer call on this context (mc_mandelbrot_render, mc_pathtrace_render, mc_*_render_rgba8):
  * kernel_ms = first launch to last kernel end (render, and the on-device conversion of the _rgba8 forms), copy_ms = the device -> host
- * copy that follows.  HIP events on the context's stream; either pointer may be NULL.  MC_ERR_INVALID_ARGUMENT before the first such
- * call.  (The reference times nothing, vulkanComputeApp.cpp:451-466 only prints progress; the apps print these next to run().) */
+ * copy that follows.  Measured with HIP events on the context's stream and recorded by the call itself once its stream is idle: this one
+ * only reads the record, and a call that fails after its launch clears it.  Either pointer may be NULL.  MC_ERR_INVALID_ARGUMENT before
+ * the first such call.  (The reference times nothing, vulkanComputeApp.cpp:451-466 only prints progress; the apps print these next to run().) */
 int mc_context_last_timing(mc_context* ctx, double* kernel_ms, double* copy_ms);
 
 /* Shader clock (MHz) the device holds with every SIMD busy on fp32 VALU work, measured in-kernel (s_memtime against the

@@ -62,13 +62,13 @@ struct mc_context {
     mc::DeviceBuffer status;
     int ensure_status();
     int check_status();   // call after the stream is idle: MC_OK, or MC_ERR_HIP with a detail message
-    // The blocking host-buffer entry points bracket their kernel launches and their device -> host copy with events on the context's
-    // stream (mc_context_last_timing): t[0] before the first launch, t[1] after the last kernel, t[2] after the copy.
+    // The device time of the last blocking host-buffer call (mc_context_last_timing, which only reads it).  Each such call clears it
+    // before its first launch and fills it once its stream is idle, from events on the context's stream: t[0] before the first launch,
+    // t[1] after the last kernel, t[2] after the copy (the banded render: t[0] and its band events).
+    struct Timing { bool valid = false; double kernel_ms = 0.0, copy_ms = 0.0; } timing;
     hipEvent_t t_ev[3] = {nullptr, nullptr, nullptr};
-    bool timing_valid = false;
-    bool banded_timing = false;          // the last blocking call was mc_mandelbrot_render_banded: its own two figures below
-    double banded_kernel_ms = 0.0, banded_copy_ms = 0.0;
-    int mark(int k);      // records t_ev[k] on the context's stream (creating the events on first use)
+    int create_events();  // t_ev, on first use (the warm-ups make them ahead of the first render)
+    int mark(int k);      // records t_ev[k] on the context's stream
 };
 
 namespace mc {
@@ -116,6 +116,10 @@ inline uint32_t tile_rows(uint32_t row_begin, uint32_t row_end, uint32_t B, uint
 // tile-local rows map to storage rows one by one (tile_row_to_storage).
 constexpr uint32_t kRowBlock = 8;
 
-inline hipStream_t pick_stream(mc_context* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+// A request's rows: at least one, in a non-empty image (row_begin < row_end <= height, width > 0); or exactly the whole image.
+template <class Params>
+bool rows_ok(const Params* p) { return p->width && p->row_begin < p->row_end && p->row_end <= p->height; }
+template <class Params>
+bool whole_image(const Params* p) { return p->row_begin == 0 && p->row_end == p->height && !p->row_stride; }
 
 }  // namespace mc

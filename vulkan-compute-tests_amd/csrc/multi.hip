@@ -126,24 +126,30 @@ static int gather_tiles(mc_multi* m, std::vector<DeviceBuffer>& tiles, DeviceBuf
     return MC_OK;
 }
 
-// Gathers the tiles of a bpp-byte-per-pixel plane to device 0 and de-interleaves them into `full`.
-static int gather_and_assemble(mc_multi* m, std::vector<DeviceBuffer>& tiles, DeviceBuffer& gathered, DeviceBuffer& full,
-                               uint32_t W, uint32_t H, uint32_t tile_rows_padded, uint32_t bpp) {
-    int rc;
-    if ((rc = gather_tiles(m, tiles, gathered, (size_t)tile_rows_padded * W * bpp))) return rc;
-    mc_context* c0 = m->ctx[0];
-    if ((rc = full.reserve((size_t)W * H * bpp))) return rc;
-    if (m->n == 1) {   // one tile = the image in storage order already: no row shuffle, any width
-        MC_HIP_TRY(hipMemcpyAsync(full.ptr, gathered.ptr, (size_t)W * H * bpp, hipMemcpyDeviceToDevice, c0->stream));
-        return MC_OK;
-    }
-    return deinterleave_rows_launch(c0, gathered.ptr, W, H, (uint32_t)m->n, kRowBlock, tile_rows_padded, bpp, full.ptr,
-                                    c0->stream);
-}
-
 static uint32_t padded_tile_rows(uint32_t H, int n) {
     // rank 0 always owns the most rows
     return tile_rows(0, H, kRowBlock, kRowBlock * (uint32_t)n);
+}
+
+// Rank i's share q of a whole-image request: row blocks i, i + n, i + 2n, ... of kRowBlock rows (sharding.shard).  False for a rank
+// past the last block (more GPUs than row blocks): it owns no rows.
+template <class Params>
+static bool rank_share(const Params* p, int i, int n, Params& q) {
+    q = *p;
+    q.row_begin = (uint32_t)i * kRowBlock; q.row_end = p->height;
+    q.row_block = kRowBlock; q.row_stride = kRowBlock * (uint32_t)n;
+    return q.row_begin < p->height;
+}
+
+// Every rank's stream idle; `check`: and its status word read (a pool kernel's tripped scheduling bound: never a silent partial image).
+static int synchronize_all(mc_multi* m, bool check) {
+    int rc;
+    for (int i = 0; i < m->n; i++) {
+        MC_HIP_TRY(hipSetDevice(m->ctx[i]->device));
+        MC_HIP_TRY(hipStreamSynchronize(m->ctx[i]->stream));
+        if (check && (rc = m->ctx[i]->check_status())) return rc;
+    }
+    return MC_OK;
 }
 
 }  // namespace mc
@@ -220,7 +226,7 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
                             uint8_t* out_rgba8) {
     if (!m || !p || (!out_rgba_f32 && !out_iters && !out_rgba8)) return MC_ERR_INVALID_ARGUMENT;
     const bool want_rgba = out_rgba_f32 || out_rgba8;
-    if (p->row_begin != 0 || p->row_end != p->height || p->row_stride) return MC_ERR_INVALID_ARGUMENT;   // whole image only
+    if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;
     const uint32_t W = p->width, H = p->height;
     const uint32_t padded = padded_tile_rows(H, m->n);
     // The exchange carries ITERATION COUNTS — 2 B/pixel (max_iter <= 65535) or 4 — never the 16-B vec4: the colour is a function
@@ -233,11 +239,9 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
         mc_context* c = m->ctx[i];
         MC_HIP_TRY(hipSetDevice(c->device));
         if ((rc = m->tile_iters[i].reserve((size_t)padded * W * ib))) return rc;
-        mc_mandelbrot_params q = *p;
-        q.row_begin = (uint32_t)i * kRowBlock; q.row_end = H;
-        q.row_block = kRowBlock; q.row_stride = kRowBlock * (uint32_t)m->n;
+        mc_mandelbrot_params q;
+        if (!rank_share(p, i, m->n, q)) continue;
         q.flags = narrow ? (p->flags | MC_MANDEL_ITERS_U16) : (p->flags & ~(uint32_t)MC_MANDEL_ITERS_U16);
-        if (q.row_begin >= H) continue;   // more GPUs than row blocks
         rc = mandelbrot_launch(c, &q, nullptr, m->tile_iters[i].ptr, c->stream);
         if (rc) return rc;
     }
@@ -257,11 +261,7 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
     }
     if (out_iters)
         MC_HIP_TRY(hipMemcpyAsync(out_iters, m->full_iters.ptr, (size_t)W * H * 4, hipMemcpyDeviceToHost, c0->stream));
-    for (int i = 0; i < m->n; i++) {
-        MC_HIP_TRY(hipSetDevice(m->ctx[i]->device));
-        MC_HIP_TRY(hipStreamSynchronize(m->ctx[i]->stream));
-    }
-    return MC_OK;
+    return synchronize_all(m, false);
 }
 
 int mc_multi_mandelbrot_render(mc_multi* m, const mc_mandelbrot_params* p, float* out_rgba_f32, uint32_t* out_iters) {
@@ -276,7 +276,7 @@ int mc_multi_mandelbrot_render_rgba8(mc_multi* m, const mc_mandelbrot_params* p,
 static int multi_pathtrace(mc_multi* m, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes,
                            const float* spheres, uint32_t n_spheres, float* out_rgba_f32, uint8_t* out_rgba8) {
     if (!m || !p || (!out_rgba_f32 && !out_rgba8)) return MC_ERR_INVALID_ARGUMENT;
-    if (p->row_begin != 0 || p->row_end != p->height || p->row_stride) return MC_ERR_INVALID_ARGUMENT;
+    if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;
     if (p->sample_begin != 0) return MC_ERR_UNSUPPORTED;   // progressive continuation: single-GPU entry points
     // the RGBA8 form converts a FINISHED render (:453 applied): refused before anything is launched on any device
     if (out_rgba8 && p->sample_end != p->spp) return MC_ERR_INVALID_ARGUMENT;
@@ -288,10 +288,8 @@ static int multi_pathtrace(mc_multi* m, const mc_pathtrace_params* p, const floa
         MC_HIP_TRY(hipSetDevice(c->device));
         if ((rc = m->tile_rgba[i].reserve((size_t)padded * W * 16))) return rc;
         if (out_rgba8 && (rc = m->tile_u8[i].reserve((size_t)padded * W * 4))) return rc;
-        mc_pathtrace_params q = *p;
-        q.row_begin = (uint32_t)i * kRowBlock; q.row_end = H;
-        q.row_block = kRowBlock; q.row_stride = kRowBlock * (uint32_t)m->n;
-        if (q.row_begin >= H) continue;
+        mc_pathtrace_params q;
+        if (!rank_share(p, i, m->n, q)) continue;
         rc = pathtrace_launch(c, &q, planes, n_planes, spheres, n_spheres, m->tile_rgba[i].ptr, c->stream);
         if (rc) return rc;
         // RGBA8 form: every device converts ITS tile (pathtracerApp.h:212-219, scale 1; tile rows in tile order, no rotation yet), so
@@ -301,8 +299,13 @@ static int multi_pathtrace(mc_multi* m, const mc_pathtrace_params* p, const floa
             return rc;
     }
     mc_context* c0 = m->ctx[0];
-    if (out_rgba_f32) {
-        if ((rc = gather_and_assemble(m, m->tile_rgba, m->gather_rgba, m->full_rgba, W, H, padded, 16))) return rc;
+    if (out_rgba_f32) {   // the fp32 tiles gathered to device 0 and de-interleaved there
+        if ((rc = gather_tiles(m, m->tile_rgba, m->gather_rgba, (size_t)padded * W * 16))) return rc;
+        if ((rc = m->full_rgba.reserve((size_t)W * H * 16))) return rc;
+        if (m->n == 1)   // one tile = the image in storage order already: no row shuffle, any width
+            MC_HIP_TRY(hipMemcpyAsync(m->full_rgba.ptr, m->gather_rgba.ptr, (size_t)W * H * 16, hipMemcpyDeviceToDevice, c0->stream));
+        else if ((rc = deinterleave_rows_launch(c0, m->gather_rgba.ptr, W, H, (uint32_t)m->n, kRowBlock, padded, 16, m->full_rgba.ptr, c0->stream)))
+            return rc;
         MC_HIP_TRY(hipMemcpyAsync(out_rgba_f32, m->full_rgba.ptr, (size_t)W * H * 16, hipMemcpyDeviceToHost, c0->stream));
     }
     if (out_rgba8) {   // the byte tiles gathered to device 0, de-interleaved and point-reflected there (pathtracerApp.h:236-243) in one pass
@@ -311,12 +314,7 @@ static int multi_pathtrace(mc_multi* m, const mc_pathtrace_params* p, const floa
         if ((rc = assemble_rgba8_launch(c0, m->gather_u8.ptr, W, H, (uint32_t)m->n, kRowBlock, padded, 1, m->full_u8.ptr, c0->stream))) return rc;
         MC_HIP_TRY(hipMemcpyAsync(out_rgba8, m->full_u8.ptr, (size_t)W * H * 4, hipMemcpyDeviceToHost, c0->stream));
     }
-    for (int i = 0; i < m->n; i++) {
-        MC_HIP_TRY(hipSetDevice(m->ctx[i]->device));
-        MC_HIP_TRY(hipStreamSynchronize(m->ctx[i]->stream));
-        if ((rc = m->ctx[i]->check_status())) return rc;   // a pool kernel's tripped scheduling bound: never a silent partial image
-    }
-    return MC_OK;
+    return synchronize_all(m, true);
 }
 
 int mc_multi_pathtrace_render(mc_multi* m, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes,

@@ -62,9 +62,9 @@ void ComputeApp::init() {
             printf("using device %d: %s (%d CUs)\n", deviceIndex, name, cus);
         }
         if (overlapStart)   // the code object, tables and device scratch of the request run() will make, while the caller goes on
-            warmThread = std::thread([this] {
+            warmThread = std::thread([this, call = warmupCall()] {
                 auto t0 = std::chrono::steady_clock::now();
-                warmStatus = warmup();
+                warmStatus = call();
                 if (warmStatus != MC_OK) { const char* d = mc_last_error_detail(); warmError = d ? d : ""; }
                 times.warmupMs = msSince(t0);
             });
@@ -124,8 +124,31 @@ void ComputeApp::run() {
     if (!quiet) { printf("run() finished in %.3f ms\n", lastRunMs); fflush(stdout); }
 }
 
-std::string ComputeApp::writePngFromStorage(const char* filename, uint32_t w, uint32_t h, float scale, bool rotate180) const {
-    return pngwriter::encodeStorageFile(filename, buffer.data(), w, h, scale, rotate180, pngThreads);
+void ComputeApp::saveImage(const char* filename, uint32_t w, uint32_t h, float scale, bool rotate180, bool announceAfterConvert) {
+    const bool streamed = progressive.active(), fused = !streamed && !gpuPostprocess && !referencePng;
+    if (streamed || fused || !announceAfterConvert) printf("writing %s\n", filename);
+    auto t0 = std::chrono::steady_clock::now();
+    std::string err;
+    times.convertMs = 0.0;
+    if (streamed) {
+        std::vector<uint8_t> png;
+        err = progressive.finish(png);
+        times.pngJoinMs = progressive.lastJoinMs(); times.pngAssembleMs = progressive.lastAssembleMs();
+        auto tw = std::chrono::steady_clock::now();
+        if (err.empty()) err = pngwriter::writeFile(filename, png);
+        times.pngWriteMs = msSince(tw);
+    } else if (fused) {
+        err = pngwriter::encodeStorageFile(filename, buffer.data(), w, h, scale, rotate180, pngThreads);
+    } else {
+        std::vector<uint8_t> image;
+        if (!gpuPostprocess) convertStorage(image, w, h, scale, rotate180);
+        times.convertMs = msSince(t0);
+        t0 = std::chrono::steady_clock::now();
+        if (announceAfterConvert) printf("writing %s\n", filename);
+        err = writePng(filename, gpuPostprocess ? rgba8.bytes() : image.data(), w, h);
+    }
+    if (!err.empty()) printf("encoder error: %s", err.c_str());   // printed, not thrown (mandelbrotApp.h:183)
+    times.pngMs = msSince(t0);
 }
 
 std::string ComputeApp::writePng(const char* filename, const uint8_t* rgba8, uint32_t w, uint32_t h) const {

@@ -14,6 +14,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -77,7 +78,8 @@ struct ComputeApp {
     // Cold-start hiding, on by default, switchable for measurements:
     //   overlapStart   init() hands mc_context_warmup_* to a helper thread as soon as the context exists (joined before run() touches
     //                  the context): the kernel family's code object, tables and device scratch are ready when run() launches, and
-    //                  the helper works while the caller allocates its storage buffer in preRun();
+    //                  the helper works while the caller allocates its storage buffer in preRun().  The call carries its own copy of
+    //                  the request (warmupCall(), built on the calling thread): the helper reads nothing run() writes;
     //   false          the round-5 order: the first launch, with everything it drags in, inside run().
     void setOverlapStart(bool o) { overlapStart = o; }
     // Streamed save (round 6, the Mandelbrot app; the caller says beforehand that the image WILL be saved — main.cpp does): run() renders
@@ -95,11 +97,6 @@ struct ComputeApp {
     // third-party codec (lodepng::encode, mandelbrotApp.h:181 / pathtracerApp.h:245): a reference tree that calls this library
     // (INTEGRATION.md route B) keeps that call and therefore its exact bytes; the standalone apps do not re-implement that codec.
     std::string writePng(const char* filename, const uint8_t* rgba8, uint32_t w, uint32_t h) const;
-    // The storage-buffer route's saveRenderedImage in one pass (round 6): the stripe workers of the PNG writer convert the rows they
-    // filter, so the RGBA8 intermediate image is never materialised; --reference-png needs that image (lodepng::encode takes it) and
-    // goes the two-step way.  Same file bytes as convertStorage + writePng.
-    bool fusedSave() const { return !gpuPostprocess && !referencePng; }
-    std::string writePngFromStorage(const char* filename, uint32_t w, uint32_t h, float scale, bool rotate180) const;
     double lastRunMilliseconds() const { return lastRunMs; }
     // Where the time of the last run() / saveRenderedImage() went (milliseconds; SURVEY §8d "end-to-end ... reported separately"):
     // device time of the kernels and of the device -> host copy (mc_context_last_timing; 0 for multi-GPU runs), the host
@@ -116,11 +113,19 @@ protected:
     void createBuffer(uint64_t bufferSizeBytes);   // vulkanComputeApp.cpp:489-533: the output storage buffer (gpuPostprocess: a quarter
                                                    // of it, for the RGBA8 image)
     void waitWarmup();                             // before the first call on ctx after init(): joins the warm-up helper
-    // First statement of every derived destructor: the helper calls the derived class's warmup(), which reads the derived object's scene
-    // tables and parameters — an object torn down before run() (preRun() threw) must not release them under the helper's feet.
-    void joinWarmupQuietly() noexcept { if (warmThread.joinable()) warmThread.join(); }
-    virtual int warmup() { return MC_OK; }                // apps: mc_context_warmup_* for the request run() will make (helper thread)
+    // Apps: mc_context_warmup_* for the request run() will make, bound to copies of everything it reads.  Called by init() on the
+    // calling thread; the helper thread runs what it returns.
+    virtual std::function<int()> warmupCall() const { return [] { return MC_OK; }; }
     static void check(int status, const char* what);
+    // saveRenderedImage's routes, with the app's conversion (mandelbrotApp.h:159-174 scale 255; pathtracerApp.h:202-243 scale 1 and the
+    // 180-degree rotation):
+    //   streamed   run() handed the bands to the PNG workers (streaming()): wait for the last stripes, write the file;
+    //   fused      the storage buffer in one pass (round 6): the PNG writer's stripe workers convert the rows they filter, so the RGBA8
+    //              image is never materialised.  Same file bytes as the two-step route;
+    //   two-step   getRenderedImage's conversion (convertStorage; --gpu-postprocess: done on the device), then the encoder
+    //              (writePng): --reference-png needs the RGBA8 image, lodepng::encode takes it.
+    // The path tracer announces the file before the conversion, the Mandelbrot app after it (announceAfterConvert), as the reference apps do.
+    void saveImage(const char* filename, uint32_t w, uint32_t h, float scale, bool rotate180, bool announceAfterConvert);
 
     mc_context* ctx = nullptr;
     mc_multi* multi = nullptr;

@@ -2,9 +2,6 @@
 #ifndef MANDELBROTAPP_H_
 #define MANDELBROTAPP_H_
 
-#include <algorithm>
-#include <chrono>
-
 #include "computeApp.h"
 #include "pngWriter.h"
 
@@ -18,7 +15,6 @@ struct MandelbrotApp : public ComputeApp {
         bufferSize = (uint64_t)sizeof(Pixel) * resx * resy;   // mandelbrotApp.h:16 (uint32_t there)
         mc_mandelbrot_default_params(resx, resy, &params);    // M=128, centre (-0.445,0), scale 2.34, kColor {0.1,0.7,0.6,0}
     }
-    virtual ~MandelbrotApp() { joinWarmupQuietly(); }
 
     // -- additions: the reference hard-codes these in the shader (mandelbrot.comp:5-6,38,40) --
     void setMaxIter(uint32_t m) { params.max_iter = m; }
@@ -35,17 +31,17 @@ struct MandelbrotApp : public ComputeApp {
         createBuffer(bufferSize);   // output buffer
     }
 
-    virtual void createCommandBuffer() override {
-        // push constant kColor (mandelbrotApp.h:139-141) and ONE dispatch over the whole image (:146)
-        params.k_color[0] = 0.1f; params.k_color[1] = 0.7f; params.k_color[2] = 0.6f; params.k_color[3] = 0.0f;
-        params.row_begin = 0; params.row_end = resy;
-    }
-
-    virtual int warmup() override {   // helper thread of init(): tables + code object of the request run() will make
+    // The request run() makes: push constant kColor (mandelbrotApp.h:139-141) and ONE dispatch over the whole image (:146)
+    mc_mandelbrot_params request() const {
         mc_mandelbrot_params q = params;
-        q.k_color[0] = 0.1f; q.k_color[1] = 0.7f; q.k_color[2] = 0.6f; q.k_color[3] = 0.0f;   // as createCommandBuffer sets it
+        q.k_color[0] = 0.1f; q.k_color[1] = 0.7f; q.k_color[2] = 0.6f; q.k_color[3] = 0.0f;
         q.row_begin = 0; q.row_end = resy;
-        return mc_context_warmup_mandelbrot(ctx, &q, (gpuPostprocess ? 1 : 0) | (streaming() ? 2 : 0));   // (bit 1: the banded render's second stream)
+        return q;
+    }
+    virtual void createCommandBuffer() override { params = request(); }
+
+    virtual std::function<int()> warmupCall() const override {   // tables + code object of that request (bit 1: the banded render's second stream)
+        return [ctx = ctx, q = request(), how = (gpuPostprocess ? 1 : 0) | (streaming() ? 2 : 0)] { return mc_context_warmup_mandelbrot(ctx, &q, how); };
     }
 
     virtual void runCommandBuffer() override {
@@ -66,37 +62,7 @@ struct MandelbrotApp : public ComputeApp {
     }
 
     virtual void saveRenderedImage(const char* png_filename = "mandelbrot.png") override {
-        std::vector<uint8_t> image;
-        constexpr float scaleFactor = 255.0f;   // mandelbrotApp.h:174
-        auto t0 = std::chrono::steady_clock::now();
-        if (progressive.active()) {   // run() streamed the bands to the PNG workers: wait for the last stripes, write the file
-            printf("writing %s\n", png_filename);
-            std::vector<uint8_t> png;
-            std::string err = progressive.finish(png);
-            times.pngJoinMs = progressive.lastJoinMs(); times.pngAssembleMs = progressive.lastAssembleMs();
-            auto tw = std::chrono::steady_clock::now();
-            if (err.empty()) err = pngwriter::writeFile(png_filename, png);
-            times.pngWriteMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-            if (!err.empty()) printf("encoder error: %s", err.c_str());
-            times.convertMs = 0.0;
-            times.pngMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return;
-        }
-        if (fusedSave()) {   // getRenderedImage's cast inside the PNG writer's stripe workers: one pass over the storage buffer
-            printf("writing %s\n", png_filename);
-            std::string err = writePngFromStorage(png_filename, resx, resy, scaleFactor, false);
-            if (!err.empty()) printf("encoder error: %s", err.c_str());
-            times.convertMs = 0.0;
-            times.pngMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return;
-        }
-        if (!gpuPostprocess) getRenderedImage(image, resx, resy, scaleFactor);   // (else: converted on the device, same cast semantics)
-        auto t1 = std::chrono::steady_clock::now();
-        printf("writing %s\n", png_filename);
-        std::string err = writePng(png_filename, gpuPostprocess ? rgba8.bytes() : image.data(), resx, resy);
-        if (!err.empty()) printf("encoder error: %s", err.c_str());   // printed, not thrown (mandelbrotApp.h:183)
-        times.convertMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        times.pngMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        saveImage(png_filename, resx, resy, 255.0f, false, true);   // mandelbrotApp.h:172-184: scale 255, "writing" after getRenderedImage
     }
 
     const HostStorage& storageBuffer() const { return buffer; }

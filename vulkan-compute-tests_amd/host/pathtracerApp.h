@@ -2,7 +2,6 @@
 #ifndef PATHTRACERAPP_H_
 #define PATHTRACERAPP_H_
 
-#include <chrono>
 #include <cstring>
 
 #include "computeApp.h"
@@ -35,7 +34,6 @@ struct PathtracerApp : public ComputeApp {
         planes.assign(pl, pl + 12 * np);
         spheres.assign(sp, sp + 12 * ns);
     }
-    virtual ~PathtracerApp() { joinWarmupQuietly(); }   // (the helper reads planes / spheres)
 
     // -- additions --
     void setMathMode(uint32_t mode) { params.math_mode = mode; }   // MC_PT_MATH_STRICT / MC_PT_MATH_FAST / MC_PT_MATH_FAST_CAREFUL
@@ -71,19 +69,24 @@ struct PathtracerApp : public ComputeApp {
     // The reference records spp dispatches, one push-constant update each, with no barrier in between
     // (pathtracerApp.h:361-376).  Here the whole samps.x range [0,spp) is ONE launch with the sample
     // loop fused in registers, accumulating in the barrier-serialised order s = 0..spp-1.
+    mc_pathtrace_params request() const {
+        mc_pathtrace_params q = params;
+        q.width = pushConst.imgdim[0]; q.height = pushConst.imgdim[1];
+        q.spp = pushConst.samps[1];
+        q.sample_begin = 0; q.sample_end = pushConst.samps[1];
+        q.row_begin = 0; q.row_end = resy;
+        return q;
+    }
     virtual void createCommandBuffer() override {
         if (!quiet) { printf("\n   ### recording fused spp loop: samples [0,%d) ###\n\n", spp); fflush(stdout); }
-        params.width = pushConst.imgdim[0]; params.height = pushConst.imgdim[1];
-        params.spp = pushConst.samps[1];
-        params.sample_begin = 0; params.sample_end = pushConst.samps[1];
-        params.row_begin = 0; params.row_end = resy;
+        params = request();
     }
 
-    virtual int warmup() override {   // helper thread of init(): what run() is going to ask for (the setters were called before init())
-        mc_pathtrace_params q = params;
-        q.width = resx; q.height = resy; q.spp = (uint32_t)spp; q.sample_begin = 0; q.sample_end = q.spp; q.row_begin = 0; q.row_end = resy;
-        return mc_context_warmup_pathtrace(ctx, &q, planes.data(), (uint32_t)planes.size() / 12, spheres.data(),
-                                           (uint32_t)spheres.size() / 12, gpuPostprocess ? 1 : 0);
+    virtual std::function<int()> warmupCall() const override {   // what run() is going to ask for (the setters were called before init())
+        return [ctx = ctx, q = request(), planes = planes, spheres = spheres, rgba8 = gpuPostprocess ? 1 : 0] {
+            return mc_context_warmup_pathtrace(ctx, &q, planes.data(), (uint32_t)planes.size() / 12, spheres.data(),
+                                               (uint32_t)spheres.size() / 12, rgba8);
+        };
     }
 
     virtual void runCommandBuffer() override {
@@ -106,28 +109,9 @@ struct PathtracerApp : public ComputeApp {
     }
 
     virtual void saveRenderedImage(const char* png_filename = "pathtracer.png") override {
-        std::vector<uint8_t> image;
-        constexpr float scaleFactor = 1.0f;   // pathtracerApp.h:227
-        printf("writing %s\n", png_filename);
-        auto t0 = std::chrono::steady_clock::now();
-        if (fusedSave()) {   // getRenderedImage + the rotation of :235-243 + the encoder in one pass over the storage buffer
-            std::string err = writePngFromStorage(png_filename, resx, resy, scaleFactor, true);
-            if (!err.empty()) printf("encoder error: %s", err.c_str());
-            times.convertMs = 0.0;
-            times.pngMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return;
-        }
-        if (!gpuPostprocess) {   // (else: converted and rotated on the device)
-            // getRenderedImage, then: due to the pinhole camera the image is upside-down and mirrored — undo that (pathtracerApp.h:235-243:
-            // every pixel of the left half swapped with its point reflection).  One pass here: each converted pixel is written to the
-            // place the swap loop would leave it in (the same bytes, incl. an odd width's untouched middle column).
-            convertStorage(image, resx, resy, scaleFactor, true);
-        }
-        auto t1 = std::chrono::steady_clock::now();
-        std::string err = writePng(png_filename, gpuPostprocess ? rgba8.bytes() : image.data(), resx, resy);
-        if (!err.empty()) printf("encoder error: %s", err.c_str());
-        times.convertMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        times.pngMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        // pathtracerApp.h:225-247: scale 1, then — the pinhole camera's image is upside-down and mirrored — every pixel of the left half
+        // swapped with its point reflection (:235-243), applied while converting: the same bytes, incl. an odd width's middle column
+        saveImage(png_filename, resx, resy, 1.0f, true, false);
     }
 
     const HostStorage& storageBuffer() const { return buffer; }
