@@ -105,6 +105,54 @@ enum { MC_PRECISION_F32 = 0, MC_PRECISION_DS = 1 /* two-float, emulateDouble.h.g
  *    n is the number of iterations that did not escape, in [0, M].
  *  - colour: the fp32 table of mc_mandelbrot_colour_lut (t = n / M in fp32), so the RGBA f32, RGBA8 and PNG outputs are the same
  *    functions of n as for the other two precisions. */
+/* MC_PRECISION_PERTURB (3): deep zooms past fp64 by perturbation (what tests/mandel_perturb_ref.py restates).  A
+ * reference orbit Z_0 .. Z_L is computed once on the host in multi-limb fixed point (mc_mandelbrot_orbit_create) and bound to the
+ * context; every pixel iterates its offset from that orbit in IEEE double.
+ *  - view: the bound orbit's centre c_ref and scale (sx, sy).  The params' eight view words must all be zero (a stale F32/DS/F64 view is
+ *    an error, not silently ignored), an orbit must be bound and p->max_iter <= the orbit's max_iter: MC_ERR_INVALID_ARGUMENT otherwise.
+ *  - per pixel, IEEE double, no contraction, source order (gx column, gy storage row, as F64's c table):
+ *      dcx = ((double)gx / (double)W - 0.5) * sx;  dcy = ((double)gy / (double)H - 0.5) * sy;   (the pixel's c is c_ref + (dcx, dcy))
+ *      dx = dy = 0, m = 0; for i in [0, M):
+ *        ax = (Z[m].x + Z[m].x) + dx;  ay = (Z[m].y + Z[m].y) + dy;
+ *        ndx = ((ax * dx) - (ay * dy)) + dcx;  ndy = ((ax * dy) + (ay * dx)) + dcy;
+ *        m = m + 1;  zx = Z[m].x + ndx;  zy = Z[m].y + ndy;  r = (zx * zx) + (zy * zy);
+ *        if (r > 2.0) break;                                                       (n = i: the iterations that did not escape)
+ *        if (m == L || r < ((ndx * ndx) + (ndy * ndy))) { dx = zx; dy = zy; m = 0; }   (rebase onto the orbit's start)
+ *        else { dx = ndx; dy = ndy; }
+ *    n = M when the loop runs out.  fp64 denormals are kept.  The colour is lut[n] of mc_mandelbrot_colour_lut, as for the others.
+ *  - interior pixels run all M iterations: the state includes m, so the Brent cycle exit of the other precisions does not apply.
+ *  - accuracy: n is exactly the loop above, not always the count of c iterated exactly.  In particular a reference orbit that escapes with
+ *    |Z_L|^2 within double rounding of 2 has that last comparison decided in double for every pixel that follows it, so such a view can be
+ *    wrong as a whole; choose a centre whose orbit clears 2 (or stays bounded).  High counts near the boundary also diverge from exact
+ *    iteration pixel by pixel, as any finite precision does (DESIGN.md §3.6 gives measured agreement).
+ *  - every single-device entry point that takes mc_mandelbrot_params renders it (row tiles, interleaved tiles, MC_MANDEL_ITERS_U16,
+ *    _device_async, _rgba8, _banded, mc_context_warmup_mandelbrot).  mc_multi_* refuse it with MC_ERR_UNSUPPORTED: multi-GPU
+ *    perturbation is out of scope (no two-GPU machine to test it on). */
+#define MC_PRECISION_PERTURB 3u
+
+/* The reference orbit of MC_PRECISION_PERTURB.  Host only: touches no device, usable without a GPU.
+ *  - centre_x / centre_y: decimal text, [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?, at most 4096 characters, |value| <= 4.
+ *    Anything else (empty, hex, inf, nan, spaces, a trailing e, |value| > 4): MC_ERR_INVALID_ARGUMENT.
+ *  - scale_x / scale_y: finite and nonzero (MC_ERR_INVALID_ARGUMENT); min(|scale_x|, |scale_y|) < 2^-960: MC_ERR_UNSUPPORTED (a
+ *    pixel offset could leave the normal doubles).  max_iter >= 1.
+ *  - arithmetic: binary fixed point with `bits` = max(64, ceil(-log2 min(|scale_x|, |scale_y|)) + 96) fractional bits — carried as whole
+ *    64-bit limbs, so the words hold `bits` rounded up to a multiple of 64 — and a 64-bit integer limb (|Z| <= 8).  Each decimal is
+ *    rounded ONCE into that format by round-to-odd (truncate; set the last bit when anything nonzero was dropped): that sticky bit makes
+ *    the later rounding to double correct, so Z_1 = c_ref is the correctly rounded double of the decimal (strtod, Python's float(s))
+ *    whenever the coordinate is 0 or at least 2^(55 - bits) in magnitude.  Products are rounded to nearest.
+ *  - Z_0 = 0, Z_{j+1} = Z_j^2 + c_ref; L = the first j >= 1 with |Z_j|^2 > 2 in that precision, or max_iter if there is none.  The table
+ *    holds Z_0 .. Z_L, each part rounded to the nearest double (ties to even).  Three multi-limb products per iteration: measured in
+ *    DESIGN.md §3.6.
+ * mc_mandelbrot_orbit_copy writes (length + 1) * 2 doubles (re, im per entry).  mc_context_bind_mandelbrot_orbit copies the table to the
+ * context's device after draining the context's launch streams (a running launch never sees it replaced); the orbit object may be
+ * destroyed afterwards.  NULL unbinds. */
+typedef struct mc_mandelbrot_orbit mc_mandelbrot_orbit;
+int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y,
+                               uint32_t max_iter, mc_mandelbrot_orbit** out);
+int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o);
+int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits);
+int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z /* (length+1)*2: re, im */);
+int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o);   /* NULL unbinds */
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1 /* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */

@@ -16,7 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mc_compute.h")
 
 MC_OK = 0
 ABI_VERSION = 3   # MC_ABI_VERSION of include/mc_compute.h this binding is written against
-PRECISION_F32, PRECISION_DS, PRECISION_F64 = 0, 1, 2
+PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB = 0, 1, 2, 3
 PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format
@@ -121,6 +121,12 @@ def lib():
             L.mc_assemble_rgba8_device_async.argtypes = [vp, vp, u32, u32, u32, u32, u32, i32, vp, vp]
             L.mc_multi_pathtrace_render_rgba8.argtypes = [vp, C.POINTER(PathtraceParams), vp, u32, vp, u32, vp]
             L.mc_multi_mandelbrot_render_rgba8.argtypes = [vp, C.POINTER(MandelbrotParams), vp]
+        if hasattr(L, "mc_mandelbrot_orbit_create"):   # MC_PRECISION_PERTURB (additions within ABI 3)
+            L.mc_mandelbrot_orbit_create.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, u32, C.POINTER(vp)]
+            L.mc_mandelbrot_orbit_destroy.argtypes = [vp]
+            L.mc_mandelbrot_orbit_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+            L.mc_mandelbrot_orbit_copy.argtypes = [vp, vp]
+            L.mc_context_bind_mandelbrot_orbit.argtypes = [vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -299,6 +305,44 @@ def pathtrace_scene_class(planes, spheres):
     return int(out.value)
 
 
+class Orbit:
+    """mc_mandelbrot_orbit: the reference orbit of MC_PRECISION_PERTURB, computed on the host (no device needed) from the centre as
+    decimal text (str, taken verbatim) and the scale as doubles.  A context manager; Context.bind_mandelbrot_orbit copies it to a device."""
+
+    def __init__(self, centre_x, centre_y, scale_x, scale_y, max_iter):
+        enc = lambda v: v.encode() if isinstance(v, str) else v
+        self._h = C.c_void_p()
+        _check(lib().mc_mandelbrot_orbit_create(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), int(max_iter),
+                                                C.byref(self._h)), "mc_mandelbrot_orbit_create")
+        n, m, b = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().mc_mandelbrot_orbit_info(self._h, C.byref(n), C.byref(m), C.byref(b)), "mc_mandelbrot_orbit_info")
+        self.length, self.max_iter, self.bits = n.value, m.value, b.value
+        self.scale = (float(scale_x), float(scale_y))
+
+    def table(self):
+        """Z_0 .. Z_L as an (L + 1, 2) float64 array (re, im)."""
+        out = np.empty((self.length + 1, 2), np.float64)
+        _check(lib().mc_mandelbrot_orbit_copy(self._h, _ptr(out)), "mc_mandelbrot_orbit_copy")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().mc_mandelbrot_orbit_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """mc_context wrapper (replaces VulkanComputeApp::init / cleanup)."""
 
@@ -344,6 +388,13 @@ class Context:
         k, c = C.c_double(0.0), C.c_double(0.0)
         _check(lib().mc_context_last_timing(self._h, C.byref(k), C.byref(c)), "mc_context_last_timing")
         return k.value, c.value
+
+    def bind_mandelbrot_orbit(self, orbit):
+        """mc_context_bind_mandelbrot_orbit: the view of MC_PRECISION_PERTURB renders on this context (None unbinds)."""
+        if orbit is not None and not orbit._h:   # a closed orbit's handle is NULL, which the C call reads as "unbind"
+            raise ValueError("Context.bind_mandelbrot_orbit: the orbit is closed")
+        _check(lib().mc_context_bind_mandelbrot_orbit(self._h, orbit._h if orbit is not None else None),
+               "mc_context_bind_mandelbrot_orbit")
 
     # ---- host-buffer forms -------------------------------------------------------------------------
     def mandelbrot(self, p, want_rgba=True, want_iters=True, out=None):

@@ -1,0 +1,533 @@
+// MC_PRECISION_PERTURB: Mandelbrot deep zooms past fp64 by perturbation (include/mc_compute.h states the contract).
+//
+//  * host: the reference orbit Z_0 .. Z_L at the view's centre, in binary fixed point of `bits` fractional bits (uint64_t limbs,
+//    unsigned __int128 products), from decimal text; rounded to a double2 table and bound to a context.
+//  * device: StatePerturb inside the escape-time loop of mandel_escape.h.  Each pixel iterates its offset d from the orbit in IEEE
+//    double, rebasing onto Z_0 when |z| < |d| or the orbit ends (Zhuoran's rebasing: no glitch detection, no second reference).
+//    The orbit is read from HBM (L2-resident: 800 KB at M = 50 000); the fast block fetches the block's U entries at its start, so
+//    no load sits on the iteration's dependency chain, and a block in which an unfinished lane rebases is replayed exactly.
+//  * IEEE double in source order: this TU is built with -ffp-contract=off like every other; fp64 denormals stay enabled.
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+#include "mandel_escape.h"
+#include "mandel_perturb.h"
+#include "mc_internal.h"
+
+// ---- host: multi-limb fixed point -----------------------------------------------------------------------------------------------
+namespace {
+
+// Sign and magnitude; m[0 .. k-1] the fractional limbs (least significant first), m[k] the integer limb.  k <= 17: 1088 >= 1056
+// fractional bits, the most a scale of 2^-960 asks for.
+constexpr int kMaxFrac = 17;
+struct Fix {
+    uint64_t m[kMaxFrac + 1];
+    bool neg;
+};
+
+struct FixOps {
+    int k;   // fractional limbs; every Fix holds k + 1 limbs
+    int n() const { return k + 1; }
+    void zero(Fix& a) const { std::memset(a.m, 0, sizeof a.m); a.neg = false; }
+    bool is_zero(const Fix& a) const {
+        for (int i = 0; i < n(); i++) if (a.m[i]) return false;
+        return true;
+    }
+    int cmp_mag(const Fix& a, const Fix& b) const {
+        for (int i = n() - 1; i >= 0; i--) if (a.m[i] != b.m[i]) return a.m[i] < b.m[i] ? -1 : 1;
+        return 0;
+    }
+    static void add_mag(const uint64_t* a, const uint64_t* b, uint64_t* r, int n) {
+        unsigned __int128 c = 0;
+        for (int i = 0; i < n; i++) { c += (unsigned __int128)a[i] + b[i]; r[i] = (uint64_t)c; c >>= 64; }
+    }
+    static void sub_mag(const uint64_t* a, const uint64_t* b, uint64_t* r, int n) {   // a >= b
+        uint64_t borrow = 0;
+        for (int i = 0; i < n; i++) {
+            uint64_t t = a[i] - b[i];
+            uint64_t b1 = a[i] < b[i];
+            r[i] = t - borrow;
+            borrow = b1 | (t < borrow);
+        }
+    }
+    // r = a + b (signed).  r may alias a or b.
+    void add(const Fix& a, const Fix& b, Fix& r) const {
+        if (a.neg == b.neg) { add_mag(a.m, b.m, r.m, n()); r.neg = a.neg; }
+        else if (cmp_mag(a, b) >= 0) { bool s = a.neg; sub_mag(a.m, b.m, r.m, n()); r.neg = s; }
+        else { bool s = b.neg; sub_mag(b.m, a.m, r.m, n()); r.neg = s; }
+        if (is_zero(r)) r.neg = false;
+    }
+    void sub(const Fix& a, const Fix& b, Fix& r) const {
+        Fix nb = b;
+        nb.neg = !b.neg && !is_zero(b);
+        add(a, nb, r);
+    }
+    // r = a * b rounded to nearest (ties away from zero) at the last fractional bit.  The integer part stays below 2^64 (|Z| <= 8).
+    void mul(const Fix& a, const Fix& b, Fix& r) const {
+        const int nn = n();
+        uint64_t p[2 * (kMaxFrac + 1)] = {};
+        for (int i = 0; i < nn; i++) {
+            unsigned __int128 c = 0;
+            const uint64_t ai = a.m[i];
+            for (int j = 0; j < nn; j++) {
+                c += (unsigned __int128)ai * b.m[j] + p[i + j];
+                p[i + j] = (uint64_t)c;
+                c >>= 64;
+            }
+            p[i + nn] = (uint64_t)c;
+        }
+        unsigned __int128 c = p[k - 1] >> 63;   // the first dropped bit
+        for (int i = 0; i < nn; i++) { c += p[k + i]; r.m[i] = (uint64_t)c; c >>= 64; }
+        r.neg = (a.neg != b.neg) && !is_zero(r);
+    }
+    void twice(Fix& a) const {   // exact
+        for (int i = n() - 1; i > 0; i--) a.m[i] = (a.m[i] << 1) | (a.m[i - 1] >> 63);
+        a.m[0] <<= 1;
+    }
+    // |a| > 2 (a >= 0 here: a sum of squares)
+    bool above_two(const Fix& a) const {
+        if (a.m[k] != 2) return a.m[k] > 2;
+        for (int i = 0; i < k; i++) if (a.m[i]) return true;
+        return false;
+    }
+    // bits [lo, lo + cnt) of the magnitude, cnt <= 64
+    uint64_t bits_at(const Fix& a, int lo, int cnt) const {
+        uint64_t v = 0;
+        for (int b = 0; b < cnt; b++) {
+            const int pos = lo + b;
+            if (pos >= 0 && pos < 64 * n() && ((a.m[pos >> 6] >> (pos & 63)) & 1u)) v |= 1ull << b;
+        }
+        return v;
+    }
+    bool any_below(const Fix& a, int pos) const {   // any bit of the magnitude below position pos
+        for (int i = 0; i < n() && 64 * i < pos; i++) {
+            const int in = pos - 64 * i;
+            const uint64_t mask = in >= 64 ? ~0ull : ((1ull << in) - 1);
+            if (a.m[i] & mask) return true;
+        }
+        return false;
+    }
+    // Nearest double, ties to even (subnormals included: the quantum below 2^-1022 is 2^-1074).
+    double to_double(const Fix& a) const {
+        int top = -1;
+        for (int i = n() - 1; i >= 0 && top < 0; i--)
+            if (a.m[i]) top = 64 * i + 63 - __builtin_clzll(a.m[i]);
+        if (top < 0) return 0.0;
+        const int F = 64 * k;
+        int shift = top - 52;
+        if (shift < F - 1074) shift = F - 1074;
+        uint64_t mant;
+        if (shift <= 0) {
+            mant = bits_at(a, 0, top + 1);
+            shift = 0;
+        } else {
+            mant = bits_at(a, shift, top - shift + 1);
+            const bool half = bits_at(a, shift - 1, 1) != 0;
+            const bool sticky = any_below(a, shift - 1);
+            if (half && (sticky || (mant & 1u))) mant++;
+        }
+        const double v = std::ldexp((double)mant, shift - F);
+        return a.neg ? -v : v;
+    }
+};
+
+// [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?, |value| <= 4, rounded to odd at the last of the k * 64 fractional bits.
+bool parse_decimal(const char* s, const FixOps& ops, Fix& out) {
+    if (!s) return false;
+    const size_t len = strnlen(s, 4097);
+    if (len == 0 || len > 4096) return false;
+    size_t i = 0;
+    bool neg = false;
+    if (s[i] == '+' || s[i] == '-') neg = s[i++] == '-';
+    std::vector<int> digits;
+    int64_t int_digits = 0;
+    while (s[i] >= '0' && s[i] <= '9') { digits.push_back(s[i++] - '0'); int_digits++; }
+    size_t frac_digits = 0;
+    if (s[i] == '.') {
+        i++;
+        while (s[i] >= '0' && s[i] <= '9') { digits.push_back(s[i++] - '0'); frac_digits++; }
+    }
+    if (int_digits == 0 && frac_digits == 0) return false;
+    int64_t e = 0;
+    if (s[i] == 'e' || s[i] == 'E') {
+        i++;
+        bool eneg = false;
+        if (s[i] == '+' || s[i] == '-') eneg = s[i++] == '-';
+        if (!(s[i] >= '0' && s[i] <= '9')) return false;
+        while (s[i] >= '0' && s[i] <= '9') {
+            if (e < 100000000) e = e * 10 + (s[i] - '0');   // saturates: far beyond any digit count of 4096 characters
+            i++;
+        }
+        if (eneg) e = -e;
+    }
+    if (i != len) return false;
+    // value = 0.d1 d2 ... x 10^point after dropping leading zeros
+    int64_t point = int_digits + e;
+    size_t first = 0;
+    while (first < digits.size() && digits[first] == 0) { first++; point--; }
+    ops.zero(out);
+    if (first == digits.size()) return true;   // zero
+    size_t last = digits.size();
+    while (digits[last - 1] == 0) last--;
+    if (point > 1) return false;               // >= 10
+    uint32_t int_part = 0;
+    if (point == 1) int_part = (uint32_t)digits[first++];
+    // Horner from the last digit: acc = floor((acc + d * 2^F) / 10) per digit gives floor(fraction * 2^F) exactly; a nonzero remainder
+    // anywhere means the fraction had more bits (the sticky bit)
+    const int k = ops.k, n = ops.n();
+    bool sticky = false;
+    auto div10 = [&]() {
+        unsigned __int128 rem = 0;
+        for (int j = n - 1; j >= 0; j--) {
+            unsigned __int128 cur = (rem << 64) | out.m[j];
+            out.m[j] = (uint64_t)(cur / 10u);
+            rem = cur % 10u;
+        }
+        if (rem) sticky = true;
+    };
+    for (size_t j = last; j > first; j--) {
+        out.m[k] += (uint64_t)digits[j - 1];
+        div10();
+    }
+    for (int64_t z = 0; z < -point && !ops.is_zero(out); z++) div10();   // the zeros between the point and the first digit (once
+                                                                          // the floor is 0 more of them change nothing but sticky)
+    out.m[k] += int_part;
+    if (sticky) out.m[0] |= 1u;   // round to odd
+    if (out.m[k] > 4) return false;
+    if (out.m[k] == 4)
+        for (int j = 0; j < k; j++) if (out.m[j]) return false;
+    out.neg = neg && !ops.is_zero(out);
+    return true;
+}
+
+}  // namespace
+
+struct mc_mandelbrot_orbit {
+    std::vector<double> z;   // (L + 1) * 2: re, im
+    uint32_t length = 0, max_iter = 0, bits = 0;
+    double scale_x = 0.0, scale_y = 0.0;
+};
+
+extern "C" {
+
+int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y, uint32_t max_iter,
+                               mc_mandelbrot_orbit** out) {
+    auto refuse = [](const char* why) {
+        mc::set_error_detail(std::string("mc_mandelbrot_orbit_create: ") + why);
+        return MC_ERR_INVALID_ARGUMENT;
+    };
+    if (!out || !centre_x || !centre_y) return refuse("NULL argument");
+    if (max_iter == 0) return refuse("max_iter must be at least 1");
+    *out = nullptr;
+    if (!std::isfinite(scale_x) || !std::isfinite(scale_y) || scale_x == 0.0 || scale_y == 0.0)
+        return refuse("scale_x and scale_y must be finite and nonzero");
+    const double smin = std::fmin(std::fabs(scale_x), std::fabs(scale_y));
+    int e = 0;
+    (void)std::frexp(smin, &e);                      // smin = f * 2^e, f in [0.5, 1): ceil(-log2 smin) = 1 - e exactly
+    int64_t bits = (int64_t)1 - e + 96;
+    if (bits < 64) bits = 64;
+    FixOps ops{(int)((bits + 63) / 64)};
+    Fix cx, cy;
+    if (ops.k > kMaxFrac) ops.k = kMaxFrac;          // (only reached below 2^-960, refused after the strings are checked)
+    if (!parse_decimal(centre_x, ops, cx))
+        return refuse("centre_x is not a decimal of at most 4096 characters with |value| <= 4");
+    if (!parse_decimal(centre_y, ops, cy))
+        return refuse("centre_y is not a decimal of at most 4096 characters with |value| <= 4");
+    if (smin < std::ldexp(1.0, -960)) {
+        mc::set_error_detail("mc_mandelbrot_orbit_create: scale below 2^-960 (pixel offsets would leave the normal doubles)");
+        return MC_ERR_UNSUPPORTED;
+    }
+    mc_mandelbrot_orbit* o = new (std::nothrow) mc_mandelbrot_orbit();
+    if (!o) return MC_ERR_OUT_OF_MEMORY;
+    try {
+        o->z.reserve(2 * ((size_t)max_iter + 1) < 2 * 65536 ? 2 * ((size_t)max_iter + 1) : 2 * 65536);
+        Fix zx, zy, sx, sy, t;
+        ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
+        o->z.push_back(0.0); o->z.push_back(0.0);
+        uint32_t L = max_iter;
+        for (uint32_t j = 0; j < max_iter; j++) {
+            ops.mul(zx, zy, t);                           // Z_{j+1} = Z_j^2 + c_ref
+            ops.twice(t);
+            ops.add(t, cy, zy);
+            ops.sub(sx, sy, t);
+            ops.add(t, cx, zx);
+            o->z.push_back(ops.to_double(zx));
+            o->z.push_back(ops.to_double(zy));
+            ops.mul(zx, zx, sx);
+            ops.mul(zy, zy, sy);
+            ops.add(sx, sy, t);
+            if (ops.above_two(t)) { L = j + 1; break; }
+        }
+        o->length = L;
+    } catch (const std::bad_alloc&) {
+        delete o;
+        return MC_ERR_OUT_OF_MEMORY;
+    }
+    o->max_iter = max_iter;
+    o->bits = (uint32_t)bits;
+    o->scale_x = scale_x;
+    o->scale_y = scale_y;
+    *out = o;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o) {
+    delete o;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits) {
+    if (!o) return MC_ERR_INVALID_ARGUMENT;
+    if (length) *length = o->length;
+    if (max_iter) *max_iter = o->max_iter;
+    if (bits) *bits = o->bits;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z) {
+    if (!o || !out_z) return MC_ERR_INVALID_ARGUMENT;
+    std::memcpy(out_z, o->z.data(), o->z.size() * sizeof(double));
+    return MC_OK;
+}
+
+}  // extern "C"
+
+namespace mc {
+
+namespace {
+
+// The orbit bound to each context.  Kept here rather than in mc_context so that mc_internal.h, which the path tracer's build id
+// covers, stays as it is.  The map is shared by every context (a context itself is used by one thread at a time): lookups lock it.
+struct Binding {
+    DeviceBuffer orbit;                // Z_0 .. Z_L, double2
+    uint32_t length = 0, max_iter = 0;
+    double scale_x = 0.0, scale_y = 0.0;
+    uint32_t generation = 0;           // a new value per bind, part of the dc table's cache key
+};
+std::mutex g_bind_mutex;
+std::unordered_map<const mc_context*, Binding> g_bindings;
+uint32_t g_generation = 0;
+
+Binding* find_binding(const mc_context* ctx) {
+    std::lock_guard<std::mutex> lock(g_bind_mutex);
+    auto it = g_bindings.find(ctx);
+    return it == g_bindings.end() ? nullptr : &it->second;
+}
+
+struct PerturbArgs {
+    uint32_t W, H, max_iter, L;
+    uint32_t row_begin, row_end, row_block, row_stride;
+    float4* __restrict__ out_rgba;        // tile-local, may be null
+    uint32_t* __restrict__ out_iters;     // tile-local, may be null
+    uint16_t* __restrict__ out_iters16;   // MC_MANDEL_ITERS_U16, may be null
+    const float4* __restrict__ lut;       // max_iter+1 entries (null when out_rgba is null)
+    const double* __restrict__ dc_tab;    // [dcx[W] | dcy[H]]: the pixel's offset from c_ref per column / per row
+    const double2* __restrict__ orbit;    // Z_0 .. Z_L
+};
+
+// One pixel's offset from the reference orbit (the loop of include/mc_compute.h, MC_PRECISION_PERTURB).  Per iteration 20 fp64 ops
+// (2 + 2 for a, 4 + 4 for the new offset, 2 for z, 3 for |z|^2, 3 for |d|^2) against F64's 8.
+struct StatePerturb {
+    static constexpr int kBlock = 8;        // the escape-time block length U: the fast block prefetches this many orbit entries
+    const double2* __restrict__ Z;
+    uint32_t L;
+    double dcx, dcy, dx, dy, zmx, zmy;      // zm = Z[m]
+    uint32_t m;
+    __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const PerturbArgs& a) {
+        Z = a.orbit;
+        L = a.L;
+        dcx = a.dc_tab[gx];
+        dcy = a.dc_tab[a.W + gy];
+        dx = dy = zmx = zmy = 0.0;
+        m = 0;
+    }
+    // the iteration up to the new z; returns r = |z|^2, leaves the new offset in ndx, ndy and z in zx, zy
+    __device__ __forceinline__ double advance(double2 z1, double& ndx, double& ndy, double& zx, double& zy) const {
+        const double ax = (zmx + zmx) + dx, ay = (zmy + zmy) + dy;
+        ndx = ((ax * dx) - (ay * dy)) + dcx;
+        ndy = ((ax * dy) + (ay * dx)) + dcy;
+        zx = z1.x + ndx;
+        zy = z1.y + ndy;
+        return (zx * zx) + (zy * zy);
+    }
+    // Exact iteration.  A lane that has escaped keeps iterating until its wave is done (its state no longer matters), and a lane past
+    // a fast block it took as finished may hold m > L: the load index is clamped so that no lane reads beyond Z_L.
+    __device__ __forceinline__ bool step() {
+        m = m + 1u;
+        const double2 z1 = Z[m < L ? m : L];
+        double ndx, ndy, zx, zy;
+        const double r = advance(z1, ndx, ndy, zx, zy);
+        if (m == L || r < ((ndx * ndx) + (ndy * ndy))) { dx = zx; dy = zy; m = 0; zmx = zmy = 0.0; }   // rebase: Z_0 = 0
+        else { dx = ndx; dy = ndy; zmx = z1.x; zmy = z1.y; }
+        return r > 2.0;
+    }
+    // Fast block: Z[m+1 .. m+U] are loaded at the block's start (acc_init), off the dependency chain; the block assumes m advances by
+    // one per iteration.  needs_exact = F64's high-word escape filter OR "this lane rebased, or reached m == L, in the block": any
+    // unfinished lane raising it replays the block exactly from the saved state (step(), one load per iteration).
+    static constexpr bool kHasFastBlock = true;
+    static constexpr uint32_t kCycleCheckBlocks = 0;   // no cycle exit: the state includes m and never repeats
+    struct Acc {
+        uint32_t hi;        // OR of the high words of |z|^2
+        bool rebase;        // some iteration rebased or reached the orbit's end
+        double2 z[kBlock];  // Z[m+1 ..], consumed one per iteration
+    };
+    __device__ __forceinline__ Acc acc_init() const {
+        Acc acc;
+        acc.hi = 0u;
+        acc.rebase = L - m <= (uint32_t)kBlock;   // m + k == L for some k in [1, U]  (m <= L)
+#pragma unroll
+        for (int k = 0; k < kBlock; k++) {
+            const uint32_t j = m + 1u + (uint32_t)k;
+            acc.z[k] = Z[j < L ? j : L];
+        }
+        return acc;
+    }
+    __device__ __forceinline__ void advance_fast(Acc& acc) {
+        const double2 z1 = acc.z[0];
+#pragma unroll
+        for (int k = 0; k + 1 < kBlock; k++) acc.z[k] = acc.z[k + 1];   // register renaming once unrolled
+        double ndx, ndy, zx, zy;
+        const double r = advance(z1, ndx, ndy, zx, zy);
+        acc.hi |= (uint32_t)((uint64_t)__double_as_longlong(r) >> 32);
+        acc.rebase |= r < ((ndx * ndx) + (ndy * ndy));
+        dx = ndx; dy = ndy; zmx = z1.x; zmy = z1.y;
+        m = m + 1u;
+    }
+    static __device__ __forceinline__ bool needs_exact(const Acc& acc) { return acc.hi > 0x3fffffffu || acc.rebase; }
+};
+
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_kernel(PerturbArgs a) {
+    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    // the tile mapping of mandelbrot_kernel (mandelbrot.hip): one wave = one 8x8 pixel tile
+    const uint32_t lane = threadIdx.x;
+    const uint32_t gx = blockIdx.x * 8u + (lane & 7u);
+    const uint32_t ty = blockIdx.y * 8u + (lane >> 3);
+    const uint32_t gy = tile_row_to_storage(ty, a.row_begin, a.row_block, a.row_stride);
+    const bool valid = gx < a.W && gy < a.row_end;
+    StatePerturb st;
+    st.init(valid ? gx : 0u, valid ? gy : 0u, a);
+    const uint32_t n = escape_time<StatePerturb, U>(st, a.max_iter, valid);
+    if (valid) {
+        const size_t idx = (size_t)ty * a.W + gx;
+        if (a.out_iters) a.out_iters[idx] = n;
+        if (a.out_iters16) a.out_iters16[idx] = (uint16_t)n;
+        if (a.out_rgba) a.out_rgba[idx] = a.lut[n];
+    }
+}
+
+// dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
+// by (W, H, precision, the bind generation): the params' view words are all zero for this precision.
+int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Binding& b, hipStream_t s) {
+    float gen;
+    std::memcpy(&gen, &b.generation, sizeof gen);   // compared bytewise
+    std::vector<float> key = {(float)p->width, (float)p->height, (float)p->precision, gen};
+    if (ctx->ctab.ptr && ctx->ctab_key.size() == key.size() &&
+        std::memcmp(ctx->ctab_key.data(), key.data(), key.size() * sizeof(float)) == 0)
+        return MC_OK;
+    const uint32_t W = p->width, H = p->height;
+    std::vector<double> tab((size_t)W + H);
+    for (uint32_t g = 0; g < W; g++) tab[g] = ((double)g / (double)W - 0.5) * b.scale_x;
+    for (uint32_t g = 0; g < H; g++) tab[W + g] = ((double)g / (double)H - 0.5) * b.scale_y;
+    int rc = ctx->drain_launch_streams();   // an earlier launch of this context may still read the old table
+    if (rc) return rc;
+    if ((rc = ctx->ctab.reserve(tab.size() * sizeof(double)))) return rc;
+    MC_HIP_TRY(hipMemcpyAsync(ctx->ctab.ptr, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    MC_HIP_TRY(hipStreamSynchronize(s));
+    ctx->ctab_key = key;
+    return MC_OK;
+}
+
+}  // namespace
+
+int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm) {
+    const Binding* b = find_binding(ctx);
+    if (!b || !b->orbit.ptr || !b->length) {
+        set_error_detail("MC_PRECISION_PERTURB: no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const float words[8] = {p->centre_x_hi, p->centre_x_lo, p->centre_y_hi, p->centre_y_lo,
+                            p->scale_x_hi, p->scale_x_lo, p->scale_y_hi, p->scale_y_lo};
+    for (float w : words)
+        if (w != 0.0f) {
+            set_error_detail("MC_PRECISION_PERTURB: the view is the bound orbit's; the params' eight view words must be zero");
+            return MC_ERR_INVALID_ARGUMENT;
+        }
+    if (p->max_iter > b->max_iter) {
+        set_error_detail("MC_PRECISION_PERTURB: max_iter above the bound orbit's");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const bool narrow = (p->flags & MC_MANDEL_ITERS_U16) != 0u;
+    if (narrow && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
+    PerturbArgs a;
+    a.lut = nullptr;
+    if (d_rgba || warm) {
+        const void* lut = nullptr;
+        int rc = mandelbrot_lut_device(ctx, p, s, &lut);
+        if (rc) return rc;
+        a.lut = warm ? nullptr : (const float4*)lut;
+    }
+    int rc = ensure_dc_table(ctx, p, *b, s);
+    if (rc) return rc;
+    a.W = p->width; a.H = p->height; a.max_iter = p->max_iter; a.L = b->length;
+    a.row_begin = p->row_begin; a.row_end = p->row_end;
+    a.row_block = p->row_stride ? p->row_block : 0u; a.row_stride = p->row_stride;
+    a.out_rgba = warm ? nullptr : (float4*)d_rgba;
+    a.out_iters = narrow ? nullptr : (uint32_t*)d_iters;
+    a.out_iters16 = narrow ? (uint16_t*)d_iters : nullptr;
+    a.dc_tab = (const double*)ctx->ctab.ptr;
+    a.orbit = (const double2*)b->orbit.ptr;
+    const uint32_t rows = tile_rows(p->row_begin, p->row_end, a.row_block, a.row_stride);
+    dim3 grid((p->width + 7u) / 8u, (rows + 7u) / 8u), block(64);
+    if (warm) {   // one tile, a handful of iterations (as launch_impl)
+        grid = dim3(1, 1);
+        a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
+    }
+    hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
+    MC_HIP_TRY(hipGetLastError());
+    return ctx->note_launch(s);
+}
+
+void perturb_release(mc_context* ctx) {
+    std::lock_guard<std::mutex> lock(g_bind_mutex);
+    auto it = g_bindings.find(ctx);
+    if (it == g_bindings.end()) return;
+    it->second.orbit.release();
+    g_bindings.erase(it);
+}
+
+}  // namespace mc
+
+extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o) {
+    if (!ctx) return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    // a running launch of this context may read the current table (or the dc table keyed by its generation): wait for the context's
+    // launch streams — not the whole device — before replacing it, as the colour table does
+    int rc = ctx->drain_launch_streams();
+    if (rc) return rc;
+    if (!o) {
+        mc::perturb_release(ctx);
+        return MC_OK;
+    }
+    mc::Binding* b;
+    {
+        std::lock_guard<std::mutex> lock(mc::g_bind_mutex);
+        b = &mc::g_bindings[ctx];    // the node stays put while other contexts bind (only this context's thread erases it)
+        b->generation = ++mc::g_generation;
+        b->length = 0;               // unusable until the copy below has completed
+    }
+    const size_t bytes = o->z.size() * sizeof(double);
+    if ((rc = b->orbit.reserve(bytes))) return rc;
+    MC_HIP_TRY(hipMemcpyAsync(b->orbit.ptr, o->z.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    b->length = o->length;
+    b->max_iter = o->max_iter;
+    b->scale_x = o->scale_x;
+    b->scale_y = o->scale_y;
+    return MC_OK;
+}

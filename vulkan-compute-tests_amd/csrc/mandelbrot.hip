@@ -2,7 +2,8 @@
 //
 // Replaces shaders/mandelbrot.comp:21-60 (fp32) and adds the two-float deep-zoom variant composed
 // from the reference's ds_* primitives (shaders/emulateDouble.h.glsl:59-139), and the
-// native fp64 variant the reference's USE_NATIVE_FP64 switch stands for (emulateDouble.h.glsl:13).
+// native fp64 variant the reference's USE_NATIVE_FP64 switch stands for (emulateDouble.h.glsl:13).  The
+// perturbation variant (MC_PRECISION_PERTURB) lives in mandel_perturb.hip; both run the escape-time loop of mandel_escape.h.
 //
 // Design (MI355X-first, not a translation of the 32x32 Vulkan workgroup):
 //  * one work-item per pixel; a wave64 owns an 8x8 pixel tile (coherent trip counts, and every
@@ -24,6 +25,8 @@
 #include <cstring>
 
 #include "ds_arith.h"
+#include "mandel_escape.h"
+#include "mandel_perturb.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -176,78 +179,6 @@ struct StateF64 {
     static __device__ __forceinline__ bool needs_exact(Acc or_of_high_words) { return or_of_high_words > 0x3fffffffu; }
 };
 
-// Runs the escape-time loop for the 64 pixels of a wave.  Returns n in [0,max_iter] per lane:
-// the number of iterations that did not escape (mandelbrot.comp:40-46).
-//
-// CONVERGED TILES (north_star: "wavefront ballot/any for early-out on converged Mandelbrot tiles").  The iteration is a
-// deterministic map of the state z (c is fixed per lane; sx, sy are functions of z), so an orbit that returns to a value it
-// has held before repeats that stretch for ever.  If lane L has not escaped up to iteration i and z_i == z_j for an earlier
-// j (compared as VALUES: +0 and -0 are interchangeable operands of +, -, x and of the comparison, and a NaN never compares
-// equal), no iteration of the cycle j..i escaped, so none ever will: the shader's loop would run to max_iter and leave
-// n = max_iter — exactly what this lane returns.  Brent's scheme at block granularity: a reference state is kept per lane,
-// compared with the state at the end of a block of U iterations (fp32: 2 compares per 8 iterations) and replaced when the
-// number of comparisons made reaches 1, 2, 4, 8, ...  A wave leaves as soon as every lane has escaped or is known to cycle:
-// at K1 that is 91 % of the interior pixels (median: iteration 88 of 1000), 2.44x fewer issued instructions and
-// 0.38 -> 0.21 ms; the iteration plane is bit-identical (tests, fuzz).  fp32 orbits inside the set collapse
-// onto a short exact cycle near their attractor; the two-float orbits of a deep zoom rarely do (checked every 16 iterations).
-template <class State, int U>
-__device__ __forceinline__ uint32_t escape_time(State& st, uint32_t max_iter, bool valid) {
-    const uint32_t lane = __lane_id();
-    const uint64_t lanebit = 1ull << lane;
-    uint64_t done = ~__ballot(valid);   // lanes outside the image never hold the wave
-    uint32_t n = max_iter;
-    uint32_t i = 0;
-    State ref = st;                     // Brent reference state (z_0 = 0: a cycle through the origin is caught too)
-    uint32_t checks = 0;                // comparisons made so far (wave-uniform)
-    for (; i + U <= max_iter; i += U) {
-        if (i != 0 && (i / (uint32_t)U) % State::kCycleCheckBlocks == 0u) {
-            // cycling lanes are finished with n = max_iter (their state stays on the cycle: harmless to keep iterating)
-            done |= __ballot(st.same_z(ref));
-            if (done == ~0ull) return n;
-            checks++;
-            if ((checks & (checks - 1u)) == 0u) ref = st;   // wave-uniform: at 1, 2, 4, 8, ... comparisons
-        }
-        if (State::kHasFastBlock && i != 0) {   // the first block is evaluated exactly: most tiles escape right there
-            // fast path: U iterations without per-iteration compares/ballots, ONE test per block; the exact
-            // per-iteration ballots below are evaluated (from the saved state) only if some unfinished lane may
-            // have escaped (or, two-float state, may have left the fast arithmetic's precondition)
-            State probe = st;
-            typename State::Acc acc = st.acc_init();
-#pragma unroll
-            for (int k = 0; k < U; k++) probe.advance_fast(acc);
-            if ((__ballot(State::needs_exact(acc)) & ~done) == 0ull) {
-                st = probe;
-                continue;
-            }
-        }
-        uint64_t b[U];
-        uint64_t any = 0;
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            b[k] = __ballot(st.step());
-            any |= b[k];
-        }
-        uint64_t newly = any & ~done;
-        if (newly) {   // wave-uniform: some lane escaped for the first time in this block
-#pragma unroll
-            for (int k = U - 1; k >= 0; k--)
-                if (b[k] & ~done & lanebit) n = i + k;
-            done |= any;
-            if (done == ~0ull) return n;
-        }
-    }
-    for (; i < max_iter; i++) {   // tail: max_iter % U iterations
-        uint64_t b = __ballot(st.step());
-        uint64_t newly = b & ~done;
-        if (newly) {
-            if (newly & lanebit) n = i;
-            done |= b;
-            if (done == ~0ull) return n;
-        }
-    }
-    return n;
-}
-
 template <class State, int U>
 __global__ void __launch_bounds__(64) mandelbrot_kernel(MandelArgs a) {
     // workgroup = one wave = one 8x8 pixel tile, lane = (lx, ly) inside the tile.  Tiles finish anywhere between 1 and
@@ -365,9 +296,11 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (!ctx || !p || (!d_rgba && !d_iters)) return MC_ERR_INVALID_ARGUMENT;
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
-    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64)
+    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64 &&
+        p->precision != MC_PRECISION_PERTURB)
         return MC_ERR_INVALID_ARGUMENT;
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
+    if (p->precision == MC_PRECISION_PERTURB) return perturb_launch(ctx, p, d_rgba, d_iters, s, warm);   // mandel_perturb.hip
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);
         if (rc) return rc;

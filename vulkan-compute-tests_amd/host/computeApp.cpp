@@ -61,6 +61,7 @@ void ComputeApp::init() {
             mc_context_device_info(ctx, name, sizeof(name), &cus, &khz);
             printf("using device %d: %s (%d CUs)\n", deviceIndex, name, cus);
         }
+        contextCreated();
         if (overlapStart)   // the code object, tables and device scratch of the request run() will make, while the caller goes on
             warmThread = std::thread([this, call = warmupCall()] {
                 auto t0 = std::chrono::steady_clock::now();

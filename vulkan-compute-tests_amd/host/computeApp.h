@@ -116,6 +116,9 @@ protected:
     // Apps: mc_context_warmup_* for the request run() will make, bound to copies of everything it reads.  Called by init() on the
     // calling thread; the helper thread runs what it returns.
     virtual std::function<int()> warmupCall() const { return [] { return MC_OK; }; }
+    // Apps: per-context state the request needs (the Mandelbrot app's perturbation orbit), set by init() on the calling thread once the
+    // context exists and before the warm-up helper starts (a context is not thread-safe).
+    virtual void contextCreated() {}
     static void check(int status, const char* what);
     // saveRenderedImage's routes, with the app's conversion (mandelbrotApp.h:159-174 scale 255; pathtracerApp.h:202-243 scale 1 and the
     // 180-degree rotation):

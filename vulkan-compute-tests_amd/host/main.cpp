@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb (perturb: X Y are decimal text)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -39,6 +39,8 @@ int main(int argc, char* argv[]) {
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
+    const char* cxText = "-0.445";   // --precision perturb: the centre as decimal text, verbatim (mc_mandelbrot_orbit_create)
+    const char* cyText = "0";
     bool viewSet = false, largeSpheres = false;
     uint32_t spherePrec = MC_PT_PREC_F32;
     for (int i = 1; i < argc; i++) {
@@ -63,9 +65,9 @@ int main(int argc, char* argv[]) {
         else if (a == "--width") { need(1); width = (uint32_t)atoi(argv[++i]); }
         else if (a == "--height") { need(1); height = (uint32_t)atoi(argv[++i]); }
         else if (a == "--max-iter") { need(1); maxIter = (uint32_t)atoi(argv[++i]); }
-        else if (a == "--centre") { need(2); cx = atof(argv[++i]); cy = atof(argv[++i]); viewSet = true; }
+        else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = true; }
         else if (a == "--scale") { need(2); sx = atof(argv[++i]); sy = atof(argv[++i]); viewSet = true; }
-        else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}}); }
+        else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}}); }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -83,13 +85,22 @@ int main(int argc, char* argv[]) {
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { printf("unknown option %s\n", a.c_str()); exit(EXIT_FAILURE); }
         else pos.push_back(argv[i]);
     }
-    (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec;
+    (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
     app.setMaxIter(maxIter);
     if (viewSet) app.setView(cx, cy, sx, sy);
     app.setPrecision(precision);
+    if (precision == MC_PRECISION_PERTURB) {   // the reference orbit, on the host: a malformed centre ends the run before a device is touched
+        mc_mandelbrot_orbit* orbit = nullptr;
+        const int rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &orbit);
+        if (rc != MC_OK) {
+            printf("--centre %s %s / --scale %g %g: %s (%s)\n", cxText, cyText, sx, sy, mc_error_string(rc), mc_last_error_detail());
+            return EXIT_FAILURE;
+        }
+        app.setOrbit(orbit);   // bound to the context by init(), before the warm-up thread starts
+    }
 #elif defined(PATHTRACER_MODE)
     const int32_t spp = pos.size() > 0 ? atoi(pos[0]) : 500;                           // samples per pixel
     const uint32_t resy = pos.size() > 1 ? static_cast<uint32_t>(atoi(pos[1])) : 600;  // vertical pixel resolution

@@ -25,6 +25,15 @@ struct MandelbrotApp : public ComputeApp {
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
+    // MC_PRECISION_PERTURB: the view is this orbit's (the app owns it); the params' view words are zero.  Bound in contextCreated().
+    void setOrbit(mc_mandelbrot_orbit* o) {
+        if (orbit) mc_mandelbrot_orbit_destroy(orbit);
+        orbit = o;
+        setView(0.0, 0.0, 0.0, 0.0);
+    }
+    ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
+    MandelbrotApp(const MandelbrotApp&) = delete;
+    MandelbrotApp& operator=(const MandelbrotApp&) = delete;
 
     virtual void preRun() override {
         if (!quiet) { printf(" * before createBuffer()\n"); fflush(stdout); }
@@ -39,6 +48,10 @@ struct MandelbrotApp : public ComputeApp {
         return q;
     }
     virtual void createCommandBuffer() override { params = request(); }
+
+    virtual void contextCreated() override {
+        if (orbit) check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
+    }
 
     virtual std::function<int()> warmupCall() const override {   // tables + code object of that request (bit 1: the banded render's second stream)
         return [ctx = ctx, q = request(), how = (gpuPostprocess ? 1 : 0) | (streaming() ? 2 : 0)] { return mc_context_warmup_mandelbrot(ctx, &q, how); };
@@ -92,6 +105,7 @@ private:
     uint32_t resx, resy;
     uint32_t workgroupSize;
     mc_mandelbrot_params params;
+    mc_mandelbrot_orbit* orbit = nullptr;
 };
 
 #endif  // MANDELBROTAPP_H_
