@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
+/* 3, un-bumped additions since: MC_PRECISION_PERTURB with mc_mandelbrot_orbit_* and mc_context_bind_mandelbrot_orbit; then
+ * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192).
+ * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
  * mc_host_alloc / mc_host_free, mc_context_last_timing, math_mode 2, scene-class bit 16; the measurement flag enums moved to
@@ -127,7 +129,35 @@ enum { MC_PRECISION_F32 = 0, MC_PRECISION_DS = 1 /* two-float, emulateDouble.h.g
  *    iteration pixel by pixel, as any finite precision does (DESIGN.md §3.6 gives measured agreement).
  *  - every single-device entry point that takes mc_mandelbrot_params renders it (row tiles, interleaved tiles, MC_MANDEL_ITERS_U16,
  *    _device_async, _rgba8, _banded, mc_context_warmup_mandelbrot).  mc_multi_* refuse it with MC_ERR_UNSUPPORTED: multi-GPU
- *    perturbation is out of scope (no two-GPU machine to test it on). */
+ *    perturbation is out of scope (no two-GPU machine to test it on).
+ *  - the loop above renders every orbit whose min(|scale_x|, |scale_y|) >= 2^-960.  An orbit of mc_mandelbrot_orbit_create_deep below
+ *    that (what tests/mandel_perturb_deep_ref.py restates) renders by RESCALED perturbation instead, in the same
+ *    IEEE double with no contraction.  pow2(k) = ldexp(1.0, k): 0 below 2^-1074, inf above 2^1023; ldexp is correctly rounded
+ *    (subnormals kept); frexp_exp(a) = the e of a = f * 2^e, f in [0.5, 1) (0 for a = 0); fmax/fabs as in C.  T = 2^-500.
+ *      ux = ((double)gx / (double)W - 0.5) * mx;  uy = ((double)gy / (double)H - 0.5) * my;   (the scale is (mx, my) * 2^E: dc = u 2^E)
+ *      w = d = 0, S = E, scaled = 1, m = 0, zm = Z[0]; for i in [0, M):          (delta = w * 2^S exactly; d = ldexp(w, S))
+ *        if (scaled && zm == (0, 0)) {                                            (a fresh exponent at Z_m = 0)
+ *          S' = max(2S, E);  px = pow2(2S - S');  pu = pow2(E - S');
+ *          nwx = (((wx * wx) - (wy * wy)) * px) + (ux * pu);  nwy = (((wx * wy) + (wy * wx)) * px) + (uy * pu);
+ *        } else {                                                                 (plain phase: S = 0, StatePerturb op for op)
+ *          S' = S;  pu = pow2(E - S);  ax = (zm.x + zm.x) + dx;  ay = (zm.y + zm.y) + dy;
+ *          nwx = ((ax * wx) - (ay * wy)) + (ux * pu);  nwy = ((ax * wy) + (ay * wx)) + (uy * pu);
+ *        }
+ *        ndx = ldexp(nwx, S');  ndy = ldexp(nwy, S');  m = m + 1;  zx = Z[m].x + ndx;  zy = Z[m].y + ndy;  r = (zx * zx) + (zy * zy);
+ *        if (r > 2.0) break;                                                       (n = i)
+ *        if (m == L || r < ((ndx * ndx) + (ndy * ndy))) {                          (rebase: m = 0, zm = Z[0], d = z)
+ *          a = fmax(fabs(zx), fabs(zy));
+ *          if (a >= T) { scaled = 0; S = 0; w = z; }
+ *          else { scaled = 1; S = (a == 0 ? E : frexp_exp(a)); w = (ldexp(zx, -S), ldexp(zy, -S)); }
+ *        } else {
+ *          zm = Z[m];  w = nw;  d = nd;  S = S';
+ *          if (scaled && fmax(fabs(ndx), fabs(ndy)) >= T) { scaled = 0; S = 0; w = nd; }          (enter the plain phase)
+ *          else if (scaled) { a = fmax(fabs(nwx), fabs(nwy));
+ *            if (a > 2^256 || a < 2^-256) { e = frexp_exp(a); w = (ldexp(nwx, -e), ldexp(nwy, -e)); S = S' + e; } }   (renormalise)
+ *        }
+ *    In the plain phase this is the loop above with dc = u * pow2(E) (for an orbit of the old scale, E = 0: exactly it).  A term that
+ *    underflows is dropped harmlessly: |2 Z_m| >= 2^-959 whenever Z_m is nonzero (the tiny-entry refusal below), and in the plain
+ *    phase |delta| >= T or a rebase has reset it.  No cycle exit, as above. */
 #define MC_PRECISION_PERTURB 3u
 
 /* The reference orbit of MC_PRECISION_PERTURB.  Host only: touches no device, usable without a GPU.
@@ -143,12 +173,24 @@ enum { MC_PRECISION_F32 = 0, MC_PRECISION_DS = 1 /* two-float, emulateDouble.h.g
  *  - Z_0 = 0, Z_{j+1} = Z_j^2 + c_ref; L = the first j >= 1 with |Z_j|^2 > 2 in that precision, or max_iter if there is none.  The table
  *    holds Z_0 .. Z_L, each part rounded to the nearest double (ties to even).  Three multi-limb products per iteration: measured in
  *    DESIGN.md §3.6.
+ * mc_mandelbrot_orbit_create_deep: the same orbit for the scale (scale_x * 2^scale_exp2, scale_y * 2^scale_exp2), exact for any
+ * int32 exponent.  The mantissas must be finite and nonzero (MC_ERR_INVALID_ARGUMENT); min |scale| < 2^-8192 is MC_ERR_UNSUPPORTED
+ * (the fixed point stops at 130 fractional limbs); bits is the formula above, from the frexp exponents plus scale_exp2, and the centre
+ * rules are the same.  When both scales are doubles and min |scale| >= 2^-960 the orbit IS mc_mandelbrot_orbit_create's for
+ * (scale_x * 2^scale_exp2, scale_y * 2^scale_exp2) and renders by the loop above (a scale above the double range there:
+ * MC_ERR_UNSUPPORTED).  Below 2^-960 the orbit is DEEP and renders by the rescaled loop, with one more refusal, beside "a reference
+ * on the hair": an entry Z_j (1 <= j <= L) that is nonzero with both parts below 2^-960 in magnitude is MC_ERR_UNSUPPORTED
+ * (mc_last_error_detail names j).  The table stays double2, and such an entry cannot be rounded to a double without losing the offset
+ * the view resolves: it happens when the centre sits on a nucleus far more closely than the view needs.  Exactly zero entries are
+ * exact and accepted (centre 0; centre -1, orbit 0, -1, 0, ...).
  * mc_mandelbrot_orbit_copy writes (length + 1) * 2 doubles (re, im per entry).  mc_context_bind_mandelbrot_orbit copies the table to the
  * context's device after draining the context's launch streams (a running launch never sees it replaced); the orbit object may be
  * destroyed afterwards.  NULL unbinds. */
 typedef struct mc_mandelbrot_orbit mc_mandelbrot_orbit;
 int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y,
                                uint32_t max_iter, mc_mandelbrot_orbit** out);
+int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                                    uint32_t max_iter, mc_mandelbrot_orbit** out);
 int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o);
 int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits);
 int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z /* (length+1)*2: re, im */);

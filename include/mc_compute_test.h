@@ -18,7 +18,11 @@ extern "C" {
  *      MC_PT_MATH_FAST the kernels selected by different flags are different instruction sequences that agree within the
  *      fast-math tolerance. */
 enum {
-    MC_MANDEL_FMA = 1u << 0       /* NON-PARITY: allow fp contraction in the fp32 Mandelbrot loop */
+    MC_MANDEL_FMA = 1u << 0,      /* NON-PARITY: allow fp contraction in the fp32 Mandelbrot loop */
+    /* bit 1 is MC_MANDEL_ITERS_U16 (include/mc_compute.h) */
+    MC_MANDEL_PERTURB_FORCE_DEEP = 1u << 2 /* MC_PRECISION_PERTURB: render any bound orbit with the deep kernel (the rescaled    */
+                                           /* loop of include/mc_compute.h) — how the tests check that its plain phase is        */
+                                           /* StatePerturb bit for bit.  Shipped code never sets it                               */
 };
 enum {
     MC_PT_GENERIC_KERNEL = 1u << 0, /* never use the axis-aligned-slab specialisation of the plane test */

@@ -5,6 +5,8 @@ the product's host layer is the C++ code in host/.  There is NO CPU fallback: if
 missing or no GPU is visible, the calls fail loudly.
 """
 import ctypes as C
+import fractions
+import math
 import os
 import re
 
@@ -19,6 +21,7 @@ ABI_VERSION = 3   # MC_ABI_VERSION of include/mc_compute.h this binding is writt
 PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB = 0, 1, 2, 3
 PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
+MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format
 PT_GENERIC_KERNEL = 1
 PT_NO_BOX_KERNEL = 4    # fast math: the general slab kernel instead of the closed-box ones
@@ -127,6 +130,9 @@ def lib():
             L.mc_mandelbrot_orbit_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
             L.mc_mandelbrot_orbit_copy.argtypes = [vp, vp]
             L.mc_context_bind_mandelbrot_orbit.argtypes = [vp, vp]
+        if hasattr(L, "mc_mandelbrot_orbit_create_deep"):
+            L.mc_mandelbrot_orbit_create_deep.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, u32,
+                                                          C.POINTER(vp)]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -305,19 +311,49 @@ def pathtrace_scene_class(planes, spheres):
     return int(out.value)
 
 
+def scale_from_text(text):
+    """A decimal scale as (mantissa, exp2) with text = mantissa * 2^exp2 to the nearest double mantissa (ties to even), the mantissa in
+    [0.5, 1] in magnitude: any depth, far below the doubles (the scale arguments of Orbit(..., scale_exp2=...))."""
+    v = fractions.Fraction(text.strip())
+    if v == 0:
+        raise ValueError(f"scale_from_text: {text!r} is zero")
+    a = abs(v)
+    e = a.numerator.bit_length() - a.denominator.bit_length()   # 2^(e-1) <= a < 2^(e+1)
+    if a >= fractions.Fraction(2) ** e:
+        e += 1                                                    # now 2^(e-1) <= a < 2^e
+    m = float(a / fractions.Fraction(2) ** e)                     # correctly rounded (int / int true division)
+    return (-m if v < 0 else m), e
+
+
 class Orbit:
     """mc_mandelbrot_orbit: the reference orbit of MC_PRECISION_PERTURB, computed on the host (no device needed) from the centre as
-    decimal text (str, taken verbatim) and the scale as doubles.  A context manager; Context.bind_mandelbrot_orbit copies it to a device."""
+    decimal text (str, taken verbatim) and the scale as doubles.  A context manager; Context.bind_mandelbrot_orbit copies it to a device.
+    scale_exp2=None: mc_mandelbrot_orbit_create.  An integer: mc_mandelbrot_orbit_create_deep, the scale (scale_x, scale_y) * 2^scale_exp2
+    (scale_from_text makes the pair from text).  `deep`: the orbit renders by the rescaled loop (min |scale| < 2^-960); then `scale`
+    holds the mantissas and `scale_exp2` the exponent, otherwise `scale` holds the doubles and `scale_exp2` is 0 (or None)."""
 
-    def __init__(self, centre_x, centre_y, scale_x, scale_y, max_iter):
+    def __init__(self, centre_x, centre_y, scale_x, scale_y, max_iter, scale_exp2=None):
         enc = lambda v: v.encode() if isinstance(v, str) else v
         self._h = C.c_void_p()
-        _check(lib().mc_mandelbrot_orbit_create(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), int(max_iter),
-                                                C.byref(self._h)), "mc_mandelbrot_orbit_create")
+        self.deep = False
+        if scale_exp2 is None:
+            _check(lib().mc_mandelbrot_orbit_create(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), int(max_iter),
+                                                    C.byref(self._h)), "mc_mandelbrot_orbit_create")
+            self.scale = (float(scale_x), float(scale_y))
+        else:
+            E = int(scale_exp2)
+            _check(lib().mc_mandelbrot_orbit_create_deep(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), E,
+                                                         int(max_iter), C.byref(self._h)), "mc_mandelbrot_orbit_create_deep")
+            emin = min(math.frexp(abs(float(scale_x))), math.frexp(abs(float(scale_y))), key=lambda fe: (fe[1], fe[0]))[1] + E
+            self.deep = emin < -959
+            if self.deep:
+                self.scale = (float(scale_x), float(scale_y))
+            else:
+                self.scale, E = (math.ldexp(float(scale_x), E), math.ldexp(float(scale_y), E)), 0
+        self.scale_exp2 = None if scale_exp2 is None else E
         n, m, b = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().mc_mandelbrot_orbit_info(self._h, C.byref(n), C.byref(m), C.byref(b)), "mc_mandelbrot_orbit_info")
         self.length, self.max_iter, self.bits = n.value, m.value, b.value
-        self.scale = (float(scale_x), float(scale_y))
 
     def table(self):
         """Z_0 .. Z_L as an (L + 1, 2) float64 array (re, im)."""

@@ -10,4 +10,20 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
 // mc_context_destroy: the context's bound orbit, if any, is freed.
 void perturb_release(mc_context* ctx);
 
+// The deep kernel (mandel_perturb_deep.hip): orbits with min |scale| < 2^-960, or any orbit under MC_MANDEL_PERTURB_FORCE_DEEP.
+// perturb_launch builds the arguments (the dc table holds the scale's mantissas: u = ((double)g / (double)n - 0.5) * mantissa).
+struct PerturbDeepArgs {
+    uint32_t W, H, max_iter, L;
+    uint32_t row_begin, row_end, row_block, row_stride;
+    float4* out_rgba;                // tile-local, may be null
+    uint32_t* out_iters;             // tile-local, may be null
+    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
+    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
+    const double* u_tab;             // [ux[W] | uy[H]]
+    const double2* orbit;            // Z_0 .. Z_L
+    int32_t exp2;                    // E: the pixel's offset is u * 2^E
+    uint32_t has_zero;               // some Z_j = 0 exactly, 1 <= j < L (centres such as 0 and -1)
+};
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s);
+
 }  // namespace mc

@@ -22,9 +22,10 @@
 // ---- host: multi-limb fixed point -----------------------------------------------------------------------------------------------
 namespace {
 
-// Sign and magnitude; m[0 .. k-1] the fractional limbs (least significant first), m[k] the integer limb.  k <= 17: 1088 >= 1056
-// fractional bits, the most a scale of 2^-960 asks for.
-constexpr int kMaxFrac = 17;
+// Sign and magnitude; m[0 .. k-1] the fractional limbs (least significant first), m[k] the integer limb.  k <= 130: 8320 >= 8288
+// fractional bits, the most a scale of 2^-8192 asks for (mc_mandelbrot_orbit_create_deep).  Every loop runs over the k + 1 limbs in
+// use, never the whole array: a shallow orbit (k = 2 or 3) does the same work as with a 17-limb array.
+constexpr int kMaxFrac = 130;
 struct Fix {
     uint64_t m[kMaxFrac + 1];
     bool neg;
@@ -62,15 +63,19 @@ struct FixOps {
         else { bool s = b.neg; sub_mag(b.m, a.m, r.m, n()); r.neg = s; }
         if (is_zero(r)) r.neg = false;
     }
+    // r = a - b: a + b with b's sign flipped (no copy of b).  r may alias a or b.
     void sub(const Fix& a, const Fix& b, Fix& r) const {
-        Fix nb = b;
-        nb.neg = !b.neg && !is_zero(b);
-        add(a, nb, r);
+        const bool bneg = !b.neg && !is_zero(b);
+        if (a.neg == bneg) { add_mag(a.m, b.m, r.m, n()); r.neg = a.neg; }
+        else if (cmp_mag(a, b) >= 0) { bool s = a.neg; sub_mag(a.m, b.m, r.m, n()); r.neg = s; }
+        else { sub_mag(b.m, a.m, r.m, n()); r.neg = bneg; }
+        if (is_zero(r)) r.neg = false;
     }
     // r = a * b rounded to nearest (ties away from zero) at the last fractional bit.  The integer part stays below 2^64 (|Z| <= 8).
     void mul(const Fix& a, const Fix& b, Fix& r) const {
         const int nn = n();
-        uint64_t p[2 * (kMaxFrac + 1)] = {};
+        uint64_t p[2 * (kMaxFrac + 1)];
+        std::memset(p, 0, 2 * nn * sizeof(uint64_t));   // the 2(k + 1) limbs in use only
         for (int i = 0; i < nn; i++) {
             unsigned __int128 c = 0;
             const uint64_t ai = a.m[i];
@@ -210,8 +215,77 @@ bool parse_decimal(const char* s, const FixOps& ops, Fix& out) {
 struct mc_mandelbrot_orbit {
     std::vector<double> z;   // (L + 1) * 2: re, im
     uint32_t length = 0, max_iter = 0, bits = 0;
-    double scale_x = 0.0, scale_y = 0.0;
+    double scale_x = 0.0, scale_y = 0.0;   // the scale as doubles; a deep orbit: the mantissas
+    int32_t scale_exp2 = 0;                // a deep orbit: the scale is (scale_x, scale_y) * 2^scale_exp2
+    bool deep = false;                     // min |scale| < 2^-960: rendered by the deep kernel (mandel_perturb_deep.hip)
 };
+
+namespace {
+
+// The orbit of both constructors.  bits and the refusal of scales below the floor are decided by the caller; deep = the tiny-entry
+// refusal of include/mc_compute.h applies.  `fn` names the entry point in the error detail.
+int make_orbit(const char* fn, const char* centre_x, const char* centre_y, int64_t bits, bool below_floor, bool deep,
+               uint32_t max_iter, mc_mandelbrot_orbit** out, mc_mandelbrot_orbit** made) {
+    auto refuse = [fn](const char* why) {
+        mc::set_error_detail(std::string(fn) + ": " + why);
+        return MC_ERR_INVALID_ARGUMENT;
+    };
+    FixOps ops{(int)((bits + 63) / 64)};
+    Fix cx, cy;
+    if (ops.k > kMaxFrac) ops.k = kMaxFrac;          // (only reached below the floor, refused after the strings are checked)
+    if (!parse_decimal(centre_x, ops, cx))
+        return refuse("centre_x is not a decimal of at most 4096 characters with |value| <= 4");
+    if (!parse_decimal(centre_y, ops, cy))
+        return refuse("centre_y is not a decimal of at most 4096 characters with |value| <= 4");
+    if (below_floor) {
+        mc::set_error_detail(std::string(fn) + (deep ? ": scale below 2^-8192 (the orbit's fixed point would need more than 130 limbs)"
+                                                     : ": scale below 2^-960 (pixel offsets would leave the normal doubles)"));
+        return MC_ERR_UNSUPPORTED;
+    }
+    mc_mandelbrot_orbit* o = new (std::nothrow) mc_mandelbrot_orbit();
+    if (!o) return MC_ERR_OUT_OF_MEMORY;
+    const double tiny = std::ldexp(1.0, -960);
+    try {
+        o->z.reserve(2 * ((size_t)max_iter + 1) < 2 * 65536 ? 2 * ((size_t)max_iter + 1) : 2 * 65536);
+        Fix zx, zy, sx, sy, t;
+        ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
+        o->z.push_back(0.0); o->z.push_back(0.0);
+        uint32_t L = max_iter;
+        for (uint32_t j = 0; j < max_iter; j++) {
+            ops.mul(zx, zy, t);                           // Z_{j+1} = Z_j^2 + c_ref
+            ops.twice(t);
+            ops.add(t, cy, zy);
+            ops.sub(sx, sy, t);
+            ops.add(t, cx, zx);
+            const double dx = ops.to_double(zx), dy = ops.to_double(zy);
+            if (deep && std::fabs(dx) < tiny && std::fabs(dy) < tiny && !(ops.is_zero(zx) && ops.is_zero(zy))) {
+                delete o;
+                mc::set_error_detail(std::string(fn) + ": orbit entry Z_" + std::to_string(j + 1) +
+                                     " is nonzero with both parts below 2^-960 (the centre sits on a nucleus far more closely than"
+                                     " the view needs; the double table cannot hold that entry)");
+                return MC_ERR_UNSUPPORTED;
+            }
+            o->z.push_back(dx);
+            o->z.push_back(dy);
+            ops.mul(zx, zx, sx);
+            ops.mul(zy, zy, sy);
+            ops.add(sx, sy, t);
+            if (ops.above_two(t)) { L = j + 1; break; }
+        }
+        o->length = L;
+    } catch (const std::bad_alloc&) {
+        delete o;
+        return MC_ERR_OUT_OF_MEMORY;
+    }
+    o->max_iter = max_iter;
+    o->bits = (uint32_t)bits;
+    o->deep = deep;
+    *made = o;
+    *out = o;
+    return MC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -231,48 +305,54 @@ int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, doubl
     (void)std::frexp(smin, &e);                      // smin = f * 2^e, f in [0.5, 1): ceil(-log2 smin) = 1 - e exactly
     int64_t bits = (int64_t)1 - e + 96;
     if (bits < 64) bits = 64;
-    FixOps ops{(int)((bits + 63) / 64)};
-    Fix cx, cy;
-    if (ops.k > kMaxFrac) ops.k = kMaxFrac;          // (only reached below 2^-960, refused after the strings are checked)
-    if (!parse_decimal(centre_x, ops, cx))
-        return refuse("centre_x is not a decimal of at most 4096 characters with |value| <= 4");
-    if (!parse_decimal(centre_y, ops, cy))
-        return refuse("centre_y is not a decimal of at most 4096 characters with |value| <= 4");
-    if (smin < std::ldexp(1.0, -960)) {
-        mc::set_error_detail("mc_mandelbrot_orbit_create: scale below 2^-960 (pixel offsets would leave the normal doubles)");
-        return MC_ERR_UNSUPPORTED;
-    }
-    mc_mandelbrot_orbit* o = new (std::nothrow) mc_mandelbrot_orbit();
-    if (!o) return MC_ERR_OUT_OF_MEMORY;
-    try {
-        o->z.reserve(2 * ((size_t)max_iter + 1) < 2 * 65536 ? 2 * ((size_t)max_iter + 1) : 2 * 65536);
-        Fix zx, zy, sx, sy, t;
-        ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
-        o->z.push_back(0.0); o->z.push_back(0.0);
-        uint32_t L = max_iter;
-        for (uint32_t j = 0; j < max_iter; j++) {
-            ops.mul(zx, zy, t);                           // Z_{j+1} = Z_j^2 + c_ref
-            ops.twice(t);
-            ops.add(t, cy, zy);
-            ops.sub(sx, sy, t);
-            ops.add(t, cx, zx);
-            o->z.push_back(ops.to_double(zx));
-            o->z.push_back(ops.to_double(zy));
-            ops.mul(zx, zx, sx);
-            ops.mul(zy, zy, sy);
-            ops.add(sx, sy, t);
-            if (ops.above_two(t)) { L = j + 1; break; }
-        }
-        o->length = L;
-    } catch (const std::bad_alloc&) {
-        delete o;
-        return MC_ERR_OUT_OF_MEMORY;
-    }
-    o->max_iter = max_iter;
-    o->bits = (uint32_t)bits;
+    mc_mandelbrot_orbit* o = nullptr;
+    const int rc = make_orbit("mc_mandelbrot_orbit_create", centre_x, centre_y, bits, smin < std::ldexp(1.0, -960), false, max_iter,
+                              out, &o);
+    if (rc) return rc;
     o->scale_x = scale_x;
     o->scale_y = scale_y;
-    *out = o;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                                    uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    auto refuse = [](const char* why) {
+        mc::set_error_detail(std::string("mc_mandelbrot_orbit_create_deep: ") + why);
+        return MC_ERR_INVALID_ARGUMENT;
+    };
+    if (!out || !centre_x || !centre_y) return refuse("NULL argument");
+    if (max_iter == 0) return refuse("max_iter must be at least 1");
+    *out = nullptr;
+    if (!std::isfinite(scale_x) || !std::isfinite(scale_y) || scale_x == 0.0 || scale_y == 0.0)
+        return refuse("scale_x and scale_y must be finite and nonzero");
+    // min |scale| = f * 2^emin, f in [0.5, 1), from the mantissas' frexp exponents plus scale_exp2 (64-bit: no overflow)
+    int ex = 0, ey = 0;
+    const double fx = std::frexp(std::fabs(scale_x), &ex), fy = std::frexp(std::fabs(scale_y), &ey);
+    const int64_t emin = (ex < ey || (ex == ey && fx <= fy) ? (int64_t)ex : (int64_t)ey) + scale_exp2;
+    int64_t bits = 1 - emin + 96;
+    if (bits < 64) bits = 64;
+    const bool deep = emin < -959;                   // min |scale| < 2^-960
+    double sx = scale_x, sy = scale_y;
+    if (!deep) {                                     // the scale is a double of at least 2^-960: exactly mc_mandelbrot_orbit_create
+        const int64_t emax = (ex > ey ? ex : ey) + (int64_t)scale_exp2;
+        if (emax > 1024) {
+            mc::set_error_detail("mc_mandelbrot_orbit_create_deep: scale above the double range");
+            return MC_ERR_UNSUPPORTED;
+        }
+        sx = std::ldexp(scale_x, scale_exp2);        // exact: both results are normal doubles
+        sy = std::ldexp(scale_y, scale_exp2);
+        if (!std::isfinite(sx) || !std::isfinite(sy)) {
+            mc::set_error_detail("mc_mandelbrot_orbit_create_deep: scale above the double range");
+            return MC_ERR_UNSUPPORTED;
+        }
+        return mc_mandelbrot_orbit_create(centre_x, centre_y, sx, sy, max_iter, out);
+    }
+    mc_mandelbrot_orbit* o = nullptr;
+    const int rc = make_orbit("mc_mandelbrot_orbit_create_deep", centre_x, centre_y, bits, emin < -8191, true, max_iter, out, &o);
+    if (rc) return rc;
+    o->scale_x = scale_x;
+    o->scale_y = scale_y;
+    o->scale_exp2 = scale_exp2;
     return MC_OK;
 }
 
@@ -306,7 +386,10 @@ namespace {
 struct Binding {
     DeviceBuffer orbit;                // Z_0 .. Z_L, double2
     uint32_t length = 0, max_iter = 0;
-    double scale_x = 0.0, scale_y = 0.0;
+    double scale_x = 0.0, scale_y = 0.0;   // a deep orbit: the mantissas
+    int32_t scale_exp2 = 0;
+    bool deep = false;                 // rendered by the deep kernel (mandel_perturb_deep.hip)
+    bool has_zero = false;             // some Z_j = 0 exactly, 1 <= j < L
     uint32_t generation = 0;           // a new value per bind, part of the dc table's cache key
 };
 std::mutex g_bind_mutex;
@@ -488,6 +571,12 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         grid = dim3(1, 1);
         a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
     }
+    if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
+        const PerturbDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
+                                   a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit, b->scale_exp2, b->has_zero ? 1u : 0u};
+        if ((rc = perturb_deep_launch(d, grid, s))) return rc;
+        return ctx->note_launch(s);
+    }
     hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
@@ -529,5 +618,10 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
     b->max_iter = o->max_iter;
     b->scale_x = o->scale_x;
     b->scale_y = o->scale_y;
+    b->scale_exp2 = o->scale_exp2;
+    b->deep = o->deep;
+    b->has_zero = false;
+    for (uint32_t j = 1; j < o->length; j++)
+        if (o->z[2 * j] == 0.0 && o->z[2 * j + 1] == 0.0) { b->has_zero = true; break; }
     return MC_OK;
 }

@@ -3,11 +3,13 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb (perturb: X Y are decimal text)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb (perturb: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
 #include <chrono>
+#include <cmath>
+#include <cmath>
 #include <cstdlib>
 #include <initializer_list>
 #include <utility>
@@ -41,6 +43,8 @@ int main(int argc, char* argv[]) {
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
     const char* cxText = "-0.445";   // --precision perturb: the centre as decimal text, verbatim (mc_mandelbrot_orbit_create)
     const char* cyText = "0";
+    const char* sxText = "2.34";     // --precision perturb: the scale as text too (strtold reaches about 1e-4951; atof stops at 1e-308)
+    const char* syText = "2.34";
     bool viewSet = false, largeSpheres = false;
     uint32_t spherePrec = MC_PT_PREC_F32;
     for (int i = 1; i < argc; i++) {
@@ -66,7 +70,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--height") { need(1); height = (uint32_t)atoi(argv[++i]); }
         else if (a == "--max-iter") { need(1); maxIter = (uint32_t)atoi(argv[++i]); }
         else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = true; }
-        else if (a == "--scale") { need(2); sx = atof(argv[++i]); sy = atof(argv[++i]); viewSet = true; }
+        else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = true; }
         else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}}); }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
@@ -85,7 +89,7 @@ int main(int argc, char* argv[]) {
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { printf("unknown option %s\n", a.c_str()); exit(EXIT_FAILURE); }
         else pos.push_back(argv[i]);
     }
-    (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText;
+    (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
@@ -94,9 +98,25 @@ int main(int argc, char* argv[]) {
     app.setPrecision(precision);
     if (precision == MC_PRECISION_PERTURB) {   // the reference orbit, on the host: a malformed centre ends the run before a device is touched
         mc_mandelbrot_orbit* orbit = nullptr;
-        const int rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &orbit);
+        // a scale below 2^-960 takes the deep constructor: (mantissa, exponent) from long double text, common exponent of the smaller
+        char* endx = nullptr;
+        char* endy = nullptr;
+        const long double lx = strtold(sxText, &endx), ly = strtold(syText, &endy);
+        if (endx == sxText || *endx || endy == syText || *endy) {
+            printf("--scale %s %s: not two decimal numbers\n", sxText, syText);
+            return EXIT_FAILURE;
+        }
+        const long double lmin = fabsl(lx) < fabsl(ly) ? fabsl(lx) : fabsl(ly);
+        int rc;
+        if (lmin != 0.0L && lmin < ldexpl(1.0L, -960)) {
+            int e = 0;
+            (void)frexpl(lmin, &e);
+            rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &orbit);
+        } else {
+            rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &orbit);
+        }
         if (rc != MC_OK) {
-            printf("--centre %s %s / --scale %g %g: %s (%s)\n", cxText, cyText, sx, sy, mc_error_string(rc), mc_last_error_detail());
+            printf("--centre %s %s / --scale %s %s: %s (%s)\n", cxText, cyText, sxText, syText, mc_error_string(rc), mc_last_error_detail());
             return EXIT_FAILURE;
         }
         app.setOrbit(orbit);   // bound to the context by init(), before the warm-up thread starts
