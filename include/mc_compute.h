@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 /* 3, un-bumped additions since: MC_PRECISION_PERTURB with mc_mandelbrot_orbit_* and mc_context_bind_mandelbrot_orbit; then
- * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192).
+ * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192); then MC_PRECISION_PERTURB_BLA with mc_mandelbrot_orbit_bla and
+ * mc_mandelbrot_orbit_bla_copy.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -195,6 +196,46 @@ int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o);
 int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits);
 int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z /* (length+1)*2: re, im */);
 int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o);   /* NULL unbinds */
+
+/* MC_PRECISION_PERTURB_BLA (4): MC_PRECISION_PERTURB with bilinear approximation (BLA): one step stands in for 2^k iterations while the
+ * offset is small enough for the linear terms to dominate (what tests/mandel_bla_ref.py restates).
+ *  - view and binding: PERTURB's rules (the eight view words zero, p->max_iter <= the orbit's max_iter, MC_MANDEL_ITERS_U16 needs
+ *    p->max_iter <= 65535: MC_ERR_INVALID_ARGUMENT otherwise), and the bound orbit must carry its table (mc_mandelbrot_orbit_bla before
+ *    mc_context_bind_mandelbrot_orbit): MC_ERR_INVALID_ARGUMENT otherwise.  Orbits with min |scale| >= 2^-960 only: a deep orbit
+ *    (mc_mandelbrot_orbit_create_deep below 2^-960) is MC_ERR_UNSUPPORTED.  mc_multi_* refuse it with MC_ERR_UNSUPPORTED.
+ *  - IEEE double, no contraction, source order, as PERTURB.  N1(v) = |v.x| + |v.y| (>= |v|, submultiplicative for complex products);
+ *    cm = 0.5 * (|sx| + |sy|) with (sx, sy) the orbit's scale (it bounds N1(dc) of every pixel); eps = 2^-53.
+ *  - the table, built on the host from Z_0 .. Z_L; an entry is (A, B, R), A and B complex, R >= 0 a radius:
+ *      level 0: one entry per step j in [1, L-2] (Z_j -> Z_{j+1}):  A = (Z_j.x + Z_j.x, Z_j.y + Z_j.y);  B = (1, 0);
+ *               R = eps * max(|A.x|, |A.y|)
+ *      level k >= 1: an entry at each m = 1 + t * 2^k with m + 2^k <= L-1, composing x = (k-1, m) then y = (k-1, m + 2^(k-1)):
+ *               A.x = (Ay.x * Ax.x) - (Ay.y * Ax.y);  A.y = (Ay.x * Ax.y) + (Ay.y * Ax.x);
+ *               B.x = ((Ay.x * Bx.x) - (Ay.y * Bx.y)) + By.x;  B.y = ((Ay.x * Bx.y) + (Ay.y * Bx.x)) + By.y;
+ *               q = (Ry - (N1(Bx) * cm)) / N1(Ax);
+ *               R = min(Rx, q) if A.x, A.y, B.x, B.y and q are all finite, N1(Ax) > 0 and q > 0;  R = 0 otherwise
+ *    so level k holds floor((L-2) / 2^k) entries (none when L < 3), the levels run while that is >= 1, and R_k(m) <= R_(k-1)(m).
+ *  - per pixel: dc as PERTURB's;  dx = dy = 0, m = 0, i = 0;  while (i < M):
+ *      K = the largest k >= 1 with: m >= 1, (m - 1) divisible by 2^k, m + 2^k <= L-1, i + 2^k <= M and (|dx| + |dy|) < R_k(m)
+ *          (the levels that pass form a prefix 1 .. K, so K may be found by bisection);
+ *      if there is one (a skip), with (A, B) = entry (K, m):
+ *          dx' = ((A.x * dx) - (A.y * dy)) + ((B.x * dcx) - (B.y * dcy));  dy' = ((A.x * dy) + (A.y * dx)) + ((B.x * dcy) + (B.y * dcx));
+ *          d = d';  m = m + 2^K;  i = i + 2^K          (no escape test and no rebase test inside the skip)
+ *      else PERTURB's iteration i exactly (its a, new offset, m = m + 1, z, r; if (r > 2.0) n = i, stop; its rebase rule), then i = i + 1.
+ *    n = M when the loop runs out; the colour is lut[n].  m <= L-1 at the top of every trip.
+ *  - accuracy: a skip drops the d^2 terms of its 2^K iterations; R keeps |d| below about eps |2 Z_j| at every step it spans, so each
+ *    dropped term is below about eps times the linear term beside it.  No escape and no rebase is tested inside a skip: a skip never
+ *    reaches Z_L (m + 2^K <= L-1), but an intermediate z = Z_j + d with |Z_j|^2 within about |d| of 2, or |Z_j| within about |d| of 0,
+ *    is not looked at.  n is this loop's, not PERTURB's; the two differ on pixels where such a test or double rounding decides
+ *    (DESIGN.md §3.8 gives measured agreement).
+ *  - interior pixels follow the orbit by skips until it ends, then run PERTURB's exact iterations: no cycle exit, as PERTURB.
+ * mc_mandelbrot_orbit_bla builds the table once and keeps it in the orbit object (about 2L entries of 5 doubles; host only, no device);
+ * *levels / *entries (either may be NULL) receive its shape.  A deep orbit: MC_ERR_UNSUPPORTED; an allocation failure:
+ * MC_ERR_OUT_OF_MEMORY.  mc_mandelbrot_orbit_bla_copy writes it level-major, (A.x, A.y, B.x, B.y, R) per entry, level k's entry for m at
+ * (sum over j < k of floor((L-2) / 2^j)) + (m - 1) / 2^k; MC_ERR_INVALID_ARGUMENT before mc_mandelbrot_orbit_bla.
+ * mc_context_bind_mandelbrot_orbit uploads the table with the orbit when the orbit has one (PERTURB's bind is unchanged otherwise). */
+#define MC_PRECISION_PERTURB_BLA 4u
+int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries);
+int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out /* entries * 5 */);
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1 /* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */

@@ -18,10 +18,11 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mc_compute.h")
 
 MC_OK = 0
 ABI_VERSION = 3   # MC_ABI_VERSION of include/mc_compute.h this binding is written against
-PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB = 0, 1, 2, 3
+PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB, PRECISION_PERTURB_BLA = 0, 1, 2, 3, 4
 PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
+MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format
 PT_GENERIC_KERNEL = 1
 PT_NO_BOX_KERNEL = 4    # fast math: the general slab kernel instead of the closed-box ones
@@ -133,6 +134,9 @@ def lib():
         if hasattr(L, "mc_mandelbrot_orbit_create_deep"):
             L.mc_mandelbrot_orbit_create_deep.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, u32,
                                                           C.POINTER(vp)]
+        if hasattr(L, "mc_mandelbrot_orbit_bla"):   # MC_PRECISION_PERTURB_BLA
+            L.mc_mandelbrot_orbit_bla.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
+            L.mc_mandelbrot_orbit_bla_copy.argtypes = [vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -359,6 +363,22 @@ class Orbit:
         """Z_0 .. Z_L as an (L + 1, 2) float64 array (re, im)."""
         out = np.empty((self.length + 1, 2), np.float64)
         _check(lib().mc_mandelbrot_orbit_copy(self._h, _ptr(out)), "mc_mandelbrot_orbit_copy")
+        return out
+
+    def bla(self):
+        """mc_mandelbrot_orbit_bla: build the BLA table of MC_PRECISION_PERTURB_BLA once (kept in the orbit; bind afterwards).
+        Returns (levels, entries)."""
+        lv, n = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().mc_mandelbrot_orbit_bla(self._h, C.byref(lv), C.byref(n)), "mc_mandelbrot_orbit_bla")
+        self.bla_levels, self.bla_entries = lv.value, n.value
+        return lv.value, n.value
+
+    def bla_table(self):
+        """The BLA table as an (entries, 5) float64 array, level-major, (A.x, A.y, B.x, B.y, R) per entry (after bla())."""
+        if not hasattr(self, "bla_entries"):
+            raise ValueError("Orbit.bla_table: call bla() first")
+        out = np.empty((self.bla_entries, 5), np.float64)
+        _check(lib().mc_mandelbrot_orbit_bla_copy(self._h, _ptr(out)), "mc_mandelbrot_orbit_bla_copy")
         return out
 
     def close(self):

@@ -26,4 +26,22 @@ struct PerturbDeepArgs {
 };
 int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s);
 
+// MC_PRECISION_PERTURB_BLA (mandel_perturb_bla.hip): PERTURB's loop with bilinear skips, for orbits rendered by the plain loop.
+// perturb_launch builds the arguments from the binding: the dc table is PERTURB's, the BLA table the orbit's (mc_mandelbrot_orbit_bla),
+// level-major with (A.x, A.y, B.x, B.y, R) per entry; level k starts at entry S(L-2) - S((L-2) >> k), S(n) = 2n - popcount(n)
+// (the sum of floor(n / 2^j) over j >= 0), so the kernel needs no offset array.
+struct PerturbBlaArgs {
+    uint32_t W, H, max_iter, L;
+    uint32_t row_begin, row_end, row_block, row_stride;
+    float4* out_rgba;                // tile-local, may be null
+    uint32_t* out_iters;             // tile-local, may be null
+    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
+    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
+    const double* dc_tab;            // [dcx[W] | dcy[H]]
+    const double2* orbit;            // Z_0 .. Z_L
+    const double* bla;               // the BLA table (null when it has no entry: L < 3)
+    uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS: write the loop-trip count in place of n
+};
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s);
+
 }  // namespace mc

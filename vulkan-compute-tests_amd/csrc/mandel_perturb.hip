@@ -218,6 +218,11 @@ struct mc_mandelbrot_orbit {
     double scale_x = 0.0, scale_y = 0.0;   // the scale as doubles; a deep orbit: the mantissas
     int32_t scale_exp2 = 0;                // a deep orbit: the scale is (scale_x, scale_y) * 2^scale_exp2
     bool deep = false;                     // min |scale| < 2^-960: rendered by the deep kernel (mandel_perturb_deep.hip)
+    // MC_PRECISION_PERTURB_BLA: the table of mc_mandelbrot_orbit_bla, level-major (A.x, A.y, B.x, B.y, R) per entry
+    std::vector<double> bla;
+    uint32_t bla_levels = 0;
+    uint64_t bla_entries = 0;
+    bool has_bla = false;                  // built (a table may have no entry: L < 3)
 };
 
 namespace {
@@ -375,6 +380,79 @@ int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z) {
     return MC_OK;
 }
 
+// The BLA table of include/mc_compute.h (MC_PRECISION_PERTURB_BLA), operation by operation.
+int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries) {
+    if (!o) {
+        mc::set_error_detail("mc_mandelbrot_orbit_bla: NULL orbit");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (o->deep) {
+        mc::set_error_detail("mc_mandelbrot_orbit_bla: a deep orbit (min |scale| < 2^-960) renders by the rescaled loop, which has no BLA");
+        return MC_ERR_UNSUPPORTED;
+    }
+    if (!o->has_bla) {
+        const uint64_t n0 = o->length >= 3 ? (uint64_t)o->length - 2 : 0;   // level 0: steps 1 .. L-2
+        uint32_t nlev = 0;
+        uint64_t total = 0;
+        for (; (n0 >> nlev) >= 1; nlev++) total += n0 >> nlev;
+        std::vector<double> t;
+        try {
+            t.resize(5 * total);
+        } catch (const std::bad_alloc&) {
+            mc::set_error_detail("mc_mandelbrot_orbit_bla: the table does not fit in host memory");
+            return MC_ERR_OUT_OF_MEMORY;
+        }
+        const double eps = std::ldexp(1.0, -53);
+        const double cm = 0.5 * (std::fabs(o->scale_x) + std::fabs(o->scale_y));
+        for (uint64_t j = 1; j <= n0; j++) {
+            double* e = &t[5 * (j - 1)];
+            const double zx = o->z[2 * j], zy = o->z[2 * j + 1];
+            e[0] = zx + zx;
+            e[1] = zy + zy;
+            e[2] = 1.0;
+            e[3] = 0.0;
+            e[4] = eps * std::fmax(std::fabs(e[0]), std::fabs(e[1]));
+        }
+        uint64_t prev = 0, off = n0;   // level k-1 starts at prev, level k at off
+        for (uint32_t k = 1; k < nlev; k++) {
+            const uint64_t cnt = n0 >> k;
+            for (uint64_t q = 0; q < cnt; q++) {
+                const double* x = &t[5 * (prev + 2 * q)];       // (k-1, m), m = 1 + q 2^k
+                const double* y = &t[5 * (prev + 2 * q + 1)];   // (k-1, m + 2^(k-1))
+                double* e = &t[5 * (off + q)];
+                e[0] = (y[0] * x[0]) - (y[1] * x[1]);
+                e[1] = (y[0] * x[1]) + (y[1] * x[0]);
+                e[2] = ((y[0] * x[2]) - (y[1] * x[3])) + y[2];
+                e[3] = ((y[0] * x[3]) + (y[1] * x[2])) + y[3];
+                const double na = std::fabs(x[0]) + std::fabs(x[1]);
+                const double nb = std::fabs(x[2]) + std::fabs(x[3]);
+                const double q_ = (y[4] - (nb * cm)) / na;
+                const bool ok = std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2]) && std::isfinite(e[3]) &&
+                                std::isfinite(q_) && na > 0.0 && q_ > 0.0;
+                e[4] = ok ? std::fmin(x[4], q_) : 0.0;
+            }
+            prev = off;
+            off += cnt;
+        }
+        o->bla.swap(t);
+        o->bla_levels = nlev;
+        o->bla_entries = total;
+        o->has_bla = true;
+    }
+    if (levels) *levels = o->bla_levels;
+    if (entries) *entries = o->bla_entries;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out) {
+    if (!o || !out || !o->has_bla) {
+        mc::set_error_detail("mc_mandelbrot_orbit_bla_copy: NULL argument, or no table (mc_mandelbrot_orbit_bla builds it)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (!o->bla.empty()) std::memcpy(out, o->bla.data(), o->bla.size() * sizeof(double));
+    return MC_OK;
+}
+
 }  // extern "C"
 
 namespace mc {
@@ -391,6 +469,12 @@ struct Binding {
     bool deep = false;                 // rendered by the deep kernel (mandel_perturb_deep.hip)
     bool has_zero = false;             // some Z_j = 0 exactly, 1 <= j < L
     uint32_t generation = 0;           // a new value per bind, part of the dc table's cache key
+    // MC_PRECISION_PERTURB_BLA: the orbit's BLA table when it had one at the bind (mc_mandelbrot_orbit_bla).  The per-level offsets
+    // follow from L (mandel_perturb.h); levels / entries are its shape.  An orbit without a table leaves bla unallocated.
+    DeviceBuffer bla;
+    uint32_t bla_levels = 0;
+    uint64_t bla_entries = 0;
+    bool has_bla = false;
 };
 std::mutex g_bind_mutex;
 std::unordered_map<const mc_context*, Binding> g_bindings;
@@ -529,24 +613,34 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
 }  // namespace
 
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm) {
+    const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
+    const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : "MC_PRECISION_PERTURB";
     const Binding* b = find_binding(ctx);
     if (!b || !b->orbit.ptr || !b->length) {
-        set_error_detail("MC_PRECISION_PERTURB: no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
+        set_error_detail(name + ": no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
         return MC_ERR_INVALID_ARGUMENT;
     }
     const float words[8] = {p->centre_x_hi, p->centre_x_lo, p->centre_y_hi, p->centre_y_lo,
                             p->scale_x_hi, p->scale_x_lo, p->scale_y_hi, p->scale_y_lo};
     for (float w : words)
         if (w != 0.0f) {
-            set_error_detail("MC_PRECISION_PERTURB: the view is the bound orbit's; the params' eight view words must be zero");
+            set_error_detail(name + ": the view is the bound orbit's; the params' eight view words must be zero");
             return MC_ERR_INVALID_ARGUMENT;
         }
     if (p->max_iter > b->max_iter) {
-        set_error_detail("MC_PRECISION_PERTURB: max_iter above the bound orbit's");
+        set_error_detail(name + ": max_iter above the bound orbit's");
         return MC_ERR_INVALID_ARGUMENT;
     }
     const bool narrow = (p->flags & MC_MANDEL_ITERS_U16) != 0u;
     if (narrow && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
+    if (bla && b->deep) {
+        set_error_detail(name + ": the bound orbit is deep (min |scale| < 2^-960); BLA covers the plain loop only");
+        return MC_ERR_UNSUPPORTED;
+    }
+    if (bla && !b->has_bla) {
+        set_error_detail(name + ": the bound orbit has no BLA table (mc_mandelbrot_orbit_bla before mc_context_bind_mandelbrot_orbit)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
     PerturbArgs a;
     a.lut = nullptr;
     if (d_rgba || warm) {
@@ -571,6 +665,14 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         grid = dim3(1, 1);
         a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
     }
+    if (bla) {   // mandel_perturb_bla.hip
+        const PerturbBlaArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
+                                  a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
+                                  b->bla_entries ? (const double*)b->bla.ptr : nullptr,
+                                  (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
+        if ((rc = perturb_bla_launch(d, grid, s))) return rc;
+        return ctx->note_launch(s);
+    }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
         const PerturbDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
                                    a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit, b->scale_exp2, b->has_zero ? 1u : 0u};
@@ -587,6 +689,7 @@ void perturb_release(mc_context* ctx) {
     auto it = g_bindings.find(ctx);
     if (it == g_bindings.end()) return;
     it->second.orbit.release();
+    it->second.bla.release();
     g_bindings.erase(it);
 }
 
@@ -609,11 +712,22 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
         b = &mc::g_bindings[ctx];    // the node stays put while other contexts bind (only this context's thread erases it)
         b->generation = ++mc::g_generation;
         b->length = 0;               // unusable until the copy below has completed
+        b->has_bla = false;
     }
     const size_t bytes = o->z.size() * sizeof(double);
     if ((rc = b->orbit.reserve(bytes))) return rc;
     MC_HIP_TRY(hipMemcpyAsync(b->orbit.ptr, o->z.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (o->has_bla && !o->bla.empty()) {   // MC_PRECISION_PERTURB_BLA's table; an orbit without one binds exactly as before
+        const size_t tbytes = o->bla.size() * sizeof(double);
+        if ((rc = b->bla.reserve(tbytes))) return rc;
+        MC_HIP_TRY(hipMemcpyAsync(b->bla.ptr, o->bla.data(), tbytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        b->bla.release();   // (a table left by an earlier bind)
+    }
     MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    b->has_bla = o->has_bla;
+    b->bla_levels = o->bla_levels;
+    b->bla_entries = o->bla_entries;
     b->length = o->length;
     b->max_iter = o->max_iter;
     b->scale_x = o->scale_x;
