@@ -30,7 +30,7 @@ extern "C" {
 
 /* 3, un-bumped additions since: MC_PRECISION_PERTURB with mc_mandelbrot_orbit_* and mc_context_bind_mandelbrot_orbit; then
  * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192); then MC_PRECISION_PERTURB_BLA with mc_mandelbrot_orbit_bla and
- * mc_mandelbrot_orbit_bla_copy.
+ * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -236,6 +236,55 @@ int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit*
 #define MC_PRECISION_PERTURB_BLA 4u
 int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries);
 int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out /* entries * 5 */);
+
+/* MC_PRECISION_PERTURB_BLA_DEEP (5): rescaled perturbation with bilinear skips, for every orbit PERTURB renders, shallow and deep
+ * (what tests/mandel_bla_deep_ref.py restates).  Below 2^-960 A, B and R of the table above leave the double range
+ * (|B| grows to about 2^-E, R shrinks below 2^-1074, cm is 2^E), so the table and the skip are carried in FLOATEXP.
+ *  - floatexp: (x, y) * 2^e with x, y doubles and e an int32, NORMALISED: max(|x|, |y|) in [0.5, 1), or x = y = 0 with e = 0.  A real
+ *    value has y = 0.  norm(x, y, e): a = max(|x|, |y|); a = 0 gives (0, 0, 0); else k = frexp_exp(a), (ldexp(x, -k), ldexp(y, -k), e + k).
+ *    mul: the complex (or real) product of the mantissas in double, source order as below, at the exponent e1 + e2, then norm.
+ *    add(p, q), mantissas in any range: a zero operand (both parts 0) gives norm of the other; else kp = ep + frexp_exp(max|p|),
+ *    kq = eq + frexp_exp(max|q|), e = max(kp, kq), norm(ldexp(px, ep - e) + ldexp(qx, eq - e), ldexp(py, ep - e) + ldexp(qy, eq - e), e).
+ *    less(a, b) for nonnegative reals: b = 0: no; a = 0: yes; else (ea, xa) < (eb, xb) lexicographically.  ldexp and frexp_exp as in
+ *    PERTURB's rescaled loop above.  Each operation is double arithmetic on mantissas followed by exact power-of-two scaling, so wherever
+ *    no mantissa operation (ldexp included) overflows or goes subnormal, a floatexp result IS the plain double result times a power of
+ *    two: on such data this table and loop compute PRECISION_PERTURB_BLA's values bit for bit.
+ *  - the table (mc_mandelbrot_orbit_bla_deep, host only): PERTURB_BLA's levels, entry positions and compositions, every value floatexp;
+ *    cm = norm(0.5 * (|mx| + |my|), 0, E) (E = 0 and (mx, my) = the scale for an orbit of the old scale):
+ *      level 0, step j:  A = norm(Z_j.x + Z_j.x, Z_j.y + Z_j.y, 0);  B = (0.5, 0, 1);  R = (max(|A.x|, |A.y|), 0, e_A - 53), 0 if A = 0
+ *      level k, x = (k-1, m), y = (k-1, m + 2^(k-1)):
+ *        A = norm((Ay.x * Ax.x) - (Ay.y * Ax.y), (Ay.x * Ax.y) + (Ay.y * Ax.x), eAy + eAx);
+ *        B = add(((Ay.x * Bx.x) - (Ay.y * Bx.y), (Ay.x * Bx.y) + (Ay.y * Bx.x), eAy + eBx), By);
+ *        na = |Ax.x| + |Ax.y|;  nb = |Bx.x| + |Bx.y|;  diff = add(Ry, (-(nb * cm.x), 0, eBx + e_cm));
+ *        R = (na > 0 and diff.x > 0) ? min(Rx, norm(diff.x / na, 0, e_diff - eAx)) by less : 0
+ *      and an entry with |e| > 2^20 in A, B or R is stored as A = B = R = 0 (every exponent then 0): exponents stay far from int32
+ *      overflow on long orbits.  As in PERTURB_BLA, R_k(m) <= R_(k-1)(m) and no entry with R > 0 spans a step with Z_j = 0.
+ *  - per pixel: u, E, and the state w, S, scaled, m of PERTURB's rescaled loop (the same start: w = d = 0, S = E, scaled = 1, m = 0);
+ *    i = 0; while (i < M):
+ *      K = PERTURB_BLA's largest level (m >= 1, alignment, m + 2^k <= L-1, i + 2^k <= M) whose radius test holds:
+ *          ldexp(|wx| + |wy|, S - e_R) < R.x       (N1(w) 2^S < R, exact: R.x is 0 or in [0.5, 1))
+ *      if there is one (a skip), with entry (A, B):
+ *          P = ((A.x * wx) - (A.y * wy), (A.x * wy) + (A.y * wx), e_A + S);  Q = ((B.x * ux) - (B.y * uy), (B.x * uy) + (B.y * ux), e_B + E);
+ *          (nx, ny, e) = add(P, Q);  m = m + 2^K;  i = i + 2^K;  no escape or rebase test, then
+ *          n = 0:                                   w = d = 0, S = E, scaled = 1;
+ *          max(|ldexp(nx, e)|, |ldexp(ny, e)|) >= T: d = w = (ldexp(nx, e), ldexp(ny, e)), S = 0, scaled = 0 (the plain phase);
+ *          otherwise:                               w = (nx, ny), S = e, d = (ldexp(nx, e), ldexp(ny, e)), scaled = 1 (w is normalised:
+ *                                                   inside the window, so the window rule changes nothing);
+ *      else the rescaled iteration i above exactly (its fresh-exponent rule at Z_m = 0, escape: n = i, stop; rebase; phase change;
+ *          window), then i = i + 1.
+ *    n = M when the loop runs out; the colour is lut[n].  Since no skip spans a Z_j = 0 step, the fresh-exponent rule stays a rule of
+ *    exact steps.  Accuracy as PERTURB_BLA's (DESIGN.md §3.9 gives measured agreement).
+ *  - view and binding: PERTURB's rules (view words, max_iter, MC_MANDEL_ITERS_U16), and the bound orbit must carry this table
+ *    (mc_mandelbrot_orbit_bla_deep before mc_context_bind_mandelbrot_orbit): MC_ERR_INVALID_ARGUMENT otherwise.  mc_multi_* refuse it
+ *    with MC_ERR_UNSUPPORTED.  Every single-device entry point renders it.
+ * mc_mandelbrot_orbit_bla_deep builds the table once and keeps it in the orbit beside any PERTURB_BLA table (one 64-byte record per
+ * entry); *levels / *entries (either may be NULL) receive its shape.  NULL: MC_ERR_INVALID_ARGUMENT; an allocation failure:
+ * MC_ERR_OUT_OF_MEMORY.  mc_mandelbrot_orbit_bla_deep_copy writes it in PERTURB_BLA's order: (A.x, A.y, B.x, B.y, R.x) per entry to
+ * mant and (e_A, e_B, e_R) to exps; MC_ERR_INVALID_ARGUMENT before mc_mandelbrot_orbit_bla_deep.  mc_context_bind_mandelbrot_orbit
+ * uploads it with the orbit when the orbit has one. */
+#define MC_PRECISION_PERTURB_BLA_DEEP 5u
+int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries);
+int mc_mandelbrot_orbit_bla_deep_copy(const mc_mandelbrot_orbit* o, double* mant /* entries * 5 */, int32_t* exps /* entries * 3 */);
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1 /* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */

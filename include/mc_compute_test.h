@@ -23,9 +23,9 @@ enum {
     MC_MANDEL_PERTURB_FORCE_DEEP = 1u << 2,/* MC_PRECISION_PERTURB: render any bound orbit with the deep kernel (the rescaled    */
                                            /* loop of include/mc_compute.h) — how the tests check that its plain phase is        */
                                            /* StatePerturb bit for bit.  Shipped code never sets it                               */
-    MC_MANDEL_BLA_COUNT_TRIPS = 1u << 3    /* MC_PRECISION_PERTURB_BLA: each pixel's loop-trip count (skips + exact iterations,   */
-                                           /* the escaping one included; in [1, M]) is written in place of n, and the colour is    */
-                                           /* lut[trips] — how the tests see skipping without a timer                              */
+    MC_MANDEL_BLA_COUNT_TRIPS = 1u << 3    /* MC_PRECISION_PERTURB_BLA and _BLA_DEEP: each pixel's loop-trip count (skips + exact */
+                                           /* iterations, the escaping one included; in [1, M]) is written in place of n, and the  */
+                                           /* colour is lut[trips] — how the tests see skipping without a timer                    */
 };
 enum {
     MC_PT_GENERIC_KERNEL = 1u << 0, /* never use the axis-aligned-slab specialisation of the plane test */

@@ -18,7 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mc_compute.h")
 
 MC_OK = 0
 ABI_VERSION = 3   # MC_ABI_VERSION of include/mc_compute.h this binding is written against
-PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB, PRECISION_PERTURB_BLA = 0, 1, 2, 3, 4
+PRECISION_F32, PRECISION_DS, PRECISION_F64, PRECISION_PERTURB, PRECISION_PERTURB_BLA, PRECISION_PERTURB_BLA_DEEP = 0, 1, 2, 3, 4, 5
 PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
@@ -137,6 +137,9 @@ def lib():
         if hasattr(L, "mc_mandelbrot_orbit_bla"):   # MC_PRECISION_PERTURB_BLA
             L.mc_mandelbrot_orbit_bla.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
             L.mc_mandelbrot_orbit_bla_copy.argtypes = [vp, vp]
+        if hasattr(L, "mc_mandelbrot_orbit_bla_deep"):   # MC_PRECISION_PERTURB_BLA_DEEP
+            L.mc_mandelbrot_orbit_bla_deep.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
+            L.mc_mandelbrot_orbit_bla_deep_copy.argtypes = [vp, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -380,6 +383,24 @@ class Orbit:
         out = np.empty((self.bla_entries, 5), np.float64)
         _check(lib().mc_mandelbrot_orbit_bla_copy(self._h, _ptr(out)), "mc_mandelbrot_orbit_bla_copy")
         return out
+
+    def bla_deep(self):
+        """mc_mandelbrot_orbit_bla_deep: build the floatexp BLA table of MC_PRECISION_PERTURB_BLA_DEEP once (kept in the orbit beside any
+        bla() table; bind afterwards).  Returns (levels, entries)."""
+        lv, n = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().mc_mandelbrot_orbit_bla_deep(self._h, C.byref(lv), C.byref(n)), "mc_mandelbrot_orbit_bla_deep")
+        self.bla_deep_levels, self.bla_deep_entries = lv.value, n.value
+        return lv.value, n.value
+
+    def bla_deep_table(self):
+        """The floatexp table as (mantissas (entries, 5) float64: A.x, A.y, B.x, B.y, R; exponents (entries, 3) int32: e_A, e_B, e_R),
+        level-major as bla_table() (after bla_deep())."""
+        if not hasattr(self, "bla_deep_entries"):
+            raise ValueError("Orbit.bla_deep_table: call bla_deep() first")
+        mant = np.empty((self.bla_deep_entries, 5), np.float64)
+        exps = np.empty((self.bla_deep_entries, 3), np.int32)
+        _check(lib().mc_mandelbrot_orbit_bla_deep_copy(self._h, _ptr(mant), _ptr(exps)), "mc_mandelbrot_orbit_bla_deep_copy")
+        return mant, exps
 
     def close(self):
         if self._h:

@@ -44,4 +44,27 @@ struct PerturbBlaArgs {
 };
 int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s);
 
+// MC_PRECISION_PERTURB_BLA_DEEP (mandel_perturb_bla_deep.hip): the rescaled loop of the deep kernel with bilinear skips, for every orbit.
+// The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one 64-byte record, its mantissas and
+// exponents together, so that a probe reads a single record.
+struct BlaDeepRec {
+    double ax, ay, bx, by, r;        // the mantissas: A = (ax, ay) * 2^ea, B = (bx, by) * 2^eb, R = r * 2^er
+    int32_t ea, eb, er, pad[3];
+};
+static_assert(sizeof(BlaDeepRec) == 64, "one table entry is one 64-byte record");
+struct PerturbBlaDeepArgs {
+    uint32_t W, H, max_iter, L;
+    uint32_t row_begin, row_end, row_block, row_stride;
+    float4* out_rgba;                // tile-local, may be null
+    uint32_t* out_iters;             // tile-local, may be null
+    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
+    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
+    const double* u_tab;             // [ux[W] | uy[H]]
+    const double2* orbit;            // Z_0 .. Z_L
+    const BlaDeepRec* bla;           // the table (null when it has no entry: L < 3)
+    int32_t exp2;                    // E: the pixel's offset is u * 2^E (0 for an orbit of the old scale)
+    uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS
+};
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s);
+
 }  // namespace mc

@@ -223,6 +223,11 @@ struct mc_mandelbrot_orbit {
     uint32_t bla_levels = 0;
     uint64_t bla_entries = 0;
     bool has_bla = false;                  // built (a table may have no entry: L < 3)
+    // MC_PRECISION_PERTURB_BLA_DEEP: the floatexp table of mc_mandelbrot_orbit_bla_deep, same layout, one record per entry
+    std::vector<mc::BlaDeepRec> bla_deep;
+    uint32_t bla_deep_levels = 0;
+    uint64_t bla_deep_entries = 0;
+    bool has_bla_deep = false;
 };
 
 namespace {
@@ -444,6 +449,126 @@ int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* 
     return MC_OK;
 }
 
+namespace {
+
+// Floatexp values of MC_PRECISION_PERTURB_BLA_DEEP (include/mc_compute.h): (x, y) * 2^e, normalised (max(|x|, |y|) in [0.5, 1), or
+// x = y = 0 with e = 0).  Exponents are formed in 64 bits here; the table's bound keeps every stored one within +-2^20.
+struct Fx {
+    double x, y;
+    int64_t e;
+};
+Fx fx_norm(double x, double y, int64_t e) {
+    const double a = std::fmax(std::fabs(x), std::fabs(y));
+    if (a == 0.0) return {0.0, 0.0, 0};
+    int k = 0;
+    (void)std::frexp(a, &k);
+    return {std::ldexp(x, -k), std::ldexp(y, -k), e + k};
+}
+// p + q for mantissas in any range: a zero operand yields the other, normalised; otherwise both are aligned with ldexp at the larger of
+// their frexp exponents, added, and the sum normalised.
+Fx fx_add(const Fx& p, const Fx& q) {
+    if (p.x == 0.0 && p.y == 0.0) return fx_norm(q.x, q.y, q.e);
+    if (q.x == 0.0 && q.y == 0.0) return fx_norm(p.x, p.y, p.e);
+    int kp = 0, kq = 0;
+    (void)std::frexp(std::fmax(std::fabs(p.x), std::fabs(p.y)), &kp);
+    (void)std::frexp(std::fmax(std::fabs(q.x), std::fabs(q.y)), &kq);
+    const int64_t e = p.e + kp > q.e + kq ? p.e + kp : q.e + kq;
+    return fx_norm(std::ldexp(p.x, (int)(p.e - e)) + std::ldexp(q.x, (int)(q.e - e)),
+                   std::ldexp(p.y, (int)(p.e - e)) + std::ldexp(q.y, (int)(q.e - e)), e);
+}
+// a < b for normalised nonnegative reals (zero below every positive value)
+bool fx_less(const Fx& a, const Fx& b) {
+    if (b.x == 0.0) return false;
+    if (a.x == 0.0) return true;
+    return a.e < b.e || (a.e == b.e && a.x < b.x);
+}
+constexpr int64_t kFxBound = int64_t(1) << 20;   // an entry with an exponent beyond +-2^20 is stored as zero (R = 0)
+
+}  // namespace
+
+// The floatexp BLA table of include/mc_compute.h (MC_PRECISION_PERTURB_BLA_DEEP), operation by operation.
+int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries) {
+    if (!o) {
+        mc::set_error_detail("mc_mandelbrot_orbit_bla_deep: NULL orbit");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (!o->has_bla_deep) {
+        const uint64_t n0 = o->length >= 3 ? (uint64_t)o->length - 2 : 0;   // level 0: steps 1 .. L-2
+        uint32_t nlev = 0;
+        uint64_t total = 0;
+        for (; (n0 >> nlev) >= 1; nlev++) total += n0 >> nlev;
+        std::vector<mc::BlaDeepRec> t;
+        try {
+            t.resize(total);
+        } catch (const std::bad_alloc&) {
+            mc::set_error_detail("mc_mandelbrot_orbit_bla_deep: the table does not fit in host memory");
+            return MC_ERR_OUT_OF_MEMORY;
+        }
+        auto put = [](mc::BlaDeepRec& r, const Fx& A, const Fx& B, const Fx& R) {
+            const bool out = A.e < -kFxBound || A.e > kFxBound || B.e < -kFxBound || B.e > kFxBound || R.e < -kFxBound || R.e > kFxBound;
+            const Fx z{0.0, 0.0, 0};
+            const Fx& a = out ? z : A;
+            const Fx& b = out ? z : B;
+            const Fx& q = out ? z : R;
+            r.ax = a.x; r.ay = a.y; r.bx = b.x; r.by = b.y; r.r = q.x;
+            r.ea = (int32_t)a.e; r.eb = (int32_t)b.e; r.er = (int32_t)q.e;
+            r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        };
+        auto get = [](const mc::BlaDeepRec& r, Fx& A, Fx& B, Fx& R) {
+            A = {r.ax, r.ay, r.ea}; B = {r.bx, r.by, r.eb}; R = {r.r, 0.0, r.er};
+        };
+        const Fx cm = fx_norm(0.5 * (std::fabs(o->scale_x) + std::fabs(o->scale_y)), 0.0, o->deep ? o->scale_exp2 : 0);
+        for (uint64_t j = 1; j <= n0; j++) {
+            const double zx = o->z[2 * j], zy = o->z[2 * j + 1];
+            const Fx A = fx_norm(zx + zx, zy + zy, 0);
+            const Fx R = A.x == 0.0 && A.y == 0.0 ? Fx{0.0, 0.0, 0} : Fx{std::fmax(std::fabs(A.x), std::fabs(A.y)), 0.0, A.e - 53};
+            put(t[j - 1], A, Fx{0.5, 0.0, 1}, R);
+        }
+        uint64_t prev = 0, off = n0;   // level k-1 starts at prev, level k at off
+        for (uint32_t k = 1; k < nlev; k++) {
+            const uint64_t cnt = n0 >> k;
+            for (uint64_t q = 0; q < cnt; q++) {
+                Fx xa, xb, xr, ya, yb, yr;
+                get(t[prev + 2 * q], xa, xb, xr);       // (k-1, m), m = 1 + q 2^k
+                get(t[prev + 2 * q + 1], ya, yb, yr);   // (k-1, m + 2^(k-1))
+                const Fx A = fx_norm((ya.x * xa.x) - (ya.y * xa.y), (ya.x * xa.y) + (ya.y * xa.x), ya.e + xa.e);
+                const Fx B = fx_add(Fx{(ya.x * xb.x) - (ya.y * xb.y), (ya.x * xb.y) + (ya.y * xb.x), ya.e + xb.e}, yb);
+                const double na = std::fabs(xa.x) + std::fabs(xa.y);
+                const double nb = std::fabs(xb.x) + std::fabs(xb.y);
+                const Fx diff = fx_add(yr, Fx{-(nb * cm.x), 0.0, xb.e + cm.e});   // Ry - N1(Bx) cm
+                Fx R{0.0, 0.0, 0};
+                if (na > 0.0 && diff.x > 0.0) {
+                    const Fx qv = fx_norm(diff.x / na, 0.0, diff.e - xa.e);
+                    R = fx_less(qv, xr) ? qv : xr;                                 // min(Rx, q); Rx = 0 gives 0
+                }
+                put(t[off + q], A, B, R);
+            }
+            prev = off;
+            off += cnt;
+        }
+        o->bla_deep.swap(t);
+        o->bla_deep_levels = nlev;
+        o->bla_deep_entries = total;
+        o->has_bla_deep = true;
+    }
+    if (levels) *levels = o->bla_deep_levels;
+    if (entries) *entries = o->bla_deep_entries;
+    return MC_OK;
+}
+
+int mc_mandelbrot_orbit_bla_deep_copy(const mc_mandelbrot_orbit* o, double* mant, int32_t* exps) {
+    if (!o || !mant || !exps || !o->has_bla_deep) {
+        mc::set_error_detail("mc_mandelbrot_orbit_bla_deep_copy: NULL argument, or no table (mc_mandelbrot_orbit_bla_deep builds it)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    for (size_t j = 0; j < o->bla_deep.size(); j++) {
+        const mc::BlaDeepRec& r = o->bla_deep[j];
+        mant[5 * j] = r.ax; mant[5 * j + 1] = r.ay; mant[5 * j + 2] = r.bx; mant[5 * j + 3] = r.by; mant[5 * j + 4] = r.r;
+        exps[3 * j] = r.ea; exps[3 * j + 1] = r.eb; exps[3 * j + 2] = r.er;
+    }
+    return MC_OK;
+}
+
 int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out) {
     if (!o || !out || !o->has_bla) {
         mc::set_error_detail("mc_mandelbrot_orbit_bla_copy: NULL argument, or no table (mc_mandelbrot_orbit_bla builds it)");
@@ -475,6 +600,10 @@ struct Binding {
     uint32_t bla_levels = 0;
     uint64_t bla_entries = 0;
     bool has_bla = false;
+    // MC_PRECISION_PERTURB_BLA_DEEP: the orbit's floatexp table when it had one at the bind (mc_mandelbrot_orbit_bla_deep), likewise
+    DeviceBuffer bla_deep;
+    uint64_t bla_deep_entries = 0;
+    bool has_bla_deep = false;
 };
 std::mutex g_bind_mutex;
 std::unordered_map<const mc_context*, Binding> g_bindings;
@@ -614,7 +743,8 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
 
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm) {
     const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
-    const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : "MC_PRECISION_PERTURB";
+    const bool bla_deep = p->precision == MC_PRECISION_PERTURB_BLA_DEEP;
+    const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : bla_deep ? "MC_PRECISION_PERTURB_BLA_DEEP" : "MC_PRECISION_PERTURB";
     const Binding* b = find_binding(ctx);
     if (!b || !b->orbit.ptr || !b->length) {
         set_error_detail(name + ": no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
@@ -639,6 +769,11 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     }
     if (bla && !b->has_bla) {
         set_error_detail(name + ": the bound orbit has no BLA table (mc_mandelbrot_orbit_bla before mc_context_bind_mandelbrot_orbit)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (bla_deep && !b->has_bla_deep) {
+        set_error_detail(name + ": the bound orbit has no deep BLA table (mc_mandelbrot_orbit_bla_deep before "
+                                "mc_context_bind_mandelbrot_orbit)");
         return MC_ERR_INVALID_ARGUMENT;
     }
     PerturbArgs a;
@@ -673,6 +808,14 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         if ((rc = perturb_bla_launch(d, grid, s))) return rc;
         return ctx->note_launch(s);
     }
+    if (bla_deep) {   // mandel_perturb_bla_deep.hip
+        const PerturbBlaDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
+                                      a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
+                                      b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
+                                      (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
+        if ((rc = perturb_bla_deep_launch(d, grid, s))) return rc;
+        return ctx->note_launch(s);
+    }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
         const PerturbDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
                                    a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit, b->scale_exp2, b->has_zero ? 1u : 0u};
@@ -690,6 +833,7 @@ void perturb_release(mc_context* ctx) {
     if (it == g_bindings.end()) return;
     it->second.orbit.release();
     it->second.bla.release();
+    it->second.bla_deep.release();
     g_bindings.erase(it);
 }
 
@@ -713,6 +857,7 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
         b->generation = ++mc::g_generation;
         b->length = 0;               // unusable until the copy below has completed
         b->has_bla = false;
+        b->has_bla_deep = false;
     }
     const size_t bytes = o->z.size() * sizeof(double);
     if ((rc = b->orbit.reserve(bytes))) return rc;
@@ -724,10 +869,19 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
     } else {
         b->bla.release();   // (a table left by an earlier bind)
     }
+    if (o->has_bla_deep && !o->bla_deep.empty()) {   // MC_PRECISION_PERTURB_BLA_DEEP's table, likewise
+        const size_t tbytes = o->bla_deep.size() * sizeof(mc::BlaDeepRec);
+        if ((rc = b->bla_deep.reserve(tbytes))) return rc;
+        MC_HIP_TRY(hipMemcpyAsync(b->bla_deep.ptr, o->bla_deep.data(), tbytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        b->bla_deep.release();
+    }
     MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
     b->has_bla = o->has_bla;
     b->bla_levels = o->bla_levels;
     b->bla_entries = o->bla_entries;
+    b->has_bla_deep = o->has_bla_deep;
+    b->bla_deep_entries = o->bla_deep_entries;
     b->length = o->length;
     b->max_iter = o->max_iter;
     b->scale_x = o->scale_x;

@@ -297,10 +297,12 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
     if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64 &&
-        p->precision != MC_PRECISION_PERTURB && p->precision != MC_PRECISION_PERTURB_BLA)
+        p->precision != MC_PRECISION_PERTURB && p->precision != MC_PRECISION_PERTURB_BLA &&
+        p->precision != MC_PRECISION_PERTURB_BLA_DEEP)
         return MC_ERR_INVALID_ARGUMENT;
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
-    if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA)
+    if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
+        p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
         return perturb_launch(ctx, p, d_rgba, d_iters, s, warm);   // mandel_perturb.hip
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);

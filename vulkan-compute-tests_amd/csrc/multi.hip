@@ -225,7 +225,8 @@ int mc_multi_destroy(mc_multi* m) {
 static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* out_rgba_f32, uint32_t* out_iters,
                             uint8_t* out_rgba8) {
     if (!m || !p || (!out_rgba_f32 && !out_iters && !out_rgba8)) return MC_ERR_INVALID_ARGUMENT;
-    if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA)
+    if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
+        p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
         return MC_ERR_UNSUPPORTED;   // single-device only (include/mc_compute.h)
     const bool want_rgba = out_rgba_f32 || out_rgba8;
     if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;

@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla (perturb: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -71,7 +71,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--max-iter") { need(1); maxIter = (uint32_t)atoi(argv[++i]); }
         else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = true; }
         else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = true; }
-        else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}, {"perturb-bla", MC_PRECISION_PERTURB_BLA}}); }
+        else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}, {"perturb-bla", MC_PRECISION_PERTURB_BLA}, {"perturb-bla-deep", MC_PRECISION_PERTURB_BLA_DEEP}}); }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -96,7 +96,8 @@ int main(int argc, char* argv[]) {
     app.setMaxIter(maxIter);
     if (viewSet) app.setView(cx, cy, sx, sy);
     app.setPrecision(precision);
-    if (precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA) {   // the reference orbit, on the host: a malformed
+    if (precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA ||
+        precision == MC_PRECISION_PERTURB_BLA_DEEP) {                                    // the reference orbit, on the host: a malformed
                                                                                          // centre ends the run before a device is touched
         mc_mandelbrot_orbit* orbit = nullptr;
         // a scale below 2^-960 takes the deep constructor: (mantissa, exponent) from long double text, common exponent of the smaller
@@ -110,7 +111,7 @@ int main(int argc, char* argv[]) {
         const long double lmin = fabsl(lx) < fabsl(ly) ? fabsl(lx) : fabsl(ly);
         if (precision == MC_PRECISION_PERTURB_BLA && lmin != 0.0L && lmin < ldexpl(1.0L, -960)) {
             printf("--precision perturb-bla --scale %s %s: below 2^-960 (a deep orbit renders by the rescaled loop, which has no BLA; "
-                   "use --precision perturb)\n", sxText, syText);
+                   "use --precision perturb or perturb-bla-deep)\n", sxText, syText);
             return EXIT_FAILURE;
         }
         int rc;
@@ -127,6 +128,11 @@ int main(int argc, char* argv[]) {
         }
         if (precision == MC_PRECISION_PERTURB_BLA && (rc = mc_mandelbrot_orbit_bla(orbit, nullptr, nullptr)) != MC_OK) {   // the table, on the host
             printf("mc_mandelbrot_orbit_bla: %s (%s)\n", mc_error_string(rc), mc_last_error_detail());
+            mc_mandelbrot_orbit_destroy(orbit);
+            return EXIT_FAILURE;
+        }
+        if (precision == MC_PRECISION_PERTURB_BLA_DEEP && (rc = mc_mandelbrot_orbit_bla_deep(orbit, nullptr, nullptr)) != MC_OK) {
+            printf("mc_mandelbrot_orbit_bla_deep: %s (%s)\n", mc_error_string(rc), mc_last_error_detail());
             mc_mandelbrot_orbit_destroy(orbit);
             return EXIT_FAILURE;
         }

@@ -25,8 +25,8 @@ struct MandelbrotApp : public ComputeApp {
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
-    // MC_PRECISION_PERTURB / _BLA: the view is this orbit's (the app owns it; for BLA main() has built its table); the params' view
-    // words are zero.  Bound in contextCreated().
+    // MC_PRECISION_PERTURB / _BLA / _BLA_DEEP: the view is this orbit's (the app owns it; for the BLA precisions main() has built the
+    // table); the params' view words are zero.  Bound in contextCreated().
     void setOrbit(mc_mandelbrot_orbit* o) {
         if (orbit) mc_mandelbrot_orbit_destroy(orbit);
         orbit = o;
