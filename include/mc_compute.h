@@ -30,7 +30,9 @@ extern "C" {
 
 /* 3, un-bumped additions since: MC_PRECISION_PERTURB with mc_mandelbrot_orbit_* and mc_context_bind_mandelbrot_orbit; then
  * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192); then MC_PRECISION_PERTURB_BLA with mc_mandelbrot_orbit_bla and
- * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy.
+ * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy;
+ * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
+ * mc_mandelbrot_recolour_device_async.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -287,8 +289,11 @@ int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint6
 int mc_mandelbrot_orbit_bla_deep_copy(const mc_mandelbrot_orbit* o, double* mant /* entries * 5 */, int32_t* exps /* entries * 3 */);
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
-    MC_MANDEL_ITERS_U16 = 1u << 1 /* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */
+    MC_MANDEL_ITERS_U16 = 1u << 1,/* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */
                                   /* format, half of the 4-B plane and an eighth of the vec4 (mc_mandelbrot_assemble_...)  */
+    /* bits 2 and 3 are measurement switches too */
+    MC_MANDEL_COLOUR_EQUALISED = 1u << 4 /* histogram-equalised colouring of a WHOLE image (mc_mandelbrot_render and            */
+                                  /* mc_mandelbrot_render_rgba8; the contract is below, at mc_mandelbrot_equalise_map)      */
 };
 
 typedef struct mc_mandelbrot_params {
@@ -325,6 +330,47 @@ int mc_mandelbrot_render_device_async(mc_context* ctx, const mc_mandelbrot_param
 /* The (max_iter+1)-entry colour table: entry n = vec4 written for iteration count n
  * (mandelbrot.comp:50-56, evaluated on the host in fp32 source order).  lut_f32: (max_iter+1)*4. */
 int mc_mandelbrot_colour_lut(uint32_t max_iter, const float k_color[4], float* lut_f32);
+
+/* ---- histogram-equalised colouring (the project's own addition: the reference colours by t = n / M only, and on the views the deep
+ *      precisions exist for the visible counts sit in a sliver of [0, M]; what tests/mandel_equalise_ref.py
+ *      restates).  A pixel's palette position is its count's RANK among the image's escaped pixels.  For counts n in [0, M],
+ *      M = max_iter, n = M meaning "did not escape":
+ *  - hist[j], j in [0, M]: the number of pixels of the WHOLE image with n = j; uint32_t (an image has fewer than 2^32 pixels:
+ *    width * height > 2^32 - 1 is MC_ERR_INVALID_ARGUMENT).
+ *  - E = hist[0] + ... + hist[M-1] (the escaped pixels); C(j) = hist[0] + ... + hist[j-1], C(0) = 0.
+ *  - the rank map, uint32_t map[M + 1]: map[M] = M; for j < M: map[j] = (M * C(j)) / E in unsigned 64-bit integer arithmetic, rounded
+ *    down (both factors are below 2^32: the product cannot overflow); if E = 0, map[j] = 0 for j < M.  So map is non-decreasing, a
+ *    count that occurs maps below M, and interior pixels keep the reference's t = 1 colour.
+ *  - colour: lut[map[n]], lut the table of mc_mandelbrot_colour_lut(M, k_color): the equalised image draws from exactly the M + 1 vec4
+ *    values the plain image draws from, and no new floating-point expression exists.  RGBA8 is mc_convert_rgba8's conversion (scale
+ *    255, no rotation) of that, as for the plain colouring.
+ * MC_MANDEL_COLOUR_EQUALISED in mc_mandelbrot_params.flags: mc_mandelbrot_render and mc_mandelbrot_render_rgba8 honour it for a whole
+ * image (row_begin = 0, row_end = height, no interleave), in all six precisions: the count plane is rendered (no vec4 leaves the render
+ * kernel), histogrammed, the table read back (4 (M + 1) bytes), mapped on the host, and the plane recoloured; out_iters still receives the
+ * plain counts, and mc_context_last_timing's kernel time spans the whole chain, the table's round trip included.  Every call that cannot see
+ * the whole image refuses the flag with MC_ERR_INVALID_ARGUMENT (mc_last_error_detail names the three calls below): a row tile or band of
+ * those two, mc_mandelbrot_render_device_async, mc_mandelbrot_render_banded, mc_mandelbrot_assemble_device_async.  mc_multi_* refuse it
+ * with MC_ERR_UNSUPPORTED.  mc_context_warmup_mandelbrot accepts it and makes the histogram and recolouring kernels resident too.
+ * By hand (tiles, several devices, one palette over a zoom sequence), three calls:
+ *
+ * mc_mandelbrot_histogram_device_async ADDS the counts of n_pixels values at d_iters (iters_bytes = 2: uint16_t, 4: uint32_t; aligned to
+ * their size) to d_hist, uint32_t[max_iter + 1] on the device, which the caller has zeroed: tiles, bands and devices accumulate into one
+ * table.  A value above max_iter is counted in bin max_iter, never outside the table.  n_pixels > 2^32 - 1: MC_ERR_INVALID_ARGUMENT.  The
+ * table is the same whatever order the adds arrive in.
+ *
+ * mc_mandelbrot_equalise_map (host only, no device): map from hist by the formula above.  NULL pointers or max_iter = 0:
+ * MC_ERR_INVALID_ARGUMENT.  The histogram's total is NOT compared with any image's size (equalising over a crop, or over the frames of a
+ * zoom sequence so that they share one palette, is a use); it is summed in 64 bits, and a total above 2^32 - 1 is
+ * MC_ERR_INVALID_ARGUMENT (the product above could wrap).
+ *
+ * mc_mandelbrot_recolour_device_async writes lut[map[n]] to d_rgba_f32 for the tile p describes (contiguous or interleaved rows, stored
+ * compactly, as everywhere); `map` is a HOST pointer to max_iter + 1 entries, each <= max_iter (MC_ERR_INVALID_ARGUMENT otherwise).
+ * lut[map[.]] is composed on the host and kept as a device table of the context, like the colour table: one gather per pixel. */
+int mc_mandelbrot_histogram_device_async(mc_context* ctx, const void* d_iters, uint32_t iters_bytes /* 2 or 4 */, uint64_t n_pixels,
+                                         uint32_t max_iter, void* d_hist /* uint32_t[max_iter + 1] */, void* stream);
+int mc_mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist /* max_iter + 1 */, uint32_t* map /* max_iter + 1 */);
+int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
+                                        const uint32_t* map /* HOST, max_iter + 1 */, void* d_rgba_f32, void* stream);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

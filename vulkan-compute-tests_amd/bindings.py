@@ -23,6 +23,7 @@ PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
 MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
+MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format
 PT_GENERIC_KERNEL = 1
 PT_NO_BOX_KERNEL = 4    # fast math: the general slab kernel instead of the closed-box ones
@@ -106,6 +107,8 @@ def lib():
         L.mc_mandelbrot_assemble_device_async.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
         L.mc_mandelbrot_default_params.argtypes = [u32, u32, C.POINTER(MandelbrotParams)]
         L.mc_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
+        if hasattr(L, "mc_mandelbrot_render_rgba8"):
+            L.mc_mandelbrot_render_rgba8.argtypes = [vp, C.POINTER(MandelbrotParams), vp]
         L.mc_mandelbrot_render_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp]
         L.mc_mandelbrot_colour_lut.argtypes = [u32, C.POINTER(f32), vp]
         L.mc_pathtrace_default_params.argtypes = [u32, u32, u32, C.POINTER(PathtraceParams)]
@@ -140,6 +143,10 @@ def lib():
         if hasattr(L, "mc_mandelbrot_orbit_bla_deep"):   # MC_PRECISION_PERTURB_BLA_DEEP
             L.mc_mandelbrot_orbit_bla_deep.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
             L.mc_mandelbrot_orbit_bla_deep_copy.argtypes = [vp, vp, vp]
+        if hasattr(L, "mc_mandelbrot_equalise_map"):   # MC_MANDEL_COLOUR_EQUALISED
+            L.mc_mandelbrot_histogram_device_async.argtypes = [vp, vp, u32, C.c_uint64, u32, vp, vp]
+            L.mc_mandelbrot_equalise_map.argtypes = [u32, vp, vp]
+            L.mc_mandelbrot_recolour_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, u32, vp, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -224,6 +231,24 @@ def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, cent
     p.row_begin, p.row_end = row_begin, height if row_end is None else row_end
     p.row_block, p.row_stride = row_block, row_stride
     return p
+
+
+def colour_lut(max_iter, k_color=(0.1, 0.7, 0.6, 0.0)):
+    """mc_mandelbrot_colour_lut (host only): float32 (max_iter + 1, 4), entry n = the vec4 written for iteration count n."""
+    k = (C.c_float * 4)(*k_color)
+    out = np.empty((max_iter + 1, 4), np.float32)
+    _check(lib().mc_mandelbrot_colour_lut(max_iter, k, _ptr(out)), "mc_mandelbrot_colour_lut")
+    return out
+
+
+def equalise_map(max_iter, hist):
+    """mc_mandelbrot_equalise_map (host only): the rank map uint32[max_iter + 1] of a histogram uint32[max_iter + 1]."""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if max_iter and h.size != max_iter + 1:
+        raise ValueError(f"equalise_map: the histogram has {h.size} bins, max_iter + 1 = {max_iter + 1} expected")
+    out = np.empty(max(h.size, 1), np.uint32)
+    _check(lib().mc_mandelbrot_equalise_map(max_iter, _ptr(h), _ptr(out)), "mc_mandelbrot_equalise_map")
+    return out
 
 
 def pathtrace_params(width, height, spp, math_mode=PT_MATH_STRICT, sample_begin=0, sample_end=None, max_depth=12,
@@ -526,6 +551,26 @@ class Context:
     def mandelbrot_device(self, p, d_rgba=0, d_iters=0, stream=0):
         _check(lib().mc_mandelbrot_render_device_async(self._h, C.byref(p), d_rgba or None, d_iters or None, stream or None),
                "mc_mandelbrot_render_device_async")
+
+    def mandelbrot_rgba8(self, p):
+        """mc_mandelbrot_render_rgba8: the rows [row_begin, row_end) rendered and converted on the device; only RGBA8 leaves the GPU."""
+        out = np.empty((p.row_end - p.row_begin, p.width, 4), np.uint8)
+        _check(lib().mc_mandelbrot_render_rgba8(self._h, C.byref(p), _ptr(out)), "mc_mandelbrot_render_rgba8")
+        return out
+
+    def mandelbrot_histogram_device(self, d_iters, iters_bytes, n_pixels, max_iter, d_hist, stream=0):
+        """mc_mandelbrot_histogram_device_async: ADDS the counts of n_pixels values (2 or 4 B each) to the device table
+        uint32[max_iter + 1]."""
+        _check(lib().mc_mandelbrot_histogram_device_async(self._h, d_iters or None, iters_bytes, n_pixels, max_iter, d_hist or None,
+                                                          stream or None), "mc_mandelbrot_histogram_device_async")
+
+    def mandelbrot_recolour_device(self, p, d_iters, iters_bytes, map_, d_rgba, stream=0):
+        """mc_mandelbrot_recolour_device_async: lut[map[n]] for the tile p describes; map_ is a host array of max_iter + 1 entries."""
+        m = np.ascontiguousarray(map_, np.uint32).reshape(-1)
+        if m.size != p.max_iter + 1:
+            raise ValueError(f"Context.mandelbrot_recolour_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_recolour_device_async(self._h, C.byref(p), d_iters or None, iters_bytes, _ptr(m), d_rgba or None,
+                                                         stream or None), "mc_mandelbrot_recolour_device_async")
 
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:

@@ -1,0 +1,355 @@
+// Histogram-equalised Mandelbrot colouring for gfx950 (MI355X): the histogram of a count plane, the rank map, the recolouring.
+// The project's own addition (the reference colours by t = n / M only, mandelbrot.comp:50-56); contract in include/mc_compute.h,
+// restated in tests/mandel_equalise_ref.py; scheme and measurements in DESIGN.md §3.10.
+//
+// The histogram kernel (the hot path: 2 or 4 B read per pixel, nothing written but the table):
+//  * every lane reads 16 B (4 uint32_t or 8 uint16_t counts) per trip of a grid-stride loop; the grid is sized from the CU count.
+//    The plane's unaligned head and its tail (fewer than 16 B each) are counted one value per lane by block 0.
+//  * the input is as skewed as a histogram's gets: interior regions are thousands of adjacent pixels with n = M, a deep frame's
+//    escaped pixels share a few hundred values.  So lanes combine inside the wave before anything reaches the table:
+//      - a wave whose lanes all hold one value in all their words (interior, flat exterior) issues ONE add of its pixel count;
+//      - otherwise, per word, up to kCombineRounds rounds elect the lowest pending lane, ballot the lanes that hold its value and let
+//        it add their population count; lanes still pending after the rounds add 1 each (their values are spread by then).
+//  * the table: a block-private LDS copy (ds_add_u32), flushed once per block with one global_atomic_add per non-zero bin.  It does not
+//    fit in general (M = 200 000 is 800 KB against 160 KB of LDS per CU), so the bins are cut into RANGES of kHistRangeBins (64 KB): a
+//    block owns one range and one share of the plane, and counts only the values of its range.  The plane is read once per range — it
+//    is the cheap part (a K4 plane is read in 0.025 ms; profiles/mandel_equalise_probe.txt), contended global atomics are not: the same
+//    wave-combined adds sent straight to the global table take 16 ms on K4's plane whatever M is.  That scheme is kept for tables of more
+//    than kHistMaxRanges ranges (max_iter >= 2^20), where the passes would cost as much.
+//  * integer adds commute: the table is bit-reproducible whatever the arrival order.  Vector atomics and vector stores only.
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
+
+#include "mandel_equalise.h"
+
+namespace mc {
+
+namespace {
+
+constexpr int kCombineRounds = 4;
+
+template <bool LDS>
+__device__ __forceinline__ void table_add(uint32_t* tab, uint32_t bin, uint32_t count) {
+    if (LDS)
+        (void)__hip_atomic_fetch_add(tab + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else
+        (void)__hip_atomic_fetch_add(tab + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One word per lane (pending == false: the lane has none), called by the whole wave.
+template <bool LDS>
+__device__ __forceinline__ void wave_combine_add(uint32_t* tab, uint32_t v, bool pending, uint32_t lane) {
+#pragma unroll
+    for (int r = 0; r < kCombineRounds; r++) {
+        const unsigned long long act = __ballot(pending);
+        if (!act) return;   // wave-uniform
+        const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
+        const uint32_t lv = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)leader);
+        const bool mine = pending && v == lv;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) table_add<LDS>(tab, lv, (uint32_t)__popcll(same));
+        pending = pending && !mine;
+    }
+    if (pending) table_add<LDS>(tab, v, 1u);
+}
+
+template <class T>
+struct Words;
+template <>
+struct Words<uint32_t> {
+    static constexpr int kPer = 4;
+    static __device__ __forceinline__ uint32_t get(const uint4& q, int j) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; }
+};
+template <>
+struct Words<uint16_t> {
+    static constexpr int kPer = 8;
+    static __device__ __forceinline__ uint32_t get(const uint4& q, int j) {
+        const uint32_t w = (j >> 1) == 0 ? q.x : (j >> 1) == 1 ? q.y : (j >> 1) == 2 ? q.z : q.w;
+        return (j & 1) ? (w >> 16) : (w & 0xffffu);
+    }
+};
+
+// head: values in front of the first 16-B boundary, nvec: whole 16-B vectors, tail: values behind them (head, tail < kPer).
+// Block b owns the bins [lo, lo + bins) of range b % n_ranges and share b / n_ranges of the plane (gridDim.x is a multiple of n_ranges);
+// LDS == false: one range, the global table itself.
+template <class T, bool LDS>
+__global__ void __launch_bounds__(256) mandel_histogram_kernel(const T* __restrict__ in, uint32_t head, uint64_t nvec, uint32_t tail,
+                                                               uint32_t max_iter, uint32_t range_bins, uint32_t n_ranges,
+                                                               uint32_t* __restrict__ hist) {
+    extern __shared__ uint32_t lds_tab[];
+    constexpr int kPer = Words<T>::kPer;
+    const uint32_t range = blockIdx.x % n_ranges, share = blockIdx.x / n_ranges, shares = gridDim.x / n_ranges;
+    const uint32_t lo = range * range_bins;
+    const uint32_t bins = max_iter - lo < range_bins ? max_iter - lo + 1u : range_bins;
+    uint32_t* tab = LDS ? lds_tab : hist;
+    if (LDS) {
+        for (uint32_t i = threadIdx.x; i < bins; i += 256u) lds_tab[i] = 0u;
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4* __restrict__ vec = reinterpret_cast<const uint4*>(in + head);
+    const uint64_t stride = (uint64_t)shares * 256u;
+    // (the loop's trip count is the same for every lane of a wave: the ballots below see whole waves)
+    for (uint64_t base = (uint64_t)share * 256u + (threadIdx.x & ~63u); base < nvec; base += stride) {
+        const uint64_t i = base + lane;
+        const bool active = i < nvec;
+        uint4 q = make_uint4(0u, 0u, 0u, 0u);
+        if (active) q = vec[i];
+        uint32_t w[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            const uint32_t v = Words<T>::get(q, j);
+            w[j] = (v > max_iter ? max_iter : v) - lo;   // the clamp of mandelbrot_assemble_kernel; in this block's range: w[j] < bins
+        }
+        // lane 0 of the wave is active here (base < nvec), and inactive lanes sit above the active ones
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)w[0]);
+        bool flat = true;
+#pragma unroll
+        for (int j = 0; j < kPer; j++) flat = flat && w[j] == first;
+        const unsigned long long act = __ballot(active);
+        if (__ballot(active && !flat) == 0ull) {   // the whole wave holds one value: one add
+            if (lane == 0u && first < bins) table_add<LDS>(tab, first, (uint32_t)__popcll(act) * (uint32_t)kPer);
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < kPer; j++) wave_combine_add<LDS>(tab, w[j], active && w[j] < bins, lane);
+    }
+    if (share == 0u && threadIdx.x < head + tail) {   // fewer than 2 * kPer values, one per lane, by the first block of every range
+        const uint64_t at = threadIdx.x < head ? (uint64_t)threadIdx.x : (uint64_t)head + nvec * kPer + (threadIdx.x - head);
+        uint32_t v = (uint32_t)in[at];
+        v = (v > max_iter ? max_iter : v) - lo;
+        if (v < bins) table_add<LDS>(tab, v, 1u);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < bins; i += 256u) {
+            const uint32_t c = lds_tab[i];
+            if (c) table_add<false>(hist, lo + i, c);
+        }
+    }
+}
+
+// d_rgba[i] = table[min(n[i], M)], table = lut[map[.]] composed on the host: ONE gather per pixel, as mandelbrot_assemble_kernel's.
+// 2-4 B read + 16 B written per pixel, one pixel per lane (the float4 stores of a wave are 1 KB contiguous).
+template <class T>
+__global__ void __launch_bounds__(256) mandel_recolour_kernel(const T* __restrict__ iters, const float4* __restrict__ table,
+                                                              float4* __restrict__ rgba, uint64_t total, uint32_t max_iter) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u) {
+        uint32_t n = (uint32_t)iters[i];
+        if (n > max_iter) n = max_iter;
+        rgba[i] = table[n];
+    }
+}
+
+// The device state of the feature, keyed by the context (csrc/mc_internal.h stays as it is; the bound orbit's record is the model).
+struct EqualiseState {
+    DeviceBuffer hist;                 // the whole-image calls' table
+    DeviceBuffer table;                // lut[map[j]], (max_iter + 1) vec4: a cached device table like the colour LUT
+    std::vector<uint32_t> table_map;   // what `table` was composed from: (map, max_iter, k_color)
+    uint32_t table_max_iter = 0;
+    float table_kcolor[4] = {0, 0, 0, 0};
+    std::vector<float> lut_host;       // mandelbrot_build_lut(lut_max_iter, lut_kcolor)
+    uint32_t lut_max_iter = 0;
+    float lut_kcolor[4] = {0, 0, 0, 0};
+    std::vector<uint32_t> hist_host, map_host;
+};
+std::mutex g_eq_mutex;
+std::unordered_map<const mc_context*, EqualiseState> g_eq_states;
+
+EqualiseState* state_of(const mc_context* ctx) {
+    std::lock_guard<std::mutex> lock(g_eq_mutex);
+    return &g_eq_states[ctx];   // the node stays put while other contexts add theirs (only this context's thread erases it)
+}
+
+}  // namespace
+
+void equalise_release(mc_context* ctx) {
+    std::lock_guard<std::mutex> lock(g_eq_mutex);
+    auto it = g_eq_states.find(ctx);
+    if (it == g_eq_states.end()) return;
+    it->second.hist.release();
+    it->second.table.release();
+    g_eq_states.erase(it);
+}
+
+int mandelbrot_histogram_launch(mc_context* ctx, const void* d_iters, uint32_t iters_bytes, uint64_t n_pixels, uint32_t max_iter,
+                                void* d_hist, hipStream_t s) {
+    if (!ctx || !d_iters || !d_hist || !max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
+    if (n_pixels > 0xffffffffull) {
+        set_error_detail("mc_mandelbrot_histogram_device_async: the table's bins are uint32_t, an image has fewer than 2^32 pixels");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_iters);
+    if (addr % iters_bytes || reinterpret_cast<uintptr_t>(d_hist) % 4u) return MC_ERR_INVALID_ARGUMENT;
+    if (max_iter == 0xffffffffu) return MC_ERR_INVALID_ARGUMENT;   // (max_iter + 1 bins must be countable in 32 bits)
+    if (!n_pixels) return MC_OK;
+    const uint64_t all_bins = (uint64_t)max_iter + 1u;
+    const uint32_t range_bins = (uint32_t)std::min<uint64_t>(all_bins, kHistRangeBins);
+    const uint32_t n_ranges = (uint32_t)((all_bins + range_bins - 1u) / range_bins);
+    const bool lds = n_ranges <= kHistMaxRanges;
+    const uint32_t per = 16u / iters_bytes;
+    uint32_t head = (uint32_t)(((16u - addr % 16u) % 16u) / iters_bytes);
+    if (head > n_pixels) head = (uint32_t)n_pixels;
+    const uint64_t nvec = (n_pixels - head) / per;
+    const uint32_t tail = (uint32_t)(n_pixels - head - nvec * per);
+    // 8 blocks of 4 waves per CU for the global table; an LDS range's size bounds the blocks a CU holds (160 KB of LDS).  Every range
+    // gets the same number of blocks (its shares of the plane), at least one.
+    const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount;
+    const size_t shared = lds ? (size_t)range_bins * 4u : 0;
+    const uint32_t per_cu = lds ? std::max<uint32_t>(1u, std::min<uint32_t>(8u, (uint32_t)((160u << 10) / shared))) : 8u;
+    const uint32_t ranges = lds ? n_ranges : 1u;
+    uint64_t shares = std::min<uint64_t>((nvec + 255u) / 256u, std::max<uint64_t>(1u, (uint64_t)cus * per_cu / ranges));
+    if (!shares) shares = 1;
+    const dim3 grid((uint32_t)(shares * ranges)), block(256);
+    const uint32_t rb = lds ? range_bins : (uint32_t)std::min<uint64_t>(all_bins, 0xffffffffull);
+    uint32_t* h = (uint32_t*)d_hist;
+    if (iters_bytes == 4u) {
+        const uint32_t* in = (const uint32_t*)d_iters;
+        if (lds) hipLaunchKernelGGL((mandel_histogram_kernel<uint32_t, true>), grid, block, shared, s, in, head, nvec, tail, max_iter, rb, ranges, h);
+        else hipLaunchKernelGGL((mandel_histogram_kernel<uint32_t, false>), grid, block, shared, s, in, head, nvec, tail, max_iter, rb, ranges, h);
+    } else {
+        const uint16_t* in = (const uint16_t*)d_iters;
+        if (lds) hipLaunchKernelGGL((mandel_histogram_kernel<uint16_t, true>), grid, block, shared, s, in, head, nvec, tail, max_iter, rb, ranges, h);
+        else hipLaunchKernelGGL((mandel_histogram_kernel<uint16_t, false>), grid, block, shared, s, in, head, nvec, tail, max_iter, rb, ranges, h);
+    }
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
+// map[M] = M; j < M: map[j] = (M * C(j)) / E in uint64_t, C(j) = hist[0] + ... + hist[j-1], E = C(M); E = 0: map[j] = 0.
+// The total is summed in 64 bits and must stay below 2^32 (both factors of the product then are): it is NOT compared with any
+// image's size — a caller may equalise over a crop or over several frames on purpose.
+int mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist, uint32_t* map) {
+    if (!max_iter || !hist || !map) return MC_ERR_INVALID_ARGUMENT;
+    uint64_t total = 0;
+    for (uint64_t j = 0; j <= max_iter; j++) total += hist[j];
+    if (total > 0xffffffffull) {
+        set_error_detail("mc_mandelbrot_equalise_map: the histogram's total exceeds 2^32 - 1");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t escaped = total - hist[max_iter];
+    uint64_t below = 0;
+    for (uint32_t j = 0; j < max_iter; j++) {
+        map[j] = escaped ? (uint32_t)(((uint64_t)max_iter * below) / escaped) : 0u;
+        below += hist[j];
+    }
+    map[max_iter] = max_iter;
+    return MC_OK;
+}
+
+int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
+                               const uint32_t* map, void* d_rgba, hipStream_t s) {
+    if (!ctx || !p || !d_iters || !map || !d_rgba || !p->max_iter || !rows_ok(p)) return MC_ERR_INVALID_ARGUMENT;
+    if (iters_bytes != 2u && iters_bytes != 4u) return MC_ERR_INVALID_ARGUMENT;
+    if (iters_bytes == 2u && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
+    if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
+    const uint32_t M = p->max_iter;
+    for (uint32_t j = 0; j <= M; j++)
+        if (map[j] > M) {
+            set_error_detail("mc_mandelbrot_recolour_device_async: a map entry exceeds max_iter");
+            return MC_ERR_INVALID_ARGUMENT;
+        }
+    EqualiseState* st = state_of(ctx);
+    const size_t entries = (size_t)M + 1;
+    const bool cached = st->table.ptr && st->table_max_iter == M && std::memcmp(st->table_kcolor, p->k_color, sizeof(float) * 4) == 0 &&
+                        st->table_map.size() == entries && std::memcmp(st->table_map.data(), map, entries * 4) == 0;
+    if (!cached) {
+        if (st->lut_host.size() != entries * 4 || st->lut_max_iter != M || std::memcmp(st->lut_kcolor, p->k_color, sizeof(float) * 4) != 0) {
+            st->lut_host.resize(entries * 4);
+            mandelbrot_build_lut(M, p->k_color, st->lut_host.data());
+            st->lut_max_iter = M;
+            std::memcpy(st->lut_kcolor, p->k_color, sizeof(float) * 4);
+        }
+        std::vector<float> composed(entries * 4);
+        for (size_t j = 0; j < entries; j++) std::memcpy(&composed[4 * j], &st->lut_host[4 * (size_t)map[j]], sizeof(float) * 4);
+        // an earlier recolouring of this context may still read the old table (possibly on another stream): wait for the streams this
+        // context has launched on — not the whole device — before replacing it, as the colour table does
+        int rc = ctx->drain_launch_streams();
+        if (rc) return rc;
+        st->table_map.clear();   // unusable until the copy below has completed
+        if ((rc = st->table.reserve(entries * 16))) return rc;
+        MC_HIP_TRY(hipMemcpyAsync(st->table.ptr, composed.data(), entries * 16, hipMemcpyHostToDevice, s));
+        MC_HIP_TRY(hipStreamSynchronize(s));   // the host vector goes out of scope
+        st->table_map.assign(map, map + entries);
+        st->table_max_iter = M;
+        std::memcpy(st->table_kcolor, p->k_color, sizeof(float) * 4);
+    }
+    const uint64_t total = (uint64_t)tile_rows(p->row_begin, p->row_end, p->row_stride ? p->row_block : 0u, p->row_stride) * p->width;
+    uint64_t blocks = (total + 255u) / 256u;
+    const uint64_t cap = (uint64_t)ctx->props.multiProcessorCount * 8u;
+    if (blocks > cap) blocks = cap;
+    if (iters_bytes == 2u)
+        hipLaunchKernelGGL(mandel_recolour_kernel<uint16_t>, dim3((uint32_t)blocks), dim3(256), 0, s, (const uint16_t*)d_iters,
+                           (const float4*)st->table.ptr, (float4*)d_rgba, total, M);
+    else
+        hipLaunchKernelGGL(mandel_recolour_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, s, (const uint32_t*)d_iters,
+                           (const float4*)st->table.ptr, (float4*)d_rgba, total, M);
+    MC_HIP_TRY(hipGetLastError());
+    return ctx->note_launch(s);   // (reads the cached composed table)
+}
+
+int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, void* d_rgba, hipStream_t s) {
+    const uint64_t npix = (uint64_t)p->width * p->height;
+    if (npix > 0xffffffffull) {
+        set_error_detail("MC_MANDEL_COLOUR_EQUALISED: the histogram's bins are uint32_t, width * height must stay below 2^32");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    EqualiseState* st = state_of(ctx);
+    const size_t entries = (size_t)p->max_iter + 1;
+    int rc = st->hist.reserve(entries * 4);
+    if (rc) return rc;
+    st->hist_host.resize(entries);
+    st->map_host.resize(entries);
+    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
+    if ((rc = mandelbrot_histogram_launch(ctx, d_iters, 4u, npix, p->max_iter, st->hist.ptr, s))) return rc;
+    MC_HIP_TRY(hipMemcpyAsync(st->hist_host.data(), st->hist.ptr, entries * 4, hipMemcpyDeviceToHost, s));
+    MC_HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = mandelbrot_equalise_map(p->max_iter, st->hist_host.data(), st->map_host.data()))) return rc;
+    return mandelbrot_recolour_launch(ctx, p, d_iters, 4u, st->map_host.data(), d_rgba, s);
+}
+
+int mandelbrot_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_t s) {
+    // scratch_iters holds at least 64 counts (mc_context_warmup_mandelbrot); scratch_rgba at least 64 vec4
+    EqualiseState* st = state_of(ctx);
+    const size_t entries = (size_t)p->max_iter + 1;
+    int rc = st->hist.reserve(entries * 4);
+    if (rc) return rc;
+    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
+    MC_HIP_TRY(hipMemsetAsync(ctx->scratch_iters.ptr, 0, 64 * 4, s));
+    if ((rc = mandelbrot_histogram_launch(ctx, ctx->scratch_iters.ptr, 4u, 64, p->max_iter, st->hist.ptr, s))) return rc;
+    std::vector<uint32_t> identity(entries);
+    for (size_t j = 0; j < entries; j++) identity[j] = (uint32_t)j;
+    mc_mandelbrot_params q = *p;
+    q.width = 8; q.height = 8; q.row_begin = 0; q.row_end = 8; q.row_block = q.row_stride = 0;
+    return mandelbrot_recolour_launch(ctx, &q, ctx->scratch_iters.ptr, 4u, identity.data(), ctx->scratch_rgba.ptr, s);
+}
+
+}  // namespace mc
+
+using namespace mc;
+
+extern "C" {
+
+int mc_mandelbrot_histogram_device_async(mc_context* ctx, const void* d_iters, uint32_t iters_bytes, uint64_t n_pixels,
+                                         uint32_t max_iter, void* d_hist, void* stream) {
+    if (!ctx) return MC_ERR_INVALID_ARGUMENT;
+    if (!d_iters || !d_hist || !max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    return mandelbrot_histogram_launch(ctx, d_iters, iters_bytes, n_pixels, max_iter, d_hist, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int mc_mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist, uint32_t* map) {
+    return mandelbrot_equalise_map(max_iter, hist, map);
+}
+
+int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
+                                        const uint32_t* map, void* d_rgba_f32, void* stream) {
+    if (!ctx || !p || !d_iters || !map || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u))
+        return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    return mandelbrot_recolour_launch(ctx, p, d_iters, iters_bytes, map, d_rgba_f32, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+}  // extern "C"

@@ -228,6 +228,10 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
     if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
         p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
         return MC_ERR_UNSUPPORTED;   // single-device only (include/mc_compute.h)
+    if (p->flags & MC_MANDEL_COLOUR_EQUALISED) {   // likewise: the histogram of the whole image is taken on one device
+        set_error_detail("mc_multi_*: MC_MANDEL_COLOUR_EQUALISED is single-device only");
+        return MC_ERR_UNSUPPORTED;
+    }
     const bool want_rgba = out_rgba_f32 || out_rgba8;
     if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;
     const uint32_t W = p->width, H = p->height;
