@@ -32,7 +32,8 @@ extern "C" {
  * mc_mandelbrot_orbit_create_deep (scales down to 2^-8192); then MC_PRECISION_PERTURB_BLA with mc_mandelbrot_orbit_bla and
  * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy;
  * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
- * mc_mandelbrot_recolour_device_async.
+ * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
+ * mc_mandelbrot_resolve_device_async.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -294,7 +295,11 @@ enum {
     /* bits 2 and 3 are measurement switches too */
     MC_MANDEL_COLOUR_EQUALISED = 1u << 4 /* histogram-equalised colouring of a WHOLE image (mc_mandelbrot_render and            */
                                   /* mc_mandelbrot_render_rgba8; the contract is below, at mc_mandelbrot_equalise_map)      */
+    /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
 };
+/* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
+ * 2, 4, 8: valid; 3, 5, 6, 7, 9 .. 15: MC_ERR_INVALID_ARGUMENT.  The contract is below, at mc_mandelbrot_resolve_device_async. */
+#define MC_MANDEL_SUPERSAMPLE(s) (((uint32_t)(s) & 15u) << 8)
 
 typedef struct mc_mandelbrot_params {
     uint32_t width, height;   /* WIDTH/HEIGHT (mandelbrot.comp:5-6); reference 2000x2000 (main.cpp:20)  */
@@ -371,6 +376,45 @@ int mc_mandelbrot_histogram_device_async(mc_context* ctx, const void* d_iters, u
 int mc_mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist /* max_iter + 1 */, uint32_t* map /* max_iter + 1 */);
 int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
                                         const uint32_t* map /* HOST, max_iter + 1 */, void* d_rgba_f32, void* stream);
+
+/* ---- s x s supersampling (the project's own addition: the reference takes ONE sample per pixel, at its corner, mandelbrot.comp:29-30;
+ *      DESIGN.md section 3.11; what tests/mandel_supersample_ref.py restates).  MC_MANDEL_SUPERSAMPLE(s) in flags, s = 2, 4 or 8:
+ *  - sample grid: an image W x H with factor s is sampled on the grid of the PLAIN image s*W x s*H with the same centre, scale, max_iter,
+ *    precision and bound orbit: sample (s*y + i, s*x + j), i, j in [0, s), belongs to pixel (y, x), and its count is by definition the
+ *    count the plain render of the s*W x s*H image gives at that position.  s*W and s*H must pass whatever the plain render demands.
+ *  - colour of a pixel: with lut the M + 1 vec4 of mc_mandelbrot_colour_lut and n(i, j) the pixel's sample counts, per component in fp32,
+ *    round-to-nearest, no contraction, sums by ADJACENT PAIRS, LEVEL BY LEVEL: tree(a_0 .. a_{k-1}) = a_0 for k = 1, else
+ *    tree(a_0 + a_1, a_2 + a_3, ...); for k = 4: (a_0 + a_1) + (a_2 + a_3).  Row sums r_i = tree(lut[n(i,0)] .. lut[n(i,s-1)]), total
+ *    t = tree(r_0 .. r_{s-1}), colour = t * (1.0f / (s*s)) — an exact scaling by a power of two.  A count above max_iter reads entry
+ *    max_iter.  A pixel whose s*s samples share one count gets exactly lut[n], the plain colour (every partial sum is a power-of-two
+ *    multiple of it): flat regions and the interior are bit-identical to the plain image; that is why only powers of two are offered.
+ *    Alpha is exactly 1.0f.
+ *  - with MC_MANDEL_COLOUR_EQUALISED: hist is the histogram of ALL s*s*W*H samples (s*s*W*H > 2^32 - 1: MC_ERR_INVALID_ARGUMENT), map is
+ *    mc_mandelbrot_equalise_map of it, and lut[n] above becomes lut[map[n]].
+ *  - RGBA8 is mc_convert_rgba8's conversion (scale 255, no rotation) of that vec4, as everywhere.
+ * mc_mandelbrot_render (out_rgba_f32) and mc_mandelbrot_render_rgba8 honour the flag in all six precisions: the count plane of the sample
+ * grid is rendered (uint16_t when max_iter <= 65535; no vec4 leaves the render kernel), [histogrammed and mapped when equalised,] and
+ * resolved.  Plain colouring: whole images, contiguous row bands (render_rgba8) and row tiles (render) — a band's bytes are the whole
+ * image's rows.  Equalised: whole images only.  out_iters with s >= 2 is MC_ERR_INVALID_ARGUMENT (a pixel has no single count: render
+ * mc_mandelbrot_supersample_params' grid plainly).  mc_context_last_timing spans the whole chain.  The sample plane is scratch of the
+ * context: 2 or 4 bytes x s*s x the tile's pixels (bound it with row bands, or with the device call below).
+ * mc_mandelbrot_render_device_async, mc_mandelbrot_render_banded and mc_mandelbrot_assemble_device_async refuse s >= 2 with
+ * MC_ERR_INVALID_ARGUMENT (mc_last_error_detail names the two calls below), mc_multi_* with MC_ERR_UNSUPPORTED.
+ * mc_context_warmup_mandelbrot accepts it and makes the resolve kernel resident too.
+ *
+ * mc_mandelbrot_supersample_params (host only, no device): q = the plain-render parameters of p's sample grid: width, height, row_begin,
+ * row_end, row_block and row_stride multiplied by s, the supersample bits and MC_MANDEL_COLOUR_EQUALISED cleared, everything else copied
+ * (q may be p).  A contiguous or interleaved tile of p is exactly the tile of q whose compact rows are, for each compact pixel row, its s
+ * sample rows in order.  s = 0 or 1 multiplies by 1.  An invalid s, a product above 2^32 - 1 or a NULL pointer: MC_ERR_INVALID_ARGUMENT.
+ *
+ * mc_mandelbrot_resolve_device_async writes the colours of p's compact tile (p carries MC_MANDEL_SUPERSAMPLE(s), s = 2, 4, 8) to
+ * d_rgba_f32 (16-byte aligned) from d_samples, what mc_mandelbrot_render_device_async(q) wrote for the same tile as counts of
+ * iters_bytes = 4 (uint32_t) or 2 (uint16_t, MC_MANDEL_ITERS_U16; max_iter <= 65535), aligned to their size.  `map` is a HOST table of
+ * max_iter + 1 entries, each <= max_iter, under mc_mandelbrot_recolour_device_async's rules and sharing its cached device table, or NULL
+ * for the plain colouring.  Tiles, several devices and a caller's own banding compose this with the histogram call above. */
+int mc_mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_params* q);
+int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes /* 2 or 4 */,
+                                       const uint32_t* map /* HOST, max_iter + 1, or NULL */, void* d_rgba_f32, void* stream);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

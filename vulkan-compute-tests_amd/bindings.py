@@ -24,6 +24,11 @@ MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
 MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
+
+
+def MANDEL_SUPERSAMPLE(s):
+    """MC_MANDEL_SUPERSAMPLE(s): s x s samples per pixel, resolved on the device (bits 8-11 of flags; 2, 4 or 8; 0 and 1: off)."""
+    return (int(s) & 15) << 8
 MANDEL_ITERS_U16 = 2   # device form: d_iters is a uint16 plane (max_iter <= 65535): the multi-GPU exchange format
 PT_GENERIC_KERNEL = 1
 PT_NO_BOX_KERNEL = 4    # fast math: the general slab kernel instead of the closed-box ones
@@ -147,6 +152,9 @@ def lib():
             L.mc_mandelbrot_histogram_device_async.argtypes = [vp, vp, u32, C.c_uint64, u32, vp, vp]
             L.mc_mandelbrot_equalise_map.argtypes = [u32, vp, vp]
             L.mc_mandelbrot_recolour_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, u32, vp, vp, vp]
+        if hasattr(L, "mc_mandelbrot_supersample_params"):   # MC_MANDEL_SUPERSAMPLE
+            L.mc_mandelbrot_supersample_params.argtypes = [C.POINTER(MandelbrotParams), C.POINTER(MandelbrotParams)]
+            L.mc_mandelbrot_resolve_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, u32, vp, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -218,10 +226,10 @@ def split_double(d):
 
 
 def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, centre=(-0.445, 0.0), scale=(2.34, 2.34),
-                      k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0):
+                      k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0, supersample=0):
     p = MandelbrotParams()
     _check(lib().mc_mandelbrot_default_params(width, height, C.byref(p)), "mc_mandelbrot_default_params")
-    p.max_iter, p.precision, p.flags = max_iter, precision, flags
+    p.max_iter, p.precision, p.flags = max_iter, precision, flags | MANDEL_SUPERSAMPLE(supersample)
     p.centre_x_hi, p.centre_x_lo = split_double(centre[0])
     p.centre_y_hi, p.centre_y_lo = split_double(centre[1])
     p.scale_x_hi, p.scale_x_lo = split_double(scale[0])
@@ -231,6 +239,14 @@ def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, cent
     p.row_begin, p.row_end = row_begin, height if row_end is None else row_end
     p.row_block, p.row_stride = row_block, row_stride
     return p
+
+
+def supersample_params(p):
+    """mc_mandelbrot_supersample_params (host only): the plain-render params of p's sample grid (s times the width, height and rows; the
+    supersample bits and MANDEL_COLOUR_EQUALISED cleared)."""
+    q = MandelbrotParams()
+    _check(lib().mc_mandelbrot_supersample_params(C.byref(p), C.byref(q)), "mc_mandelbrot_supersample_params")
+    return q
 
 
 def colour_lut(max_iter, k_color=(0.1, 0.7, 0.6, 0.0)):
@@ -571,6 +587,17 @@ class Context:
             raise ValueError(f"Context.mandelbrot_recolour_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
         _check(lib().mc_mandelbrot_recolour_device_async(self._h, C.byref(p), d_iters or None, iters_bytes, _ptr(m), d_rgba or None,
                                                          stream or None), "mc_mandelbrot_recolour_device_async")
+
+    def mandelbrot_resolve_device(self, p, d_samples, iters_bytes, map_, d_rgba, stream=0):
+        """mc_mandelbrot_resolve_device_async: the colours of p's tile (p carries MANDEL_SUPERSAMPLE(s)) from the sample plane that
+        mandelbrot_device(supersample_params(p)) wrote; map_ is a host array of max_iter + 1 entries, or None for the plain colouring."""
+        m = None
+        if map_ is not None:
+            m = np.ascontiguousarray(map_, np.uint32).reshape(-1)
+            if m.size != p.max_iter + 1:
+                raise ValueError(f"Context.mandelbrot_resolve_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_resolve_device_async(self._h, C.byref(p), d_samples or None, iters_bytes, _ptr(m), d_rgba or None,
+                                                        stream or None), "mc_mandelbrot_resolve_device_async")
 
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:

@@ -20,6 +20,14 @@ int mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist, uint32_t* m
 // d_rgba[i] = lut[map[min(n[i], max_iter)]] for the compact tile p describes; map is a HOST table.
 int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
                                const uint32_t* map, void* d_rgba, hipStream_t s);
+// lut[map[.]] as a cached device table of the context ((max_iter + 1) vec4), composed on the host when (map, max_iter, k_color) changes;
+// a map entry above max_iter is MC_ERR_INVALID_ARGUMENT, the detail string starting with `who`.
+int mandelbrot_composed_table(mc_context* ctx, const mc_mandelbrot_params* p, const uint32_t* map, const char* who, hipStream_t s,
+                              const void** d_table);
+// The histogram of n_values counts at d_iters (2 or 4 B each), read back, and its rank map (a host table of the context's side record,
+// valid until the next call).  Synchronises s once (the table round trip).
+int mandelbrot_equalise_plane_map(mc_context* ctx, uint32_t max_iter, const void* d_iters, uint32_t iters_bytes, uint64_t n_values,
+                                  hipStream_t s, const uint32_t** map);
 // The whole-image chain after the count plane has been rendered into d_iters (uint32_t) on s: histogram, table to the host, map,
 // recolour into d_rgba.  Synchronises s once (the table round trip).
 int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, void* d_rgba, hipStream_t s);
@@ -27,5 +35,18 @@ int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, co
 int mandelbrot_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_t s);
 // mc_context_destroy: the context's histogram and composed colour table, if any, are freed.
 void equalise_release(mc_context* ctx);
+
+// ---- s x s supersampling (MC_MANDEL_SUPERSAMPLE, mandel_resolve.hip) ----
+// The factor in p's flags: 0 where the bits say 0 or 1 ("off"), else 2..15 (only 2, 4 and 8 are valid).
+inline uint32_t supersample_of(const mc_mandelbrot_params* p) {
+    const uint32_t s = (p->flags >> 8) & 15u;
+    return s <= 1u ? 0u : s;
+}
+// q = the plain-render params of p's sample grid (mc_mandelbrot_supersample_params).
+int mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_params* q);
+// d_rgba = the box-filtered colours of p's compact tile from the sample plane mc_mandelbrot_render_device_async(q) wrote for it;
+// map: a HOST table of max_iter + 1 entries, or nullptr for the plain colouring.
+int mandelbrot_resolve_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes,
+                              const uint32_t* map, void* d_rgba, hipStream_t s);
 
 }  // namespace mc

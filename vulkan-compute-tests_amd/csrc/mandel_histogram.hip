@@ -239,16 +239,13 @@ int mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist, uint32_t* m
     return MC_OK;
 }
 
-int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
-                               const uint32_t* map, void* d_rgba, hipStream_t s) {
-    if (!ctx || !p || !d_iters || !map || !d_rgba || !p->max_iter || !rows_ok(p)) return MC_ERR_INVALID_ARGUMENT;
-    if (iters_bytes != 2u && iters_bytes != 4u) return MC_ERR_INVALID_ARGUMENT;
-    if (iters_bytes == 2u && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
-    if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
+// lut[map[.]] composed on the host and kept as a device table of the context (the recolouring and the supersampling resolve share it).
+int mandelbrot_composed_table(mc_context* ctx, const mc_mandelbrot_params* p, const uint32_t* map, const char* who, hipStream_t s,
+                              const void** d_table) {
     const uint32_t M = p->max_iter;
     for (uint32_t j = 0; j <= M; j++)
         if (map[j] > M) {
-            set_error_detail("mc_mandelbrot_recolour_device_async: a map entry exceeds max_iter");
+            set_error_detail(std::string(who) + ": a map entry exceeds max_iter");
             return MC_ERR_INVALID_ARGUMENT;
         }
     EqualiseState* st = state_of(ctx);
@@ -276,18 +273,48 @@ int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, c
         st->table_max_iter = M;
         std::memcpy(st->table_kcolor, p->k_color, sizeof(float) * 4);
     }
+    *d_table = st->table.ptr;
+    return MC_OK;
+}
+
+int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
+                               const uint32_t* map, void* d_rgba, hipStream_t s) {
+    if (!ctx || !p || !d_iters || !map || !d_rgba || !p->max_iter || !rows_ok(p)) return MC_ERR_INVALID_ARGUMENT;
+    if (iters_bytes != 2u && iters_bytes != 4u) return MC_ERR_INVALID_ARGUMENT;
+    if (iters_bytes == 2u && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
+    if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
+    const uint32_t M = p->max_iter;
+    const void* table = nullptr;
+    if (int rc = mandelbrot_composed_table(ctx, p, map, "mc_mandelbrot_recolour_device_async", s, &table)) return rc;
     const uint64_t total = (uint64_t)tile_rows(p->row_begin, p->row_end, p->row_stride ? p->row_block : 0u, p->row_stride) * p->width;
     uint64_t blocks = (total + 255u) / 256u;
     const uint64_t cap = (uint64_t)ctx->props.multiProcessorCount * 8u;
     if (blocks > cap) blocks = cap;
     if (iters_bytes == 2u)
         hipLaunchKernelGGL(mandel_recolour_kernel<uint16_t>, dim3((uint32_t)blocks), dim3(256), 0, s, (const uint16_t*)d_iters,
-                           (const float4*)st->table.ptr, (float4*)d_rgba, total, M);
+                           (const float4*)table, (float4*)d_rgba, total, M);
     else
         hipLaunchKernelGGL(mandel_recolour_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, s, (const uint32_t*)d_iters,
-                           (const float4*)st->table.ptr, (float4*)d_rgba, total, M);
+                           (const float4*)table, (float4*)d_rgba, total, M);
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);   // (reads the cached composed table)
+}
+
+int mandelbrot_equalise_plane_map(mc_context* ctx, uint32_t max_iter, const void* d_iters, uint32_t iters_bytes, uint64_t n_values,
+                                  hipStream_t s, const uint32_t** map) {
+    EqualiseState* st = state_of(ctx);
+    const size_t entries = (size_t)max_iter + 1;
+    int rc = st->hist.reserve(entries * 4);
+    if (rc) return rc;
+    st->hist_host.resize(entries);
+    st->map_host.resize(entries);
+    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
+    if ((rc = mandelbrot_histogram_launch(ctx, d_iters, iters_bytes, n_values, max_iter, st->hist.ptr, s))) return rc;
+    MC_HIP_TRY(hipMemcpyAsync(st->hist_host.data(), st->hist.ptr, entries * 4, hipMemcpyDeviceToHost, s));
+    MC_HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = mandelbrot_equalise_map(max_iter, st->hist_host.data(), st->map_host.data()))) return rc;
+    *map = st->map_host.data();
+    return MC_OK;
 }
 
 int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, void* d_rgba, hipStream_t s) {
@@ -296,18 +323,9 @@ int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, co
         set_error_detail("MC_MANDEL_COLOUR_EQUALISED: the histogram's bins are uint32_t, width * height must stay below 2^32");
         return MC_ERR_INVALID_ARGUMENT;
     }
-    EqualiseState* st = state_of(ctx);
-    const size_t entries = (size_t)p->max_iter + 1;
-    int rc = st->hist.reserve(entries * 4);
-    if (rc) return rc;
-    st->hist_host.resize(entries);
-    st->map_host.resize(entries);
-    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
-    if ((rc = mandelbrot_histogram_launch(ctx, d_iters, 4u, npix, p->max_iter, st->hist.ptr, s))) return rc;
-    MC_HIP_TRY(hipMemcpyAsync(st->hist_host.data(), st->hist.ptr, entries * 4, hipMemcpyDeviceToHost, s));
-    MC_HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = mandelbrot_equalise_map(p->max_iter, st->hist_host.data(), st->map_host.data()))) return rc;
-    return mandelbrot_recolour_launch(ctx, p, d_iters, 4u, st->map_host.data(), d_rgba, s);
+    const uint32_t* map = nullptr;
+    if (int rc = mandelbrot_equalise_plane_map(ctx, p->max_iter, d_iters, 4u, npix, s, &map)) return rc;
+    return mandelbrot_recolour_launch(ctx, p, d_iters, 4u, map, d_rgba, s);
 }
 
 int mandelbrot_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_t s) {

@@ -232,6 +232,11 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
         set_error_detail("mc_multi_*: MC_MANDEL_COLOUR_EQUALISED is single-device only");
         return MC_ERR_UNSUPPORTED;
     }
+    if (((p->flags >> 8) & 15u) > 1u) {   // MC_MANDEL_SUPERSAMPLE: the resolve runs on the device that holds the samples
+        set_error_detail("mc_multi_*: MC_MANDEL_SUPERSAMPLE is single-device only (mc_mandelbrot_supersample_params, "
+                         "mc_mandelbrot_resolve_device_async per device)");
+        return MC_ERR_UNSUPPORTED;
+    }
     const bool want_rgba = out_rgba_f32 || out_rgba8;
     if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;
     const uint32_t W = p->width, H = p->height;
