@@ -33,7 +33,7 @@ extern "C" {
  * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy;
  * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
  * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
- * mc_mandelbrot_resolve_device_async.
+ * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -293,8 +293,10 @@ enum {
     MC_MANDEL_ITERS_U16 = 1u << 1,/* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */
                                   /* format, half of the 4-B plane and an eighth of the vec4 (mc_mandelbrot_assemble_...)  */
     /* bits 2 and 3 are measurement switches too */
-    MC_MANDEL_COLOUR_EQUALISED = 1u << 4 /* histogram-equalised colouring of a WHOLE image (mc_mandelbrot_render and            */
+    MC_MANDEL_COLOUR_EQUALISED = 1u << 4,/* histogram-equalised colouring of a WHOLE image (mc_mandelbrot_render and            */
                                   /* mc_mandelbrot_render_rgba8; the contract is below, at mc_mandelbrot_equalise_map)      */
+    MC_MANDEL_SUPERSAMPLE_ADAPTIVE = 1u << 5 /* with MC_MANDEL_SUPERSAMPLE(s): only pixels whose count differs from a neighbour's  */
+                                  /* get their s x s samples (the contract is below, at mc_context_last_refined)            */
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
@@ -403,7 +405,7 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
  * mc_context_warmup_mandelbrot accepts it and makes the resolve kernel resident too.
  *
  * mc_mandelbrot_supersample_params (host only, no device): q = the plain-render parameters of p's sample grid: width, height, row_begin,
- * row_end, row_block and row_stride multiplied by s, the supersample bits and MC_MANDEL_COLOUR_EQUALISED cleared, everything else copied
+ * row_end, row_block and row_stride multiplied by s, the supersample bits, MC_MANDEL_COLOUR_EQUALISED and MC_MANDEL_SUPERSAMPLE_ADAPTIVE cleared, everything else copied
  * (q may be p).  A contiguous or interleaved tile of p is exactly the tile of q whose compact rows are, for each compact pixel row, its s
  * sample rows in order.  s = 0 or 1 multiplies by 1.  An invalid s, a product above 2^32 - 1 or a NULL pointer: MC_ERR_INVALID_ARGUMENT.
  *
@@ -415,6 +417,39 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
 int mc_mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_params* q);
 int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes /* 2 or 4 */,
                                        const uint32_t* map /* HOST, max_iter + 1, or NULL */, void* d_rgba_f32, void* stream);
+
+/* ---- adaptive supersampling (the project's own addition; what tests/mandel_adaptive_ref.py restates).
+ *      MC_MANDEL_SUPERSAMPLE_ADAPTIVE in flags, valid only together with MC_MANDEL_SUPERSAMPLE(s), s = 2, 4 or 8 (alone:
+ *      MC_ERR_INVALID_ARGUMENT from every call): a pixel gets its s*s samples only where its count differs from a neighbour's.
+ *  - samples: the section above's, unchanged: sample (s*y + i, s*x + j) of pixel (y, x) has the count n(s*y + i, s*x + j) of the plain
+ *    s*W x s*H render.
+ *  - anchor: a(y, x) = n(s*y, s*x).  The anchor plane IS the plain W x H image's count plane, bit for bit, in every precision:
+ *    (s*x) / (s*W) and x / W are the same float and the same double because s is a power of two, and the rest of a sample's arithmetic
+ *    is a function of that quotient.
+ *  - refined: pixel (y, x) is refined iff a(y', x') != a(y, x) for some (y', x') with |y' - y| <= 1, |x' - x| <= 1 inside the image
+ *    (neighbours outside the image do not exist).
+ *  - colour: a refined pixel gets the section above's colour of its s*s samples (the same pairwise tree, the same 1 / (s*s) scaling); any
+ *    other pixel gets lut[a].  So the image equals the fully supersampled one on every pixel that is refined or whose samples share one
+ *    count; the two differ only on unrefined pixels with mixed samples, which is the stated approximation.
+ *  - with MC_MANDEL_COLOUR_EQUALISED: the histogram is the ANCHOR plane's (W*H values: the map is the plain equalised image's map), and
+ *    lut[.] becomes lut[map[.]] for refined and unrefined pixels alike; an unrefined pixel is bit-identical to the plain equalised image.
+ *  - the image is the same bits from run to run.
+ * mc_mandelbrot_render (out_rgba_f32; out_iters refused as for every s >= 2) and mc_mandelbrot_render_rgba8 honour the bit in all six
+ * precisions for WHOLE images only (row_begin = 0, row_end = height, no interleave; width * height <= 2^32 - 1, and s * width and
+ * s * height <= 2^32 - 1 as for every s >= 2: the list render reads the sample grid's c table): a tile or band cannot
+ * see its neighbours' anchors and is MC_ERR_INVALID_ARGUMENT, mc_last_error_detail saying so.  The chain: the plain W x H render (anchor
+ * plane, uint16_t when max_iter <= 65535, and the plain colours), [its histogram, map and recolouring when equalised,] a device list of
+ * the refined pixels, 4 bytes back to the host (the list's length), and a render of the list's samples that resolves each pixel between
+ * the lanes that computed its samples; no sample plane exists (scratch: 2 or 4 bytes of anchor and 4 bytes of list per pixel).
+ * mc_context_last_timing spans the whole chain.  mc_mandelbrot_resolve_device_async refuses the bit (it resolves a full plane); the calls
+ * that refuse s >= 2 keep refusing; mc_multi_* answer MC_ERR_UNSUPPORTED.  mc_mandelbrot_supersample_params clears the bit in q.
+ * mc_context_warmup_mandelbrot accepts it and makes the list and list-render kernels resident too.
+ * It pays where the picture has bands or interior and costs where nearly every pixel is an edge (the plain pass comes on top): see the
+ * use / do-not-use line of DESIGN.md section 3.12, and read the share of every call with:
+ *
+ * mc_context_last_refined: the refined pixels and the image's pixels of the context's last successful adaptive render; either pointer may
+ * be NULL; MC_ERR_INVALID_ARGUMENT before the first such render. */
+int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

@@ -61,6 +61,13 @@ int mc_test_rand01(mc_context* ctx, const uint32_t* xyz, float* out, size_t n);
  * 12 ds_mul with the one-fma error term (the two-float Mandelbrot's fast block; equals op 2 for |hi| in [2^-50, 2^60));
  * n pairs of (hi,lo). */
 int mc_test_ds_op(mc_context* ctx, int op, const float* a, const float* b, float* out, size_t n);
+/* The refine list of MC_MANDEL_SUPERSAMPLE_ADAPTIVE (include/mc_compute.h) on a caller's DEVICE plane of W x H counts (iters_bytes 2:
+ * uint16_t, 4: uint32_t): the indices y * W + x of the refined pixels are written to d_list (device, room for W * H uint32_t) in no
+ * particular order, their number to *d_count (device; zeroed by the call).  Asynchronous on `stream` (NULL = the context's stream).
+ * (Named mc_hook_*, not mc_test_*: the five mc_test_* functions above are the device-function evaluators tests/test_abi.py counts; this
+ * one runs a kernel of the product library on a caller's plane.) */
+int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_bytes, uint32_t width, uint32_t height, uint32_t* d_list,
+                          uint32_t* d_count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ PT_MATH_STRICT, PT_MATH_FAST, PT_MATH_FAST_CAREFUL = 0, 1, 2
 MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
 MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
+MANDEL_SUPERSAMPLE_ADAPTIVE = 32   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE: with MANDEL_SUPERSAMPLE(s), only pixels whose count differs from a neighbour's are sampled s x s
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
@@ -155,6 +156,8 @@ def lib():
         if hasattr(L, "mc_mandelbrot_supersample_params"):   # MC_MANDEL_SUPERSAMPLE
             L.mc_mandelbrot_supersample_params.argtypes = [C.POINTER(MandelbrotParams), C.POINTER(MandelbrotParams)]
             L.mc_mandelbrot_resolve_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, u32, vp, vp, vp]
+        if hasattr(L, "mc_context_last_refined"):   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE
+            L.mc_context_last_refined.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -184,6 +187,8 @@ def test_lib():
                                          C.POINTER(C.c_uint32)]
         L.mc_test_rand01.argtypes = [vp, vp, vp, C.c_size_t]
         L.mc_test_ds_op.argtypes = [vp, i32, vp, vp, vp, C.c_size_t]
+        if hasattr(L, "mc_hook_mandel_refine"):   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE
+            L.mc_hook_mandel_refine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         _test_lib = L
     return _test_lib
 
@@ -226,10 +231,12 @@ def split_double(d):
 
 
 def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, centre=(-0.445, 0.0), scale=(2.34, 2.34),
-                      k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0, supersample=0):
+                      k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0, supersample=0,
+                      adaptive=False):
+    """adaptive: MANDEL_SUPERSAMPLE_ADAPTIVE beside supersample= (only pixels whose count differs from a neighbour's are sampled s x s)."""
     p = MandelbrotParams()
     _check(lib().mc_mandelbrot_default_params(width, height, C.byref(p)), "mc_mandelbrot_default_params")
-    p.max_iter, p.precision, p.flags = max_iter, precision, flags | MANDEL_SUPERSAMPLE(supersample)
+    p.max_iter, p.precision, p.flags = max_iter, precision, flags | MANDEL_SUPERSAMPLE(supersample) | (MANDEL_SUPERSAMPLE_ADAPTIVE if adaptive else 0)
     p.centre_x_hi, p.centre_x_lo = split_double(centre[0])
     p.centre_y_hi, p.centre_y_lo = split_double(centre[1])
     p.scale_x_hi, p.scale_x_lo = split_double(scale[0])
@@ -243,7 +250,7 @@ def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, cent
 
 def supersample_params(p):
     """mc_mandelbrot_supersample_params (host only): the plain-render params of p's sample grid (s times the width, height and rows; the
-    supersample bits and MANDEL_COLOUR_EQUALISED cleared)."""
+    supersample bits, MANDEL_COLOUR_EQUALISED and MANDEL_SUPERSAMPLE_ADAPTIVE cleared)."""
     q = MandelbrotParams()
     _check(lib().mc_mandelbrot_supersample_params(C.byref(p), C.byref(q)), "mc_mandelbrot_supersample_params")
     return q
@@ -507,6 +514,12 @@ class Context:
         _check(lib().mc_context_last_timing(self._h, C.byref(k), C.byref(c)), "mc_context_last_timing")
         return k.value, c.value
 
+    def last_refined(self):
+        """(refined, pixels) of the last successful adaptive render on this context (mc_context_last_refined)."""
+        r, n = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mc_context_last_refined(self._h, C.byref(r), C.byref(n)), "mc_context_last_refined")
+        return r.value, n.value
+
     def bind_mandelbrot_orbit(self, orbit):
         """mc_context_bind_mandelbrot_orbit: the view of MC_PRECISION_PERTURB renders on this context (None unbinds)."""
         if orbit is not None and not orbit._h:   # a closed orbit's handle is NULL, which the C call reads as "unbind"
@@ -666,6 +679,11 @@ class Context:
         _check(test_lib().mc_test_ds_op(self._h, DS_OPS[op], _ptr(a), _ptr(b), _ptr(out),
                                    a.shape[0]), "mc_test_ds_op")
         return out
+
+    def test_mandel_refine(self, d_plane, iters_bytes, width, height, d_list, d_count, stream=0):
+        """mc_hook_mandel_refine: the refine list of the W x H count plane at device pointer d_plane into d_list (device, W * H uint32), its
+        length into d_count (device, one uint32).  Asynchronous on `stream`; the list's order is unspecified."""
+        _check(test_lib().mc_hook_mandel_refine(self._h, d_plane, iters_bytes, width, height, d_list, d_count, stream), "mc_hook_mandel_refine")
 
 
 class Multi:

@@ -1,12 +1,15 @@
 // MC_PRECISION_PERTURB (mandel_perturb.hip): the entry points the rest of the library calls.
 #pragma once
+#include "mandel_adaptive.h"
 #include "mc_internal.h"
 
 namespace mc {
 
 // launch_impl (mandelbrot.hip) hands precision 3 over after its common checks: orbit / view / max_iter checks, the colour and dc tables,
 // the launch.  warm = the cold-start warm-up's one-tile launch (mc_context_warmup_mandelbrot).
-int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm);
+// list: the list render of mandel_adaptive.h (p is the sample grid), or nullptr.
+int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
+                   const SampleList* list = nullptr);
 // mc_context_destroy: the context's bound orbit, if any, is freed.
 void perturb_release(mc_context* ctx);
 
@@ -24,7 +27,7 @@ struct PerturbDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E
     uint32_t has_zero;               // some Z_j = 0 exactly, 1 <= j < L (centres such as 0 and -1)
 };
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s);
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
 // MC_PRECISION_PERTURB_BLA (mandel_perturb_bla.hip): PERTURB's loop with bilinear skips, for orbits rendered by the plain loop.
 // perturb_launch builds the arguments from the binding: the dc table is PERTURB's, the BLA table the orbit's (mc_mandelbrot_orbit_bla),
@@ -42,7 +45,7 @@ struct PerturbBlaArgs {
     const double* bla;               // the BLA table (null when it has no entry: L < 3)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS: write the loop-trip count in place of n
 };
-int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s);
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
 // MC_PRECISION_PERTURB_BLA_DEEP (mandel_perturb_bla_deep.hip): the rescaled loop of the deep kernel with bilinear skips, for every orbit.
 // The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one 64-byte record, its mantissas and
@@ -65,6 +68,6 @@ struct PerturbBlaDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E (0 for an orbit of the old scale)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS
 };
-int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s);
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
 }  // namespace mc

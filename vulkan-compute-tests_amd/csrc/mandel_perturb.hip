@@ -717,6 +717,16 @@ __global__ void __launch_bounds__(64) mandel_perturb_kernel(PerturbArgs a) {
     }
 }
 
+// The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_list_kernel(PerturbArgs a, SampleList l) {
+    const SampleLane ln = sample_lane(l);
+    StatePerturb st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    const uint32_t n = escape_time<StatePerturb, U>(st, a.max_iter, ln.valid);
+    sample_resolve(l, ln, n, a.max_iter);
+}
+
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
 // by (W, H, precision, the bind generation): the params' view words are all zero for this precision.
 int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Binding& b, hipStream_t s) {
@@ -741,7 +751,8 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
 
 }  // namespace
 
-int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm) {
+int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
+                   const SampleList* list) {
     const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
     const bool bla_deep = p->precision == MC_PRECISION_PERTURB_BLA_DEEP;
     const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : bla_deep ? "MC_PRECISION_PERTURB_BLA_DEEP" : "MC_PRECISION_PERTURB";
@@ -800,12 +811,21 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         grid = dim3(1, 1);
         a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
     }
+    SampleList l{};
+    if (list) {   // a wave takes 64 / s^2 entries; the kernel's own outputs stay unused
+        a.out_rgba = nullptr; a.out_iters = nullptr; a.out_iters16 = nullptr; a.lut = nullptr;
+        l = *list;
+        if (warm) l.count = 1u;
+        const uint32_t per = 64u >> (2u * l.log2s);
+        grid = dim3((l.count + per - 1u) / per);
+        list = &l;
+    }
     if (bla) {   // mandel_perturb_bla.hip
         const PerturbBlaArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
                                   a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
                                   b->bla_entries ? (const double*)b->bla.ptr : nullptr,
                                   (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_launch(d, grid, s))) return rc;
+        if ((rc = perturb_bla_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
     if (bla_deep) {   // mandel_perturb_bla_deep.hip
@@ -813,16 +833,17 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
                                       a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
                                       b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
                                       (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_deep_launch(d, grid, s))) return rc;
+        if ((rc = perturb_bla_deep_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
         const PerturbDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
                                    a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit, b->scale_exp2, b->has_zero ? 1u : 0u};
-        if ((rc = perturb_deep_launch(d, grid, s))) return rc;
+        if ((rc = perturb_deep_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
-    hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
+    if (!list) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
 }

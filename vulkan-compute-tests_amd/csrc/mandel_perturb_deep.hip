@@ -178,10 +178,21 @@ __global__ void __launch_bounds__(64) mandel_perturb_deep_kernel(PerturbDeepArgs
     }
 }
 
+// The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_deep_list_kernel(PerturbDeepArgs a, SampleList l) {
+    const SampleLane ln = sample_lane(l);
+    StateDeep st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    const uint32_t n = escape_time<StateDeep, U>(st, a.max_iter, ln.valid);
+    sample_resolve(l, ln, n, a.max_iter);
+}
+
 }  // namespace
 
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list) {
+    if (!list) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }

@@ -155,7 +155,7 @@ int mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_p
     out.width = p->width * s; out.height = p->height * s;
     out.row_begin = p->row_begin * s; out.row_end = p->row_end * s;
     out.row_block = p->row_block * s; out.row_stride = p->row_stride * s;
-    out.flags &= ~((uint32_t)MC_MANDEL_SUPERSAMPLE(15) | (uint32_t)MC_MANDEL_COLOUR_EQUALISED);
+    out.flags &= ~((uint32_t)MC_MANDEL_SUPERSAMPLE(15) | (uint32_t)MC_MANDEL_COLOUR_EQUALISED | (uint32_t)MC_MANDEL_SUPERSAMPLE_ADAPTIVE);
     *q = out;
     return MC_OK;
 }
@@ -200,6 +200,11 @@ int mc_mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbro
 int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes,
                                        const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_samples || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
+    if (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) {
+        set_error_detail("mc_mandelbrot_resolve_device_async: MC_MANDEL_SUPERSAMPLE_ADAPTIVE: this call resolves a FULL sample plane; the adaptive "
+                         "render is mc_mandelbrot_render / mc_mandelbrot_render_rgba8 of a whole image");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
     MC_HIP_TRY(hipSetDevice(ctx->device));
     return mandelbrot_resolve_launch(ctx, p, d_samples, iters_bytes, map, d_rgba_f32, stream ? (hipStream_t)stream : ctx->stream);
 }

@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "ds_arith.h"
+#include "mandel_adaptive.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
 #include "mc_internal.h"
@@ -201,6 +202,17 @@ __global__ void __launch_bounds__(64) mandelbrot_kernel(MandelArgs a) {
     }
 }
 
+// The same per-lane state under the list mapping of mandel_adaptive.h: `a` describes the sample grid, a lane is one sample of a refined
+// pixel, and the pixel's colour is resolved between the lanes (no count leaves the kernel).
+template <class State, int U>
+__global__ void __launch_bounds__(64) mandelbrot_list_kernel(MandelArgs a, SampleList l) {
+    const SampleLane ln = sample_lane(l);
+    State st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    const uint32_t n = escape_time<State, U>(st, a.max_iter, ln.valid);
+    sample_resolve(l, ln, n, a.max_iter);
+}
+
 }  // namespace
 
 // colour(n) = d + e*cos(6.28318*(f*t+g)), t = n/M — mandelbrot.comp:50-56, evaluated in fp32 in source
@@ -292,7 +304,9 @@ int mandelbrot_lut_device(mc_context* ctx, const mc_mandelbrot_params* p, hipStr
 
 // warm = the cold-start warm-up (mc_context_warmup_mandelbrot): the tables of the REAL request are built and uploaded, then ONE 8 x 8
 // tile is run for at most 32 iterations into d_iters — enough for the runtime to load this code object and create the kernel.
-static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm) {
+// list = the list render of mandel_adaptive.h (p is the sample grid, d_rgba the image the list's pixels are written to, d_iters unused).
+static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
+                       const SampleList* list = nullptr) {
     if (!ctx || !p || (!d_rgba && !d_iters)) return MC_ERR_INVALID_ARGUMENT;
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
@@ -303,7 +317,7 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
     if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
         p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
-        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm);   // mandel_perturb.hip
+        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm, list);   // mandel_perturb.hip
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);
         if (rc) return rc;
@@ -331,14 +345,26 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
         grid = dim3(1, 1);
         a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
     }
-    if (p->precision == MC_PRECISION_DS) {
-        hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
-    } else if (p->precision == MC_PRECISION_F64) {
-        hipLaunchKernelGGL((mandelbrot_kernel<StateF64, 8>), grid, block, 0, s, a);
-    } else if (p->flags & MC_MANDEL_FMA) {
-        hipLaunchKernelGGL((mandelbrot_kernel<StateF32<true>, 8>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((mandelbrot_kernel<StateF32<false>, 8>), grid, block, 0, s, a);
+    if (!list) {
+        if (p->precision == MC_PRECISION_DS) {
+            hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
+        } else if (p->precision == MC_PRECISION_F64) {
+            hipLaunchKernelGGL((mandelbrot_kernel<StateF64, 8>), grid, block, 0, s, a);
+        } else if (p->flags & MC_MANDEL_FMA) {
+            hipLaunchKernelGGL((mandelbrot_kernel<StateF32<true>, 8>), grid, block, 0, s, a);
+        } else {
+            hipLaunchKernelGGL((mandelbrot_kernel<StateF32<false>, 8>), grid, block, 0, s, a);
+        }
+    } else {   // a wave takes 64 / s^2 entries; the kernel's own outputs stay unused
+        a.out_rgba = nullptr; a.out_iters = nullptr; a.out_iters16 = nullptr; a.lut = nullptr;
+        const uint32_t per = 64u >> (2u * list->log2s);
+        SampleList l = *list;
+        if (warm) l.count = 1u;
+        grid = dim3((l.count + per - 1u) / per);
+        if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_kernel<StateDS, 4>), grid, block, 0, s, a, l);
+        else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF64, 8>), grid, block, 0, s, a, l);
+        else if (p->flags & MC_MANDEL_FMA) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<true>, 8>), grid, block, 0, s, a, l);
+        else hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<false>, 8>), grid, block, 0, s, a, l);
     }
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
@@ -346,6 +372,11 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
 
 int mandelbrot_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s) {
     return launch_impl(ctx, p, d_rgba, d_iters, s, false);
+}
+
+int mandelbrot_list_launch(mc_context* ctx, const mc_mandelbrot_params* grid, const SampleList& l, hipStream_t s, bool warm) {
+    if (!l.list || !l.count || !l.img_w || !l.table || !l.out_rgba || l.log2s < 1u || l.log2s > 3u) return MC_ERR_INVALID_ARGUMENT;
+    return launch_impl(ctx, grid, l.out_rgba, nullptr, s, warm, &l);
 }
 
 int mandelbrot_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters_scratch, hipStream_t s) {

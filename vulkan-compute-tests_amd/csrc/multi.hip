@@ -237,6 +237,10 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
                          "mc_mandelbrot_resolve_device_async per device)");
         return MC_ERR_UNSUPPORTED;
     }
+    if (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) {   // (the bit without a factor: every call refuses it)
+        set_error_detail("mc_multi_*: MC_MANDEL_SUPERSAMPLE_ADAPTIVE is single-device only");
+        return MC_ERR_UNSUPPORTED;
+    }
     const bool want_rgba = out_rgba_f32 || out_rgba8;
     if (!whole_image(p)) return MC_ERR_INVALID_ARGUMENT;
     const uint32_t W = p->width, H = p->height;

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "ds_arith.h"
+#include "mandel_adaptive.h"
 #include "mc_internal.h"
 #include "mc_math.h"
 #include "../../include/mc_compute_test.h"
@@ -205,6 +206,16 @@ int mc_test_ds_op(mc_context* ctx, int op, const float* a, const float* b, float
                                            (const float*)x, (const float*)y, (float*)o, n_);
                     },
                     n, op, 0);
+}
+
+// The refine list of MC_MANDEL_SUPERSAMPLE_ADAPTIVE on a caller's device plane (mandel_refine.hip's step 1, nothing else of the chain).
+int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_bytes, uint32_t width, uint32_t height, uint32_t* d_list,
+                          uint32_t* d_count, void* stream) {
+    if (!ctx || !d_count) return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MC_HIP_TRY(hipMemsetAsync(d_count, 0, 4, s));
+    return mandelbrot_refine_launch(ctx, d_plane, iters_bytes, width, height, d_list, d_count, s);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised (histogram-equalised colouring of the whole image), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised (histogram-equalised colouring of the whole image), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -40,6 +40,7 @@ int main(int argc, char* argv[]) {
     int pngThreads = 0;
     uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
+    bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -90,6 +91,13 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--adaptive") {   // supersample only the pixels whose count differs from a neighbour's
+            adaptive = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--adaptive: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -107,6 +115,7 @@ int main(int argc, char* argv[]) {
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { printf("unknown option %s\n", a.c_str()); exit(EXIT_FAILURE); }
         else pos.push_back(argv[i]);
     }
+    if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
     (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -121,6 +130,7 @@ int main(int argc, char* argv[]) {
     }
     if (supersample > 1u) {   // the sample plane is resolved by the whole-image calls: never the banded, streamed save
         app.setSupersample(supersample);
+        if (adaptive) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_ADAPTIVE);   // (whole-image calls as well: the save is never streamed)
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --supersample renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     }
@@ -199,6 +209,9 @@ int main(int argc, char* argv[]) {
         app.preRun();
         printf("now running app!\n");
         app.run();
+#if defined(MANDELBROT_MODE)
+        if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
+#endif
         auto t0 = std::chrono::steady_clock::now();
         if (outFile) app.saveRenderedImage(outFile);
         else app.saveRenderedImage();

@@ -83,6 +83,13 @@ struct MandelbrotApp : public ComputeApp {
 
     const HostStorage& storageBuffer() const { return buffer; }
 
+    // --adaptive: how many pixels the last render sampled s x s (the share above which plain supersampling is the faster call: DESIGN.md §3.12)
+    void printRefined() {
+        uint64_t refined = 0, pixels = 0;
+        check(mc_context_last_refined(ctx, &refined, &pixels), "mc_context_last_refined");
+        printf("refined %llu of %llu pixels\n", (unsigned long long)refined, (unsigned long long)pixels);
+    }
+
 private:
     // The image in row bands of kBandRows through mc_mandelbrot_render_banded: band k + 1 is launched on a second stream before band k has
     // finished, and every band is handed to the PNG workers as it arrives.  At K4 (5120 rows: 8 bands) the 50 ms of filter + deflate run
