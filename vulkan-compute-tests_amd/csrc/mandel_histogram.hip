@@ -19,10 +19,9 @@
 //  * integer adds commute: the table is bit-reproducible whatever the arrival order.  Vector atomics and vector stores only.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 #include "mandel_equalise.h"
+#include "mandel_side_record.h"
 
 namespace mc {
 
@@ -143,7 +142,7 @@ __global__ void __launch_bounds__(256) mandel_recolour_kernel(const T* __restric
     }
 }
 
-// The device state of the feature, keyed by the context (csrc/mc_internal.h stays as it is; the bound orbit's record is the model).
+// The device state of the feature, a side record of the context (mandel_side_record.h).
 struct EqualiseState {
     DeviceBuffer hist;                 // the whole-image calls' table
     DeviceBuffer table;                // lut[map[j]], (max_iter + 1) vec4: a cached device table like the colour LUT
@@ -155,23 +154,15 @@ struct EqualiseState {
     float lut_kcolor[4] = {0, 0, 0, 0};
     std::vector<uint32_t> hist_host, map_host;
 };
-std::mutex g_eq_mutex;
-std::unordered_map<const mc_context*, EqualiseState> g_eq_states;
-
-EqualiseState* state_of(const mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_eq_mutex);
-    return &g_eq_states[ctx];   // the node stays put while other contexts add theirs (only this context's thread erases it)
-}
+SideRecords<EqualiseState> g_eq_states;
 
 }  // namespace
 
 void equalise_release(mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_eq_mutex);
-    auto it = g_eq_states.find(ctx);
-    if (it == g_eq_states.end()) return;
-    it->second.hist.release();
-    it->second.table.release();
-    g_eq_states.erase(it);
+    g_eq_states.erase(ctx, [](EqualiseState& st) {
+        st.hist.release();
+        st.table.release();
+    });
 }
 
 int mandelbrot_histogram_launch(mc_context* ctx, const void* d_iters, uint32_t iters_bytes, uint64_t n_pixels, uint32_t max_iter,
@@ -248,7 +239,7 @@ int mandelbrot_composed_table(mc_context* ctx, const mc_mandelbrot_params* p, co
             set_error_detail(std::string(who) + ": a map entry exceeds max_iter");
             return MC_ERR_INVALID_ARGUMENT;
         }
-    EqualiseState* st = state_of(ctx);
+    EqualiseState* st = g_eq_states.get(ctx);
     const size_t entries = (size_t)M + 1;
     const bool cached = st->table.ptr && st->table_max_iter == M && std::memcmp(st->table_kcolor, p->k_color, sizeof(float) * 4) == 0 &&
                         st->table_map.size() == entries && std::memcmp(st->table_map.data(), map, entries * 4) == 0;
@@ -302,7 +293,7 @@ int mandelbrot_recolour_launch(mc_context* ctx, const mc_mandelbrot_params* p, c
 
 int mandelbrot_equalise_plane_map(mc_context* ctx, uint32_t max_iter, const void* d_iters, uint32_t iters_bytes, uint64_t n_values,
                                   hipStream_t s, const uint32_t** map) {
-    EqualiseState* st = state_of(ctx);
+    EqualiseState* st = g_eq_states.get(ctx);
     const size_t entries = (size_t)max_iter + 1;
     int rc = st->hist.reserve(entries * 4);
     if (rc) return rc;
@@ -330,7 +321,7 @@ int mandelbrot_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, co
 
 int mandelbrot_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, hipStream_t s) {
     // scratch_iters holds at least 64 counts (mc_context_warmup_mandelbrot); scratch_rgba at least 64 vec4
-    EqualiseState* st = state_of(ctx);
+    EqualiseState* st = g_eq_states.get(ctx);
     const size_t entries = (size_t)p->max_iter + 1;
     int rc = st->hist.reserve(entries * 4);
     if (rc) return rc;

@@ -1,6 +1,7 @@
 // MC_PRECISION_PERTURB (mandel_perturb.hip): the entry points the rest of the library calls.
 #pragma once
 #include "mandel_adaptive.h"
+#include "mandel_target.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -16,14 +17,7 @@ void perturb_release(mc_context* ctx);
 // The deep kernel (mandel_perturb_deep.hip): orbits with min |scale| < 2^-960, or any orbit under MC_MANDEL_PERTURB_FORCE_DEEP.
 // perturb_launch builds the arguments (the dc table holds the scale's mantissas: u = ((double)g / (double)n - 0.5) * mantissa).
 struct PerturbDeepArgs {
-    uint32_t W, H, max_iter, L;
-    uint32_t row_begin, row_end, row_block, row_stride;
-    float4* out_rgba;                // tile-local, may be null
-    uint32_t* out_iters;             // tile-local, may be null
-    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
-    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
-    const double* u_tab;             // [ux[W] | uy[H]]
-    const double2* orbit;            // Z_0 .. Z_L
+    MandelTarget t;                  // t.table: [ux[W] | uy[H]]
     int32_t exp2;                    // E: the pixel's offset is u * 2^E
     uint32_t has_zero;               // some Z_j = 0 exactly, 1 <= j < L (centres such as 0 and -1)
 };
@@ -34,14 +28,7 @@ int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, cons
 // level-major with (A.x, A.y, B.x, B.y, R) per entry; level k starts at entry S(L-2) - S((L-2) >> k), S(n) = 2n - popcount(n)
 // (the sum of floor(n / 2^j) over j >= 0), so the kernel needs no offset array.
 struct PerturbBlaArgs {
-    uint32_t W, H, max_iter, L;
-    uint32_t row_begin, row_end, row_block, row_stride;
-    float4* out_rgba;                // tile-local, may be null
-    uint32_t* out_iters;             // tile-local, may be null
-    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
-    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
-    const double* dc_tab;            // [dcx[W] | dcy[H]]
-    const double2* orbit;            // Z_0 .. Z_L
+    MandelTarget t;                  // t.table: [dcx[W] | dcy[H]]
     const double* bla;               // the BLA table (null when it has no entry: L < 3)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS: write the loop-trip count in place of n
 };
@@ -56,14 +43,7 @@ struct BlaDeepRec {
 };
 static_assert(sizeof(BlaDeepRec) == 64, "one table entry is one 64-byte record");
 struct PerturbBlaDeepArgs {
-    uint32_t W, H, max_iter, L;
-    uint32_t row_begin, row_end, row_block, row_stride;
-    float4* out_rgba;                // tile-local, may be null
-    uint32_t* out_iters;             // tile-local, may be null
-    uint16_t* out_iters16;           // MC_MANDEL_ITERS_U16, may be null
-    const float4* lut;               // max_iter+1 entries (null when out_rgba is null)
-    const double* u_tab;             // [ux[W] | uy[H]]
-    const double2* orbit;            // Z_0 .. Z_L
+    MandelTarget t;                  // t.table: [ux[W] | uy[H]]
     const BlaDeepRec* bla;           // the table (null when it has no entry: L < 3)
     int32_t exp2;                    // E: the pixel's offset is u * 2^E (0 for an orbit of the old scale)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS

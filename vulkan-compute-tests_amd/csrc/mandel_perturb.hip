@@ -7,16 +7,16 @@
 //    The orbit is read from HBM (L2-resident: 800 KB at M = 50 000); the fast block fetches the block's U entries at its start, so
 //    no load sits on the iteration's dependency chain, and a block in which an unfinished lane rebases is replayed exactly.
 //  * IEEE double in source order: this TU is built with -ffp-contract=off like every other; fp64 denormals stay enabled.
+#include <atomic>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <new>
-#include <unordered_map>
 #include <vector>
 
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
+#include "mandel_side_record.h"
 #include "mc_internal.h"
 
 // ---- host: multi-limb fixed point -----------------------------------------------------------------------------------------------
@@ -584,8 +584,7 @@ namespace mc {
 
 namespace {
 
-// The orbit bound to each context.  Kept here rather than in mc_context so that mc_internal.h, which the path tracer's build id
-// covers, stays as it is.  The map is shared by every context (a context itself is used by one thread at a time): lookups lock it.
+// The orbit bound to each context (a side record: mandel_side_record.h).
 struct Binding {
     DeviceBuffer orbit;                // Z_0 .. Z_L, double2
     uint32_t length = 0, max_iter = 0;
@@ -605,25 +604,11 @@ struct Binding {
     uint64_t bla_deep_entries = 0;
     bool has_bla_deep = false;
 };
-std::mutex g_bind_mutex;
-std::unordered_map<const mc_context*, Binding> g_bindings;
-uint32_t g_generation = 0;
-
-Binding* find_binding(const mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_bind_mutex);
-    auto it = g_bindings.find(ctx);
-    return it == g_bindings.end() ? nullptr : &it->second;
-}
+SideRecords<Binding> g_bindings;
+std::atomic<uint32_t> g_generation{0};
 
 struct PerturbArgs {
-    uint32_t W, H, max_iter, L;
-    uint32_t row_begin, row_end, row_block, row_stride;
-    float4* __restrict__ out_rgba;        // tile-local, may be null
-    uint32_t* __restrict__ out_iters;     // tile-local, may be null
-    uint16_t* __restrict__ out_iters16;   // MC_MANDEL_ITERS_U16, may be null
-    const float4* __restrict__ lut;       // max_iter+1 entries (null when out_rgba is null)
-    const double* __restrict__ dc_tab;    // [dcx[W] | dcy[H]]: the pixel's offset from c_ref per column / per row
-    const double2* __restrict__ orbit;    // Z_0 .. Z_L
+    MandelTarget t;   // t.table: [dcx[W] | dcy[H]], the pixel's offset from c_ref per column / per row
 };
 
 // One pixel's offset from the reference orbit (the loop of include/mc_compute.h, MC_PRECISION_PERTURB).  Per iteration 20 fp64 ops
@@ -635,10 +620,10 @@ struct StatePerturb {
     double dcx, dcy, dx, dy, zmx, zmy;      // zm = Z[m]
     uint32_t m;
     __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const PerturbArgs& a) {
-        Z = a.orbit;
-        L = a.L;
-        dcx = a.dc_tab[gx];
-        dcy = a.dc_tab[a.W + gy];
+        Z = a.t.orbit;
+        L = a.t.L;
+        dcx = a.t.table[gx];
+        dcy = a.t.table[a.t.W + gy];
         dx = dy = zmx = zmy = 0.0;
         m = 0;
     }
@@ -700,21 +685,10 @@ struct StatePerturb {
 template <int U>
 __global__ void __launch_bounds__(64) mandel_perturb_kernel(PerturbArgs a) {
     static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    // the tile mapping of mandelbrot_kernel (mandelbrot.hip): one wave = one 8x8 pixel tile
-    const uint32_t lane = threadIdx.x;
-    const uint32_t gx = blockIdx.x * 8u + (lane & 7u);
-    const uint32_t ty = blockIdx.y * 8u + (lane >> 3);
-    const uint32_t gy = tile_row_to_storage(ty, a.row_begin, a.row_block, a.row_stride);
-    const bool valid = gx < a.W && gy < a.row_end;
+    const TileLane ln = tile_lane(a.t);
     StatePerturb st;
-    st.init(valid ? gx : 0u, valid ? gy : 0u, a);
-    const uint32_t n = escape_time<StatePerturb, U>(st, a.max_iter, valid);
-    if (valid) {
-        const size_t idx = (size_t)ty * a.W + gx;
-        if (a.out_iters) a.out_iters[idx] = n;
-        if (a.out_iters16) a.out_iters16[idx] = (uint16_t)n;
-        if (a.out_rgba) a.out_rgba[idx] = a.lut[n];
-    }
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    tile_store(a.t, ln, escape_time<StatePerturb, U>(st, a.t.max_iter, ln.valid));
 }
 
 // The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
@@ -723,8 +697,8 @@ __global__ void __launch_bounds__(64) mandel_perturb_list_kernel(PerturbArgs a, 
     const SampleLane ln = sample_lane(l);
     StatePerturb st;
     st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    const uint32_t n = escape_time<StatePerturb, U>(st, a.max_iter, ln.valid);
-    sample_resolve(l, ln, n, a.max_iter);
+    const uint32_t n = escape_time<StatePerturb, U>(st, a.t.max_iter, ln.valid);
+    sample_resolve(l, ln, n, a.t.max_iter);
 }
 
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
@@ -756,7 +730,7 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
     const bool bla_deep = p->precision == MC_PRECISION_PERTURB_BLA_DEEP;
     const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : bla_deep ? "MC_PRECISION_PERTURB_BLA_DEEP" : "MC_PRECISION_PERTURB";
-    const Binding* b = find_binding(ctx);
+    const Binding* b = g_bindings.find(ctx);
     if (!b || !b->orbit.ptr || !b->length) {
         set_error_detail(name + ": no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
         return MC_ERR_INVALID_ARGUMENT;
@@ -772,8 +746,11 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         set_error_detail(name + ": max_iter above the bound orbit's");
         return MC_ERR_INVALID_ARGUMENT;
     }
-    const bool narrow = (p->flags & MC_MANDEL_ITERS_U16) != 0u;
-    if (narrow && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
+    MandelTarget t;
+    dim3 grid, block(64);
+    SampleList l{};
+    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, list, &t, &grid, &l)) return rc;   // mandel_target.h
+    if (list) list = &l;
     if (bla && b->deep) {
         set_error_detail(name + ": the bound orbit is deep (min |scale| < 2^-960); BLA covers the plain loop only");
         return MC_ERR_UNSUPPORTED;
@@ -787,61 +764,32 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
                                 "mc_context_bind_mandelbrot_orbit)");
         return MC_ERR_INVALID_ARGUMENT;
     }
-    PerturbArgs a;
-    a.lut = nullptr;
-    if (d_rgba || warm) {
-        const void* lut = nullptr;
-        int rc = mandelbrot_lut_device(ctx, p, s, &lut);
-        if (rc) return rc;
-        a.lut = warm ? nullptr : (const float4*)lut;
-    }
-    int rc = ensure_dc_table(ctx, p, *b, s);
-    if (rc) return rc;
-    a.W = p->width; a.H = p->height; a.max_iter = p->max_iter; a.L = b->length;
-    a.row_begin = p->row_begin; a.row_end = p->row_end;
-    a.row_block = p->row_stride ? p->row_block : 0u; a.row_stride = p->row_stride;
-    a.out_rgba = warm ? nullptr : (float4*)d_rgba;
-    a.out_iters = narrow ? nullptr : (uint32_t*)d_iters;
-    a.out_iters16 = narrow ? (uint16_t*)d_iters : nullptr;
-    a.dc_tab = (const double*)ctx->ctab.ptr;
-    a.orbit = (const double2*)b->orbit.ptr;
-    const uint32_t rows = tile_rows(p->row_begin, p->row_end, a.row_block, a.row_stride);
-    dim3 grid((p->width + 7u) / 8u, (rows + 7u) / 8u), block(64);
-    if (warm) {   // one tile, a handful of iterations (as launch_impl)
-        grid = dim3(1, 1);
-        a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
-    }
-    SampleList l{};
-    if (list) {   // a wave takes 64 / s^2 entries; the kernel's own outputs stay unused
-        a.out_rgba = nullptr; a.out_iters = nullptr; a.out_iters16 = nullptr; a.lut = nullptr;
-        l = *list;
-        if (warm) l.count = 1u;
-        const uint32_t per = 64u >> (2u * l.log2s);
-        grid = dim3((l.count + per - 1u) / per);
-        list = &l;
-    }
+    const void* lut = nullptr;
+    int rc;
+    if ((d_rgba || warm) && (rc = mandelbrot_lut_device(ctx, p, s, &lut))) return rc;
+    if ((rc = ensure_dc_table(ctx, p, *b, s))) return rc;
+    t.L = b->length;
+    t.lut = t.out_rgba ? (const float4*)lut : nullptr;
+    t.table = (const double*)ctx->ctab.ptr;
+    t.orbit = (const double2*)b->orbit.ptr;
     if (bla) {   // mandel_perturb_bla.hip
-        const PerturbBlaArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
-                                  a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
-                                  b->bla_entries ? (const double*)b->bla.ptr : nullptr,
+        const PerturbBlaArgs d = {t, b->bla_entries ? (const double*)b->bla.ptr : nullptr,
                                   (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
         if ((rc = perturb_bla_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
     if (bla_deep) {   // mandel_perturb_bla_deep.hip
-        const PerturbBlaDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
-                                      a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit,
-                                      b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
+        const PerturbBlaDeepArgs d = {t, b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
                                       (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
         if ((rc = perturb_bla_deep_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
-        const PerturbDeepArgs d = {a.W, a.H, a.max_iter, a.L, a.row_begin, a.row_end, a.row_block, a.row_stride, a.out_rgba,
-                                   a.out_iters, a.out_iters16, a.lut, a.dc_tab, a.orbit, b->scale_exp2, b->has_zero ? 1u : 0u};
+        const PerturbDeepArgs d = {t, b->scale_exp2, b->has_zero ? 1u : 0u};
         if ((rc = perturb_deep_launch(d, grid, s, list))) return rc;
         return ctx->note_launch(s);
     }
+    const PerturbArgs a = {t};
     if (!list) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
     MC_HIP_TRY(hipGetLastError());
@@ -849,13 +797,11 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
 }
 
 void perturb_release(mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_bind_mutex);
-    auto it = g_bindings.find(ctx);
-    if (it == g_bindings.end()) return;
-    it->second.orbit.release();
-    it->second.bla.release();
-    it->second.bla_deep.release();
-    g_bindings.erase(it);
+    g_bindings.erase(ctx, [](Binding& b) {
+        b.orbit.release();
+        b.bla.release();
+        b.bla_deep.release();
+    });
 }
 
 }  // namespace mc
@@ -871,15 +817,11 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
         mc::perturb_release(ctx);
         return MC_OK;
     }
-    mc::Binding* b;
-    {
-        std::lock_guard<std::mutex> lock(mc::g_bind_mutex);
-        b = &mc::g_bindings[ctx];    // the node stays put while other contexts bind (only this context's thread erases it)
-        b->generation = ++mc::g_generation;
-        b->length = 0;               // unusable until the copy below has completed
-        b->has_bla = false;
-        b->has_bla_deep = false;
-    }
+    mc::Binding* b = mc::g_bindings.get(ctx);
+    b->generation = ++mc::g_generation;
+    b->length = 0;                   // unusable until the copy below has completed
+    b->has_bla = false;
+    b->has_bla_deep = false;
     const size_t bytes = o->z.size() * sizeof(double);
     if ((rc = b->orbit.reserve(bytes))) return rc;
     MC_HIP_TRY(hipMemcpyAsync(b->orbit.ptr, o->z.data(), bytes, hipMemcpyHostToDevice, ctx->stream));

@@ -22,20 +22,11 @@ namespace {
 __device__ __forceinline__ uint64_t level_sum(uint64_t n) { return 2u * n - (uint64_t)__popcll(n); }
 
 __global__ void __launch_bounds__(64) mandel_perturb_bla_kernel(PerturbBlaArgs a) {
-    // the tile mapping of mandelbrot_kernel (mandelbrot.hip): one wave = one 8x8 pixel tile
-    const uint32_t lane = threadIdx.x;
-    const uint32_t gx = blockIdx.x * 8u + (lane & 7u);
-    const uint32_t ty = blockIdx.y * 8u + (lane >> 3);
-    const uint32_t gy = tile_row_to_storage(ty, a.row_begin, a.row_block, a.row_stride);
-    const bool valid = gx < a.W && gy < a.row_end;
+    const TileLane ln = tile_lane(a.t);
+    const uint32_t gx = ln.gx, gy = ln.gy;
+    const bool valid = ln.valid;
 #include "mandel_perturb_bla_loop.h"
-    if (valid) {
-        const uint32_t v = a.count_trips ? trips : n;   // trips <= M: every trip but an escaping one advances i by at least one
-        const size_t idx = (size_t)ty * a.W + gx;
-        if (a.out_iters) a.out_iters[idx] = v;
-        if (a.out_iters16) a.out_iters16[idx] = (uint16_t)v;
-        if (a.out_rgba) a.out_rgba[idx] = a.lut[v];
-    }
+    tile_store(a.t, ln, a.count_trips ? trips : n);   // trips <= M: every trip but an escaping one advances i by at least one
 }
 
 // The same loop under the list mapping of mandel_adaptive.h: a describes the sample grid, a lane is one sample of a refined pixel, and
@@ -45,7 +36,7 @@ __global__ void __launch_bounds__(64) mandel_perturb_bla_list_kernel(PerturbBlaA
     const uint32_t gx = ln.gx, gy = ln.gy;
     const bool valid = ln.valid;
 #include "mandel_perturb_bla_loop.h"
-    sample_resolve(l, ln, a.count_trips ? trips : n, a.max_iter);
+    sample_resolve(l, ln, a.count_trips ? trips : n, a.t.max_iter);
 }
 
 }  // namespace

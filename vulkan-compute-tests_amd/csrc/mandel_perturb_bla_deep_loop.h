@@ -4,13 +4,13 @@
 // Why not a __device__ function: the tile kernel's listing is the project's invariant, and the same loop inlined from a function comes
 // out of the register allocator with the operands of one v_add3_u32 swapped and two v_ldexp_f64 pairs in another order.  Lexically
 // inside the kernel it is unchanged.
-    const double2* __restrict__ Z = a.orbit;
+    const double2* __restrict__ Z = a.t.orbit;
     const BlaDeepRec* __restrict__ T = a.bla;
-    const uint32_t L = a.L, M = a.max_iter;
+    const uint32_t L = a.t.L, M = a.t.max_iter;
     const int32_t E = a.exp2;
     const uint64_t n0 = L >= 3u ? (uint64_t)L - 2u : 0u;   // level 0's entries
     const uint64_t s0 = level_sum(n0);
-    const double ux = a.u_tab[valid ? gx : 0u], uy = a.u_tab[a.W + (valid ? gy : 0u)];
+    const double ux = a.t.table[valid ? gx : 0u], uy = a.t.table[a.t.W + (valid ? gy : 0u)];
     double wx = 0.0, wy = 0.0, dx = 0.0, dy = 0.0;   // delta = w * 2^S;  d = ldexp(w, S)
     int32_t S = E;
     bool scaled = true;

@@ -4,12 +4,12 @@
 // Why not a __device__ function: the tile kernel's listing is the project's invariant, and the same loop inlined from a function comes
 // out of the register allocator with the operands of one v_add3_u32 swapped and one v_mov_b32 moved.  Lexically inside the kernel it is
 // unchanged.
-    const double2* __restrict__ Z = a.orbit;
+    const double2* __restrict__ Z = a.t.orbit;
     const double* __restrict__ T = a.bla;
-    const uint32_t L = a.L, M = a.max_iter;
+    const uint32_t L = a.t.L, M = a.t.max_iter;
     const uint64_t n0 = L >= 3u ? (uint64_t)L - 2u : 0u;   // level 0's entries
     const uint64_t s0 = level_sum(n0);
-    const double dcx = a.dc_tab[valid ? gx : 0u], dcy = a.dc_tab[a.W + (valid ? gy : 0u)];
+    const double dcx = a.t.table[valid ? gx : 0u], dcy = a.t.table[a.t.W + (valid ? gy : 0u)];
     double dx = 0.0, dy = 0.0;
     uint32_t m = 0u, i = valid ? 0u : M, n = M, trips = 0u;
     while (i < M) {

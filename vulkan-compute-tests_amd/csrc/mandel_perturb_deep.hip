@@ -38,12 +38,12 @@ struct StateDeep {
     uint32_t m;
     bool scaled;
     __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const PerturbDeepArgs& a) {
-        Z = a.orbit;
-        L = a.L;
+        Z = a.t.orbit;
+        L = a.t.L;
         E = a.exp2;
         zeros = a.has_zero != 0u;
-        ux = a.u_tab[gx];
-        uy = a.u_tab[a.W + gy];
+        ux = a.t.table[gx];
+        uy = a.t.table[a.t.W + gy];
         wx = wy = dx = dy = zmx = zmy = 0.0;
         S = E;                               // the start: delta = 0 in the scaled phase at exponent E
         m = 0;
@@ -161,21 +161,10 @@ struct StateDeep {
 template <int U>
 __global__ void __launch_bounds__(64) mandel_perturb_deep_kernel(PerturbDeepArgs a) {
     static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    // the tile mapping of mandelbrot_kernel (mandelbrot.hip): one wave = one 8x8 pixel tile
-    const uint32_t lane = threadIdx.x;
-    const uint32_t gx = blockIdx.x * 8u + (lane & 7u);
-    const uint32_t ty = blockIdx.y * 8u + (lane >> 3);
-    const uint32_t gy = tile_row_to_storage(ty, a.row_begin, a.row_block, a.row_stride);
-    const bool valid = gx < a.W && gy < a.row_end;
+    const TileLane ln = tile_lane(a.t);
     StateDeep st;
-    st.init(valid ? gx : 0u, valid ? gy : 0u, a);
-    const uint32_t n = escape_time<StateDeep, U>(st, a.max_iter, valid);
-    if (valid) {
-        const size_t idx = (size_t)ty * a.W + gx;
-        if (a.out_iters) a.out_iters[idx] = n;
-        if (a.out_iters16) a.out_iters16[idx] = (uint16_t)n;
-        if (a.out_rgba) a.out_rgba[idx] = a.lut[n];
-    }
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    tile_store(a.t, ln, escape_time<StateDeep, U>(st, a.t.max_iter, ln.valid));
 }
 
 // The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
@@ -184,8 +173,8 @@ __global__ void __launch_bounds__(64) mandel_perturb_deep_list_kernel(PerturbDee
     const SampleLane ln = sample_lane(l);
     StateDeep st;
     st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    const uint32_t n = escape_time<StateDeep, U>(st, a.max_iter, ln.valid);
-    sample_resolve(l, ln, n, a.max_iter);
+    const uint32_t n = escape_time<StateDeep, U>(st, a.t.max_iter, ln.valid);
+    sample_resolve(l, ln, n, a.t.max_iter);
 }
 
 }  // namespace

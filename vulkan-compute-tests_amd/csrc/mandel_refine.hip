@@ -14,11 +14,10 @@
 //    other in its side record and swaps the two slots around the anchor pass, so that neither is rebuilt from call to call.
 //  * the context's state lives in a side record (as mandel_histogram.hip's), not in mc_internal.h.
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
 #include "mandel_adaptive.h"
 #include "mandel_equalise.h"
+#include "mandel_side_record.h"
 
 namespace mc {
 
@@ -51,7 +50,7 @@ __global__ void __launch_bounds__(256) mandel_refine_kernel(const T* __restrict_
     if (refined) list[base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))] = (uint32_t)idx;
 }
 
-// The context's adaptive state.  Kept here rather than in mc_context (as the equalised colouring's): mc_internal.h stays as it is.
+// The context's adaptive state, a side record of the context (mandel_side_record.h).
 struct AdaptiveState {
     DeviceBuffer list, counter;     // W * H indices; one uint32_t
     DeviceBuffer img_tab;           // the c / dc table slot that is NOT in ctx->ctab at the moment (the image's, between calls)
@@ -60,13 +59,7 @@ struct AdaptiveState {
     bool reported = false;          // mc_context_last_refined
     uint64_t refined = 0, pixels = 0;
 };
-std::mutex g_ad_mutex;
-std::unordered_map<const mc_context*, AdaptiveState> g_ad_states;
-
-AdaptiveState* state_of(const mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_ad_mutex);
-    return &g_ad_states[ctx];   // the node stays put while other contexts add theirs (only this context's thread erases it)
-}
+SideRecords<AdaptiveState> g_ad_states;
 
 uint32_t log2_of(uint32_t s) { return s == 2u ? 1u : s == 4u ? 2u : 3u; }
 
@@ -80,13 +73,11 @@ void plain_params(const mc_mandelbrot_params* p, uint32_t iters_bytes, mc_mandel
 }  // namespace
 
 void adaptive_release(mc_context* ctx) {
-    std::lock_guard<std::mutex> lock(g_ad_mutex);
-    auto it = g_ad_states.find(ctx);
-    if (it == g_ad_states.end()) return;
-    it->second.list.release();
-    it->second.counter.release();
-    it->second.img_tab.release();
-    g_ad_states.erase(it);
+    g_ad_states.erase(ctx, [](AdaptiveState& st) {
+        st.list.release();
+        st.counter.release();
+        st.img_tab.release();
+    });
 }
 
 int mandelbrot_refine_launch(mc_context* ctx, const void* d_plane, uint32_t iters_bytes, uint32_t W, uint32_t H, uint32_t* d_list,
@@ -131,7 +122,7 @@ int adaptive_check(const mc_mandelbrot_params* p, const char* who) {
 }
 
 int mandelbrot_adaptive_reserve(mc_context* ctx, const mc_mandelbrot_params* p) {
-    AdaptiveState* st = state_of(ctx);
+    AdaptiveState* st = g_ad_states.get(ctx);
     const size_t npix = (size_t)p->width * p->height;
     int rc;
     if ((rc = ctx->scratch_iters.reserve(std::max(npix, (size_t)64) * (p->max_iter <= 65535u ? 2u : 4u)))) return rc;
@@ -148,7 +139,7 @@ int mandelbrot_adaptive_launch(mc_context* ctx, const mc_mandelbrot_params* p, h
     int rc;
     if ((rc = mandelbrot_supersample_params(p, &grid))) return rc;
     plain_params(p, iters_bytes, &plain);
-    AdaptiveState* st = state_of(ctx);
+    AdaptiveState* st = g_ad_states.get(ctx);
     // anchor pass on the image's table (the side record's slot), the context's slot keeping the grid's for the list pass.  Nothing else
     // reads ctx->ctab between the two swaps (one thread per context, mandelbrot_launch only).  AFTER the call the context's slot holds
     // the GRID's table: a plain render of the same image that follows rebuilds its table once (the price of adding no second slot to
@@ -195,7 +186,7 @@ int mandelbrot_adaptive_warmup(mc_context* ctx, const mc_mandelbrot_params* p, h
     // place (the warm-up of the grid's plain render ran before this)
     int rc = mandelbrot_adaptive_reserve(ctx, p);
     if (rc) return rc;
-    AdaptiveState* st = state_of(ctx);
+    AdaptiveState* st = g_ad_states.get(ctx);
     const uint32_t iters_bytes = p->max_iter <= 65535u ? 2u : 4u;
     mc_mandelbrot_params plain;
     plain_params(p, 4u, &plain);
@@ -226,7 +217,7 @@ using namespace mc;
 
 extern "C" int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels) {
     if (!ctx) return MC_ERR_INVALID_ARGUMENT;
-    AdaptiveState* st = state_of(ctx);
+    AdaptiveState* st = g_ad_states.get(ctx);
     if (!st->reported) {
         set_error_detail("mc_context_last_refined: no adaptive render has succeeded on this context");
         return MC_ERR_INVALID_ARGUMENT;

@@ -28,6 +28,7 @@
 #include "mandel_adaptive.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
+#include "mandel_target.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -185,21 +186,10 @@ __global__ void __launch_bounds__(64) mandelbrot_kernel(MandelArgs a) {
     // workgroup = one wave = one 8x8 pixel tile, lane = (lx, ly) inside the tile.  Tiles finish anywhere between 1 and
     // max_iter iterations apart, so the unit the hardware schedules is the tile itself: a 4-wave block would keep its
     // place on the CU until its slowest tile is through (K1: 0.208 -> 0.200 ms).
-    const uint32_t lane = threadIdx.x;
-    const uint32_t tile_x = blockIdx.x, tile_y = blockIdx.y;
-    const uint32_t gx = tile_x * 8u + (lane & 7u);
-    const uint32_t ty = tile_y * 8u + (lane >> 3);   // tile-local row
-    const uint32_t gy = tile_row_to_storage(ty, a.row_begin, a.row_block, a.row_stride);
-    const bool valid = gx < a.W && gy < a.row_end;                            // mandelbrot.comp:27-28
+    const TileLane ln = tile_lane(a);
     State st;
-    st.init(valid ? gx : 0u, valid ? gy : 0u, a);
-    uint32_t n = escape_time<State, U>(st, a.max_iter, valid);
-    if (valid) {
-        size_t idx = (size_t)ty * a.W + gx;                                    // :59 (row-major, tile-local)
-        if (a.out_iters) a.out_iters[idx] = n;
-        if (a.out_iters16) a.out_iters16[idx] = (uint16_t)n;
-        if (a.out_rgba) a.out_rgba[idx] = a.lut[n];
-    }
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    tile_store(a, ln, escape_time<State, U>(st, a.max_iter, ln.valid));
 }
 
 // The same per-lane state under the list mapping of mandel_adaptive.h: `a` describes the sample grid, a lane is one sample of a refined
@@ -327,24 +317,13 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
         if (rc) return rc;
     }
     MandelArgs a;
+    dim3 grid, block(64);
+    SampleList l{};
+    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, list, &a, &grid, &l)) return rc;   // mandel_target.h
     a.c_tab = (const float*)ctx->ctab.ptr;
-    a.W = p->width; a.H = p->height; a.max_iter = p->max_iter;
-    a.row_begin = p->row_begin; a.row_end = p->row_end;
-    a.row_block = p->row_stride ? p->row_block : 0u; a.row_stride = p->row_stride;
     a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
     a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
-    a.out_rgba = warm ? nullptr : (float4*)d_rgba;
-    const bool narrow = (p->flags & MC_MANDEL_ITERS_U16) != 0u;
-    if (narrow && p->max_iter > 65535u) return MC_ERR_INVALID_ARGUMENT;
-    a.out_iters = narrow ? nullptr : (uint32_t*)d_iters;
-    a.out_iters16 = narrow ? (uint16_t*)d_iters : nullptr;
     a.lut = a.out_rgba ? (const float4*)ctx->lut.ptr : nullptr;
-    const uint32_t rows = tile_rows(p->row_begin, p->row_end, a.row_block, a.row_stride);
-    dim3 grid((p->width + 7u) / 8u, (rows + 7u) / 8u), block(64);
-    if (warm) {   // one tile, a handful of iterations; d_iters holds at least rows x W counts (the caller's scratch)
-        grid = dim3(1, 1);
-        a.max_iter = p->max_iter < 32u ? p->max_iter : 32u;
-    }
     if (!list) {
         if (p->precision == MC_PRECISION_DS) {
             hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
@@ -355,12 +334,7 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
         } else {
             hipLaunchKernelGGL((mandelbrot_kernel<StateF32<false>, 8>), grid, block, 0, s, a);
         }
-    } else {   // a wave takes 64 / s^2 entries; the kernel's own outputs stay unused
-        a.out_rgba = nullptr; a.out_iters = nullptr; a.out_iters16 = nullptr; a.lut = nullptr;
-        const uint32_t per = 64u >> (2u * list->log2s);
-        SampleList l = *list;
-        if (warm) l.count = 1u;
-        grid = dim3((l.count + per - 1u) / per);
+    } else {
         if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_kernel<StateDS, 4>), grid, block, 0, s, a, l);
         else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF64, 8>), grid, block, 0, s, a, l);
         else if (p->flags & MC_MANDEL_FMA) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<true>, 8>), grid, block, 0, s, a, l);
