@@ -33,7 +33,8 @@ extern "C" {
  * mc_mandelbrot_orbit_bla_copy; then MC_PRECISION_PERTURB_BLA_DEEP with mc_mandelbrot_orbit_bla_deep and mc_mandelbrot_orbit_bla_deep_copy;
  * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
  * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
- * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined.
+ * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined; then
+ * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -195,6 +196,22 @@ int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, doubl
                                uint32_t max_iter, mc_mandelbrot_orbit** out);
 int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
                                     uint32_t max_iter, mc_mandelbrot_orbit** out);
+/* mc_mandelbrot_orbit_create_device: the SAME object as mc_mandelbrot_orbit_create_deep with the same arguments (the plain constructor's
+ * orbit where that one forwards to it), its iteration loop run on ctx's device instead of the host (it pays from
+ * the limb count measured there upward, and loses on shallow orbits).  Pure integer arithmetic: bits, length, max_iter, the scale fields
+ * and every bit of the table Z_0 .. Z_L are the host constructor's, signed zeros and subnormals included, and everything that takes an orbit
+ * takes this one, on any context.  The refusals are mc_mandelbrot_orbit_create_deep's, with the same status and the same text after
+ * the function's name in mc_last_error_detail, and every refusal of the arguments comes before anything is launched; ctx == NULL is
+ * MC_ERR_INVALID_ARGUMENT.  Blocking, on the context's stream; neither the context's bound orbit nor its render scratch is touched.  The
+ * orbit is computed by one workgroup in several launches of at most C / (k + 1)^2 iterations each, clamped to [1, 65536] (k + 1 = the
+ * limb count, C sized so that a launch stays near 50 ms at most); the state between launches lives in device memory, the host reads
+ * its status word and j (8 bytes) and the launch's table entries (16 B each) after every launch and stops on escape or refusal.
+ * mc_context_last_orbit_timing: the last successful device orbit of the context: device_ms = first launch to the end of the last kernel
+ * (HIP events; the reads between launches included), the number of launches, and the limb count k + 1.  Any pointer may be NULL;
+ * MC_ERR_INVALID_ARGUMENT before the first such call. */
+int mc_mandelbrot_orbit_create_device(mc_context* ctx, const char* centre_x, const char* centre_y, double scale_x, double scale_y,
+                                      int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out);
+int mc_context_last_orbit_timing(mc_context* ctx, double* device_ms, uint32_t* launches, uint32_t* limbs);
 int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o);
 int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits);
 int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z /* (length+1)*2: re, im */);

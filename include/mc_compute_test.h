@@ -68,6 +68,19 @@ int mc_test_ds_op(mc_context* ctx, int op, const float* a, const float* b, float
  * one runs a kernel of the product library on a caller's plane.) */
 int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_bytes, uint32_t width, uint32_t height, uint32_t* d_list,
                           uint32_t* d_count, void* stream);
+/* The arithmetic of mc_mandelbrot_orbit_create_device (csrc/mandel_orbit_fix.h), piece by piece.  Numbers are k + 1 uint64_t limbs, least
+ * significant first: k fractional limbs and the integer limb, 1 <= k <= 130 (MC_ERR_INVALID_ARGUMENT otherwise).
+ * mc_hook_orbit_mul_host: out = (a * b + 2^(64k - 1)) >> 64k, its low k + 1 limbs, by the shared header's columns and carry resolution run
+ *   as lane loops on the CPU (no device).  mc_hook_orbit_mul_device: the same phases as the kernel runs them, one workgroup on ctx's device.
+ * mc_hook_orbit_to_double_host: the shared to_double (top-bit search, 53 bits, half bit, sticky bit; the subnormal floor) of the magnitude
+ *   `limbs` with sign `neg`, on the CPU.
+ * mc_hook_orbit_create_lanes_host: mc_mandelbrot_orbit_create_deep with the iteration loop replaced by the kernel's phases as lane loops
+ *   on the CPU (no device): the whole device algorithm, checkable on a box without a GPU. */
+int mc_hook_orbit_mul_host(int k, const uint64_t* a_limbs, const uint64_t* b_limbs, uint64_t* out_limbs);
+int mc_hook_orbit_mul_device(mc_context* ctx, int k, const uint64_t* a_limbs, const uint64_t* b_limbs, uint64_t* out_limbs);
+int mc_hook_orbit_to_double_host(int k, const uint64_t* limbs, int neg, double* out);
+int mc_hook_orbit_create_lanes_host(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                                    uint32_t max_iter, mc_mandelbrot_orbit** out);
 
 #ifdef __cplusplus
 }

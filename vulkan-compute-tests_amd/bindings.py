@@ -143,6 +143,10 @@ def lib():
         if hasattr(L, "mc_mandelbrot_orbit_create_deep"):
             L.mc_mandelbrot_orbit_create_deep.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, u32,
                                                           C.POINTER(vp)]
+        if hasattr(L, "mc_mandelbrot_orbit_create_device"):   # the orbit's loop on the device
+            L.mc_mandelbrot_orbit_create_device.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, u32,
+                                                            C.POINTER(vp)]
+            L.mc_context_last_orbit_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u32), C.POINTER(u32)]
         if hasattr(L, "mc_mandelbrot_orbit_bla"):   # MC_PRECISION_PERTURB_BLA
             L.mc_mandelbrot_orbit_bla.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
             L.mc_mandelbrot_orbit_bla_copy.argtypes = [vp, vp]
@@ -189,6 +193,12 @@ def test_lib():
         L.mc_test_ds_op.argtypes = [vp, i32, vp, vp, vp, C.c_size_t]
         if hasattr(L, "mc_hook_mandel_refine"):   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE
             L.mc_hook_mandel_refine.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "mc_hook_orbit_mul_host"):   # mc_mandelbrot_orbit_create_device's arithmetic
+            L.mc_hook_orbit_mul_host.argtypes = [i32, vp, vp, vp]
+            L.mc_hook_orbit_mul_device.argtypes = [vp, i32, vp, vp, vp]
+            L.mc_hook_orbit_to_double_host.argtypes = [i32, vp, i32, C.POINTER(C.c_double)]
+            L.mc_hook_orbit_create_lanes_host.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, C.c_uint32,
+                                                          C.POINTER(vp)]
         _test_lib = L
     return _test_lib
 
@@ -385,20 +395,28 @@ class Orbit:
     decimal text (str, taken verbatim) and the scale as doubles.  A context manager; Context.bind_mandelbrot_orbit copies it to a device.
     scale_exp2=None: mc_mandelbrot_orbit_create.  An integer: mc_mandelbrot_orbit_create_deep, the scale (scale_x, scale_y) * 2^scale_exp2
     (scale_from_text makes the pair from text).  `deep`: the orbit renders by the rescaled loop (min |scale| < 2^-960); then `scale`
-    holds the mantissas and `scale_exp2` the exponent, otherwise `scale` holds the doubles and `scale_exp2` is 0 (or None)."""
+    holds the mantissas and `scale_exp2` the exponent, otherwise `scale` holds the doubles and `scale_exp2` is 0 (or None).
+    device=ctx (with an integer scale_exp2): mc_mandelbrot_orbit_create_device, the same object with its iteration loop run on that
+    context's device; Context.last_orbit_timing() then reports it."""
 
-    def __init__(self, centre_x, centre_y, scale_x, scale_y, max_iter, scale_exp2=None):
+    def __init__(self, centre_x, centre_y, scale_x, scale_y, max_iter, scale_exp2=None, device=None):
         enc = lambda v: v.encode() if isinstance(v, str) else v
         self._h = C.c_void_p()
         self.deep = False
+        if device is not None and scale_exp2 is None:
+            raise ValueError("Orbit: device= takes the scale as (scale_x, scale_y) * 2^scale_exp2; pass scale_exp2 (0 for plain doubles)")
         if scale_exp2 is None:
             _check(lib().mc_mandelbrot_orbit_create(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), int(max_iter),
                                                     C.byref(self._h)), "mc_mandelbrot_orbit_create")
             self.scale = (float(scale_x), float(scale_y))
         else:
             E = int(scale_exp2)
-            _check(lib().mc_mandelbrot_orbit_create_deep(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), E,
-                                                         int(max_iter), C.byref(self._h)), "mc_mandelbrot_orbit_create_deep")
+            if device is not None:
+                _check(lib().mc_mandelbrot_orbit_create_device(device._h, enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), E,
+                                                               int(max_iter), C.byref(self._h)), "mc_mandelbrot_orbit_create_device")
+            else:
+                _check(lib().mc_mandelbrot_orbit_create_deep(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), E,
+                                                             int(max_iter), C.byref(self._h)), "mc_mandelbrot_orbit_create_deep")
             emin = min(math.frexp(abs(float(scale_x))), math.frexp(abs(float(scale_y))), key=lambda fe: (fe[1], fe[0]))[1] + E
             self.deep = emin < -959
             if self.deep:
@@ -513,6 +531,12 @@ class Context:
         k, c = C.c_double(0.0), C.c_double(0.0)
         _check(lib().mc_context_last_timing(self._h, C.byref(k), C.byref(c)), "mc_context_last_timing")
         return k.value, c.value
+
+    def last_orbit_timing(self):
+        """(device_ms, launches, limbs) of the last successful Orbit(..., device=this context) (mc_context_last_orbit_timing)."""
+        ms, n, k1 = C.c_double(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().mc_context_last_orbit_timing(self._h, C.byref(ms), C.byref(n), C.byref(k1)), "mc_context_last_orbit_timing")
+        return ms.value, n.value, k1.value
 
     def last_refined(self):
         """(refined, pixels) of the last successful adaptive render on this context (mc_context_last_refined)."""

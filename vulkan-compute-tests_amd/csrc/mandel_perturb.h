@@ -50,4 +50,22 @@ struct PerturbBlaDeepArgs {
 };
 int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
+// mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): make_orbit's iteration loop on the context's device.  cx, cy: the centre's
+// k + 1 limbs.  z holds Z_0 on entry and Z_0 .. Z_L on success (*length = L); kOrbitTinyEntry: the tiny-entry refusal at Z_(*tiny_j).
+// A launch runs at most orbit_launch_iters(k) = kOrbitLaunchWork / (k + 1)^2 iterations, clamped to [1, 65536].  3.2e7 gives 1864
+// iterations at k = 130: 49 ms at the 26.3 us per iteration measured there (which also lists what the rule gives at the
+// smaller limb counts, where an iteration's fixed part outweighs its products).
+constexpr uint64_t kOrbitLaunchWork = 32000000ull;
+constexpr int kOrbitTinyEntry = -1;
+uint32_t orbit_launch_iters(int k);
+int orbit_device_run(mc_context* ctx, int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter,
+                     bool deep, std::vector<double>& z, uint32_t* length, uint32_t* tiny_j);
+// The kernel's phases as lane loops on the host (no device): what libmc_compute_test.so's mc_hook_orbit_create_lanes_host calls.
+int orbit_lanes_run(int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter, bool deep,
+                    std::vector<double>& z, uint32_t* length, uint32_t* tiny_j);
+int orbit_create_lanes(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter,
+                       mc_mandelbrot_orbit** out);
+// mc_context_destroy: the context's orbit state, slice and events are freed.
+void orbit_device_release(mc_context* ctx);
+
 }  // namespace mc

@@ -232,10 +232,14 @@ struct mc_mandelbrot_orbit {
 
 namespace {
 
-// The orbit of both constructors.  bits and the refusal of scales below the floor are decided by the caller; deep = the tiny-entry
+// Where the iteration loop runs: here (FixOps), on ctx's device (mandel_orbit_device.hip), or as that kernel's lane loops on the host.
+enum class OrbitLoop { Host, Device, Lanes };
+
+// The orbit of every constructor.  bits and the refusal of scales below the floor are decided by the caller; deep = the tiny-entry
 // refusal of include/mc_compute.h applies.  `fn` names the entry point in the error detail.
 int make_orbit(const char* fn, const char* centre_x, const char* centre_y, int64_t bits, bool below_floor, bool deep,
-               uint32_t max_iter, mc_mandelbrot_orbit** out, mc_mandelbrot_orbit** made) {
+               uint32_t max_iter, mc_mandelbrot_orbit** out, mc_mandelbrot_orbit** made, OrbitLoop loop = OrbitLoop::Host,
+               mc_context* ctx = nullptr) {
     auto refuse = [fn](const char* why) {
         mc::set_error_detail(std::string(fn) + ": " + why);
         return MC_ERR_INVALID_ARGUMENT;
@@ -255,34 +259,47 @@ int make_orbit(const char* fn, const char* centre_x, const char* centre_y, int64
     mc_mandelbrot_orbit* o = new (std::nothrow) mc_mandelbrot_orbit();
     if (!o) return MC_ERR_OUT_OF_MEMORY;
     const double tiny = std::ldexp(1.0, -960);
+    auto refuse_tiny = [fn, o](uint32_t j1) {
+        delete o;
+        mc::set_error_detail(std::string(fn) + ": orbit entry Z_" + std::to_string(j1) +
+                             " is nonzero with both parts below 2^-960 (the centre sits on a nucleus far more closely than"
+                             " the view needs; the double table cannot hold that entry)");
+        return MC_ERR_UNSUPPORTED;
+    };
     try {
-        o->z.reserve(2 * ((size_t)max_iter + 1) < 2 * 65536 ? 2 * ((size_t)max_iter + 1) : 2 * 65536);
-        Fix zx, zy, sx, sy, t;
-        ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
-        o->z.push_back(0.0); o->z.push_back(0.0);
-        uint32_t L = max_iter;
-        for (uint32_t j = 0; j < max_iter; j++) {
-            ops.mul(zx, zy, t);                           // Z_{j+1} = Z_j^2 + c_ref
-            ops.twice(t);
-            ops.add(t, cy, zy);
-            ops.sub(sx, sy, t);
-            ops.add(t, cx, zx);
-            const double dx = ops.to_double(zx), dy = ops.to_double(zy);
-            if (deep && std::fabs(dx) < tiny && std::fabs(dy) < tiny && !(ops.is_zero(zx) && ops.is_zero(zy))) {
-                delete o;
-                mc::set_error_detail(std::string(fn) + ": orbit entry Z_" + std::to_string(j + 1) +
-                                     " is nonzero with both parts below 2^-960 (the centre sits on a nucleus far more closely than"
-                                     " the view needs; the double table cannot hold that entry)");
-                return MC_ERR_UNSUPPORTED;
+        if (loop != OrbitLoop::Host) {
+            o->z.push_back(0.0); o->z.push_back(0.0);
+            uint32_t L = 0, tiny_j = 0;
+            const int rc = loop == OrbitLoop::Device
+                               ? mc::orbit_device_run(ctx, ops.k, cx.m, cy.m, cx.neg, cy.neg, max_iter, deep, o->z, &L, &tiny_j)
+                               : mc::orbit_lanes_run(ops.k, cx.m, cy.m, cx.neg, cy.neg, max_iter, deep, o->z, &L, &tiny_j);
+            if (rc == mc::kOrbitTinyEntry) return refuse_tiny(tiny_j);
+            if (rc) { delete o; return rc; }
+            o->length = L;
+        } else {
+            o->z.reserve(2 * ((size_t)max_iter + 1) < 2 * 65536 ? 2 * ((size_t)max_iter + 1) : 2 * 65536);
+            Fix zx, zy, sx, sy, t;
+            ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
+            o->z.push_back(0.0); o->z.push_back(0.0);
+            uint32_t L = max_iter;
+            for (uint32_t j = 0; j < max_iter; j++) {
+                ops.mul(zx, zy, t);                           // Z_{j+1} = Z_j^2 + c_ref
+                ops.twice(t);
+                ops.add(t, cy, zy);
+                ops.sub(sx, sy, t);
+                ops.add(t, cx, zx);
+                const double dx = ops.to_double(zx), dy = ops.to_double(zy);
+                if (deep && std::fabs(dx) < tiny && std::fabs(dy) < tiny && !(ops.is_zero(zx) && ops.is_zero(zy)))
+                    return refuse_tiny(j + 1);
+                o->z.push_back(dx);
+                o->z.push_back(dy);
+                ops.mul(zx, zx, sx);
+                ops.mul(zy, zy, sy);
+                ops.add(sx, sy, t);
+                if (ops.above_two(t)) { L = j + 1; break; }
             }
-            o->z.push_back(dx);
-            o->z.push_back(dy);
-            ops.mul(zx, zx, sx);
-            ops.mul(zy, zy, sy);
-            ops.add(sx, sy, t);
-            if (ops.above_two(t)) { L = j + 1; break; }
+            o->length = L;
         }
-        o->length = L;
     } catch (const std::bad_alloc&) {
         delete o;
         return MC_ERR_OUT_OF_MEMORY;
@@ -295,14 +312,11 @@ int make_orbit(const char* fn, const char* centre_x, const char* centre_y, int64
     return MC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y, uint32_t max_iter,
-                               mc_mandelbrot_orbit** out) {
-    auto refuse = [](const char* why) {
-        mc::set_error_detail(std::string("mc_mandelbrot_orbit_create: ") + why);
+// mc_mandelbrot_orbit_create under the name `fn`, its loop where `loop` says.
+int create_plain(const char* fn, OrbitLoop loop, mc_context* ctx, const char* centre_x, const char* centre_y, double scale_x,
+                 double scale_y, uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    auto refuse = [fn](const char* why) {
+        mc::set_error_detail(std::string(fn) + ": " + why);
         return MC_ERR_INVALID_ARGUMENT;
     };
     if (!out || !centre_x || !centre_y) return refuse("NULL argument");
@@ -316,18 +330,18 @@ int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, doubl
     int64_t bits = (int64_t)1 - e + 96;
     if (bits < 64) bits = 64;
     mc_mandelbrot_orbit* o = nullptr;
-    const int rc = make_orbit("mc_mandelbrot_orbit_create", centre_x, centre_y, bits, smin < std::ldexp(1.0, -960), false, max_iter,
-                              out, &o);
+    const int rc = make_orbit(fn, centre_x, centre_y, bits, smin < std::ldexp(1.0, -960), false, max_iter, out, &o, loop, ctx);
     if (rc) return rc;
     o->scale_x = scale_x;
     o->scale_y = scale_y;
     return MC_OK;
 }
 
-int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
-                                    uint32_t max_iter, mc_mandelbrot_orbit** out) {
-    auto refuse = [](const char* why) {
-        mc::set_error_detail(std::string("mc_mandelbrot_orbit_create_deep: ") + why);
+// mc_mandelbrot_orbit_create_deep under the name `fn`; a scale that is a double of at least 2^-960 goes to create_plain under `fn_plain`.
+int create_deep(const char* fn, const char* fn_plain, OrbitLoop loop, mc_context* ctx, const char* centre_x, const char* centre_y,
+                double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    auto refuse = [fn](const char* why) {
+        mc::set_error_detail(std::string(fn) + ": " + why);
         return MC_ERR_INVALID_ARGUMENT;
     };
     if (!out || !centre_x || !centre_y) return refuse("NULL argument");
@@ -346,24 +360,56 @@ int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, 
     if (!deep) {                                     // the scale is a double of at least 2^-960: exactly mc_mandelbrot_orbit_create
         const int64_t emax = (ex > ey ? ex : ey) + (int64_t)scale_exp2;
         if (emax > 1024) {
-            mc::set_error_detail("mc_mandelbrot_orbit_create_deep: scale above the double range");
+            mc::set_error_detail(std::string(fn) + ": scale above the double range");
             return MC_ERR_UNSUPPORTED;
         }
         sx = std::ldexp(scale_x, scale_exp2);        // exact: both results are normal doubles
         sy = std::ldexp(scale_y, scale_exp2);
         if (!std::isfinite(sx) || !std::isfinite(sy)) {
-            mc::set_error_detail("mc_mandelbrot_orbit_create_deep: scale above the double range");
+            mc::set_error_detail(std::string(fn) + ": scale above the double range");
             return MC_ERR_UNSUPPORTED;
         }
-        return mc_mandelbrot_orbit_create(centre_x, centre_y, sx, sy, max_iter, out);
+        return create_plain(fn_plain, loop, ctx, centre_x, centre_y, sx, sy, max_iter, out);
     }
     mc_mandelbrot_orbit* o = nullptr;
-    const int rc = make_orbit("mc_mandelbrot_orbit_create_deep", centre_x, centre_y, bits, emin < -8191, true, max_iter, out, &o);
+    const int rc = make_orbit(fn, centre_x, centre_y, bits, emin < -8191, true, max_iter, out, &o, loop, ctx);
     if (rc) return rc;
     o->scale_x = scale_x;
     o->scale_y = scale_y;
     o->scale_exp2 = scale_exp2;
     return MC_OK;
+}
+
+}  // namespace
+
+int mc::orbit_create_lanes(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                           uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    return create_deep("orbit_create_lanes", "orbit_create_lanes", OrbitLoop::Lanes, nullptr, centre_x, centre_y, scale_x, scale_y,
+                       scale_exp2, max_iter, out);
+}
+
+extern "C" {
+
+int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y, uint32_t max_iter,
+                               mc_mandelbrot_orbit** out) {
+    return create_plain("mc_mandelbrot_orbit_create", OrbitLoop::Host, nullptr, centre_x, centre_y, scale_x, scale_y, max_iter, out);
+}
+
+int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                                    uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    return create_deep("mc_mandelbrot_orbit_create_deep", "mc_mandelbrot_orbit_create", OrbitLoop::Host, nullptr, centre_x, centre_y,
+                       scale_x, scale_y, scale_exp2, max_iter, out);
+}
+
+// The same object with the iteration loop on ctx's device: mandel_orbit_device.hip.  Every refusal of the arguments comes first.
+int mc_mandelbrot_orbit_create_device(mc_context* ctx, const char* centre_x, const char* centre_y, double scale_x, double scale_y,
+                                      int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    if (!ctx) {
+        mc::set_error_detail("mc_mandelbrot_orbit_create_device: NULL argument");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    return create_deep("mc_mandelbrot_orbit_create_device", "mc_mandelbrot_orbit_create_device", OrbitLoop::Device, ctx, centre_x,
+                       centre_y, scale_x, scale_y, scale_exp2, max_iter, out);
 }
 
 int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o) {

@@ -6,6 +6,8 @@
 
 #include "ds_arith.h"
 #include "mandel_adaptive.h"
+#include "mandel_orbit_fix.h"
+#include "mandel_perturb.h"
 #include "mc_internal.h"
 #include "mc_math.h"
 #include "../../include/mc_compute_test.h"
@@ -216,6 +218,72 @@ int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_b
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     MC_HIP_TRY(hipMemsetAsync(d_count, 0, 4, s));
     return mandelbrot_refine_launch(ctx, d_plane, iters_bytes, width, height, d_list, d_count, s);
+}
+
+// ---- the device orbit's arithmetic (mandel_orbit_fix.h) ------------------------------------------------------------------------------
+namespace {
+
+void orbit_load(orbitfix::Mem& m, int k, const uint64_t* a, uint32_t* dst) {
+    m.k = k;
+    m.H = 2 * (k + 1);
+    for (int i = 0; i <= k; i++) { dst[2 * i] = (uint32_t)a[i]; dst[2 * i + 1] = (uint32_t)(a[i] >> 32); }
+}
+
+// a, b, out: H half-limbs each
+__global__ void __launch_bounds__(orbitfix::kLanes) test_orbit_mul_kernel(int k, const uint32_t* __restrict__ a,
+                                                                          const uint32_t* __restrict__ b, uint32_t* __restrict__ out) {
+    __shared__ orbitfix::Mem m;
+    const int lane = (int)threadIdx.x, H = 2 * (k + 1);
+    if (lane == 0) { m.k = k; m.H = H; }
+    for (int h = lane; h < orbitfix::kHalfPad; h += orbitfix::kLanes) { m.zx[h] = h < H ? a[h] : 0u; m.zy[h] = h < H ? b[h] : 0u; }
+    __syncthreads();
+    for (int ph = 0; ph < 3; ph++) {
+        orbitfix::mul_phase(m, ph, lane);
+        __syncthreads();
+    }
+    for (int h = lane; h < H; h += orbitfix::kLanes) out[h] = m.pr[h];
+}
+
+}  // namespace
+
+int mc_hook_orbit_mul_host(int k, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+    if (k < 1 || k > orbitfix::kMaxFrac || !a || !b || !out) return MC_ERR_INVALID_ARGUMENT;
+    std::vector<orbitfix::Mem> mem(1);
+    orbitfix::Mem& m = mem[0];
+    orbit_load(m, k, a, m.zx);
+    orbit_load(m, k, b, m.zy);
+    for (int ph = 0; ph < 3; ph++)
+        for (int lane = 0; lane < orbitfix::kLanes; lane++) orbitfix::mul_phase(m, ph, lane);
+    for (int i = 0; i <= k; i++) out[i] = (uint64_t)m.pr[2 * i] | ((uint64_t)m.pr[2 * i + 1] << 32);
+    return MC_OK;
+}
+
+int mc_hook_orbit_to_double_host(int k, const uint64_t* limbs, int neg, double* out) {
+    if (k < 1 || k > orbitfix::kMaxFrac || !limbs || !out) return MC_ERR_INVALID_ARGUMENT;
+    std::vector<orbitfix::Mem> mem(1);
+    orbitfix::Mem& m = mem[0];
+    orbit_load(m, k, limbs, m.zx);
+    m.top[0] = -1;
+    for (int lane = 0; lane < orbitfix::kLanes; lane++) orbitfix::top_scan(m, 0, lane);
+    for (int lane = 0; lane < orbitfix::kLanes; lane++) orbitfix::sticky_scan(m, 0, lane);
+    *out = orbitfix::to_double(m.zx, k, m.top[0], m.sticky[0] != 0u, neg != 0);
+    return MC_OK;
+}
+
+int mc_hook_orbit_mul_device(mc_context* ctx, int k, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+    if (!ctx || k < 1 || k > orbitfix::kMaxFrac || !a || !b || !out) return MC_ERR_INVALID_ARGUMENT;
+    const size_t bytes = (size_t)(k + 1) * sizeof(uint64_t);   // (little-endian host: a limb is its two half-limbs in order)
+    return run_test(ctx, a, bytes, b, bytes, out, bytes,
+                    [](void* x, void* y, void* o, size_t, hipStream_t s, int k_, int) {
+                        hipLaunchKernelGGL(test_orbit_mul_kernel, dim3(1), dim3(orbitfix::kLanes), 0, s, k_, (const uint32_t*)x,
+                                           (const uint32_t*)y, (uint32_t*)o);
+                    },
+                    1, k, 0);
+}
+
+int mc_hook_orbit_create_lanes_host(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
+                                    uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    return orbit_create_lanes(centre_x, centre_y, scale_x, scale_y, scale_exp2, max_iter, out);
 }
 
 }  // extern "C"

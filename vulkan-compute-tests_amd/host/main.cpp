@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised (histogram-equalised colouring of the whole image), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised (histogram-equalised colouring of the whole image), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -41,6 +41,9 @@ int main(int argc, char* argv[]) {
     uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
     bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
+    enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
+    uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
+    bool orbitSet = false;              // given at all: the run prints its "orbit:" line
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -98,6 +101,15 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--orbit") {   // where the perturbation precisions compute their reference orbit
+            need(1);
+            orbitWhere = choice(argv[++i], {{"host", (uint32_t)kOrbitHost}, {"device", (uint32_t)kOrbitDevice}, {"auto", (uint32_t)kOrbitAuto}});
+            orbitSet = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--orbit: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -116,7 +128,7 @@ int main(int argc, char* argv[]) {
         else pos.push_back(argv[i]);
     }
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
-    (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
+    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
@@ -137,7 +149,6 @@ int main(int argc, char* argv[]) {
     if (precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA ||
         precision == MC_PRECISION_PERTURB_BLA_DEEP) {                                    // the reference orbit, on the host: a malformed
                                                                                          // centre ends the run before a device is touched
-        mc_mandelbrot_orbit* orbit = nullptr;
         // a scale below 2^-960 takes the deep constructor: (mantissa, exponent) from long double text, common exponent of the smaller
         char* endx = nullptr;
         char* endy = nullptr;
@@ -152,29 +163,63 @@ int main(int argc, char* argv[]) {
                    "use --precision perturb or perturb-bla-deep)\n", sxText, syText);
             return EXIT_FAILURE;
         }
-        int rc;
-        if (lmin != 0.0L && lmin < ldexpl(1.0L, -960)) {
-            int e = 0;
-            (void)frexpl(lmin, &e);
-            rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &orbit);
+        const bool deepScale = lmin != 0.0L && lmin < ldexpl(1.0L, -960);
+        int e = 0;
+        (void)frexpl(lmin, &e);
+        // --orbit auto: the device from kOrbitAutoLimbs limbs upward (the orbit's k + 1, from the constructors' bits = 1 - e + 96, at least
+        // 64), the host below.  130: the smallest measured limb count from which the device's whole call is at least 20 % below the host's
+        // (profiles/orbit_device_probe.txt: 0.78 of the host's time there, 1.04 at 106 limbs).
+        constexpr long kOrbitAutoLimbs = 130;
+        const long bits = 1L - e + 96 < 64 ? 64 : 1L - e + 96;
+        const bool onDevice = gpus <= 1 && (orbitWhere == kOrbitDevice ||
+                                            (orbitWhere == kOrbitAuto && kOrbitAutoLimbs > 0 && lmin != 0.0L && (bits + 63) / 64 + 1 >= kOrbitAutoLimbs));
+        // the orbit and its tables on ctx's device (or the host: ctx == nullptr); the message the run ends with, or "" after setOrbit()
+        auto makeOrbit = [=, &app](mc_context* ctx) -> std::string {
+            auto message = [](const char* fmt, auto... args) {
+                char buf[8192];
+                snprintf(buf, sizeof buf, fmt, args...);
+                return std::string(buf);
+            };
+            mc_mandelbrot_orbit* made = nullptr;
+            const auto t0 = std::chrono::steady_clock::now();
+            int rc;
+            if (ctx) {
+                if (deepScale) rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &made);
+                else rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, sx, sy, 0, maxIter, &made);
+            } else if (deepScale) {
+                rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &made);
+            } else {
+                rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &made);
+            }
+            const double orbitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (rc != MC_OK)
+                return message("--centre %s %s / --scale %s %s: %s (%s)", cxText, cyText, sxText, syText, mc_error_string(rc), mc_last_error_detail());
+            if (orbitSet) {
+                uint32_t obits = 0, launches = 0;
+                mc_mandelbrot_orbit_info(made, nullptr, nullptr, &obits);
+                if (ctx) mc_context_last_orbit_timing(ctx, nullptr, &launches, nullptr);
+                printf("orbit: %.3f ms (%s, %u bits, %u launches)\n", orbitMs, ctx ? "device" : "host", obits, launches);
+            }
+            if (precision == MC_PRECISION_PERTURB_BLA && (rc = mc_mandelbrot_orbit_bla(made, nullptr, nullptr)) != MC_OK) {   // the table, on the host
+                mc_mandelbrot_orbit_destroy(made);
+                return message("mc_mandelbrot_orbit_bla: %s (%s)", mc_error_string(rc), mc_last_error_detail());
+            }
+            if (precision == MC_PRECISION_PERTURB_BLA_DEEP && (rc = mc_mandelbrot_orbit_bla_deep(made, nullptr, nullptr)) != MC_OK) {
+                mc_mandelbrot_orbit_destroy(made);
+                return message("mc_mandelbrot_orbit_bla_deep: %s (%s)", mc_error_string(rc), mc_last_error_detail());
+            }
+            app.setOrbit(made);   // bound to the context by init(), before the warm-up thread starts
+            return std::string();
+        };
+        if (onDevice) {
+            app.setOrbitFactory(makeOrbit);   // needs the context: made in init(), once it exists
         } else {
-            rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &orbit);
+            const std::string err = makeOrbit(nullptr);
+            if (!err.empty()) {
+                printf("%s\n", err.c_str());
+                return EXIT_FAILURE;
+            }
         }
-        if (rc != MC_OK) {
-            printf("--centre %s %s / --scale %s %s: %s (%s)\n", cxText, cyText, sxText, syText, mc_error_string(rc), mc_last_error_detail());
-            return EXIT_FAILURE;
-        }
-        if (precision == MC_PRECISION_PERTURB_BLA && (rc = mc_mandelbrot_orbit_bla(orbit, nullptr, nullptr)) != MC_OK) {   // the table, on the host
-            printf("mc_mandelbrot_orbit_bla: %s (%s)\n", mc_error_string(rc), mc_last_error_detail());
-            mc_mandelbrot_orbit_destroy(orbit);
-            return EXIT_FAILURE;
-        }
-        if (precision == MC_PRECISION_PERTURB_BLA_DEEP && (rc = mc_mandelbrot_orbit_bla_deep(orbit, nullptr, nullptr)) != MC_OK) {
-            printf("mc_mandelbrot_orbit_bla_deep: %s (%s)\n", mc_error_string(rc), mc_last_error_detail());
-            mc_mandelbrot_orbit_destroy(orbit);
-            return EXIT_FAILURE;
-        }
-        app.setOrbit(orbit);   // bound to the context by init(), before the warm-up thread starts
     }
 #elif defined(PATHTRACER_MODE)
     const int32_t spp = pos.size() > 0 ? atoi(pos[0]) : 500;                           // samples per pixel

@@ -34,6 +34,10 @@ struct MandelbrotApp : public ComputeApp {
         orbit = o;
         setView(0.0, 0.0, 0.0, 0.0);
     }
+    // --orbit device | auto: the orbit is made on the context's device (mc_mandelbrot_orbit_create_device), so only once the context
+    // exists: contextCreated() calls the factory before the bind and before the warm-up helper starts.  It calls setOrbit(), or
+    // returns the message the run ends with.
+    void setOrbitFactory(std::function<std::string(mc_context*)> f) { orbitFactory = std::move(f); }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
     MandelbrotApp(const MandelbrotApp&) = delete;
     MandelbrotApp& operator=(const MandelbrotApp&) = delete;
@@ -53,6 +57,10 @@ struct MandelbrotApp : public ComputeApp {
     virtual void createCommandBuffer() override { params = request(); }
 
     virtual void contextCreated() override {
+        if (orbitFactory) {
+            const std::string err = orbitFactory(ctx);
+            if (!err.empty()) throw std::runtime_error(err);
+        }
         if (orbit) check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
     }
 
@@ -116,6 +124,7 @@ private:
     uint32_t workgroupSize;
     mc_mandelbrot_params params;
     mc_mandelbrot_orbit* orbit = nullptr;
+    std::function<std::string(mc_context*)> orbitFactory;
 };
 
 #endif  // MANDELBROTAPP_H_
