@@ -1,0 +1,274 @@
+// The reference orbit's host code (csrc/mandel_orbit.cpp) alone, for a sanitizer: this file, that one, no HIP and no library.
+//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude
+//       tools/orbit_host_check.cpp vulkan-compute-tests_amd/csrc/mandel_orbit.cpp -o orbit_host_check && ./orbit_host_check
+// (tests/test_mandel_orbit_sanitized.py does exactly that).  The cases are the smallest that reach each bound of that code: the limb
+// counts 1, 3, 17 and 130 (at 130 both fixed arrays of FixOps are full), every refusal, the parser's length and exponent limits, the
+// rounding to double at zero, below 2^-1022 and below 2^-1074, and both BLA tables at the lengths where a level is empty, single or odd.
+// A failed check prints its line and exits 1; the last line of a clean run is "orbit_host_check: <n> cases OK".
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../vulkan-compute-tests_amd/csrc/mandel_orbit.h"
+
+static std::string g_detail;
+void mc::set_error_detail(const std::string& s) { g_detail = s; }
+
+static int g_cases = 0;
+#define CHECK(cond)                                                                        \
+    do {                                                                                   \
+        if (!(cond)) {                                                                     \
+            std::printf("orbit_host_check: line %d: %s  [%s]\n", __LINE__, #cond, g_detail.c_str()); \
+            std::exit(1);                                                                  \
+        }                                                                                  \
+    } while (0)
+
+static bool starts_with(const std::string& s, const char* p) { return s.rfind(p, 0) == 0; }
+
+// A period-3 nucleus to 400 digits (tests/mandel_perturb_deep_ref.py: nucleus(3, NUCLEUS3, 1500, 400)): Z_3 is about 1e-400.
+static const char* const kNucleusX =
+    "-0.1225611668766536199752455518207356540526966911136034280053580146769596724359594546308864535788748"
+    "4817581131604359328853085120144219686207392593333543076083097977731453156822007766377592251457888826"
+    "6856875067518528879100464614830578927561614275943817068375927722452437391689322387453436454068494611"
+    "2309062801400318200906471261983368314376340932176817145623984702633464164562538602910335803821581532"
+    "773";
+static const char* const kNucleusY =
+    "0.74486176661974423659317042860439236724016308490682457420184759215441521783783976779114375493296415"
+    "9039252804873377366033438940727045047654259489042923780775650657326505538360482036291417505977187767"
+    "7021432904657232576721829572589287026372017545401840679367062598723047060014669726074691769823085559"
+    "6333164829693545154156517837526706429699885026451688149555770783160702748473472453161086804183656524"
+    "77";
+
+struct Orbit {
+    mc_mandelbrot_orbit* o = nullptr;
+    uint32_t L = 0, M = 0, bits = 0;
+    std::vector<double> z;
+    ~Orbit() { mc_mandelbrot_orbit_destroy(o); }
+    void read() {
+        CHECK(o != nullptr);
+        CHECK(mc_mandelbrot_orbit_info(o, &L, &M, &bits) == MC_OK);
+        CHECK(L >= 1 && L <= M);
+        z.assign(2 * ((size_t)L + 1), -1.0);   // exactly the size the copy writes
+        CHECK(mc_mandelbrot_orbit_copy(o, z.data()) == MC_OK);
+        CHECK(z[0] == 0.0 && z[1] == 0.0);
+        for (double v : z) CHECK(std::isfinite(v) && std::fabs(v) <= 8.0);
+    }
+};
+
+// Both tables of one orbit: shape, the copies into buffers of exactly their size, and the invariants of include/mc_compute.h.
+static void check_tables(Orbit& a, bool deep) {
+    const uint32_t L = a.L;
+    uint32_t want_levels = 0;
+    uint64_t want_entries = 0;
+    for (uint64_t n0 = L >= 3 ? L - 2 : 0; (n0 >> want_levels) >= 1; want_levels++) want_entries += n0 >> want_levels;
+    double one[5] = {0, 0, 0, 0, 0};
+    int32_t one_e[3] = {0, 0, 0};
+    uint32_t lev = 99;
+    uint64_t ent = 99;
+    if (deep) {
+        CHECK(mc_mandelbrot_orbit_bla(a.o, &lev, &ent) == MC_ERR_UNSUPPORTED && starts_with(g_detail, "mc_mandelbrot_orbit_bla: a deep orbit"));
+    } else {
+        CHECK(mc_mandelbrot_orbit_bla_copy(a.o, one) == MC_ERR_INVALID_ARGUMENT);   // no table yet
+        CHECK(mc_mandelbrot_orbit_bla(a.o, &lev, &ent) == MC_OK && lev == want_levels && ent == want_entries);
+        lev = ent = 99;
+        CHECK(mc_mandelbrot_orbit_bla(a.o, &lev, &ent) == MC_OK && lev == want_levels && ent == want_entries);   // built once
+        CHECK(mc_mandelbrot_orbit_bla(a.o, nullptr, nullptr) == MC_OK);
+        std::vector<double> t(5 * ent, -1.0);
+        CHECK(mc_mandelbrot_orbit_bla_copy(a.o, ent ? t.data() : one) == MC_OK);
+        for (uint64_t j = 0; j < ent; j++) CHECK(t[5 * j + 4] >= 0.0 && std::isfinite(t[5 * j + 4]));
+    }
+    CHECK(mc_mandelbrot_orbit_bla_deep_copy(a.o, one, one_e) == MC_ERR_INVALID_ARGUMENT);   // no table yet
+    lev = ent = 99;
+    CHECK(mc_mandelbrot_orbit_bla_deep(a.o, &lev, &ent) == MC_OK && lev == want_levels && ent == want_entries);
+    lev = ent = 99;
+    CHECK(mc_mandelbrot_orbit_bla_deep(a.o, &lev, &ent) == MC_OK && lev == want_levels && ent == want_entries);
+    CHECK(mc_mandelbrot_orbit_bla_deep(a.o, nullptr, nullptr) == MC_OK);
+    std::vector<double> mant(5 * ent, -1.0);
+    std::vector<int32_t> exps(3 * ent, 7);
+    CHECK(mc_mandelbrot_orbit_bla_deep_copy(a.o, ent ? mant.data() : one, ent ? exps.data() : one_e) == MC_OK);
+    CHECK(a.o->bla_deep.size() == ent);
+    for (uint64_t j = 0; j < ent; j++) {
+        const mc::BlaDeepRec& r = a.o->bla_deep[j];
+        CHECK(r.pad[0] == 0 && r.pad[1] == 0 && r.pad[2] == 0);
+        CHECK(mant[5 * j + 4] >= 0.0 && mant[5 * j + 4] == r.r && exps[3 * j] == r.ea && exps[3 * j + 1] == r.eb && exps[3 * j + 2] == r.er);
+        for (int q = 0; q < 3; q++) CHECK(exps[3 * j + q] >= -(1 << 20) && exps[3 * j + q] <= (1 << 20));
+    }
+    g_cases++;
+}
+
+// One orbit at a given limb count: scale_exp2 == INT32_MIN stands for mc_mandelbrot_orbit_create.
+static void check_orbit(const char* cx, const char* cy, double sx, double sy, int32_t exp2, uint32_t M, uint32_t bits, bool escapes,
+                        bool deep) {
+    Orbit a;
+    const int rc = exp2 == INT32_MIN ? mc_mandelbrot_orbit_create(cx, cy, sx, sy, M, &a.o)
+                                     : mc_mandelbrot_orbit_create_deep(cx, cy, sx, sy, exp2, M, &a.o);
+    CHECK(rc == MC_OK);
+    a.read();
+    CHECK(a.bits == bits && a.M == M && a.o->deep == deep);
+    CHECK(escapes ? a.L < M : a.L == M);
+    CHECK(a.z[2] == std::strtod(cx, nullptr) && a.z[3] == std::strtod(cy, nullptr));   // Z_1 = c, correctly rounded
+    check_tables(a, deep);
+}
+
+static void check_refusal(int rc, mc_mandelbrot_orbit* o, int status, const char* detail_head) {
+    CHECK(rc == status);
+    CHECK(o == nullptr);
+    CHECK(starts_with(g_detail, detail_head));
+    g_cases++;
+}
+
+// The parser through mc_mandelbrot_orbit_create at one iteration: accepted text gives Z_1 = strtod(text), refused text status 1.
+static void check_text(const std::string& s, bool accepted) {
+    Orbit a;
+    g_detail.clear();
+    const int rc = mc_mandelbrot_orbit_create(s.c_str(), "0.25", 1e-12, 1e-12, 1, &a.o);
+    if (!accepted) {
+        check_refusal(rc, a.o, MC_ERR_INVALID_ARGUMENT, "mc_mandelbrot_orbit_create: centre_x is not a decimal");
+        mc_mandelbrot_orbit* o = nullptr;
+        check_refusal(mc_mandelbrot_orbit_create("0.25", s.c_str(), 1e-12, 1e-12, 1, &o), o, MC_ERR_INVALID_ARGUMENT,
+                      "mc_mandelbrot_orbit_create: centre_y is not a decimal");
+        return;
+    }
+    CHECK(rc == MC_OK);
+    a.read();
+    CHECK(a.L == 1 && a.z[2] == std::strtod(s.c_str(), nullptr) && a.z[3] == 0.25);
+    g_cases++;
+}
+
+int main() {
+    const char *esc_x = "-0.75", *esc_y = "0.1", *in_x = "-0.1", *in_y = "0.2";
+    // ---- limb counts at the edges, an escaping and a non-escaping centre each
+    check_orbit(esc_x, esc_y, 1e10, 1e10, INT32_MIN, 1000, 64, true, false);                    // k = 1
+    check_orbit(in_x, in_y, 1e10, 3e10, INT32_MIN, 1000, 64, false, false);
+    check_orbit(esc_x, esc_y, 1e-20, 1e-20, INT32_MIN, 1000, 163, true, false);                 // k = 3
+    check_orbit(in_x, in_y, 1e-20, 3e-20, INT32_MIN, 1000, 163, false, false);
+    check_orbit(esc_x, esc_y, std::ldexp(1.0, -960), 1.0, INT32_MIN, 300, 1056, true, false);   // k = 17: the plain constructor's floor
+    check_orbit(in_x, in_y, std::ldexp(1.0, -960), 1.0, INT32_MIN, 300, 1056, false, false);
+    check_orbit(in_x, in_y, 0.5, 0.75, -959, 300, 1056, false, false);                          // the same through _create_deep
+    check_orbit(in_x, in_y, 0.5, 0.75, -960, 300, 1057, false, true);                           // the first deep scale
+    check_orbit(esc_x, esc_y, 1.0, 1.0, -8192, 300, 8288, true, true);                          // k = 130: both fixed arrays full
+    check_orbit(in_x, in_y, 1.0, 1.0, -8192, 300, 8288, false, true);
+    check_orbit(in_x, in_y, -1.0, 1.5, -8192, 40, 8288, false, true);
+
+    // ---- refusals: status, detail, *out NULL
+    mc_mandelbrot_orbit* o = nullptr;
+    check_refusal(mc_mandelbrot_orbit_create(in_x, in_y, std::ldexp(1.0, -961), 1e-10, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create: scale below 2^-960");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 1.0, -8193, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create_deep: scale below 2^-8192");   // k is clamped to 130 before the strings are parsed
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 1.0, INT32_MIN, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create_deep: scale below 2^-8192");
+    check_refusal(mc_mandelbrot_orbit_create_deep("-0.1x", in_y, 1.0, 1.0, -8193, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create_deep: centre_x is not a decimal");   // the strings first, below the floor too
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 1.0, 1100, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create_deep: scale above the double range");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 1.0, INT32_MAX, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create_deep: scale above the double range");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.5, 1.0, 1024, 10, &o), o, MC_ERR_UNSUPPORTED,
+                  "mc_mandelbrot_orbit_create_deep: scale above the double range");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, "0.2x", 0.5, 0.5, -10, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create: centre_y is not a decimal");   // a shallow scale names the plain constructor
+    check_refusal(mc_mandelbrot_orbit_create(in_x, in_y, 1e-10, 1e-10, 0, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create: max_iter must be at least 1");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 1.0, -3000, 0, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create_deep: max_iter must be at least 1");
+    check_refusal(mc_mandelbrot_orbit_create(nullptr, in_y, 1e-10, 1e-10, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create: NULL argument");
+    check_refusal(mc_mandelbrot_orbit_create(in_x, nullptr, 1e-10, 1e-10, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create: NULL argument");
+    check_refusal(mc_mandelbrot_orbit_create(in_x, in_y, 1e-10, 1e-10, 10, nullptr), nullptr, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create: NULL argument");
+    check_refusal(mc_mandelbrot_orbit_create_deep(in_x, nullptr, 1.0, 1.0, -3000, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                  "mc_mandelbrot_orbit_create_deep: NULL argument");
+    const double bad[4] = {0.0, -0.0, INFINITY, NAN};
+    for (double b : bad) {
+        check_refusal(mc_mandelbrot_orbit_create(in_x, in_y, b, 1e-10, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                      "mc_mandelbrot_orbit_create: scale_x and scale_y must be finite and nonzero");
+        check_refusal(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, b, -3000, 10, &o), o, MC_ERR_INVALID_ARGUMENT,
+                      "mc_mandelbrot_orbit_create_deep: scale_x and scale_y must be finite and nonzero");
+    }
+    CHECK(mc_mandelbrot_orbit_info(nullptr, nullptr, nullptr, nullptr) == MC_ERR_INVALID_ARGUMENT);
+    CHECK(mc_mandelbrot_orbit_copy(nullptr, nullptr) == MC_ERR_INVALID_ARGUMENT);
+    CHECK(mc_mandelbrot_orbit_bla(nullptr, nullptr, nullptr) == MC_ERR_INVALID_ARGUMENT);
+    CHECK(mc_mandelbrot_orbit_bla_deep(nullptr, nullptr, nullptr) == MC_ERR_INVALID_ARGUMENT);
+    CHECK(mc_mandelbrot_orbit_destroy(nullptr) == MC_OK);
+    g_cases++;
+
+    // ---- the parser
+    check_text("0.5" + std::string(4093, '0'), true);      // 4096 characters: the longest accepted
+    check_text("0.5" + std::string(4094, '0'), false);     // 4097
+    check_text(std::string(4095, '0') + "1", true);        // 4096 digits before the point
+    check_text("." + std::string(4094, '9') + "5", true);  // 4095 digits after it, none before
+    for (const char* s : {"", ".", "1e", "1e+", "+.", "-", "1e999999999999", "4." "000000000000000000000000000000" "1", "0x1p-2", "nan",
+                          "5", "40e-1x"})
+        check_text(s, false);
+    for (const char* s : {"0e-999999999999", "0e999999999999", "-0.0", "0", "4", "-4", "4.", "40e-1", "+.5", "7e-5",
+                          "0.1000000000000000055511151231257827021181583404541015625", "3.9999999999999999999", "0.000001234567890123e+2"})
+        check_text(s, true);
+    // Zeros after the point down to an all-zero floor: 1e-101 at 64 fractional bits (the `z < -point` loop stops at the zero floor), and
+    // the same with a saturated exponent.  The value is below the last bit, so it is rounded to odd there: Z_1 = 2^-64, not strtod's.
+    for (const std::string& s : {"0." + std::string(100, '0') + "1", std::string("1e-999999999999")}) {
+        Orbit a;
+        CHECK(mc_mandelbrot_orbit_create(s.c_str(), "-0", 1e10, 1e10, 1, &a.o) == MC_OK);
+        a.read();
+        CHECK(a.bits == 64 && a.z[2] == std::ldexp(1.0, -64) && a.z[3] == 0.0);
+        g_cases++;
+    }
+
+    // ---- rounding to double
+    for (const char* c : {"0", "-1"}) {   // exact zero entries, deep: accepted (the tiny-entry refusal is for nonzero entries)
+        Orbit a;
+        CHECK(mc_mandelbrot_orbit_create_deep(c, "0", 0.5255518873824417, 0.5255518873824417, -3321, 50, &a.o) == MC_OK);
+        a.read();
+        CHECK(a.L == 50 && a.o->deep && a.z[4] == 0.0 && a.z[5] == 0.0);
+        check_tables(a, true);
+        Orbit b;                          // both builders on an orbit through zero
+        CHECK(mc_mandelbrot_orbit_create(c, "0", 1e-10, 1e-10, 50, &b.o) == MC_OK);
+        b.read();
+        CHECK(b.L == 50 && b.z[4] == 0.0 && b.z[5] == 0.0);
+        check_tables(b, false);
+    }
+    check_refusal(mc_mandelbrot_orbit_create_deep(kNucleusX, kNucleusY, 0.5255518873824417, 0.5255518873824417, -3321, 100, &o), o,
+                  MC_ERR_UNSUPPORTED, "mc_mandelbrot_orbit_create_deep: orbit entry Z_3 is nonzero with both parts below 2^-960");
+    {   // the same centre at a shallow scale is accepted: Z_3, about 1e-400, is below half of 2^-1074 and rounds to zero
+        Orbit a;
+        CHECK(mc_mandelbrot_orbit_create(kNucleusX, kNucleusY, 1e-200, 1e-200, 100, &a.o) == MC_OK);
+        a.read();
+        CHECK(a.L == 100);
+        g_cases++;
+    }
+    {   // the centre cut to 312 digits at 2^-950 (1046 bits): Z_3, about 1e-312, is a subnormal double (the 2^-1074 quantum of to_double)
+        Orbit a;
+        const std::string x(kNucleusX, 2 + 1 + 312), y(kNucleusY, 2 + 312);
+        CHECK(mc_mandelbrot_orbit_create(x.c_str(), y.c_str(), std::ldexp(1.0, -950), std::ldexp(1.0, -950), 100, &a.o) == MC_OK);
+        a.read();
+        const double m3 = std::fmax(std::fabs(a.z[6]), std::fabs(a.z[7]));
+        CHECK(a.bits == 1046 && m3 > 0.0 && m3 < std::ldexp(1.0, -1022));
+        check_tables(a, false);
+    }
+
+    // ---- tables: no entry (L <= 2), one entry (L = 3), an odd tail on a level (L = 5), 2^n + 2
+    for (uint32_t L : {1u, 2u, 3u, 4u, 5u, 6u, 10u, 18u, 34u, 35u}) {
+        Orbit a;
+        CHECK(mc_mandelbrot_orbit_create(in_x, in_y, 1e-20, 1e-20, L, &a.o) == MC_OK);
+        a.read();
+        CHECK(a.L == L);
+        check_tables(a, false);
+        Orbit d;
+        CHECK(mc_mandelbrot_orbit_create_deep(in_x, in_y, 0.75, 0.5, -1000, L, &d.o) == MC_OK);
+        d.read();
+        CHECK(d.L == L && d.o->deep);
+        check_tables(d, true);
+    }
+    {   // an escaping orbit of length 2: centre 1 (Z_1 = 1, Z_2 = 2, |Z_2|^2 > 2)
+        Orbit a;
+        CHECK(mc_mandelbrot_orbit_create("1", "0", 1e-3, 1e-3, 100, &a.o) == MC_OK);
+        a.read();
+        CHECK(a.L == 2);
+        check_tables(a, false);
+    }
+    std::printf("orbit_host_check: %d cases OK\n", g_cases);
+    return 0;
+}

@@ -5,7 +5,7 @@
 //  * the orbit is computed in launches of at most orbit_launch_iters(k) iterations.  Between launches the state (status, j, the signs,
 //    zx, zy, sx, sy and the rounded zx zy) lives in device memory; the host reads (status, j), 8 bytes, and the slice after each launch.
 //    Nothing spins and nothing synchronises across workgroups.
-//  * parsing, validation and the object are make_orbit's (mandel_perturb.hip): this file is the loop only.
+//  * parsing, validation and the object are orbit_create's (mandel_orbit.cpp): this file is the loop, handed to it as an OrbitLoop.
 #include <cstring>
 #include <new>
 
@@ -88,13 +88,7 @@ void init_state(std::vector<uint32_t>& st, int k, const uint64_t* cx, const uint
     }
 }
 
-}  // namespace
-
-uint32_t orbit_launch_iters(int k) {
-    const uint64_t n = (uint64_t)k + 1u, it = kOrbitLaunchWork / (n * n);
-    return (uint32_t)(it < 1u ? 1u : it > 65536u ? 65536u : it);
-}
-
+// The loop on ctx's device, otherwise an OrbitLoop (mandel_orbit.h).
 int orbit_device_run(mc_context* ctx, int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter,
                      bool deep, std::vector<double>& z, uint32_t* length, uint32_t* tiny_j) {
     MC_HIP_TRY(hipSetDevice(ctx->device));
@@ -129,7 +123,7 @@ int orbit_device_run(mc_context* ctx, int k, const uint64_t* cx, const uint64_t*
         const size_t got = head[1] - j0;
         if (got) {
             const size_t at = z.size();
-            z.resize(at + 2 * got);   // (std::bad_alloc: caught by make_orbit)
+            z.resize(at + 2 * got);   // (std::bad_alloc: caught by orbit_create)
             MC_HIP_TRY(hipMemcpyAsync(&z[at], d->slice.ptr, 2 * got * sizeof(double), hipMemcpyDeviceToHost, s));
             MC_HIP_TRY(hipStreamSynchronize(s));
         } else if (head[0] == kRunning) {
@@ -180,6 +174,19 @@ int orbit_lanes_run(int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, 
     return MC_OK;
 }
 
+}  // namespace
+
+uint32_t orbit_launch_iters(int k) {
+    const uint64_t n = (uint64_t)k + 1u, it = kOrbitLaunchWork / (n * n);
+    return (uint32_t)(it < 1u ? 1u : it > 65536u ? 65536u : it);
+}
+
+int orbit_create_lanes(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter,
+                       mc_mandelbrot_orbit** out) {
+    return orbit_create("orbit_create_lanes", "orbit_create_lanes", orbit_lanes_run, centre_x, centre_y, scale_x, scale_y, scale_exp2,
+                        max_iter, out);
+}
+
 void orbit_device_release(mc_context* ctx) {
     g_orbit_devices.erase(ctx, [](OrbitDevice& d) {
         d.state.release();
@@ -190,6 +197,18 @@ void orbit_device_release(mc_context* ctx) {
 }
 
 }  // namespace mc
+
+// The object of mc_mandelbrot_orbit_create_deep with the iteration loop on ctx's device.  Every refusal of the arguments comes first.
+extern "C" int mc_mandelbrot_orbit_create_device(mc_context* ctx, const char* centre_x, const char* centre_y, double scale_x,
+                                                 double scale_y, int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    if (!ctx) {
+        mc::set_error_detail("mc_mandelbrot_orbit_create_device: NULL argument");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const char* fn = "mc_mandelbrot_orbit_create_device";
+    return mc::orbit_create(fn, fn, [ctx](auto&&... a) { return mc::orbit_device_run(ctx, a...); }, centre_x, centre_y, scale_x, scale_y,
+                            scale_exp2, max_iter, out);
+}
 
 extern "C" int mc_context_last_orbit_timing(mc_context* ctx, double* device_ms, uint32_t* launches, uint32_t* limbs) {
     if (!ctx) return MC_ERR_INVALID_ARGUMENT;

@@ -1,4 +1,4 @@
-// The reference orbit's multi-limb arithmetic in lane-parallel form: one iteration of make_orbit (mandel_perturb.hip)
+// The reference orbit's multi-limb arithmetic in lane-parallel form: one iteration of host_loop (mandel_orbit.cpp)
 // as six phases over 1024 lanes.  The same source runs as the threads of one workgroup on the device (mandel_orbit_device.hip, a barrier
 // after each phase) and as lane loops on the host (lanes 0 .. 1023 in order, phase by phase), so a CPU build can be stepped and tested
 // without a GPU.  Pure integer arithmetic up to the final (double)mant * 2^e, which is exact: the results equal FixOps bit for bit.

@@ -1,6 +1,7 @@
 // MC_PRECISION_PERTURB (mandel_perturb.hip): the entry points the rest of the library calls.
 #pragma once
 #include "mandel_adaptive.h"
+#include "mandel_orbit.h"
 #include "mandel_target.h"
 #include "mc_internal.h"
 
@@ -35,13 +36,7 @@ struct PerturbBlaArgs {
 int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
 // MC_PRECISION_PERTURB_BLA_DEEP (mandel_perturb_bla_deep.hip): the rescaled loop of the deep kernel with bilinear skips, for every orbit.
-// The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one 64-byte record, its mantissas and
-// exponents together, so that a probe reads a single record.
-struct BlaDeepRec {
-    double ax, ay, bx, by, r;        // the mantissas: A = (ax, ay) * 2^ea, B = (bx, by) * 2^eb, R = r * 2^er
-    int32_t ea, eb, er, pad[3];
-};
-static_assert(sizeof(BlaDeepRec) == 64, "one table entry is one 64-byte record");
+// The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one BlaDeepRec (mandel_orbit.h).
 struct PerturbBlaDeepArgs {
     MandelTarget t;                  // t.table: [ux[W] | uy[H]]
     const BlaDeepRec* bla;           // the table (null when it has no entry: L < 3)
@@ -50,19 +45,14 @@ struct PerturbBlaDeepArgs {
 };
 int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
 
-// mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): make_orbit's iteration loop on the context's device.  cx, cy: the centre's
-// k + 1 limbs.  z holds Z_0 on entry and Z_0 .. Z_L on success (*length = L); kOrbitTinyEntry: the tiny-entry refusal at Z_(*tiny_j).
+// mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): orbit_create's iteration loop (mandel_orbit.h) on the context's device.
 // A launch runs at most orbit_launch_iters(k) = kOrbitLaunchWork / (k + 1)^2 iterations, clamped to [1, 65536].  3.2e7 gives 1864
 // iterations at k = 130: 49 ms at the 26.3 us per iteration measured there (which also lists what the rule gives at the
 // smaller limb counts, where an iteration's fixed part outweighs its products).
 constexpr uint64_t kOrbitLaunchWork = 32000000ull;
-constexpr int kOrbitTinyEntry = -1;
 uint32_t orbit_launch_iters(int k);
-int orbit_device_run(mc_context* ctx, int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter,
-                     bool deep, std::vector<double>& z, uint32_t* length, uint32_t* tiny_j);
-// The kernel's phases as lane loops on the host (no device): what libmc_compute_test.so's mc_hook_orbit_create_lanes_host calls.
-int orbit_lanes_run(int k, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter, bool deep,
-                    std::vector<double>& z, uint32_t* length, uint32_t* tiny_j);
+// The constructor with the kernel's phases as lane loops on the host (no device): what libmc_compute_test.so's
+// mc_hook_orbit_create_lanes_host calls.
 int orbit_create_lanes(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter,
                        mc_mandelbrot_orbit** out);
 // mc_context_destroy: the context's orbit state, slice and events are freed.
