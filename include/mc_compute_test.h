@@ -44,7 +44,8 @@ enum {
 #define MC_PT_FORCE_S(s) ((uint32_t)(s) << 8) /* force the sample-parallel width: 1, 4 or 16 (0 = automatic) */
 
 /* fn: 0 mc_sin, 1 mc_cos, 2 mc_log2, 3 mc_exp2, 4 pow(x,0.45), 5 inversesqrt, 6 sqrt, 7 1/x,
- * 8/9 sin/cos via the fused mc_sincos; fast=1 evaluates the MC_PT_MATH_FAST variants instead. */
+ * 8/9 sin/cos via the fused mc_sincos; fast=1 evaluates the MC_PT_MATH_FAST variants instead, fast=2 the careful tier's
+ * unguarded short forms (fn 5, 6, 7 only; any other fn is MC_ERR_INVALID_ARGUMENT). */
 int mc_test_math(mc_context* ctx, int fn, int fast, const float* in, float* out, size_t n);
 /* Strict (a[3i], a[3i+1], a[3i+2]) / s[i] as the path tracer divides a colour by a probability, by pi, by the sample count (short
  * division inside its window, IEEE expansion outside); with_y != 0: the reciprocal RN(1/s) is supplied instead of computed. */

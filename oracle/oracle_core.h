@@ -65,6 +65,17 @@ namespace mcmath {
 inline float as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 inline uint32_t as_uint(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
+// float -> int32 of the quadrant count, WRITTEN OUT: truncation in range, saturation to INT32_MAX / INT32_MIN outside it, NaN -> 0.
+// This is what the device's conversion instruction (v_cvt_i32_f32) computes for every input; a bare (int)q is undefined in
+// C++ for |q| >= 2^31 and for NaN, and x86's cvttss2si resolves it differently (INT32_MIN for all of them).  q is already an
+// integer here.  Only |x| >= 2^31 * pi/2 ~ 3.37e9 and NaN reach the saturated branches: far outside the ranges for which
+// DESIGN.md section 4 claims accuracy (the result there is DEFINED, not accurate).
+inline int quadrant_i32(float q) {
+    if (q != q) return 0;
+    if (q >= 2147483648.0f) return INT32_MAX;
+    if (q <= -2147483648.0f) return INT32_MIN;
+    return (int)q;
+}
 // Cody–Waite split of pi/2 (2x the cephes DP1..DP3 constants), then cephes sinf/cosf minimax kernels.
 inline void sincos_reduce(float x, float& r, int& k) {
     const float TWO_OVER_PI = 0.636619772367581343f;
@@ -75,7 +86,7 @@ inline void sincos_reduce(float x, float& r, int& k) {
     r = std::fmaf(q, -PIO2_HI, x);
     r = std::fmaf(q, -PIO2_MID, r);
     r = std::fmaf(q, -PIO2_LO, r);
-    k = (int)q;
+    k = quadrant_i32(q);
 }
 inline float sin_kernel(float r) {
     float z = r * r;
@@ -98,7 +109,7 @@ inline float mc_sin(float x) {
 inline float mc_cos(float x) {
     float r; int k; sincos_reduce(x, r, k);
     float c = (k & 1) ? sin_kernel(r) : cos_kernel(r);
-    return ((k + 1) & 2) ? -c : c;
+    return (((uint32_t)k + 1u) & 2u) ? -c : c;   // k + 1 modulo 2^32 (k may be INT32_MAX, see quadrant_i32)
 }
 
 // log2 for x >= 0 (x == 0 -> -inf); exp2 for y <= 0 (y < -125 -> 0).  Used only as

@@ -668,8 +668,12 @@ class Context:
 
     # ---- device self-tests ---------------------------------------------------------------------------
     def test_math(self, fn, x, fast=False):
+        """mc_test_math: fast = False / 0 the strict functions, True / 1 the fast tier's, 2 the careful tier's short forms without
+        their window tests (rsqrt, sqrt and rcp only)."""
         code = {"sin": 0, "cos": 1, "log2": 2, "exp2": 3, "pow045": 4, "rsqrt": 5, "sqrt": 6, "rcp": 7, "sincos_s": 8,
                 "sincos_c": 9}[fn]
+        if int(fast) == 2 and code not in (5, 6, 7):
+            raise ValueError(f"Context.test_math: the careful tier (fast=2) has rsqrt, sqrt and rcp only, not {fn}")
         x = np.ascontiguousarray(x, np.float32).reshape(-1)
         out = np.empty_like(x)
         _check(test_lib().mc_test_math(self._h, code, int(fast), _ptr(x), _ptr(out), x.size), "mc_test_math")

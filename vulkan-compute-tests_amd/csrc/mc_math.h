@@ -132,6 +132,11 @@ template <int Fast> __device__ __forceinline__ float inversesqrt(float a) {
 }
 
 // ---- strict sin / cos ------------------------------------------------------------------------------
+// The quadrant count k = (int)q below IS, by definition, what the conversion instruction (v_cvt_i32_f32) computes: truncation in range,
+// saturation to INT32_MAX / INT32_MIN for |q| >= 2^31 (|x| >= 2^31 * pi/2 ~ 3.37e9, +-inf), 0 for NaN; and k + 1 in mc_cos / mc_sincos
+// is taken modulo 2^32.  The oracle writes the same definition out (oracle/oracle_core.h quadrant_i32) and
+// tests/test_gpu_math_edges.py compares the two on every stratum of fp32.  Out there the result is DEFINED, not accurate: accuracy is
+// claimed only for the ranges of DESIGN.md section 4 (nothing rendered leaves [0, 2 pi]).
 __device__ __forceinline__ void sincos_reduce(float x, float& r, int& k) {
     const float TWO_OVER_PI = 0.636619772367581343f;
     const float PIO2_HI = 1.5703125f;

@@ -33,6 +33,13 @@ __global__ void test_math_kernel(int fn, int fast, const float* __restrict__ in,
             case 9: { float s, c; dm::mc_sincos(x, s, c); r = c; } break;
             default: break;
         }
+    } else if (fast == 2) {   // the careful tier: the short forms without their window tests (mc_math.h); only fn 5, 6, 7 have one
+        switch (fn) {
+            case 5: r = dm::inversesqrt<2>(x); break;
+            case 6: r = dm::fsqrt<2>(x); break;
+            case 7: r = dm::fdiv<2>(1.0f, x); break;
+            default: break;
+        }
     } else {
         const float two_pi = 2.0f * 3.141592653589793f;
         switch (fn) {
@@ -116,7 +123,7 @@ static int run_test(mc_context* ctx, const void* in_a, size_t bytes_a, const voi
 }
 
 int mc_test_math(mc_context* ctx, int fn, int fast, const float* in, float* out, size_t n) {
-    if (!ctx || !in || !out || !n) return MC_ERR_INVALID_ARGUMENT;
+    if (!ctx || !in || !out || !n || fast < 0 || fast > 2 || (fast == 2 && (fn < 5 || fn > 7))) return MC_ERR_INVALID_ARGUMENT;
     return run_test(ctx, in, n * 4, nullptr, 0, out, n * 4,
                     [](void* a, void*, void* o, size_t n_, hipStream_t s, int fn_, int fast_) {
                         hipLaunchKernelGGL(test_math_kernel, dim3((unsigned)((n_ + 255) / 256)), dim3(256), 0, s, fn_, fast_,
