@@ -34,7 +34,8 @@ extern "C" {
  * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
  * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
  * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined; then
- * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing.
+ * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing; then MC_MANDEL_COLOUR_SMOOTH with mc_mandelbrot_render_smooth,
+ * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -312,8 +313,10 @@ enum {
     /* bits 2 and 3 are measurement switches too */
     MC_MANDEL_COLOUR_EQUALISED = 1u << 4,/* histogram-equalised colouring of a WHOLE image (mc_mandelbrot_render and            */
                                   /* mc_mandelbrot_render_rgba8; the contract is below, at mc_mandelbrot_equalise_map)      */
-    MC_MANDEL_SUPERSAMPLE_ADAPTIVE = 1u << 5 /* with MC_MANDEL_SUPERSAMPLE(s): only pixels whose count differs from a neighbour's  */
+    MC_MANDEL_SUPERSAMPLE_ADAPTIVE = 1u << 5,/* with MC_MANDEL_SUPERSAMPLE(s): only pixels whose count differs from a neighbour's  */
                                   /* get their s x s samples (the contract is below, at mc_context_last_refined)            */
+    MC_MANDEL_COLOUR_SMOOTH = 1u << 6 /* smooth colouring by a fractional escape count (the contract is below, at           */
+                                  /* mc_mandelbrot_render_smooth); bit 7 is free                                            */
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
@@ -395,6 +398,64 @@ int mc_mandelbrot_histogram_device_async(mc_context* ctx, const void* d_iters, u
 int mc_mandelbrot_equalise_map(uint32_t max_iter, const uint32_t* hist /* max_iter + 1 */, uint32_t* map /* max_iter + 1 */);
 int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_iters, uint32_t iters_bytes,
                                         const uint32_t* map /* HOST, max_iter + 1 */, void* d_rgba_f32, void* stream);
+
+/* ---- smooth colouring (the project's own addition: the reference colours by the integer count, one flat colour per count; DESIGN.md
+ *      section 3.14; what tests/mandel_smooth_ref.py restates).  MC_MANDEL_COLOUR_SMOOTH in mc_mandelbrot_params.flags.  A pixel gets a
+ *      SMOOTH COUNT q, a uint32_t in 24.8 fixed point: q / 256 is its fractional iteration count.
+ *  - escape state: n is the pixel's count, unchanged.  For n < M (M = max_iter), (zx, zy) is the z of iteration i = n, the one whose test
+ *    r > 2 succeeded, and (cx, cy) the pixel's c, both taken as doubles:
+ *      F32: the two floats of z converted (exact); the pixel's float c from the c table, converted.
+ *      DS: (double)hi + (double)lo of zx, zy; the same sum of the c table's pairs.
+ *      F64: as they are; the c table's doubles.
+ *      PERTURB, PERTURB_BLA: the loop's zx, zy (Z[m] + nd); c = (Z[1].x + dcx, Z[1].y + dcy).  Z_1 is c_ref correctly rounded.
+ *      deep orbits, PERTURB_BLA_DEEP: the same zx, zy; c = (Z[1].x + ldexp(ux, E), Z[1].y + ldexp(uy, E)), ldexp correctly rounded, 0
+ *      when it underflows.  For an orbit of the old scale this is the PERTURB row.
+ *  - smooth_count(n, M, zx, zy, cx, cy), in IEEE double, no contraction, source order:
+ *      if (n >= M) return 256 * M;
+ *      k = 0;  r = (zx*zx) + (zy*zy);
+ *      while (!(r > 65536.0) && k < 64) {            // a NaN keeps running to the cap
+ *          t = ((zx*zx) - (zy*zy)) + cx;  zy = ((2.0*zx)*zy) + cy;  zx = t;  k++;  r = (zx*zx) + (zy*zy);
+ *      }
+ *      rf = (float)r;                                 // round to nearest even
+ *      if (!(rf > 65536.0f)) rf = 65536.0f;           // the cap was hit, or NaN
+ *      if (rf > FLT_MAX) rf = FLT_MAX;                // inf
+ *      l = mc_log2(rf);  s = l * 0.0625f;  t = mc_log2(s);      // fp32; the strict log2 of the library (oracle: mc_math("log2")), op for op
+ *      if (!(t > 0.0f)) t = 0.0f;  if (t > 1.0f) t = 1.0f;
+ *      F = (uint32_t)(256.0f * (1.0f - t));          // 0 .. 256
+ *      q = min(256 * (uint64_t)(n + k) + F, 256 * (uint64_t)M - 1);
+ *    The fractional count is (n + k) + 1 - log2(log2 r / 16): continuous across the radius-256 threshold (r = 65536 gives +1, r = 65536^2
+ *    gives +0, the value the pixel would have had one iteration earlier).  Interior pixels have q = 256 M exactly; an escaped pixel never
+ *    reaches 256 M.  The flag needs max_iter <= 2^24 - 1 (MC_ERR_INVALID_ARGUMENT above).
+ *  - colour: idx = q >> 8, fr = q & 255.  q = 256 M gives lut[M]; otherwise, per component, in fp32 with no contraction,
+ *    a + ((b - a) * w) with a = lut[idx], b = lut[idx + 1], w = (float)fr * 0.00390625f, lut the table of mc_mandelbrot_colour_lut; alpha
+ *    is 1.0f.  fr = 0 gives lut[idx].  RGBA8 is mc_convert_rgba8's conversion of that vec4, as everywhere.
+ *  - KNOWN LIMIT: the reference's escape threshold is |z|^2 > 2, not 4, so some "escaped" pixels are in the set (the antenna near
+ *    c = -1.9) or wander long before they leave.  Such pixels hit the 64-iteration cap and get q = 256 (n + 64) + 256: in F32, 52 of the
+ *    115 093 escaped pixels of the reference view at 400 x 400, M = 128 (0.045 %; tests/test_mandel_smooth_host.py restates it); in F64,
+ *    93 016 of the 39 321 599 escaped pixels of the K4 view at 7680 x 5120, M = 50 000 (0.24 %, measured on the device).  The continuation
+ *    is 4 iterations in the median and 5 - 7 at the 95th percentile on those views.
+ * Every single-device call that takes mc_mandelbrot_params honours the flag in all six precisions: mc_mandelbrot_render (out_iters still
+ * receives n), mc_mandelbrot_render_device_async, mc_mandelbrot_render_rgba8 (whole images and bands), mc_mandelbrot_render_banded, row
+ * tiles and interleaved tiles, MC_MANDEL_ITERS_U16 for the n plane, and mc_context_warmup_mandelbrot, which makes the smooth
+ * instantiation resident.  Together with MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_SUPERSAMPLE(s >= 2) or MC_MANDEL_SUPERSAMPLE_ADAPTIVE it is
+ * MC_ERR_INVALID_ARGUMENT (mc_last_error_detail says which: a rank map or a resolve over fractional counts does not exist yet); so it is
+ * together with the measurement switch MC_MANDEL_FMA of mc_compute_test.h (the contraction switch has no smooth kernel).  The calls
+ * that build colours from a plane of integer counts refuse it with MC_ERR_INVALID_ARGUMENT: mc_mandelbrot_recolour_device_async,
+ * mc_mandelbrot_resolve_device_async, mc_mandelbrot_assemble_device_async (mc_mandelbrot_histogram_device_async takes no params and so
+ * sees no flag: it counts whatever plane it is given).  mc_multi_* refuse it with MC_ERR_UNSUPPORTED.
+ *
+ * mc_mandelbrot_render_smooth / _device_async: p must carry the flag; any output may be NULL, at least one must be given; the smooth
+ * plane is always uint32_t (the device form: aligned to 4), tiles are stored compactly as everywhere; the rest follows
+ * mc_mandelbrot_render / mc_mandelbrot_render_device_async.
+ * mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour (host only, no device): the same source as the kernels' epilogue.
+ * smooth_count: n <= max_iter <= 2^24 - 1.  smooth_colour writes count vec4 values for count q values; a q above 256 max_iter is
+ * MC_ERR_INVALID_ARGUMENT. */
+int mc_mandelbrot_render_smooth(mc_context* ctx, const mc_mandelbrot_params* p, float* out_rgba_f32, uint32_t* out_iters,
+                                uint32_t* out_smooth);
+int mc_mandelbrot_render_smooth_device_async(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba_f32, void* d_iters,
+                                             void* d_smooth, void* stream);
+int mc_mandelbrot_smooth_count(uint32_t n, uint32_t max_iter, double zx, double zy, double cx, double cy, uint32_t* q);
+int mc_mandelbrot_smooth_colour(uint32_t max_iter, const float k_color[4], const uint32_t* q, uint64_t count, float* out_rgba_f32);
 
 /* ---- s x s supersampling (the project's own addition: the reference takes ONE sample per pixel, at its corner, mandelbrot.comp:29-30;
  *      DESIGN.md section 3.11; what tests/mandel_supersample_ref.py restates).  MC_MANDEL_SUPERSAMPLE(s) in flags, s = 2, 4 or 8:

@@ -24,6 +24,7 @@ MANDEL_FMA = 1
 MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any bound orbit renders by the deep kernel
 MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
 MANDEL_SUPERSAMPLE_ADAPTIVE = 32   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE: with MANDEL_SUPERSAMPLE(s), only pixels whose count differs from a neighbour's are sampled s x s
+MANDEL_COLOUR_SMOOTH = 64       # MC_MANDEL_COLOUR_SMOOTH: smooth colouring by a fractional escape count, 24.8 fixed point (include/mc_compute.h)
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
@@ -162,6 +163,11 @@ def lib():
             L.mc_mandelbrot_resolve_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, u32, vp, vp, vp]
         if hasattr(L, "mc_context_last_refined"):   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE
             L.mc_context_last_refined.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "mc_mandelbrot_smooth_count"):   # MC_MANDEL_COLOUR_SMOOTH
+            L.mc_mandelbrot_render_smooth.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp]
+            L.mc_mandelbrot_render_smooth_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
+            L.mc_mandelbrot_smooth_count.argtypes = [u32, u32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(u32)]
+            L.mc_mandelbrot_smooth_colour.argtypes = [u32, C.POINTER(f32), vp, C.c_uint64, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -281,6 +287,30 @@ def equalise_map(max_iter, hist):
         raise ValueError(f"equalise_map: the histogram has {h.size} bins, max_iter + 1 = {max_iter + 1} expected")
     out = np.empty(max(h.size, 1), np.uint32)
     _check(lib().mc_mandelbrot_equalise_map(max_iter, _ptr(h), _ptr(out)), "mc_mandelbrot_equalise_map")
+    return out
+
+
+def smooth_count(n, max_iter, zx, zy, cx, cy):
+    """mc_mandelbrot_smooth_count (host only): q, the 24.8 fixed-point smooth count, of each escape state.  n: the counts; (zx, zy): the z
+    of the iteration that escaped; (cx, cy): the pixel's c (arrays of one shape, or scalars); returns uint32 of that shape."""
+    n, zx, zy, cx, cy = np.broadcast_arrays(np.asarray(n, np.uint32), *(np.asarray(v, np.float64) for v in (zx, zy, cx, cy)))
+    out = np.empty(n.shape, np.uint32)
+    fn = lib().mc_mandelbrot_smooth_count
+    q = C.c_uint32()
+    flat = out.reshape(-1)
+    for i, (a, b, c, d, e) in enumerate(zip(n.ravel().tolist(), zx.ravel().tolist(), zy.ravel().tolist(), cx.ravel().tolist(),
+                                            cy.ravel().tolist())):
+        _check(fn(a, max_iter, b, c, d, e, C.byref(q)), "mc_mandelbrot_smooth_count")
+        flat[i] = q.value
+    return out
+
+
+def smooth_colour(max_iter, q, k_color=(0.1, 0.7, 0.6, 0.0)):
+    """mc_mandelbrot_smooth_colour (host only): float32 (..., 4), the colour of each smooth count q (q <= 256 * max_iter)."""
+    qa = np.ascontiguousarray(q, np.uint32)
+    k = (C.c_float * 4)(*k_color)
+    out = np.empty(qa.shape + (4,), np.float32)
+    _check(lib().mc_mandelbrot_smooth_colour(max_iter, k, _ptr(qa), qa.size, _ptr(out)), "mc_mandelbrot_smooth_colour")
     return out
 
 
@@ -563,6 +593,16 @@ class Context:
         _check(lib().mc_mandelbrot_render(self._h, C.byref(p), _ptr(rgba), _ptr(iters)), "mc_mandelbrot_render")
         return rgba, iters
 
+    def mandelbrot_smooth(self, p, want_rgba=True, want_iters=True, want_smooth=True):
+        """mc_mandelbrot_render_smooth (p carries MANDEL_COLOUR_SMOOTH): (rgba float32, n uint32, q uint32) of p's tile, None where not
+        wanted.  q is the smooth count in 24.8 fixed point."""
+        rows = tile_rows(p)
+        rgba = np.empty((rows, p.width, 4), np.float32) if want_rgba else None
+        iters = np.empty((rows, p.width), np.uint32) if want_iters else None
+        smooth = np.empty((rows, p.width), np.uint32) if want_smooth else None
+        _check(lib().mc_mandelbrot_render_smooth(self._h, C.byref(p), _ptr(rgba), _ptr(iters), _ptr(smooth)), "mc_mandelbrot_render_smooth")
+        return rgba, iters, smooth
+
     def mandelbrot_banded(self, p, band_rows, rgba8=False):
         """mc_mandelbrot_render_banded: the image (rows [row_begin, row_end)) rendered in pipelined row bands; returns the image — the fp32
         storage buffer, or RGBA8 converted on the device — and the rows_done values the callback heard, in the order it heard them."""
@@ -604,6 +644,11 @@ class Context:
     def mandelbrot_device(self, p, d_rgba=0, d_iters=0, stream=0):
         _check(lib().mc_mandelbrot_render_device_async(self._h, C.byref(p), d_rgba or None, d_iters or None, stream or None),
                "mc_mandelbrot_render_device_async")
+
+    def mandelbrot_smooth_device(self, p, d_rgba=0, d_iters=0, d_smooth=0, stream=0):
+        """mc_mandelbrot_render_smooth_device_async: the device form of mandelbrot_smooth (d_smooth: a uint32 plane)."""
+        _check(lib().mc_mandelbrot_render_smooth_device_async(self._h, C.byref(p), d_rgba or None, d_iters or None, d_smooth or None,
+                                                              stream or None), "mc_mandelbrot_render_smooth_device_async")
 
     def mandelbrot_rgba8(self, p):
         """mc_mandelbrot_render_rgba8: the rows [row_begin, row_end) rendered and converted on the device; only RGBA8 leaves the GPU."""

@@ -26,8 +26,14 @@ namespace mc {
 // The State interface: init (per kernel), step() = one exact iteration, reporting "escaped now"; kHasFastBlock, Acc, acc_init(),
 // advance_fast(acc) and needs_exact(acc) = the block of U iterations without per-iteration ballots, replayed exactly from the saved
 // state when some unfinished lane raises needs_exact; same_z() and kCycleCheckBlocks = the cycle exit.
-template <class State, int U>
-__device__ __forceinline__ uint32_t escape_time(State& st, uint32_t max_iter, bool valid) {
+//
+// Cap: NoCapture, or a type whose latch(escaped, st) is called after every EXACT step (EscapeCapture of mandel_smooth.h keeps the z of
+// the lane's first escape).  An unfinished lane's escape is only ever detected in an exact step: a fast block in which one may have
+// escaped is replayed.  With NoCapture the loop is the one it was.
+struct NoCapture {};
+template <class State, int U, class Cap = NoCapture>
+__device__ __forceinline__ uint32_t escape_time(State& st, uint32_t max_iter, bool valid, [[maybe_unused]] Cap* cap = nullptr) {
+    constexpr bool kCapture = !__is_same(Cap, NoCapture);
     const uint32_t lane = __lane_id();
     const uint64_t lanebit = 1ull << lane;
     uint64_t done = ~__ballot(valid);   // lanes outside the image never hold the wave
@@ -62,7 +68,13 @@ __device__ __forceinline__ uint32_t escape_time(State& st, uint32_t max_iter, bo
         uint64_t any = 0;
 #pragma unroll
         for (int k = 0; k < U; k++) {
-            b[k] = __ballot(st.step());
+            if constexpr (kCapture) {
+                const bool e = st.step();
+                cap->latch(e, st);
+                b[k] = __ballot(e);
+            } else {
+                b[k] = __ballot(st.step());
+            }
             any |= b[k];
         }
         uint64_t newly = any & ~done;
@@ -75,7 +87,14 @@ __device__ __forceinline__ uint32_t escape_time(State& st, uint32_t max_iter, bo
         }
     }
     for (; i < max_iter; i++) {   // tail: max_iter % U iterations
-        uint64_t b = __ballot(st.step());
+        uint64_t b;
+        if constexpr (kCapture) {
+            const bool e = st.step();
+            cap->latch(e, st);
+            b = __ballot(e);
+        } else {
+            b = __ballot(st.step());
+        }
         uint64_t newly = b & ~done;
         if (newly) {
             if (newly & lanebit) n = i;

@@ -10,8 +10,14 @@ namespace mc {
 // launch_impl (mandelbrot.hip) hands precision 3 over after its common checks: orbit / view / max_iter checks, the colour and dc tables,
 // the launch.  warm = the cold-start warm-up's one-tile launch (mc_context_warmup_mandelbrot).
 // list: the list render of mandel_adaptive.h (p is the sample grid), or nullptr.
+// d_smooth: the q plane of MC_MANDEL_COLOUR_SMOOTH, or nullptr; the flag in p selects the smooth instantiation of whichever kernel runs.
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                   const SampleList* list = nullptr);
+                   const SampleList* list = nullptr, void* d_smooth = nullptr);
+// What the four launchers below take for MC_MANDEL_COLOUR_SMOOTH: on = the smooth instantiation (no list), q = its plane (may be null).
+struct SmoothOut {
+    bool on = false;
+    uint32_t* q = nullptr;
+};
 // mc_context_destroy: the context's bound orbit, if any, is freed.
 void perturb_release(mc_context* ctx);
 
@@ -22,7 +28,7 @@ struct PerturbDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E
     uint32_t has_zero;               // some Z_j = 0 exactly, 1 <= j < L (centres such as 0 and -1)
 };
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
 
 // MC_PRECISION_PERTURB_BLA (mandel_perturb_bla.hip): PERTURB's loop with bilinear skips, for orbits rendered by the plain loop.
 // perturb_launch builds the arguments from the binding: the dc table is PERTURB's, the BLA table the orbit's (mc_mandelbrot_orbit_bla),
@@ -33,7 +39,7 @@ struct PerturbBlaArgs {
     const double* bla;               // the BLA table (null when it has no entry: L < 3)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS: write the loop-trip count in place of n
 };
-int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
 
 // MC_PRECISION_PERTURB_BLA_DEEP (mandel_perturb_bla_deep.hip): the rescaled loop of the deep kernel with bilinear skips, for every orbit.
 // The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one BlaDeepRec (mandel_orbit.h).
@@ -43,7 +49,7 @@ struct PerturbBlaDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E (0 for an orbit of the old scale)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS
 };
-int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr);
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
 
 // mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): orbit_create's iteration loop (mandel_orbit.h) on the context's device.
 // A launch runs at most orbit_launch_iters(k) = kOrbitLaunchWork / (k + 1)^2 iterations, clamped to [1, 65536].  3.2e7 gives 1864

@@ -14,6 +14,7 @@
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
 #include "mandel_side_record.h"
+#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -83,6 +84,17 @@ struct StatePerturb {
         else { dx = ndx; dy = ndy; zmx = z1.x; zmy = z1.y; }
         return r > 2.0;
     }
+    // MC_MANDEL_COLOUR_SMOOTH: the z the last step() tested.  After a rebase it is d itself (Z_0 = 0 is not added: a -0 stays -0); otherwise
+    // Z[m] + d, the very addition step() made.  c = Z_1 + dc (Z_1 is c_ref correctly rounded).
+    __device__ __forceinline__ void escape_z(double& x, double& y) const {
+        x = m == 0u ? dx : zmx + dx;
+        y = m == 0u ? dy : zmy + dy;
+    }
+    __device__ __forceinline__ void escape_c(double& x, double& y) const {
+        const double2 z1 = Z[1];
+        x = z1.x + dcx;
+        y = z1.y + dcy;
+    }
     // Fast block: Z[m+1 .. m+U] are loaded at the block's start (acc_init), off the dependency chain; the block assumes m advances by
     // one per iteration.  needs_exact = F64's high-word escape filter OR "this lane rebased, or reached m == L, in the block": any
     // unfinished lane raising it replays the block exactly from the saved state (step(), one load per iteration).
@@ -137,6 +149,20 @@ __global__ void __launch_bounds__(64) mandel_perturb_list_kernel(PerturbArgs a, 
     sample_resolve(l, ln, n, a.t.max_iter);
 }
 
+// MC_MANDEL_COLOUR_SMOOTH: the escape z latched in the exact steps, then the shared epilogue (mandel_smooth.h).
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_smooth_kernel(PerturbArgs a, uint32_t* __restrict__ out_smooth) {
+    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const TileLane ln = tile_lane(a.t);
+    StatePerturb st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    EscapeCapture cap;
+    const uint32_t n = escape_time<StatePerturb, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
+    double cx, cy;
+    st.escape_c(cx, cy);
+    smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
+}
+
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
 // by (W, H, precision, the bind generation): the params' view words are all zero for this precision.
 int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Binding& b, hipStream_t s) {
@@ -162,7 +188,8 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
 }  // namespace
 
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                   const SampleList* list) {
+                   const SampleList* list, void* d_smooth) {
+    const SmoothOut smooth = {(p->flags & MC_MANDEL_COLOUR_SMOOTH) != 0u && !list, (uint32_t*)d_smooth};
     const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
     const bool bla_deep = p->precision == MC_PRECISION_PERTURB_BLA_DEEP;
     const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : bla_deep ? "MC_PRECISION_PERTURB_BLA_DEEP" : "MC_PRECISION_PERTURB";
@@ -211,23 +238,24 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     if (bla) {   // mandel_perturb_bla.hip
         const PerturbBlaArgs d = {t, b->bla_entries ? (const double*)b->bla.ptr : nullptr,
                                   (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_launch(d, grid, s, list))) return rc;
+        if ((rc = perturb_bla_launch(d, grid, s, list, smooth))) return rc;
         return ctx->note_launch(s);
     }
     if (bla_deep) {   // mandel_perturb_bla_deep.hip
         const PerturbBlaDeepArgs d = {t, b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
                                       (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_deep_launch(d, grid, s, list))) return rc;
+        if ((rc = perturb_bla_deep_launch(d, grid, s, list, smooth))) return rc;
         return ctx->note_launch(s);
     }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
         const PerturbDeepArgs d = {t, b->scale_exp2, b->has_zero ? 1u : 0u};
-        if ((rc = perturb_deep_launch(d, grid, s, list))) return rc;
+        if ((rc = perturb_deep_launch(d, grid, s, list, smooth))) return rc;
         return ctx->note_launch(s);
     }
     const PerturbArgs a = {t};
-    if (!list) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
+    if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
+    else if (list) hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
+    else hipLaunchKernelGGL((mandel_perturb_smooth_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, smooth.q);
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
 }

@@ -12,6 +12,7 @@
 //    the same level, a wave shares m and every table read is wave-uniform (one cache line per probe).
 //  * IEEE double in source order (-ffp-contract=off), fp64 denormals kept.
 #include "mandel_perturb.h"
+#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -21,6 +22,7 @@ namespace {
 // S(n) = sum over j >= 0 of floor(n / 2^j) = 2n - popcount(n): level k of the table starts at entry S(n) - S(n >> k), n = L - 2
 __device__ __forceinline__ uint64_t level_sum(uint64_t n) { return 2u * n - (uint64_t)__popcll(n); }
 
+#define MC_BLA_ON_ESCAPE(zx, zy)
 __global__ void __launch_bounds__(64) mandel_perturb_bla_kernel(PerturbBlaArgs a) {
     const TileLane ln = tile_lane(a.t);
     const uint32_t gx = ln.gx, gy = ln.gy;
@@ -38,11 +40,27 @@ __global__ void __launch_bounds__(64) mandel_perturb_bla_list_kernel(PerturbBlaA
 #include "mandel_perturb_bla_loop.h"
     sample_resolve(l, ln, a.count_trips ? trips : n, a.t.max_iter);
 }
+#undef MC_BLA_ON_ESCAPE
+
+// MC_MANDEL_COLOUR_SMOOTH: the loop's escaping z kept (the loop leaves at its one escape test), then the shared epilogue
+// (mandel_smooth.h) with c = Z_1 + dc.
+#define MC_BLA_ON_ESCAPE(zx, zy) ezx = zx; ezy = zy;
+__global__ void __launch_bounds__(64) mandel_perturb_bla_smooth_kernel(PerturbBlaArgs a, uint32_t* __restrict__ out_smooth) {
+    const TileLane ln = tile_lane(a.t);
+    const uint32_t gx = ln.gx, gy = ln.gy;
+    const bool valid = ln.valid;
+    double ezx = 0.0, ezy = 0.0;
+#include "mandel_perturb_bla_loop.h"
+    const double2 c1 = Z[1];
+    smooth_tile_store(a.t, ln, out_smooth, n, a.count_trips ? trips : n, ezx, ezy, c1.x + dcx, c1.y + dcy);
+}
+#undef MC_BLA_ON_ESCAPE
 
 }  // namespace
 
-int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list) {
-    if (!list) hipLaunchKernelGGL(mandel_perturb_bla_kernel, grid, dim3(64), 0, s, a);
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
+    if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
+    else if (!list) hipLaunchKernelGGL(mandel_perturb_bla_kernel, grid, dim3(64), 0, s, a);
     else hipLaunchKernelGGL(mandel_perturb_bla_list_kernel, grid, dim3(64), 0, s, a, *list);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;

@@ -12,6 +12,7 @@
 //  * a table entry is one 64-byte record (5 mantissas, 3 exponents), so a probe is one record read.
 //  * IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
 #include "mandel_perturb.h"
+#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -29,6 +30,7 @@ __device__ __forceinline__ int frexp_exp(double x) { return __builtin_amdgcn_fre
 // S(n) = sum over j >= 0 of floor(n / 2^j) = 2n - popcount(n): level k of the table starts at entry S(n) - S(n >> k), n = L - 2
 __device__ __forceinline__ uint64_t level_sum(uint64_t n) { return 2u * n - (uint64_t)__popcll(n); }
 
+#define MC_BLA_ON_ESCAPE(zx, zy)
 __global__ void __launch_bounds__(64) mandel_perturb_bla_deep_kernel(PerturbBlaDeepArgs a) {
     const TileLane ln = tile_lane(a.t);
     const uint32_t gx = ln.gx, gy = ln.gy;
@@ -46,11 +48,27 @@ __global__ void __launch_bounds__(64) mandel_perturb_bla_deep_list_kernel(Pertur
 #include "mandel_perturb_bla_deep_loop.h"
     sample_resolve(l, ln, a.count_trips ? trips : n, a.t.max_iter);
 }
+#undef MC_BLA_ON_ESCAPE
+
+// MC_MANDEL_COLOUR_SMOOTH: the loop's escaping z kept (the loop leaves at its one escape test), then the shared epilogue
+// (mandel_smooth.h) with c = Z_1 + ldexp(u, E).
+#define MC_BLA_ON_ESCAPE(zx, zy) ezx = zx; ezy = zy;
+__global__ void __launch_bounds__(64) mandel_perturb_bla_deep_smooth_kernel(PerturbBlaDeepArgs a, uint32_t* __restrict__ out_smooth) {
+    const TileLane ln = tile_lane(a.t);
+    const uint32_t gx = ln.gx, gy = ln.gy;
+    const bool valid = ln.valid;
+    double ezx = 0.0, ezy = 0.0;
+#include "mandel_perturb_bla_deep_loop.h"
+    const double2 c1 = Z[1];
+    smooth_tile_store(a.t, ln, out_smooth, n, a.count_trips ? trips : n, ezx, ezy, c1.x + ldexp2(ux, E), c1.y + ldexp2(uy, E));
+}
+#undef MC_BLA_ON_ESCAPE
 
 }  // namespace
 
-int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list) {
-    if (!list) hipLaunchKernelGGL(mandel_perturb_bla_deep_kernel, grid, dim3(64), 0, s, a);
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
+    if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_deep_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
+    else if (!list) hipLaunchKernelGGL(mandel_perturb_bla_deep_kernel, grid, dim3(64), 0, s, a);
     else hipLaunchKernelGGL(mandel_perturb_bla_deep_list_kernel, grid, dim3(64), 0, s, a, *list);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;

@@ -1,6 +1,7 @@
 // The per-pixel loop of mandel_perturb_bla_deep.hip, included TEXTUALLY into the body of each of its kernels (no include guard: it is a
 // fragment, not a header).  In scope at the include: a (the kernel's arguments), gx, gy (the lane's column and row in the dc / u table)
 // and valid (false: the lane runs no trip).  It leaves n (the count) and trips (the loop trips) behind.
+// MC_BLA_ON_ESCAPE(zx, zy) is the includer's: empty, or the smooth instantiation's capture of the escaping z (mandel_smooth.h).
 // Why not a __device__ function: the tile kernel's listing is the project's invariant, and the same loop inlined from a function comes
 // out of the register allocator with the operands of one v_add3_u32 swapped and two v_ldexp_f64 pairs in another order.  Lexically
 // inside the kernel it is unchanged.
@@ -102,7 +103,7 @@
             m = m + 1u;
             const double zx = z1.x + ndx, zy = z1.y + ndy;
             const double r = (zx * zx) + (zy * zy);
-            if (r > 2.0) { n = i; break; }
+            if (r > 2.0) { MC_BLA_ON_ESCAPE(zx, zy) n = i; break; }
             if (m == L || r < ((ndx * ndx) + (ndy * ndy))) {                 // rebase: Z_0 = 0, delta = z
                 m = 0u;
                 dx = zx; dy = zy;

@@ -11,6 +11,7 @@
 // IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
+#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -97,6 +98,17 @@ struct StateDeep {
         }
         return r > 2.0;
     }
+    // MC_MANDEL_COLOUR_SMOOTH: the z the last step() tested (as StatePerturb: d after a rebase, else Z[m] + d, step()'s own addition);
+    // c = Z_1 + ldexp(u, E).
+    __device__ __forceinline__ void escape_z(double& x, double& y) const {
+        x = m == 0u ? dx : zmx + dx;
+        y = m == 0u ? dy : zmy + dy;
+    }
+    __device__ __forceinline__ void escape_c(double& x, double& y) const {
+        const double2 z1 = Z[1];
+        x = z1.x + ldexp2(ux, E);
+        y = z1.y + ldexp2(uy, E);
+    }
     // Fast block: the general formula with S fixed, u * 2^(E - S) formed once per block, Z[m+1 .. m+U] fetched at the block's start.
     // needs_exact = the escape filter of F64 / PERTURB, OR a rebase or m reaching L, OR (scaled lanes) a Z = 0 step ahead (m = 0, or
     // a table with zeros), a renormalisation or a phase change somewhere in the block.  The last three are tested on the high words
@@ -177,11 +189,26 @@ __global__ void __launch_bounds__(64) mandel_perturb_deep_list_kernel(PerturbDee
     sample_resolve(l, ln, n, a.t.max_iter);
 }
 
+// MC_MANDEL_COLOUR_SMOOTH: the escape z latched in the exact steps, then the shared epilogue (mandel_smooth.h).
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_deep_smooth_kernel(PerturbDeepArgs a, uint32_t* __restrict__ out_smooth) {
+    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const TileLane ln = tile_lane(a.t);
+    StateDeep st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    EscapeCapture cap;
+    const uint32_t n = escape_time<StateDeep, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
+    double cx, cy;
+    st.escape_c(cx, cy);
+    smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
+}
+
 }  // namespace
 
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list) {
-    if (!list) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
+    if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
+    else if (list) hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
+    else hipLaunchKernelGGL((mandel_perturb_deep_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, smooth.q);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }

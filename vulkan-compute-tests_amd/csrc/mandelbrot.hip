@@ -28,6 +28,8 @@
 #include "mandel_adaptive.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
+#include "mandel_smooth.h"
+#include "mandel_smooth_host.h"
 #include "mandel_target.h"
 #include "mc_internal.h"
 
@@ -77,6 +79,9 @@ struct StateF32 {
     __device__ __forceinline__ bool step() { return advance() > 2.0f; }   // :44
     // z is the orbit's complete state (sx, sy are functions of it): equal z => equal future (see escape_time)
     __device__ __forceinline__ bool same_z(const StateF32& o) const { return zx == o.zx && zy == o.zy; }
+    // MC_MANDEL_COLOUR_SMOOTH: the z the last step() tested and the lane's c, as doubles (exact conversions)
+    __device__ __forceinline__ void escape_z(double& x, double& y) const { x = (double)zx; y = (double)zy; }
+    __device__ __forceinline__ void escape_c(double& x, double& y) const { x = (double)cx; y = (double)cy; }
     static constexpr uint32_t kCycleCheckBlocks = 1;   // compare with the reference state after every block (8 iterations)
     // Conservative escape filter on the bit pattern of |z|^2 (>= 0, or NaN after an overflow): every value
     // > 2.0f has bit 30 set or is 0x40000001..., every value < 2.0f has bit 30 clear, so the bitwise OR of a
@@ -136,6 +141,9 @@ struct StateDS {
     __device__ __forceinline__ bool same_z(const StateDS& o) const {
         return zx.hi == o.zx.hi && zx.lo == o.zx.lo && zy.hi == o.zy.hi && zy.lo == o.zy.lo;
     }
+    // MC_MANDEL_COLOUR_SMOOTH: (double)hi + (double)lo of z and c
+    __device__ __forceinline__ void escape_z(double& x, double& y) const { x = (double)zx.hi + (double)zx.lo; y = (double)zy.hi + (double)zy.lo; }
+    __device__ __forceinline__ void escape_c(double& x, double& y) const { x = (double)cx.hi + (double)cx.lo; y = (double)cy.hi + (double)cy.lo; }
     static constexpr uint32_t kCycleCheckBlocks = 4;   // every 4 blocks (16 iterations): deep-zoom views have few cycling pixels
     __device__ __forceinline__ bool step() {
         ds2 zxy = ds_mul(zx, zy);
@@ -169,6 +177,8 @@ struct StateF64 {
     }
     __device__ __forceinline__ bool step() { return advance() > 2.0; }
     __device__ __forceinline__ bool same_z(const StateF64& o) const { return zx == o.zx && zy == o.zy; }
+    __device__ __forceinline__ void escape_z(double& x, double& y) const { x = zx; y = zy; }   // MC_MANDEL_COLOUR_SMOOTH
+    __device__ __forceinline__ void escape_c(double& x, double& y) const { x = cx; y = cy; }
     static constexpr uint32_t kCycleCheckBlocks = 1;   // every block (8 iterations), as fp32: 2 v_cmp_f64 against ~66 VALU ops
     // StateF32's filter on the HIGH word of |z|^2 (>= 0, or NaN): every value >= 2.0 (and inf, and any NaN) has a high word
     // >= 0x40000000, every value < 2.0 one <= 0x3fffffff.  So the OR of a block's high words exceeds 0x3fffffff whenever one of
@@ -201,6 +211,20 @@ __global__ void __launch_bounds__(64) mandelbrot_list_kernel(MandelArgs a, Sampl
     st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
     const uint32_t n = escape_time<State, U>(st, a.max_iter, ln.valid);
     sample_resolve(l, ln, n, a.max_iter);
+}
+
+// MC_MANDEL_COLOUR_SMOOTH (mandel_smooth.h): the same loop with the z of each lane's first escape latched, then the shared epilogue —
+// c as the state read it from the table, the fp64 continuation to radius 256, q and the interpolated colour.
+template <class State, int U>
+__global__ void __launch_bounds__(64) mandelbrot_smooth_kernel(MandelArgs a, uint32_t* __restrict__ out_smooth) {
+    const TileLane ln = tile_lane(a);
+    State st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    double cx, cy;
+    st.escape_c(cx, cy);   // (before the loop: the state's c never changes, and the loop's registers are free again after it)
+    EscapeCapture cap;
+    const uint32_t n = escape_time<State, U, EscapeCapture>(st, a.max_iter, ln.valid, &cap);
+    smooth_tile_store(a, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
 }
 
 }  // namespace
@@ -295,9 +319,14 @@ int mandelbrot_lut_device(mc_context* ctx, const mc_mandelbrot_params* p, hipStr
 // warm = the cold-start warm-up (mc_context_warmup_mandelbrot): the tables of the REAL request are built and uploaded, then ONE 8 x 8
 // tile is run for at most 32 iterations into d_iters — enough for the runtime to load this code object and create the kernel.
 // list = the list render of mandel_adaptive.h (p is the sample grid, d_rgba the image the list's pixels are written to, d_iters unused).
+// d_smooth: the q plane of MC_MANDEL_COLOUR_SMOOTH (null: not wanted); the flag selects the smooth instantiation of every tile kernel.
 static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                       const SampleList* list = nullptr) {
-    if (!ctx || !p || (!d_rgba && !d_iters)) return MC_ERR_INVALID_ARGUMENT;
+                       const SampleList* list = nullptr, void* d_smooth = nullptr) {
+    if (!ctx || !p || (!d_rgba && !d_iters && !d_smooth)) return MC_ERR_INVALID_ARGUMENT;
+    const bool smooth = (p->flags & MC_MANDEL_COLOUR_SMOOTH) != 0u;
+    if (d_smooth && !smooth) return MC_ERR_INVALID_ARGUMENT;
+    if (smooth && list) return MC_ERR_INVALID_ARGUMENT;   // (the list kernels have no smooth instantiation: the entry points refuse the pair)
+    if (int rc = smooth_refuse_combination(p, "MC_MANDEL_COLOUR_SMOOTH")) return rc;
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
     if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64 &&
@@ -307,7 +336,7 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
     if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
         p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
-        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm, list);   // mandel_perturb.hip
+        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm, list, d_smooth);   // mandel_perturb.hip
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);
         if (rc) return rc;
@@ -324,7 +353,7 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
     a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
     a.lut = a.out_rgba ? (const float4*)ctx->lut.ptr : nullptr;
-    if (!list) {
+    if (!list && !smooth) {
         if (p->precision == MC_PRECISION_DS) {
             hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
         } else if (p->precision == MC_PRECISION_F64) {
@@ -334,11 +363,16 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
         } else {
             hipLaunchKernelGGL((mandelbrot_kernel<StateF32<false>, 8>), grid, block, 0, s, a);
         }
-    } else {
+    } else if (list) {
         if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_kernel<StateDS, 4>), grid, block, 0, s, a, l);
         else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF64, 8>), grid, block, 0, s, a, l);
         else if (p->flags & MC_MANDEL_FMA) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<true>, 8>), grid, block, 0, s, a, l);
         else hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<false>, 8>), grid, block, 0, s, a, l);
+    } else {   // (last: the smooth kernels are instantiated after the existing ones, whose listings stay as they were)
+        uint32_t* q = (uint32_t*)d_smooth;
+        if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateDS, 4>), grid, block, 0, s, a, q);
+        else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateF64, 8>), grid, block, 0, s, a, q);
+        else hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateF32<false>, 8>), grid, block, 0, s, a, q);
     }
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
@@ -346,6 +380,11 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
 
 int mandelbrot_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s) {
     return launch_impl(ctx, p, d_rgba, d_iters, s, false);
+}
+
+int mandelbrot_smooth_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, void* d_smooth, hipStream_t s) {
+    if (!p || !(p->flags & MC_MANDEL_COLOUR_SMOOTH)) return MC_ERR_INVALID_ARGUMENT;
+    return launch_impl(ctx, p, d_rgba, d_iters, s, false, nullptr, d_smooth);
 }
 
 int mandelbrot_list_launch(mc_context* ctx, const mc_mandelbrot_params* grid, const SampleList& l, hipStream_t s, bool warm) {

@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised (histogram-equalised colouring of the whole image), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised|smooth (equalised: histogram-equalised colouring of the whole image; smooth: fractional escape counts, no bands), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -38,7 +38,7 @@ int main(int argc, char* argv[]) {
     bool quiet = false, gpuPost = false, timingJson = false, referencePng = false, overlapStart = true, fullTeardown = false;
     int streamedSave = ComputeApp::kStreamAuto;
     int pngThreads = 0;
-    uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED)
+    uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED) | smooth (MC_MANDEL_COLOUR_SMOOTH)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
     bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
@@ -79,8 +79,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = true; }
         else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}, {"perturb-bla", MC_PRECISION_PERTURB_BLA}, {"perturb-bla-deep", MC_PRECISION_PERTURB_BLA_DEEP}}); }
         else if (a == "--colour") {   // reference: t = n / M (mandelbrot.comp:50-56) | equalised: the count's rank among the image's escaped pixels
+                                      // | smooth: the fractional escape count, interpolated between neighbouring palette entries
             need(1);
-            colour = choice(argv[++i], {{"reference", 0u}, {"equalised", (uint32_t)MC_MANDEL_COLOUR_EQUALISED}});
+            colour = choice(argv[++i], {{"reference", 0u}, {"equalised", (uint32_t)MC_MANDEL_COLOUR_EQUALISED},
+                                        {"smooth", (uint32_t)MC_MANDEL_COLOUR_SMOOTH}});
 #if !defined(MANDELBROT_MODE)
             printf("--colour: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
@@ -135,7 +137,10 @@ int main(int argc, char* argv[]) {
     app.setMaxIter(maxIter);
     if (viewSet) app.setView(cx, cy, sx, sy);
     app.setPrecision(precision);
-    if (colour) {   // the histogram needs the whole image: one mc_mandelbrot_render(_rgba8), never the banded, streamed save
+    if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
+        if (supersample > 1u) { printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
+        app.setColourFlags(colour);
+    } else if (colour) {   // the histogram needs the whole image: one mc_mandelbrot_render(_rgba8), never the banded, streamed save
         app.setColourFlags(colour);
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour equalised renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;

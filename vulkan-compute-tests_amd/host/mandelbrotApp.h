@@ -24,7 +24,7 @@ struct MandelbrotApp : public ComputeApp {
         split(sx, params.scale_x_hi, params.scale_x_lo);
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
-    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED (main.cpp --colour equalised)
+    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_COLOUR_SMOOTH (main.cpp --colour)
     void setSupersample(uint32_t s) { params.flags |= MC_MANDEL_SUPERSAMPLE(s); }   // 2, 4 or 8 (main.cpp --supersample)
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
     // MC_PRECISION_PERTURB / _BLA / _BLA_DEEP: the view is this orbit's (the app owns it; for the BLA precisions main() has built the
