@@ -35,7 +35,8 @@ extern "C" {
  * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
  * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined; then
  * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing; then MC_MANDEL_COLOUR_SMOOTH with mc_mandelbrot_render_smooth,
- * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour.
+ * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour; then MC_MANDEL_COLOUR_DISTANCE with
+ * mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -315,8 +316,10 @@ enum {
                                   /* mc_mandelbrot_render_rgba8; the contract is below, at mc_mandelbrot_equalise_map)      */
     MC_MANDEL_SUPERSAMPLE_ADAPTIVE = 1u << 5,/* with MC_MANDEL_SUPERSAMPLE(s): only pixels whose count differs from a neighbour's  */
                                   /* get their s x s samples (the contract is below, at mc_context_last_refined)            */
-    MC_MANDEL_COLOUR_SMOOTH = 1u << 6 /* smooth colouring by a fractional escape count (the contract is below, at           */
-                                  /* mc_mandelbrot_render_smooth); bit 7 is free                                            */
+    MC_MANDEL_COLOUR_SMOOTH = 1u << 6,/* smooth colouring by a fractional escape count (the contract is below, at           */
+                                  /* mc_mandelbrot_render_smooth)                                                           */
+    MC_MANDEL_COLOUR_DISTANCE = 1u << 7 /* the smooth colour shaded by a boundary distance estimate, of a WHOLE image (the      */
+                                  /* contract is below, at mc_mandelbrot_render_distance); set WITHOUT MC_MANDEL_COLOUR_SMOOTH */
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
@@ -456,6 +459,60 @@ int mc_mandelbrot_render_smooth_device_async(mc_context* ctx, const mc_mandelbro
                                              void* d_smooth, void* stream);
 int mc_mandelbrot_smooth_count(uint32_t n, uint32_t max_iter, double zx, double zy, double cx, double cy, uint32_t* q);
 int mc_mandelbrot_smooth_colour(uint32_t max_iter, const float k_color[4], const uint32_t* q, uint64_t count, float* out_rgba_f32);
+
+/* ---- distance shading (the project's own addition: no colouring of counts shows filaments thinner than a pixel, a distance estimate does;
+ *      DESIGN.md section 3.15; what tests/mandel_distance_ref.py restates).  MC_MANDEL_COLOUR_DISTANCE in mc_mandelbrot_params.flags.  The
+ *      smooth count nu = q / 256 is the potential in disguise, G ~ 2^(-nu), so the exterior estimate d ~ 2 G / |grad G| is
+ *      2 / (ln 2 |grad nu|): a function of the smooth plane alone, by finite differences between neighbouring pixels, in PIXEL PITCHES
+ *      whatever the zoom depth, for every precision at once.
+ *  - input: the WHOLE image's smooth plane q(y, x), uint32_t, W x H, storage rows; 256 M means interior (M = max_iter).
+ *  - distance plane D, float per pixel, in pixel pitches:
+ *      an interior pixel has D = 0.0f; an escaped pixel with an interior 4-neighbour inside the image has D = 0.0f; otherwise, differences
+ *      as int64_t:
+ *        gx = q(y, x+1) - q(y, x-1) for 0 < x < W-1; at a border the one-sided difference doubled: gx = 2 (q(y, 1) - q(y, 0)) at x = 0,
+ *        gx = 2 (q(y, W-1) - q(y, W-2)) at x = W-1; gx = 0 when W = 1.  gy is the same along storage rows (y-1, y+1, H).
+ *      then, in IEEE double, no contraction, source order:
+ *        a = (double)gx;  b = (double)gy;  g2 = (a*a) + (b*b);
+ *        g2 == 0: D = 4096.0f (above every other value: the largest, at g2 = 1, is 1477.3...);
+ *        else D = (float)(1477.3197218702985 / sqrt(g2)), sqrt and the division correctly rounded, the conversion round-to-nearest-even.
+ *      The constant is the double literal for 1024 / ln 2: the central difference spans two pixels and q carries 8 fractional bits.
+ *      Differences reach 2^33, so g2 may exceed 2^53 and round: it is still one IEEE expression, the same on both sides.
+ *  - colour, with threshold T (a finite float > 0, in pixels): an interior pixel gets lut[M], unchanged.  Every other pixel: base = the
+ *    smooth colour of q (mc_mandelbrot_smooth_colour's expression); w = D >= T ? 1.0f : D / T, a correctly rounded fp32 division;
+ *    rgb = base.rgb * w in fp32; alpha is 1.0f.  RGBA8 is mc_convert_rgba8's conversion of that vec4, as everywhere.
+ *  - STATED LIMITS: pixel pitches assume square pixels; with scale_x / W != scale_y / H the two differences are each in their own pitch
+ *    (documented, not corrected).  Below about two pixels the value is a shading weight, not a distance: it scatters and mostly reads low,
+ *    i.e. darker (DESIGN.md section 3.15 has the measured agreement with the analytic estimate).  Smooth colouring's known limit carries
+ *    over: pixels that hit the 64-iteration cap have steep q around them and come out dark.
+ * The flag is a colouring of its own: it implies the smooth count and is set WITHOUT MC_MANDEL_COLOUR_SMOOTH.  mc_mandelbrot_render
+ * (out_iters still receives n) and mc_mandelbrot_render_rgba8 honour it for WHOLE images only (row_begin = 0, row_end = height, no
+ * interleave), in all six precisions, with T = 1.0f: the smooth render of the q plane through the existing kernels (no vec4 leaves the
+ * render kernel), the stencil, for _rgba8 the conversion; q is scratch of the context, 4 bytes per pixel; mc_context_last_timing spans the
+ * chain; max_iter <= 2^24 - 1 as for smooth.  MC_ERR_INVALID_ARGUMENT, mc_last_error_detail naming the flag and the calls to use: a row
+ * tile or band of those two; the flag passed to mc_mandelbrot_render_device_async, mc_mandelbrot_render_banded,
+ * mc_mandelbrot_render_smooth / _device_async, mc_mandelbrot_recolour_device_async, mc_mandelbrot_resolve_device_async or
+ * mc_mandelbrot_assemble_device_async; the flag together with MC_MANDEL_COLOUR_SMOOTH, MC_MANDEL_COLOUR_EQUALISED,
+ * MC_MANDEL_SUPERSAMPLE(s >= 2), MC_MANDEL_SUPERSAMPLE_ADAPTIVE or the measurement switch MC_MANDEL_FMA.  mc_multi_* refuse it with
+ * MC_ERR_UNSUPPORTED.  mc_context_warmup_mandelbrot accepts it and makes the smooth instantiation and the stencil kernel resident;
+ * mc_mandelbrot_supersample_params copies the bit like any other.
+ *
+ * mc_mandelbrot_render_distance: the blocking whole-image call with all four planes (colours, n, q, D); any output may be NULL, at least
+ * one must be given; p must carry the flag; T = 1.0f.
+ * mc_mandelbrot_distance_device_async: the stage by hand.  d_smooth is the WHOLE image's dense q plane (W x H uint32_t, aligned to 4),
+ * what mc_mandelbrot_render_smooth_device_async wrote for the whole image; the outputs are the contiguous rows [row_begin, row_end) of p,
+ * stored compactly, so a caller can band its output (interleave: MC_ERR_INVALID_ARGUMENT).  Either output may be NULL, not both;
+ * d_distance_f32 is aligned to 4, d_rgba_f32 to 16; threshold_px must be finite and > 0; p carries the flag; the context's cached colour
+ * table is used.
+ * mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour (host only, no device): the same source as the kernel.  distance_plane
+ * writes width * height floats; distance_colour writes count vec4 values from count (q, D) pairs.  A q above 256 max_iter, a NULL
+ * pointer, a zero size, max_iter = 0 or above 2^24 - 1, or a threshold that is not finite and > 0: MC_ERR_INVALID_ARGUMENT. */
+int mc_mandelbrot_render_distance(mc_context* ctx, const mc_mandelbrot_params* p, float* out_rgba_f32, uint32_t* out_iters,
+                                  uint32_t* out_smooth, float* out_distance);
+int mc_mandelbrot_distance_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth, float threshold_px,
+                                        void* d_distance_f32, void* d_rgba_f32, void* stream);
+int mc_mandelbrot_distance_plane(uint32_t width, uint32_t height, uint32_t max_iter, const uint32_t* q, float* out_distance);
+int mc_mandelbrot_distance_colour(uint32_t max_iter, const float k_color[4], const uint32_t* q, const float* distance, uint64_t count,
+                                  float threshold_px, float* out_rgba_f32);
 
 /* ---- s x s supersampling (the project's own addition: the reference takes ONE sample per pixel, at its corner, mandelbrot.comp:29-30;
  *      DESIGN.md section 3.11; what tests/mandel_supersample_ref.py restates).  MC_MANDEL_SUPERSAMPLE(s) in flags, s = 2, 4 or 8:

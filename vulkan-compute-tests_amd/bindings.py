@@ -25,6 +25,7 @@ MANDEL_PERTURB_FORCE_DEEP = 4   # test switch (include/mc_compute_test.h): any b
 MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTURB_BLA writes each pixel's loop-trip count in place of n
 MANDEL_SUPERSAMPLE_ADAPTIVE = 32   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE: with MANDEL_SUPERSAMPLE(s), only pixels whose count differs from a neighbour's are sampled s x s
 MANDEL_COLOUR_SMOOTH = 64       # MC_MANDEL_COLOUR_SMOOTH: smooth colouring by a fractional escape count, 24.8 fixed point (include/mc_compute.h)
+MANDEL_COLOUR_DISTANCE = 128    # MC_MANDEL_COLOUR_DISTANCE: the smooth colour shaded by a boundary distance estimate, whole images; set without MANDEL_COLOUR_SMOOTH
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
@@ -168,6 +169,11 @@ def lib():
             L.mc_mandelbrot_render_smooth_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
             L.mc_mandelbrot_smooth_count.argtypes = [u32, u32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(u32)]
             L.mc_mandelbrot_smooth_colour.argtypes = [u32, C.POINTER(f32), vp, C.c_uint64, vp]
+        if hasattr(L, "mc_mandelbrot_distance_plane"):   # MC_MANDEL_COLOUR_DISTANCE
+            L.mc_mandelbrot_render_distance.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
+            L.mc_mandelbrot_distance_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, f32, vp, vp, vp]
+            L.mc_mandelbrot_distance_plane.argtypes = [u32, u32, u32, vp, vp]
+            L.mc_mandelbrot_distance_colour.argtypes = [u32, C.POINTER(f32), vp, vp, C.c_uint64, f32, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -311,6 +317,30 @@ def smooth_colour(max_iter, q, k_color=(0.1, 0.7, 0.6, 0.0)):
     k = (C.c_float * 4)(*k_color)
     out = np.empty(qa.shape + (4,), np.float32)
     _check(lib().mc_mandelbrot_smooth_colour(max_iter, k, _ptr(qa), qa.size, _ptr(out)), "mc_mandelbrot_smooth_colour")
+    return out
+
+
+def distance_plane(max_iter, q):
+    """mc_mandelbrot_distance_plane (host only): float32 (H, W), the distance estimate in pixel pitches of the WHOLE image's smooth plane
+    q (uint32 (H, W); 256 * max_iter means interior)."""
+    qa = np.ascontiguousarray(q, np.uint32)
+    if qa.ndim != 2:
+        raise ValueError("distance_plane: q is a (H, W) plane")
+    out = np.empty(qa.shape, np.float32)
+    _check(lib().mc_mandelbrot_distance_plane(qa.shape[1], qa.shape[0], max_iter, _ptr(qa), _ptr(out)), "mc_mandelbrot_distance_plane")
+    return out
+
+
+def distance_colour(max_iter, q, distance, threshold_px=1.0, k_color=(0.1, 0.7, 0.6, 0.0)):
+    """mc_mandelbrot_distance_colour (host only): float32 (..., 4), the smooth colour of each q dimmed by min(D / threshold_px, 1)."""
+    qa = np.ascontiguousarray(q, np.uint32)
+    da = np.ascontiguousarray(distance, np.float32)
+    if da.shape != qa.shape:
+        raise ValueError("distance_colour: q and distance have one shape")
+    k = (C.c_float * 4)(*k_color)
+    out = np.empty(qa.shape + (4,), np.float32)
+    _check(lib().mc_mandelbrot_distance_colour(max_iter, k, _ptr(qa), _ptr(da), qa.size, threshold_px, _ptr(out)),
+           "mc_mandelbrot_distance_colour")
     return out
 
 
@@ -603,6 +633,18 @@ class Context:
         _check(lib().mc_mandelbrot_render_smooth(self._h, C.byref(p), _ptr(rgba), _ptr(iters), _ptr(smooth)), "mc_mandelbrot_render_smooth")
         return rgba, iters, smooth
 
+    def mandelbrot_distance(self, p, want_rgba=True, want_iters=True, want_smooth=True, want_distance=True):
+        """mc_mandelbrot_render_distance (p carries MANDEL_COLOUR_DISTANCE, a whole image): (rgba float32, n uint32, q uint32, D float32),
+        None where not wanted.  D is the distance estimate in pixel pitches; the colours are shaded with a threshold of one pixel."""
+        shape = (p.height, p.width)
+        rgba = np.empty(shape + (4,), np.float32) if want_rgba else None
+        iters = np.empty(shape, np.uint32) if want_iters else None
+        smooth = np.empty(shape, np.uint32) if want_smooth else None
+        dist = np.empty(shape, np.float32) if want_distance else None
+        _check(lib().mc_mandelbrot_render_distance(self._h, C.byref(p), _ptr(rgba), _ptr(iters), _ptr(smooth), _ptr(dist)),
+               "mc_mandelbrot_render_distance")
+        return rgba, iters, smooth, dist
+
     def mandelbrot_banded(self, p, band_rows, rgba8=False):
         """mc_mandelbrot_render_banded: the image (rows [row_begin, row_end)) rendered in pipelined row bands; returns the image — the fp32
         storage buffer, or RGBA8 converted on the device — and the rows_done values the callback heard, in the order it heard them."""
@@ -655,6 +697,12 @@ class Context:
         out = np.empty((p.row_end - p.row_begin, p.width, 4), np.uint8)
         _check(lib().mc_mandelbrot_render_rgba8(self._h, C.byref(p), _ptr(out)), "mc_mandelbrot_render_rgba8")
         return out
+
+    def mandelbrot_distance_device(self, p, d_smooth, threshold_px=1.0, d_distance=0, d_rgba=0, stream=0):
+        """mc_mandelbrot_distance_device_async: D (float32) and / or the shaded colours of p's rows [row_begin, row_end), stored compactly,
+        from d_smooth, the WHOLE image's uint32 smooth plane."""
+        _check(lib().mc_mandelbrot_distance_device_async(self._h, C.byref(p), d_smooth or None, threshold_px, d_distance or None,
+                                                         d_rgba or None, stream or None), "mc_mandelbrot_distance_device_async")
 
     def mandelbrot_histogram_device(self, d_iters, iters_bytes, n_pixels, max_iter, d_hist, stream=0):
         """mc_mandelbrot_histogram_device_async: ADDS the counts of n_pixels values (2 or 4 B each) to the device table

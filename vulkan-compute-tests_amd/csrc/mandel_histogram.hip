@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "mandel_distance_host.h"
 #include "mandel_equalise.h"
 #include "mandel_side_record.h"
 #include "mandel_smooth_host.h"
@@ -359,6 +360,7 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
     if (!ctx || !p || !d_iters || !map || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u))
         return MC_ERR_INVALID_ARGUMENT;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
+    if (int rc = distance_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     MC_HIP_TRY(hipSetDevice(ctx->device));
     return mandelbrot_recolour_launch(ctx, p, d_iters, iters_bytes, map, d_rgba_f32, stream ? (hipStream_t)stream : ctx->stream);
 }

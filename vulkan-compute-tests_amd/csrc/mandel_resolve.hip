@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "mandel_equalise.h"
+#include "mandel_distance_host.h"
 #include "mandel_smooth_host.h"
 
 namespace mc {
@@ -202,6 +203,7 @@ int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_para
                                        const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_samples || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
+    if (int rc = distance_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) {
         set_error_detail("mc_mandelbrot_resolve_device_async: MC_MANDEL_SUPERSAMPLE_ADAPTIVE: this call resolves a FULL sample plane; the adaptive "
                          "render is mc_mandelbrot_render / mc_mandelbrot_render_rgba8 of a whole image");

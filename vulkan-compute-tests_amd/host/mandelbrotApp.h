@@ -24,7 +24,7 @@ struct MandelbrotApp : public ComputeApp {
         split(sx, params.scale_x_hi, params.scale_x_lo);
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
-    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_COLOUR_SMOOTH (main.cpp --colour)
+    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, _SMOOTH, _DISTANCE (main.cpp --colour)
     void setSupersample(uint32_t s) { params.flags |= MC_MANDEL_SUPERSAMPLE(s); }   // 2, 4 or 8 (main.cpp --supersample)
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
     // MC_PRECISION_PERTURB / _BLA / _BLA_DEEP: the view is this orbit's (the app owns it; for the BLA precisions main() has built the
@@ -75,6 +75,11 @@ struct MandelbrotApp : public ComputeApp {
             else check(mc_mandelbrot_render_rgba8(ctx, &params, rgba8.bytes()), "mc_mandelbrot_render_rgba8");
             return;
         }
+        if (!multi && (params.flags & MC_MANDEL_COLOUR_DISTANCE)) {   // the colours and D from one render (printDistanceShare reads D)
+            distance.resize((size_t)resx * resy);
+            check(mc_mandelbrot_render_distance(ctx, &params, buffer.data(), nullptr, nullptr, distance.data()), "mc_mandelbrot_render_distance");
+            return;
+        }
         if (multi) check(mc_multi_mandelbrot_render(multi, &params, buffer.data(), nullptr), "mc_multi_mandelbrot_render");
         else check(mc_mandelbrot_render(ctx, &params, buffer.data(), nullptr), "mc_mandelbrot_render");
     }
@@ -96,6 +101,19 @@ struct MandelbrotApp : public ComputeApp {
         uint64_t refined = 0, pixels = 0;
         check(mc_context_last_refined(ctx, &refined, &pixels), "mc_context_last_refined");
         printf("refined %llu of %llu pixels\n", (unsigned long long)refined, (unsigned long long)pixels);
+    }
+
+    // --colour distance: the share of pixels whose distance estimate is below one pixel, the ones the shading darkens.  D came with the
+    // colours where the storage buffer was rendered; the RGBA8 route (--gpu-postprocess) left none behind and renders the plane once more.
+    void printDistanceShare() {
+        if (distance.empty()) {
+            distance.resize((size_t)resx * resy);
+            check(mc_mandelbrot_render_distance(ctx, &params, nullptr, nullptr, nullptr, distance.data()), "mc_mandelbrot_render_distance");
+        }
+        uint64_t below = 0;
+        for (float d : distance) below += d < 1.0f ? 1u : 0u;
+        printf("distance below 1 pixel: %llu of %llu pixels (%.2f %%)\n", (unsigned long long)below, (unsigned long long)distance.size(),
+               100.0 * (double)below / (double)distance.size());
     }
 
 private:
@@ -124,6 +142,7 @@ private:
     uint32_t workgroupSize;
     mc_mandelbrot_params params;
     mc_mandelbrot_orbit* orbit = nullptr;
+    std::vector<float> distance;   // --colour distance: D of the last render
     std::function<std::string(mc_context*)> orbitFactory;
 };
 
