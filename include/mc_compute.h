@@ -36,7 +36,9 @@ extern "C" {
  * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined; then
  * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing; then MC_MANDEL_COLOUR_SMOOTH with mc_mandelbrot_render_smooth,
  * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour; then MC_MANDEL_COLOUR_DISTANCE with
- * mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour.
+ * mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour; then
+ * zoom sequences: mc_mandelbrot_zoom_ratio, mc_mandelbrot_zoom_compose, mc_mandelbrot_zoom_compose_device_async and mc_mandelbrot_zoom_create,
+ * _push, _frame and _destroy.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -585,6 +587,71 @@ int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_para
  * mc_context_last_refined: the refined pixels and the image's pixels of the context's last successful adaptive render; either pointer may
  * be NULL; MC_ERR_INVALID_ARGUMENT before the first such render. */
 int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels);
+
+/* ---- zoom sequences (the project's own addition: the reference renders one still; what tests/mandel_zoom_ref.py
+ *      restates).  A zoom renders one KEYFRAME per octave (the scale halves from one to the next, the centre stays) and composes every
+ *      frame in between from the two keyframes that bracket it: pure geometry in pixel units, one memory-bound kernel for all six
+ *      precisions and every colouring.
+ *  - inputs: two keyframes `wide` and `deep`, each W x H vec4 fp32 in storage rows, row-major, exactly what mc_mandelbrot_render writes;
+ *    `deep` shows the same centre at half the scale of `wide` and may be absent (NULL).  r, a double in [0.5, 1]: the frame's scale is r
+ *    times the wide keyframe's.
+ *  - per output pixel (gx, gy), in IEEE double, no contraction, source order:
+ *      X = (((double)gx - 0.5 * (double)W) * r) + 0.5 * (double)W;  Y the same with gy and H;
+ *      r2 = r + r;  X2, Y2 the same expression with r2.
+ *    source: the pixel reads `deep` at (X2, Y2) iff deep is present and 0 <= X2 <= W-1 and 0 <= Y2 <= H-1; otherwise `wide` at (X, Y).
+ *  - taps at (X, Y) of the chosen image: x0 = clamp((int64)floor(X), 0, W-1), x1 = min(x0 + 1, W-1), rows the same with y0, y1;
+ *    fx = (float)(X - (double)x0), fy likewise, converted round-to-nearest-even.  For W >= 2 the clamp of x0 never acts (X lies in
+ *    [0, W-1]); it exists for W = 1 or H = 1.
+ *  - value, per component in fp32, no contraction, a_yx the four taps, mix(a, b, f) = (f == 0.0f) ? a : a + ((b - a) * f):
+ *      top = mix(a00, a01, fx);  bot = mix(a10, a11, fx);  v = mix(top, bot, fy);  alpha is exactly 1.0f.
+ *    (The f == 0 case is what makes the identities below hold for EVERY input: the bare expression turns a -0.0f, which the distance
+ *    shading writes, into +0.0f, and an infinite tap into NaN.  Everywhere else it is the bare expression.)
+ *  - RGBA8 is mc_convert_rgba8's conversion (scale 255, no rotation) of that vec4.
+ *  - consequences: r = 1 with deep absent gives `wide` bit for bit (X = gx exactly, every weight 0); r = 0.5 gives `deep` bit
+ *    for bit on EVERY pixel (X2 = gx exactly); a linear ramp over the plane is reproduced to rounding.  On inputs in [0, 1] no component
+ *    exceeds 1.0, so the byte conversion cannot wrap.
+ *  - STATED LIMIT: the central region is `deep` minified by up to 2 x through one bilinear tap, which aliases; keyframes rendered with
+ *    MC_MANDEL_SUPERSAMPLE are the documented answer (a wider filter is a later step).  MC_MANDEL_COLOUR_EQUALISED ranks each keyframe by
+ *    itself, so the palette shifts between octaves (one map over a sequence: the by-hand histogram calls above).
+ *
+ * mc_mandelbrot_zoom_ratio (host only): r = exp2(-(double)step / (double)steps_per_octave); exactly 1.0 at step 0 and exactly 0.5 at
+ * step == steps_per_octave.  step > steps_per_octave or steps_per_octave == 0: MC_ERR_INVALID_ARGUMENT.  It exists so that an
+ * application, a binding and a test take r from ONE place: two exp2 need not agree in the last bit, and one bit of r changes fx.
+ * mc_mandelbrot_zoom_compose (host only, no device): the contract above on host buffers, the same source as the kernel.  At least one
+ * output must be given; a NULL wide, a zero size, or r outside [0.5, 1] or NaN: MC_ERR_INVALID_ARGUMENT, mc_last_error_detail saying which.
+ * mc_mandelbrot_zoom_compose_device_async: the stage by hand, on device pointers.  d_wide, d_deep and d_rgba_f32 are 16-byte aligned,
+ * d_rgba8 4-byte aligned; either output may be NULL, not both; an output that overlaps a keyframe or the other output is refused;
+ * asynchronous on `stream` (NULL: the context's).  The refusals above apply, all MC_ERR_INVALID_ARGUMENT.
+ *
+ * The sequence object.  mc_mandelbrot_zoom_create allocates two W x H vec4 slots on ctx's device (a failure: MC_ERR_OUT_OF_MEMORY); the
+ * context must outlive it.  mc_mandelbrot_zoom_push renders p into a slot: exactly what mc_mandelbrot_render(ctx, p, out_rgba_f32, NULL)
+ * would write, bit for bit, kept on the device with no host copy (the plain colouring renders straight into the slot; every other mode's
+ * chain ends in the context's scratch and is copied device to device).  p is a whole image of the sequence's size (row_begin = 0,
+ * row_end = height, no interleave, no MC_MANDEL_ITERS_U16: MC_ERR_INVALID_ARGUMENT otherwise) with any flag combination the blocking
+ * whole-image render accepts with colours (plain, equalised, smooth, distance, supersample, adaptive), in any precision - the three
+ * perturbation precisions use the context's bound orbit - and the precision may change from one keyframe to the next.  The blocking
+ * render's own refusals pass through unchanged.  The slots rotate: wide <- the previous keyframe, deep <- the new one.  From the second
+ * push on the keyframe's scale must be EXACTLY half the previous keyframe's on both axes: for F32 / DS / F64 the view words read as
+ * (double)hi + (double)lo, for the perturbation precisions the bound orbit's (scale_x, scale_y) * 2^scale_exp2, compared as (frexp
+ * mantissa, exponent) pairs so that deep orbits compare exactly; a mismatch is MC_ERR_INVALID_ARGUMENT with both scales in
+ * mc_last_error_detail, and the sequence is unchanged.  The CENTRE is the caller's responsibility: decimal text and float words cannot be
+ * compared exactly, so it is not compared.  A push that is refused (MC_ERR_INVALID_ARGUMENT,
+ * MC_ERR_UNSUPPORTED: its own refusals and the blocking render's) leaves the sequence as it was, with one keyframe held or two; after any
+ * other failure (a HIP error, out of memory) the newest keyframe alone is left.
+ * mc_mandelbrot_zoom_frame (blocking) composes the frame at r into either or both host outputs; with one keyframe pushed it composes from
+ * that keyframe alone (deep absent), with none it is MC_ERR_INVALID_ARGUMENT.  The RGBA8 form is written by the compose kernel itself: no
+ * vec4 frame is materialised.  Both calls fill mc_context_last_timing (push: copy_ms = 0) and use the context's scratch like any blocking
+ * call; neither disturbs a later render on the context.  mc_multi_* is not involved. */
+int mc_mandelbrot_zoom_ratio(uint32_t step, uint32_t steps_per_octave, double* r);
+int mc_mandelbrot_zoom_compose(uint32_t width, uint32_t height, const float* wide, const float* deep /* or NULL */, double r,
+                               float* out_rgba_f32 /* or NULL */, uint8_t* out_rgba8 /* or NULL */);
+int mc_mandelbrot_zoom_compose_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_wide, const void* d_deep,
+                                            double r, void* d_rgba_f32, void* d_rgba8, void* stream);
+typedef struct mc_mandelbrot_zoom mc_mandelbrot_zoom;
+int mc_mandelbrot_zoom_create(mc_context* ctx, uint32_t width, uint32_t height, mc_mandelbrot_zoom** out);
+int mc_mandelbrot_zoom_push(mc_mandelbrot_zoom* z, const mc_mandelbrot_params* p);
+int mc_mandelbrot_zoom_frame(mc_mandelbrot_zoom* z, double r, float* out_rgba_f32, uint8_t* out_rgba8);
+int mc_mandelbrot_zoom_destroy(mc_mandelbrot_zoom* z);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

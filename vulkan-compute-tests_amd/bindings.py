@@ -9,6 +9,7 @@ import fractions
 import math
 import os
 import re
+import weakref
 
 import numpy as np
 
@@ -174,6 +175,15 @@ def lib():
             L.mc_mandelbrot_distance_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, f32, vp, vp, vp]
             L.mc_mandelbrot_distance_plane.argtypes = [u32, u32, u32, vp, vp]
             L.mc_mandelbrot_distance_colour.argtypes = [u32, C.POINTER(f32), vp, vp, C.c_uint64, f32, vp]
+        if hasattr(L, "mc_mandelbrot_zoom_compose"):   # zoom sequences
+            dbl = C.c_double
+            L.mc_mandelbrot_zoom_ratio.argtypes = [u32, u32, C.POINTER(dbl)]
+            L.mc_mandelbrot_zoom_compose.argtypes = [u32, u32, vp, vp, dbl, vp, vp]
+            L.mc_mandelbrot_zoom_compose_device_async.argtypes = [vp, u32, u32, vp, vp, dbl, vp, vp, vp]
+            L.mc_mandelbrot_zoom_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+            L.mc_mandelbrot_zoom_push.argtypes = [vp, C.POINTER(MandelbrotParams)]
+            L.mc_mandelbrot_zoom_frame.argtypes = [vp, dbl, vp, vp]
+            L.mc_mandelbrot_zoom_destroy.argtypes = [vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -342,6 +352,37 @@ def distance_colour(max_iter, q, distance, threshold_px=1.0, k_color=(0.1, 0.7, 
     _check(lib().mc_mandelbrot_distance_colour(max_iter, k, _ptr(qa), _ptr(da), qa.size, threshold_px, _ptr(out)),
            "mc_mandelbrot_distance_colour")
     return out
+
+
+def zoom_ratio(step, steps_per_octave):
+    """mc_mandelbrot_zoom_ratio (host only): r = 2^(-step / steps_per_octave), exactly 1.0 and 0.5 at the ends.  The one place a frame's r
+    comes from: one bit of r changes a tap's weight."""
+    r = C.c_double(0.0)
+    _check(lib().mc_mandelbrot_zoom_ratio(int(step), int(steps_per_octave), C.byref(r)), "mc_mandelbrot_zoom_ratio")
+    return r.value
+
+
+def _keyframe(a, what):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"{what}: a keyframe is a float32 (H, W, 4) array")
+    return a
+
+
+def zoom_compose(wide, deep, r, want_rgba=True, want_rgba8=False):
+    """mc_mandelbrot_zoom_compose (host only): the frame whose scale is r times the keyframe wide's, composed from wide and deep (float32
+    (H, W, 4) each; deep shows half the scale, or None).  Returns (rgba float32 (H, W, 4), rgba8 uint8 (H, W, 4)), None where not wanted."""
+    w = _keyframe(wide, "zoom_compose")
+    d = None
+    if deep is not None:
+        d = _keyframe(deep, "zoom_compose")
+        if d.shape != w.shape:
+            raise ValueError("zoom_compose: the two keyframes have one shape")
+    H, W = w.shape[:2]
+    rgba = np.empty((H, W, 4), np.float32) if want_rgba else None
+    rgba8 = np.empty((H, W, 4), np.uint8) if want_rgba8 else None
+    _check(lib().mc_mandelbrot_zoom_compose(W, H, _ptr(w), _ptr(d), float(r), _ptr(rgba), _ptr(rgba8)), "mc_mandelbrot_zoom_compose")
+    return rgba, rgba8
 
 
 def pathtrace_params(width, height, spp, math_mode=PT_MATH_STRICT, sample_begin=0, sample_end=None, max_depth=12,
@@ -553,9 +594,15 @@ class Context:
         self._h = C.c_void_p()
         _check(lib().mc_context_create(device, C.byref(self._h)), "mc_context_create")
         self.device = device
+        self._zooms = []   # weak references to the Zoom objects made on this context: closed with it, before it
 
     def close(self):
         if self._h:
+            for ref in getattr(self, "_zooms", []):   # their device slots are freed while the context still exists
+                z = ref()
+                if z is not None:
+                    z.close()
+            self._zooms = []
             lib().mc_context_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -729,6 +776,16 @@ class Context:
         _check(lib().mc_mandelbrot_resolve_device_async(self._h, C.byref(p), d_samples or None, iters_bytes, _ptr(m), d_rgba or None,
                                                         stream or None), "mc_mandelbrot_resolve_device_async")
 
+    def zoom_compose_device(self, width, height, d_wide, d_deep, r, d_rgba=0, d_rgba8=0, stream=0):
+        """mc_mandelbrot_zoom_compose_device_async: the frame at r from the device keyframes d_wide and d_deep (0: absent) into the vec4
+        buffer d_rgba and / or the RGBA8 buffer d_rgba8."""
+        _check(lib().mc_mandelbrot_zoom_compose_device_async(self._h, width, height, d_wide or None, d_deep or None, float(r), d_rgba or None,
+                                                             d_rgba8 or None, stream or None), "mc_mandelbrot_zoom_compose_device_async")
+
+    def zoom(self, width, height):
+        """mc_mandelbrot_zoom_create: a zoom sequence of width x height frames on this context (a context manager)."""
+        return Zoom(self, width, height)
+
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:
             planes, spheres = default_scene()
@@ -805,6 +862,46 @@ class Context:
         """mc_hook_mandel_refine: the refine list of the W x H count plane at device pointer d_plane into d_list (device, W * H uint32), its
         length into d_count (device, one uint32).  Asynchronous on `stream`; the list's order is unspecified."""
         _check(test_lib().mc_hook_mandel_refine(self._h, d_plane, iters_bytes, width, height, d_list, d_count, stream), "mc_hook_mandel_refine")
+
+
+class Zoom:
+    """mc_mandelbrot_zoom: two keyframe slots on a context's device.  push(p) renders a keyframe (each at exactly half the previous one's
+    scale); frame(r) composes the frame whose scale is r times the wider held keyframe's (r from zoom_ratio).  Closing the context closes the zooms
+    made on it first."""
+
+    def __init__(self, ctx, width, height):
+        self._h = C.c_void_p()
+        self._ctx = ctx   # (kept alive: the slots are freed on its device)
+        self.width, self.height = int(width), int(height)
+        _check(lib().mc_mandelbrot_zoom_create(ctx._h, self.width, self.height, C.byref(self._h)), "mc_mandelbrot_zoom_create")
+        ctx._zooms = [r for r in ctx._zooms if r() is not None] + [weakref.ref(self)]
+
+    def push(self, p):
+        _check(lib().mc_mandelbrot_zoom_push(self._h, C.byref(p)), "mc_mandelbrot_zoom_push")
+
+    def frame(self, r, want_rgba=True, want_rgba8=False):
+        """(rgba float32 (H, W, 4), rgba8 uint8 (H, W, 4)), None where not wanted."""
+        rgba = np.empty((self.height, self.width, 4), np.float32) if want_rgba else None
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        _check(lib().mc_mandelbrot_zoom_frame(self._h, float(r), _ptr(rgba), _ptr(rgba8)), "mc_mandelbrot_zoom_frame")
+        return rgba, rgba8
+
+    def close(self):
+        if self._h:   # (the context is still open: Context.close closes its zooms before itself)
+            lib().mc_mandelbrot_zoom_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Multi:

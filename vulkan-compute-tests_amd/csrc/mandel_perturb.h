@@ -20,6 +20,9 @@ struct SmoothOut {
 };
 // mc_context_destroy: the context's bound orbit, if any, is freed.
 void perturb_release(mc_context* ctx);
+// The bound orbit's scale, (scale_x, scale_y) * 2^scale_exp2 as the orbit object holds it; false when no orbit is bound (the zoom
+// sequence compares successive keyframes' scales: api.hip).
+bool perturb_bound_scale(mc_context* ctx, double* scale_x, double* scale_y, int32_t* scale_exp2);
 
 // The deep kernel (mandel_perturb_deep.hip): orbits with min |scale| < 2^-960, or any orbit under MC_MANDEL_PERTURB_FORCE_DEEP.
 // perturb_launch builds the arguments (the dc table holds the scale's mantissas: u = ((double)g / (double)n - 0.5) * mantissa).

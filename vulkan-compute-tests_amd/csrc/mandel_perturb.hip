@@ -268,6 +268,15 @@ void perturb_release(mc_context* ctx) {
     });
 }
 
+bool perturb_bound_scale(mc_context* ctx, double* scale_x, double* scale_y, int32_t* scale_exp2) {
+    const Binding* b = g_bindings.find(ctx);
+    if (!b || !b->length) return false;
+    *scale_x = b->scale_x;
+    *scale_y = b->scale_y;
+    *scale_exp2 = b->scale_exp2;
+    return true;
+}
+
 }  // namespace mc
 
 extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o) {

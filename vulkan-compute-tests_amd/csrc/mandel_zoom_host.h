@@ -1,0 +1,19 @@
+// Mandelbrot zoom sequences, host side: the compose stage's launcher and the argument checks the entry points share (mandel_zoom.hip; the
+// sequence object is api.hip's, beside the blocking render whose chain it drives).  The arithmetic is in mandel_zoom.h.
+#pragma once
+#include <string>
+
+#include "mc_internal.h"
+
+namespace mc {
+
+// r of a frame: in [0.5, 1], not NaN.  who: the entry point's name for the refusal.
+int zoom_check_ratio(double r, const char* who);
+
+// mandel_zoom.hip: the frame at r from the W x H vec4 keyframes d_wide and d_deep (or null) into d_rgba_f32 (vec4) and / or d_rgba8
+// (4 bytes per pixel), on s.  Pointers are checked for alignment (16 bytes; d_rgba8: 4) and the outputs against every other buffer for
+// overlap.
+int mandelbrot_zoom_launch(mc_context* ctx, uint32_t W, uint32_t H, const void* d_wide, const void* d_deep, double r, void* d_rgba_f32,
+                           void* d_rgba8, const char* who, hipStream_t s);
+
+}  // namespace mc

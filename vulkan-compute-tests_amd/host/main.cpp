@@ -4,6 +4,8 @@
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
 // --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised|smooth|distance (equalised: histogram-equalised colouring of the whole image; smooth: fractional escape counts, no bands; distance: the smooth colour darkened where the boundary is closer than a pixel), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
+// --zoom K F (the Mandelbrot app: --centre / --scale is the DEEPEST of K + 1 keyframes one octave apart; K * F + 1 frames, each composed on
+// the device from the two keyframes that bracket it and written as <out>_%05u.<ext>),
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -44,6 +46,8 @@ int main(int argc, char* argv[]) {
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
     uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
+    int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
+    bool zoomSet = false;
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -112,6 +116,16 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--zoom") {   // a zoom sequence: K + 1 keyframes, K * F + 1 frames composed from them
+            need(2);
+            zoomK = atoi(argv[++i]);
+            zoomF = atoi(argv[++i]);
+            zoomSet = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--zoom: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -130,6 +144,12 @@ int main(int argc, char* argv[]) {
         else pos.push_back(argv[i]);
     }
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
+    if (zoomSet && (zoomK < 1 || zoomF < 1)) {
+        printf("usage: --zoom K F: K octaves (keyframes K + 1, the given view the deepest) of F frames each, both at least 1; got %d %d\n", zoomK, zoomF);
+        exit(EXIT_FAILURE);
+    }
+    if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
+    (void)zoomSet;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -155,6 +175,20 @@ int main(int argc, char* argv[]) {
         if (adaptive) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_ADAPTIVE);   // (whole-image calls as well: the save is never streamed)
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --supersample renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
+    }
+    if (zoomSet) {   // every frame is composed from keyframes rendered whole: never the banded, streamed save
+        if (streamedSave == ComputeApp::kStreamOn) printf("note: --zoom composes every frame from whole keyframes; --streamed-save has no effect\n");
+        streamedSave = ComputeApp::kStreamOff;
+        // (without --centre / --scale the still's view is the default params' float words: the same doubles here)
+        if (!viewSet) { cx = (double)-0.445f; cy = 0.0; sx = sy = (double)2.34f; }
+        // the widest keyframe's scale must be one a view can hold: the view words are floats (the perturbation precisions carry their
+        // scale in the orbit, whose constructor answers for it)
+        const bool orbitView = precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA || precision == MC_PRECISION_PERTURB_BLA_DEEP;
+        if (!orbitView && !(std::fabs(std::ldexp(sx, zoomK)) <= 3.0e38 && std::fabs(std::ldexp(sy, zoomK)) <= 3.0e38)) {
+            printf("--zoom %d %d: the first keyframe's scale, --scale x 2^%d, is beyond what a view holds (3e38)\n", zoomK, zoomF, zoomK);
+            return EXIT_FAILURE;
+        }
+        app.setZoom((uint32_t)zoomK, (uint32_t)zoomF, cx, cy, sx, sy, nullptr);
     }
     if (precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA ||
         precision == MC_PRECISION_PERTURB_BLA_DEEP) {                                    // the reference orbit, on the host: a malformed
@@ -184,7 +218,8 @@ int main(int argc, char* argv[]) {
         const bool onDevice = gpus <= 1 && (orbitWhere == kOrbitDevice ||
                                             (orbitWhere == kOrbitAuto && kOrbitAutoLimbs > 0 && lmin != 0.0L && (bits + 63) / 64 + 1 >= kOrbitAutoLimbs));
         // the orbit and its tables on ctx's device (or the host: ctx == nullptr); the message the run ends with, or "" after setOrbit()
-        auto makeOrbit = [=, &app](mc_context* ctx) -> std::string {
+        // shift: --zoom's keyframes, the scale's exponent raised by that much (0: the view itself)
+        auto makeOrbit = [=, &app](mc_context* ctx, int shift) -> std::string {
             auto message = [](const char* fmt, auto... args) {
                 char buf[8192];
                 snprintf(buf, sizeof buf, fmt, args...);
@@ -193,11 +228,15 @@ int main(int argc, char* argv[]) {
             mc_mandelbrot_orbit* made = nullptr;
             const auto t0 = std::chrono::steady_clock::now();
             int rc;
+            // (mantissa, exponent): exact at any depth and under any shift.  EVERY keyframe of a zoom takes this form, the last one
+            // (shift 0) too: mc_mandelbrot_zoom_push compares successive scales exactly, and the plain constructor's strtod of the text
+            // need not be the double this mantissa gives
+            const bool expForm = deepScale || zoomSet;
             if (ctx) {
-                if (deepScale) rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &made);
+                if (expForm) rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e + shift, maxIter, &made);
                 else rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, sx, sy, 0, maxIter, &made);
-            } else if (deepScale) {
-                rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e, maxIter, &made);
+            } else if (expForm) {
+                rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e + shift, maxIter, &made);
             } else {
                 rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &made);
             }
@@ -221,10 +260,13 @@ int main(int argc, char* argv[]) {
             app.setOrbit(made);   // bound to the context by init(), before the warm-up thread starts
             return std::string();
         };
-        if (onDevice) {
-            app.setOrbitFactory(makeOrbit);   // needs the context: made in init(), once it exists
+        if (zoomSet) {   // one orbit per keyframe, made by runZoom() as the keyframes come
+            app.setZoom((uint32_t)zoomK, (uint32_t)zoomF, cx, cy, sx, sy,
+                        [makeOrbit, onDevice](mc_context* c, int shift) { return makeOrbit(onDevice ? c : nullptr, shift); });
+        } else if (onDevice) {
+            app.setOrbitFactory([makeOrbit](mc_context* c) { return makeOrbit(c, 0); });   // needs the context: made in init(), once it exists
         } else {
-            const std::string err = makeOrbit(nullptr);
+            const std::string err = makeOrbit(nullptr, 0);
             if (!err.empty()) {
                 printf("%s\n", err.c_str());
                 return EXIT_FAILURE;
@@ -263,6 +305,17 @@ int main(int argc, char* argv[]) {
         const double initMs = since(tStart);
         app.preRun();
         printf("now running app!\n");
+#if defined(MANDELBROT_MODE)
+        if (zoomSet) {   // keyframes, frames and files in one pass (MandelbrotApp::runZoom)
+            app.runZoom(outFile ? outFile : "mandelbrot.png");
+            if (!fullTeardown) {
+                fflush(stdout);
+                fflush(stderr);
+                std::_Exit(EXIT_SUCCESS);
+            }
+            return EXIT_SUCCESS;
+        }
+#endif
         app.run();
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)

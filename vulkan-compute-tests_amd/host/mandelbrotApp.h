@@ -2,6 +2,9 @@
 #ifndef MANDELBROTAPP_H_
 #define MANDELBROTAPP_H_
 
+#include <chrono>
+#include <cmath>
+
 #include "computeApp.h"
 #include "pngWriter.h"
 
@@ -38,6 +41,14 @@ struct MandelbrotApp : public ComputeApp {
     // exists: contextCreated() calls the factory before the bind and before the warm-up helper starts.  It calls setOrbit(), or
     // returns the message the run ends with.
     void setOrbitFactory(std::function<std::string(mc_context*)> f) { orbitFactory = std::move(f); }
+    // --zoom K F: the view (cx, cy, sx, sy) is the DEEPEST of K + 1 keyframes, keyframe j at that scale x 2^(K - j).
+    // keyOrbit, for the perturbation precisions: makes keyframe j's orbit (the scale's exponent shifted by K - j) and hands it to
+    // setOrbit(), or returns the message the run ends with; runZoom() binds it.  The warm-up is skipped: no orbit is bound before the
+    // first keyframe, and every keyframe is a render of its own.
+    void setZoom(uint32_t K, uint32_t F, double cx, double cy, double sx, double sy, std::function<std::string(mc_context*, int)> keyOrbit) {
+        zoomK = K; zoomF = F; zoomCx = cx; zoomCy = cy; zoomSx = sx; zoomSy = sy;
+        zoomOrbit = std::move(keyOrbit);
+    }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
     MandelbrotApp(const MandelbrotApp&) = delete;
     MandelbrotApp& operator=(const MandelbrotApp&) = delete;
@@ -65,6 +76,7 @@ struct MandelbrotApp : public ComputeApp {
     }
 
     virtual std::function<int()> warmupCall() const override {   // tables + code object of that request (bit 1: the banded render's second stream)
+        if (zoomK) return [] { return (int)MC_OK; };
         return [ctx = ctx, q = request(), how = (gpuPostprocess ? 1 : 0) | (streaming() ? 2 : 0)] { return mc_context_warmup_mandelbrot(ctx, &q, how); };
     }
 
@@ -95,6 +107,69 @@ struct MandelbrotApp : public ComputeApp {
     }
 
     const HostStorage& storageBuffer() const { return buffer; }
+
+    // --zoom K F: K + 1 keyframes through mc_mandelbrot_zoom_push, K * F + 1 frames through mc_mandelbrot_zoom_frame, each saved as it
+    // arrives under `out` with _%05u before its extension.  Frame 0 is keyframe 0 (composed from it alone at r = 1); once keyframe j >= 1
+    // is pushed, frames (j - 1) F + 1 .. j F follow from keyframes j - 1 and j at r = mc_mandelbrot_zoom_ratio(1 .. F, F), the last of
+    // them (r = 0.5) being keyframe j bit for bit.  --gpu-postprocess takes the RGBA8 form: the compose kernel writes the bytes itself.
+    void runZoom(const char* out) {
+        using clock = std::chrono::steady_clock;
+        auto ms = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+        if (multi) throw std::runtime_error("--zoom: one GPU (the keyframes stay on the context's device)");
+        createCommandBuffer();
+        waitWarmup();
+        const auto tStart = clock::now();
+        mc_mandelbrot_zoom* z = nullptr;
+        check(mc_mandelbrot_zoom_create(ctx, resx, resy, &z), "mc_mandelbrot_zoom_create");
+        struct Guard { mc_mandelbrot_zoom* z; ~Guard() { mc_mandelbrot_zoom_destroy(z); } } guard{z};
+        const std::string name(out);
+        size_t dot = name.find_last_of('.');
+        const size_t slash = name.find_last_of('/');
+        if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) dot = name.size();
+        double keyMs = 0.0, composeMs = 0.0, saveMs = 0.0;
+        uint32_t frames = 0;
+        auto emit = [&](double r) {
+            auto t = clock::now();
+            check(mc_mandelbrot_zoom_frame(z, r, gpuPostprocess ? nullptr : buffer.data(), gpuPostprocess ? rgba8.bytes() : nullptr),
+                  "mc_mandelbrot_zoom_frame");
+            composeMs += ms(t);
+            char num[16];
+            snprintf(num, sizeof num, "_%05u", frames);
+            const std::string file = name.substr(0, dot) + num + name.substr(dot);
+            t = clock::now();
+            saveImage(file.c_str(), resx, resy, 255.0f, false, true);
+            saveMs += ms(t);
+            frames++;
+        };
+        for (uint32_t j = 0; j <= zoomK; j++) {
+            const int shift = (int)(zoomK - j);
+            const auto t = clock::now();
+            if (zoomOrbit) {
+                const std::string err = zoomOrbit(ctx, shift);
+                if (!err.empty()) throw std::runtime_error(err);
+                check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
+            } else {
+                setView(zoomCx, zoomCy, std::ldexp(zoomSx, shift), std::ldexp(zoomSy, shift));
+            }
+            check(mc_mandelbrot_zoom_push(z, &params), "mc_mandelbrot_zoom_push");
+            const double pushMs = ms(t);
+            keyMs += pushMs;
+            double kernel = 0.0;
+            (void)mc_context_last_timing(ctx, &kernel, nullptr);
+            printf("keyframe %u of %u: the view's scale x 2^%d, %.3f ms (kernels %.3f ms)\n", j, zoomK, shift, pushMs, kernel);
+            if (j == 0) {
+                emit(1.0);
+            } else {
+                for (uint32_t s = 1; s <= zoomF; s++) {
+                    double r = 0.0;
+                    check(mc_mandelbrot_zoom_ratio(s, zoomF, &r), "mc_mandelbrot_zoom_ratio");
+                    emit(r);
+                }
+            }
+        }
+        printf("zoom: %u keyframes in %.3f ms, %u frames composed in %.3f ms and saved in %.3f ms, %.3f ms in all\n", zoomK + 1, keyMs, frames,
+               composeMs, saveMs, ms(tStart));
+    }
 
     // --adaptive: how many pixels the last render sampled s x s (the share above which plain supersampling is the faster call: DESIGN.md §3.12)
     void printRefined() {
@@ -144,6 +219,9 @@ private:
     mc_mandelbrot_orbit* orbit = nullptr;
     std::vector<float> distance;   // --colour distance: D of the last render
     std::function<std::string(mc_context*)> orbitFactory;
+    uint32_t zoomK = 0, zoomF = 0;   // --zoom K F; 0: a still
+    double zoomCx = 0.0, zoomCy = 0.0, zoomSx = 0.0, zoomSy = 0.0;
+    std::function<std::string(mc_context*, int)> zoomOrbit;
 };
 
 #endif  // MANDELBROTAPP_H_
