@@ -743,6 +743,75 @@ int mc_mandelbrot_render_banded(mc_context* ctx, const mc_mandelbrot_params* p, 
 int mc_pathtrace_render_rgba8(mc_context* ctx, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes,
                               const float* spheres, uint32_t n_spheres, uint8_t* out_rgba8);
 
+/* ---- Path-tracer denoiser (no reference counterpart; additions within ABI 3) ------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over a vec4 plane, steered by two guide planes that hold
+ * what the CENTRE ray of each pixel hits.  Everything here is strict arithmetic whatever the render's math_mode: every operation one
+ * IEEE-754 fp32 operation in the order stated (no contraction, correctly rounded divide and square root), so that the host calls, the
+ * device kernels and tests/pt_denoise_ref.py agree bit for bit.  csrc/pt_denoise.h is the one source of both.
+ *
+ * THE GUIDES.  Per pixel (gx, gy) of a width x height image the camera ray of pathTracer.comp:352-362 with the sub-sample bracket
+ * (0.5 + vec2((samps.x/2)%2, samps.x%2) + tent) replaced by the constant 1.0:
+ *     sx = (((float)gx + 0.5f) / (float)width - 0.5f) * 0.036f;   sy = (((float)gy + 0.5f) / (float)height - 0.5f) * 0.024f;
+ *     spos = (cam.o + cx * sx) + cy * sy;   d = normalize(lc - spos);   ray (lc, d),
+ *   cam.o, cx, cy, lc as the shader forms them (:352-353, :360), dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, normalize(a) = a * (1 / sqrt(dot(a, a))).
+ *   intersect() of pathTracer.comp:112-131, 316-341 with the fp32 sphere test, planes then spheres in table order: the hit id and t are the
+ *   ones the strict path tracer finds for that ray.  x = lc + d * t;  n = the plane's equation.xyz, or normalize(x - centre) of a sphere;
+ *   nl = dot(n, d) < 0 ? n : -n (:390).
+ *     normal_t    = (nl.x, nl.y, nl.z, t)
+ *     position_id = (x.x, x.y, x.z, (float)id)      id: planes 0 .. n_planes-1, spheres n_planes + i
+ *   a miss writes (0, 0, 0, 1e20) and (0, 0, 0, -1).  Both planes are in STORAGE order, element (height - 1 - gy) * width + gx (:349), so
+ *   they line up with the render's buffer.  Any scene of up to 2^20 objects; either table may be empty.
+ *
+ * THE FILTER.  P = passes passes over W x H planes in storage coordinates, pass i = 0 .. P-1 with step s = 2^i reading the previous pass's
+ * plane (pass 0: rgba).  kc_i = (float)4^i / (sigma_colour * sigma_colour): the colour tolerance halves every pass.  For pixel p = (x, y):
+ *   - id_p = position_id[p].w < 0: out[p] = in[p], all four components.
+ *   - otherwise sw = sr = sg = sb = 0, and for the 25 taps in row-major order (b = -2 .. 2 outer, a = -2 .. 2 inner), q = (x + s*a, y + s*b):
+ *       skip q outside the image; skip q with id_q != id_p;
+ *       dc2 = (dr*dr + dg*dg) + db*db over in[q].rgb - in[p].rgb;  dn2 likewise over the normals;  dx2 likewise over the positions;
+ *       e = (dc2 * kc_i + dn2 * k_normal) + dx2 * k_position;   w = (h[b] * h[a]) * exp2(-e),  h = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *       sw = sw + w;  sr = sr + w * in[q].r;  sg and sb likewise;
+ *     out[p].rgb = (sr / sw, sg / sw, sb / sw);  out[p].w = in[p].w.  The centre tap has e = 0, so sw >= 9/64.
+ *   exp2 is the library's strict exp2 (the one behind the strict path tracer's pow): 0 below -125, else n = rint(y), f = y - n, a degree-6
+ *   polynomial in f by fma, times 2^n.
+ * sigma_colour is in units of the plane being filtered: the default, 128, suits the final buffer of a render (0 .. 255.5, gamma-encoded);
+ * a caller that filters a partial linear accumulator passes its own.
+ *
+ * mc_pathtrace_denoise_default_params: passes = 5, sigma_colour = 128, k_normal = 8, k_position = 4, flags = 0.
+ * mc_pathtrace_guides, mc_pathtrace_denoise: host only, no device, usable without a GPU, the same source as the kernels.  out may be rgba.
+ * mc_pathtrace_guides_device_async, mc_pathtrace_denoise_device_async: on device pointers (16-byte aligned vec4 planes), asynchronous on
+ *   `stream` (NULL: the context's); the scene tables are host pointers, copied to the device before the call returns.  Their scratch (the
+ *   scene records; two planes between the passes) is the context's, shared with the blocking calls: calls on one context follow one
+ *   another on one stream, as everywhere.  d_out may equal d_rgba; otherwise every input is left as it was, and an output that overlaps
+ *   an input in any other way is refused.
+ * mc_pathtrace_render_denoised (blocking): the render of p (any math_mode), the guides, the filter, and for out_rgba8 the conversion and
+ *   rotation of mc_pathtrace_render_rgba8 - that is, exactly the chain of the separate calls.  Exactly one of out_rgba_f32 (width*height*4
+ *   floats) and out_rgba8 (width*height*4 bytes) is non-NULL.  Whole images and whole renders only: row_begin = 0, row_end = height, no
+ *   interleave, sample_begin = 0, sample_end = spp (the filter runs on the final, encoded buffer: the last sample encodes in place, :453);
+ *   d->width and d->height equal p's.  mc_context_last_timing covers all of it; mc_context_warmup_pathtrace prepares its render as ever.
+ * Refused with MC_ERR_INVALID_ARGUMENT and a detail string: a NULL pointer, a zero size, passes outside 1 .. 8, a sigma_colour that is not
+ *   finite and above 0 (or whose fp32 square is not), a negative or non-finite k_normal or k_position, flags other than 0, a row tile or a
+ *   sample range in mc_pathtrace_render_denoised.  More than 2^20 objects: MC_ERR_UNSUPPORTED.
+ * STATED LIMITS: a mirror or glass first hit is guided by the sphere's own surface, so what is seen in it or through it is protected by
+ *   the colour weight alone.  mc_multi_* has no denoised form: gather the image, then filter it on one device. */
+typedef struct mc_pathtrace_denoise_params {
+    uint32_t width, height;
+    uint32_t passes;        /* 1..8 */
+    float sigma_colour;     /* > 0 */
+    float k_normal;         /* >= 0 */
+    float k_position;       /* >= 0 */
+    uint32_t flags;         /* 0 */
+} mc_pathtrace_denoise_params;
+int mc_pathtrace_denoise_default_params(uint32_t width, uint32_t height, mc_pathtrace_denoise_params* d);
+int mc_pathtrace_guides(uint32_t width, uint32_t height, const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres,
+                        float* out_normal_t, float* out_position_id);
+int mc_pathtrace_guides_device_async(mc_context* ctx, uint32_t width, uint32_t height, const float* planes, uint32_t n_planes,
+                                     const float* spheres, uint32_t n_spheres, void* d_normal_t, void* d_position_id, void* stream);
+int mc_pathtrace_denoise(const mc_pathtrace_denoise_params* d, const float* rgba, const float* normal_t, const float* position_id, float* out);
+int mc_pathtrace_denoise_device_async(mc_context* ctx, const mc_pathtrace_denoise_params* d, const void* d_rgba, const void* d_normal_t,
+                                      const void* d_position_id, void* d_out, void* stream);
+int mc_pathtrace_render_denoised(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_denoise_params* d, const float* planes,
+                                 uint32_t n_planes, const float* spheres, uint32_t n_spheres, float* out_rgba_f32, uint8_t* out_rgba8);
+
 /* ---- cold start (no reference counterpart: vkCreateComputePipelines compiles the shader inside preRun, vulkanComputeApp.cpp:589-643,
  *      before anything is timed; here the runtime loads a kernel family's code object on its first launch, 8 - 12 ms, and the first
  *      full-size launch would pay for it) -----------------------------------------------------------------------------------------

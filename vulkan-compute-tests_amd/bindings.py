@@ -75,6 +75,12 @@ class PathtraceParams(C.Structure):
                 ("math_mode", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class PathtraceDenoiseParams(C.Structure):
+    """mc_pathtrace_denoise_params (include/mc_compute.h): the a-trous filter's size, pass count and weights."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("sigma_colour", C.c_float),
+                ("k_normal", C.c_float), ("k_position", C.c_float), ("flags", C.c_uint32)]
+
+
 def declared_symbols():
     """Every function name include/mc_compute.h declares (used by the export test)."""
     text = open(HEADER_PATH).read()
@@ -184,6 +190,14 @@ def lib():
             L.mc_mandelbrot_zoom_push.argtypes = [vp, C.POINTER(MandelbrotParams)]
             L.mc_mandelbrot_zoom_frame.argtypes = [vp, dbl, vp, vp]
             L.mc_mandelbrot_zoom_destroy.argtypes = [vp]
+        if hasattr(L, "mc_pathtrace_denoise"):   # the path-tracer denoiser
+            dp = C.POINTER(PathtraceDenoiseParams)
+            L.mc_pathtrace_denoise_default_params.argtypes = [u32, u32, dp]
+            L.mc_pathtrace_guides.argtypes = [u32, u32, vp, u32, vp, u32, vp, vp]
+            L.mc_pathtrace_guides_device_async.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, vp, vp]
+            L.mc_pathtrace_denoise.argtypes = [dp, vp, vp, vp, vp]
+            L.mc_pathtrace_denoise_device_async.argtypes = [vp, dp, vp, vp, vp, vp, vp]
+            L.mc_pathtrace_render_denoised.argtypes = [vp, C.POINTER(PathtraceParams), dp, vp, u32, vp, u32, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -395,6 +409,51 @@ def pathtrace_params(width, height, spp, math_mode=PT_MATH_STRICT, sample_begin=
     p.row_block, p.row_stride = row_block, row_stride
     p.flags = flags
     return p
+
+
+def pathtrace_denoise_params(width, height, passes=None, sigma_colour=None, k_normal=None, k_position=None, flags=0):
+    """mc_pathtrace_denoise_default_params (passes 5, sigma_colour 128, k_normal 8, k_position 4), then the values given."""
+    d = PathtraceDenoiseParams()
+    _check(lib().mc_pathtrace_denoise_default_params(width, height, C.byref(d)), "mc_pathtrace_denoise_default_params")
+    if passes is not None:
+        d.passes = passes
+    if sigma_colour is not None:
+        d.sigma_colour = sigma_colour
+    if k_normal is not None:
+        d.k_normal = k_normal
+    if k_position is not None:
+        d.k_position = k_position
+    d.flags = flags
+    return d
+
+
+def _scene_tables(planes, spheres):
+    if planes is None or spheres is None:
+        planes, spheres = default_scene()
+    return np.ascontiguousarray(planes, np.float32).reshape(-1), np.ascontiguousarray(spheres, np.float32).reshape(-1)
+
+
+def pathtrace_guides(width, height, planes=None, spheres=None):
+    """mc_pathtrace_guides (host only): what the centre ray of each pixel hits, as two float32 (height, width, 4) planes in storage order:
+    normal_t = (nl, t) and position_id = (x, id); a miss is (0, 0, 0, 1e20) and (0, 0, 0, -1)."""
+    planes, spheres = _scene_tables(planes, spheres)
+    nt = np.empty((height, width, 4), np.float32)
+    pid = np.empty((height, width, 4), np.float32)
+    _check(lib().mc_pathtrace_guides(width, height, _ptr(planes), planes.size // 12, _ptr(spheres), spheres.size // 12, _ptr(nt), _ptr(pid)),
+           "mc_pathtrace_guides")
+    return nt, pid
+
+
+def pathtrace_denoise(d, rgba, normal_t, position_id):
+    """mc_pathtrace_denoise (host only): the a-trous filter of d over the float32 (height, width, 4) plane rgba, steered by the guide planes."""
+    shape = (d.height, d.width, 4)
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (rgba, normal_t, position_id)]
+    for a in arrs:
+        if a.shape != shape:
+            raise ValueError(f"pathtrace_denoise: every plane is float32 of shape {shape}, got {a.shape}")
+    out = np.empty(shape, np.float32)
+    _check(lib().mc_pathtrace_denoise(C.byref(d), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(out)), "mc_pathtrace_denoise")
+    return out
 
 
 def tile_rows(p):
@@ -785,6 +844,30 @@ class Context:
     def zoom(self, width, height):
         """mc_mandelbrot_zoom_create: a zoom sequence of width x height frames on this context (a context manager)."""
         return Zoom(self, width, height)
+
+    def pathtrace_guides_device(self, width, height, d_normal_t, d_position_id, planes=None, spheres=None, stream=0):
+        """mc_pathtrace_guides_device_async: the guide planes of a width x height image into two device vec4 planes."""
+        planes, spheres = _scene_tables(planes, spheres)
+        _check(lib().mc_pathtrace_guides_device_async(self._h, width, height, _ptr(planes), planes.size // 12, _ptr(spheres), spheres.size // 12,
+                                                      d_normal_t or None, d_position_id or None, stream or None),
+               "mc_pathtrace_guides_device_async")
+
+    def pathtrace_denoise_device(self, d, d_rgba, d_normal_t, d_position_id, d_out, stream=0):
+        """mc_pathtrace_denoise_device_async: the filter of d from the device plane d_rgba into d_out (which may be d_rgba)."""
+        _check(lib().mc_pathtrace_denoise_device_async(self._h, C.byref(d), d_rgba or None, d_normal_t or None, d_position_id or None,
+                                                       d_out or None, stream or None), "mc_pathtrace_denoise_device_async")
+
+    def pathtrace_denoised(self, p, d=None, planes=None, spheres=None, rgba8=False):
+        """mc_pathtrace_render_denoised: render, guides and filter in one blocking call.  Returns the float32 (height, width, 4) storage
+        buffer, or with rgba8 the uint8 image converted and rotated as mc_pathtrace_render_rgba8 does.  d: default parameters when None."""
+        planes, spheres = _scene_tables(planes, spheres)
+        if d is None:
+            d = pathtrace_denoise_params(p.width, p.height)
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        _check(lib().mc_pathtrace_render_denoised(self._h, C.byref(p), C.byref(d), _ptr(planes), planes.size // 12, _ptr(spheres),
+                                                  spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None),
+               "mc_pathtrace_render_denoised")
+        return out
 
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:

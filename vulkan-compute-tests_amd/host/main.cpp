@@ -48,6 +48,7 @@ int main(int argc, char* argv[]) {
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
+    uint32_t denoise = 0;               // --denoise [P]: the path tracer's a-trous filter with P passes (mc_pathtrace_render_denoised); 0 = off
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -126,6 +127,23 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--denoise" || a.rfind("--denoise=", 0) == 0) {   // render + guide planes + a-trous filter on the device
+            // P is optional (default 5): `--denoise=P`, or `--denoise P` where the next argument is a number (so the positional spp and
+            // resy go in front of a bare --denoise)
+            const char* v = nullptr;
+            if (a.size() > 9) v = argv[i] + 10;
+            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') v = argv[++i];
+            const int passes = v ? atoi(v) : 5;
+            if (passes < 1 || passes > 8 || (v && std::strspn(v, "0123456789") != std::strlen(v))) {
+                printf("--denoise %s: the pass count is 1 .. 8\n", v ? v : "");
+                exit(EXIT_FAILURE);
+            }
+            denoise = (uint32_t)passes;
+#if !defined(PATHTRACER_MODE)
+            printf("--denoise: a path tracer option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -149,7 +167,8 @@ int main(int argc, char* argv[]) {
         exit(EXIT_FAILURE);
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
-    (void)zoomSet;
+    if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
+    (void)zoomSet; (void)denoise;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -281,6 +300,7 @@ int main(int argc, char* argv[]) {
     app.setMathMode(mathMode);
     if (largeSpheres) app.useLargeSphereWalls();
     app.setSpherePrecision(spherePrec);
+    app.setDenoise(denoise);
 #endif
     app.setNumGpus(gpus);
     app.setQuiet(quiet);
@@ -321,6 +341,7 @@ int main(int argc, char* argv[]) {
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
 #endif
+        if (denoise) printf("denoise: %u passes, %.3f ms device time (render + guides + filter)\n", denoise, app.timing().kernelMs);
         auto t0 = std::chrono::steady_clock::now();
         if (outFile) app.saveRenderedImage(outFile);
         else app.saveRenderedImage();
@@ -334,10 +355,10 @@ int main(int argc, char* argv[]) {
             printf("{\"timing_ms\": {\"init\": %.3f, \"alloc\": %.3f, \"run\": %.3f, \"kernel\": %.3f, \"copy\": %.3f, \"convert\": %.3f, "
                    "\"png\": %.3f, \"total\": %.3f, \"warmup\": %.3f, \"warmup_wait\": %.3f, \"streamed_bands\": %d, "
                    "\"png_join\": %.3f, \"png_assemble\": %.3f, \"png_write\": %.3f}, "
-                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, "
+                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, \"denoise\": %u, "
                    "\"main_at_ms\": %.3f, \"end_at_ms\": %.3f}\n",
                    initMs, t.allocMs, t.runMs, t.kernelMs, t.copyMs, t.convertMs, t.pngMs, since(tStart), t.warmupMs,
-                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false",
+                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false", denoise,
                    // CLOCK_MONOTONIC at main()'s first timed statement and now: a parent that reads the same clock around the process
                    // gets what `total` cannot contain — loading + static initialisers before main(), teardown after it
                    std::chrono::duration<double, std::milli>(tStart.time_since_epoch()).count(),

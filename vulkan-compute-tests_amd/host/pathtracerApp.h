@@ -55,6 +55,9 @@ struct PathtracerApp : public ComputeApp {
         planes.assign(dummyPlane, dummyPlane + 12);
         spheres.swap(sp);
     }
+    // --denoise [P]: run() renders, makes the guide planes and filters on the device (mc_pathtrace_render_denoised) with the default
+    // weights and P passes; 0 = off, and then run() is what it was.  One GPU (main.cpp refuses --gpus above 1).
+    void setDenoise(uint32_t passes) { denoisePasses = passes; }
     void setScene(const float* pl, uint32_t np, const float* sp, uint32_t ns) {
         planes.assign(pl, pl + 12 * np);
         spheres.assign(sp, sp + 12 * ns);
@@ -91,6 +94,15 @@ struct PathtracerApp : public ComputeApp {
 
     virtual void runCommandBuffer() override {
         const uint32_t np = (uint32_t)planes.size() / 12, ns = (uint32_t)spheres.size() / 12;
+        if (denoisePasses) {   // both routes: the storage buffer, or (--gpu-postprocess) the RGBA8 image converted and rotated on the device
+            mc_pathtrace_denoise_params d;
+            mc_pathtrace_denoise_default_params(params.width, params.height, &d);
+            d.passes = denoisePasses;
+            check(mc_pathtrace_render_denoised(ctx, &params, &d, planes.data(), np, spheres.data(), ns, gpuPostprocess ? nullptr : buffer.data(),
+                                               gpuPostprocess ? rgba8.bytes() : nullptr),
+                  "mc_pathtrace_render_denoised");
+            return;
+        }
         if (gpuPostprocess) {   // render + float->u8 + 180-degree rotation on the device (pathtracerApp.h:202-243), 4 B/pixel copied
             if (multi) check(mc_multi_pathtrace_render_rgba8(multi, &params, planes.data(), np, spheres.data(), ns, rgba8.bytes()),
                              "mc_multi_pathtrace_render_rgba8");
@@ -123,6 +135,7 @@ private:
     int32_t spp;
     uint32_t workgroupSize;
     mc_pathtrace_params params;
+    uint32_t denoisePasses = 0;
     std::vector<float> planes, spheres;
 };
 
