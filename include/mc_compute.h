@@ -812,6 +812,51 @@ int mc_pathtrace_denoise_device_async(mc_context* ctx, const mc_pathtrace_denois
 int mc_pathtrace_render_denoised(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_denoise_params* d, const float* planes,
                                  uint32_t n_planes, const float* spheres, uint32_t n_spheres, float* out_rgba_f32, uint8_t* out_rgba8);
 
+/* ---- Path tracer through a bounding-volume hierarchy over the spheres (no reference counterpart; additions within ABI 3; DESIGN.md
+ *      section 3.18) ---------------------------------------------------------------------------------------------------------------
+ * The plain calls test every object for every ray, as the shader's loop does (pathTracer.comp:112-131).  An mc_pathtrace_accel holds a
+ * scene's tables and a tree over its spheres; the calls below render through it and return WHAT THE PLAIN CALLS RETURN: in
+ * MC_PT_MATH_STRICT the same bits as mc_pathtrace_render, hence as the oracle.  A sphere's hit parameter depends on the ray and that sphere
+ * alone, so the loop returns the smallest one, ties to the lowest table index, planes before spheres; the walk visits a subset of the spheres,
+ * breaks ties by index, and skips a node only where no sphere in it can pass the fp32 test below the parameter held (csrc/pt_bvh.h has the
+ * proof: boxes grown per ray and per node by eta_ray * (an upper bound of |c - o| + |r|), eta_ray = 1.01 (sqrt(2e-6 + 1.3 | |d|^2 - 1 |) + 1e-6),
+ * at most 2^-9 for | |d|^2 - 1 | <= 2^-20; a direction with | |d|^2 - 1 | > 0.01 or a NaN culls nothing).  Planes stay a linear list tested
+ * first; a sphere whose box cannot be formed (a centre or radius that is not finite, an edge that overflows) stays on a second linear list.
+ *
+ * mc_pathtrace_accel_create / _destroy / _info / _copy / _intersect: host only, no device, usable without a GPU.  create copies the tables
+ *   (12 floats per object, as mc_pathtrace_render takes them); the build is deterministic — the same tables give the same bytes (_copy
+ *   writes them: nodes, leaf spheres, leaf indices, the unboxed list; mc_pathtrace_accel_stats.bytes in all).  destroy(NULL) is MC_OK.
+ * mc_pathtrace_accel_intersect: intersect() for n_rays rays (origins, dirs: 3 floats each; out_id: -1 or planes 0 .. n_planes-1, spheres
+ *   n_planes + i; out_t: the parameter, 1e20-or-above for a miss as the loop leaves it) by the SAME source the kernels run.
+ * mc_pathtrace_render_accel, _render_accel_device_async, _render_accel_rgba8: as mc_pathtrace_render, _render_device_async and
+ *   _render_rgba8 with the object in place of the tables: sample ranges, row tiles and interleaved row blocks are honoured and compose bit
+ *   for bit (strict) with one another and with the plain calls' parts.  MC_PT_MATH_STRICT runs the strict tier; MC_PT_MATH_FAST and
+ *   MC_PT_MATH_FAST_CAREFUL both run the careful tier, and mc_pathtrace_accel_select_kernel reports it (kernel = MC_PT_KERNEL_BVH).
+ *   The device copy of an object is made once per (object, context), on first use, and freed by mc_pathtrace_accel_destroy or by
+ *   mc_context_destroy of that context, whichever comes first (mc_pathtrace_accel_stats.device_copies counts them).
+ * Refused with a detail string: a NULL pointer, an object that is not live (destroyed), an empty image / row range / sample range, flags
+ *   other than 0 (MC_ERR_INVALID_ARGUMENT); more than 2^20 objects, MC_PT_PRECISION(x) with x != MC_PT_PREC_F32 — named in the detail —
+ *   (MC_ERR_UNSUPPORTED).  The automatic choice of mc_pathtrace_render* is unchanged: it never selects this kernel. */
+typedef struct mc_pathtrace_accel mc_pathtrace_accel;
+typedef struct mc_pathtrace_accel_stats {
+    uint32_t n_planes, n_spheres; /* the tables' sizes; n_planes is the length of the first linear list                       */
+    uint32_t nodes, depth, leaves; /* of the tree (depth: nodes on the longest root-to-leaf path; 0, 0, 0 without boxed spheres) */
+    uint32_t boxed;               /* spheres in the tree                                                                      */
+    uint32_t unboxed;             /* spheres on the second linear list                                                        */
+    uint32_t device_copies;       /* contexts holding a device copy at the moment                                            */
+    uint64_t bytes;               /* of the structure: 32 per node, 20 per boxed sphere, 4 per unboxed sphere                 */
+} mc_pathtrace_accel_stats;
+int mc_pathtrace_accel_create(const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres, mc_pathtrace_accel** out);
+int mc_pathtrace_accel_destroy(mc_pathtrace_accel* a);
+int mc_pathtrace_accel_info(const mc_pathtrace_accel* a, mc_pathtrace_accel_stats* out);
+int mc_pathtrace_accel_copy(const mc_pathtrace_accel* a, void* out_bytes, uint64_t capacity);
+int mc_pathtrace_accel_intersect(const mc_pathtrace_accel* a, uint64_t n_rays, const float* origins, const float* dirs, int32_t* out_id,
+                                 float* out_t);
+int mc_pathtrace_render_accel(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, float* out_rgba_f32);
+int mc_pathtrace_render_accel_device_async(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, void* d_rgba_f32,
+                                           void* stream);
+int mc_pathtrace_render_accel_rgba8(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, uint8_t* out_rgba8);
+
 /* ---- cold start (no reference counterpart: vkCreateComputePipelines compiles the shader inside preRun, vulkanComputeApp.cpp:589-643,
  *      before anything is timed; here the runtime loads a kernel family's code object on its first launch, 8 - 12 ms, and the first
  *      full-size launch would pay for it) -----------------------------------------------------------------------------------------
@@ -869,7 +914,8 @@ enum {
     MC_PT_KERNEL_SLAB = 1,           /* 6 axis-aligned planes + 3 spheres, round-synchronous                                 */
     MC_PT_KERNEL_BOX = 3,            /* closed-box scene facts at compile time, round-synchronous (fast math)                */
     MC_PT_KERNEL_POOL = 4,           /* the sample-pool kernel (the default for the reference scene, both math modes)        */
-    MC_PT_KERNEL_GENERIC_MEMORY = 5  /* any scene, records read from memory (large scenes)                                   */
+    MC_PT_KERNEL_GENERIC_MEMORY = 5, /* any scene, records read from memory (large scenes)                                   */
+    MC_PT_KERNEL_BVH = 6             /* mc_pathtrace_render_accel*: spheres through a BVH, records read from memory; never automatic */
 };
 typedef struct mc_pathtrace_kernel_info {
     uint32_t kernel;          /* MC_PT_KERNEL_*                                                                             */
@@ -880,6 +926,8 @@ typedef struct mc_pathtrace_kernel_info {
 } mc_pathtrace_kernel_info;
 int mc_pathtrace_select_kernel(const mc_pathtrace_params* p, const float* planes, uint32_t n_planes, const float* spheres,
                                uint32_t n_spheres, mc_pathtrace_kernel_info* out);
+/* The same for mc_pathtrace_render_accel*: kernel = MC_PT_KERNEL_BVH, the width, the tier that runs, the launches.  Validates like them. */
+int mc_pathtrace_accel_select_kernel(const mc_pathtrace_accel* a, const mc_pathtrace_params* p, mc_pathtrace_kernel_info* out);
 
 /* ---- stream / tiling helpers ------------------------------------------------------------------ */
 int mc_context_synchronize(mc_context* ctx);

@@ -75,6 +75,16 @@ class PathtraceParams(C.Structure):
                 ("math_mode", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class PathtraceKernelInfo(C.Structure):
+    _fields_ = [("kernel", C.c_uint32), ("lanes_per_pixel", C.c_uint32), ("math_mode", C.c_uint32), ("launches", C.c_uint32)]
+
+
+class PathtraceAccelStats(C.Structure):
+    """mc_pathtrace_accel_stats (include/mc_compute.h): the shape of an mc_pathtrace_accel's tree and its two linear lists."""
+    _fields_ = [("n_planes", C.c_uint32), ("n_spheres", C.c_uint32), ("nodes", C.c_uint32), ("depth", C.c_uint32), ("leaves", C.c_uint32),
+                ("boxed", C.c_uint32), ("unboxed", C.c_uint32), ("device_copies", C.c_uint32), ("bytes", C.c_uint64)]
+
+
 class PathtraceDenoiseParams(C.Structure):
     """mc_pathtrace_denoise_params (include/mc_compute.h): the a-trous filter's size, pass count and weights."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("sigma_colour", C.c_float),
@@ -198,6 +208,17 @@ def lib():
             L.mc_pathtrace_denoise.argtypes = [dp, vp, vp, vp, vp]
             L.mc_pathtrace_denoise_device_async.argtypes = [vp, dp, vp, vp, vp, vp, vp]
             L.mc_pathtrace_render_denoised.argtypes = [vp, C.POINTER(PathtraceParams), dp, vp, u32, vp, u32, vp, vp]
+        if hasattr(L, "mc_pathtrace_accel_create"):   # the path tracer through a sphere BVH
+            pp, u64 = C.POINTER(PathtraceParams), C.c_uint64
+            L.mc_pathtrace_accel_create.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
+            L.mc_pathtrace_accel_destroy.argtypes = [vp]
+            L.mc_pathtrace_accel_info.argtypes = [vp, C.POINTER(PathtraceAccelStats)]
+            L.mc_pathtrace_accel_copy.argtypes = [vp, vp, u64]
+            L.mc_pathtrace_accel_intersect.argtypes = [vp, u64, vp, vp, vp, vp]
+            L.mc_pathtrace_accel_select_kernel.argtypes = [vp, pp, C.POINTER(PathtraceKernelInfo)]
+            L.mc_pathtrace_render_accel.argtypes = [vp, vp, pp, vp]
+            L.mc_pathtrace_render_accel_device_async.argtypes = [vp, vp, pp, vp, vp]
+            L.mc_pathtrace_render_accel_rgba8.argtypes = [vp, vp, pp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -463,11 +484,8 @@ def tile_rows(p):
 PT_SCENE_SLAB, PT_SCENE_LIGHTS_INSIDE, PT_SCENE_SPHERES_DISJOINT, PT_SCENE_LIGHT_ENCLOSED, PT_SCENE_MANY_SPHERES = 1, 2, 4, 8, 16
 PT_SCENE_SPECULAR = 32
 PT_KERNEL_GENERIC, PT_KERNEL_SLAB, PT_KERNEL_BOX, PT_KERNEL_POOL, PT_KERNEL_GENERIC_MEMORY = 0, 1, 3, 4, 5
-PT_KERNEL_NAMES = {0: "generic", 1: "slab", 3: "box", 4: "pool", 5: "generic_memory"}
-
-
-class PathtraceKernelInfo(C.Structure):
-    _fields_ = [("kernel", C.c_uint32), ("lanes_per_pixel", C.c_uint32), ("math_mode", C.c_uint32), ("launches", C.c_uint32)]
+PT_KERNEL_BVH = 6
+PT_KERNEL_NAMES = {0: "generic", 1: "slab", 3: "box", 4: "pool", 5: "generic_memory", 6: "bvh"}
 
 
 def pathtrace_select_kernel(p, planes=None, spheres=None):
@@ -481,6 +499,65 @@ def pathtrace_select_kernel(p, planes=None, spheres=None):
     fn.argtypes = [C.POINTER(PathtraceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(PathtraceKernelInfo)]
     _check(fn(C.byref(p), _ptr(planes), planes.shape[0], _ptr(spheres), spheres.shape[0], C.byref(out)), "mc_pathtrace_select_kernel")
     return out
+
+
+class PathtraceAccel:
+    """mc_pathtrace_accel: a scene's tables and the BVH over its spheres (host only: no device is needed to make or query one).
+    Context.pathtrace_accel / pathtrace_accel_device / pathtrace_accel_rgba8 render through it."""
+
+    def __init__(self, planes=None, spheres=None):
+        self._h = C.c_void_p()
+        if planes is None or spheres is None:
+            planes, spheres = default_scene()
+        planes = np.ascontiguousarray(planes, np.float32).reshape(-1)
+        spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1)
+        self.n_planes, self.n_spheres = planes.size // 12, spheres.size // 12
+        _check(lib().mc_pathtrace_accel_create(_ptr(planes), self.n_planes, _ptr(spheres), self.n_spheres, C.byref(self._h)),
+               "mc_pathtrace_accel_create")
+
+    def info(self):
+        st = PathtraceAccelStats()
+        _check(lib().mc_pathtrace_accel_info(self._h, C.byref(st)), "mc_pathtrace_accel_info")
+        return {name: int(getattr(st, name)) for name, _ in PathtraceAccelStats._fields_}
+
+    def bytes(self):
+        """The structure's bytes (nodes, leaf spheres, leaf indices, unboxed list): equal for equal tables."""
+        out = np.zeros(self.info()["bytes"], np.uint8)
+        _check(lib().mc_pathtrace_accel_copy(self._h, _ptr(out), out.size), "mc_pathtrace_accel_copy")
+        return out
+
+    def intersect(self, origins, dirs):
+        """mc_pathtrace_accel_intersect: (id, t) per ray, id int32 (-1: miss), t float32; origins and dirs are (n, 3) float32."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("PathtraceAccel.intersect: origins and dirs must have the same shape")
+        ids = np.empty(o.shape[0], np.int32)
+        t = np.empty(o.shape[0], np.float32)
+        _check(lib().mc_pathtrace_accel_intersect(self._h, o.shape[0], _ptr(o), _ptr(d), _ptr(ids), _ptr(t)), "mc_pathtrace_accel_intersect")
+        return ids, t
+
+    def select_kernel(self, p):
+        out = PathtraceKernelInfo()
+        _check(lib().mc_pathtrace_accel_select_kernel(self._h, C.byref(p), C.byref(out)), "mc_pathtrace_accel_select_kernel")
+        return out
+
+    def close(self):
+        if self._h:
+            _check(lib().mc_pathtrace_accel_destroy(self._h), "mc_pathtrace_accel_destroy")
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def build_id():
@@ -868,6 +945,22 @@ class Context:
                                                   spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None),
                "mc_pathtrace_render_denoised")
         return out
+
+    def pathtrace_accel(self, accel, p, acc=None):
+        """mc_pathtrace_render_accel: Context.pathtrace through a PathtraceAccel (acc: the accumulator a sample range continues)."""
+        rows = tile_rows(p)
+        out = np.zeros((rows, p.width, 4), np.float32) if acc is None else np.ascontiguousarray(acc, np.float32).copy()
+        _check(lib().mc_pathtrace_render_accel(self._h, accel._h, C.byref(p), _ptr(out)), "mc_pathtrace_render_accel")
+        return out
+
+    def pathtrace_accel_rgba8(self, accel, p):
+        out = np.empty((p.height, p.width, 4), np.uint8)
+        _check(lib().mc_pathtrace_render_accel_rgba8(self._h, accel._h, C.byref(p), _ptr(out)), "mc_pathtrace_render_accel_rgba8")
+        return out
+
+    def pathtrace_accel_device(self, accel, p, d_rgba, stream=0):
+        _check(lib().mc_pathtrace_render_accel_device_async(self._h, accel._h, C.byref(p), d_rgba or None, stream or None),
+               "mc_pathtrace_render_accel_device_async")
 
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:

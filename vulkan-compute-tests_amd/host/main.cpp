@@ -58,6 +58,8 @@ int main(int argc, char* argv[]) {
     const char* syText = "2.34";
     bool viewSet = false, largeSpheres = false;
     uint32_t spherePrec = MC_PT_PREC_F32;
+    const char* sceneFile = nullptr;    // --scene FILE: the path tracer's tables from a text file, one `plane` or `sphere` and 12 floats per line
+    uint32_t accel = 0;                 // --accel linear | bvh: the plain calls (every ray tests every object) or mc_pathtrace_render_accel*
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](int n) { if (i + n >= argc) { printf("missing value for %s\n", a.c_str()); exit(EXIT_FAILURE); } };
@@ -158,6 +160,8 @@ int main(int argc, char* argv[]) {
             need(1);
             spherePrec = choice(argv[++i], {{"f32", MC_PT_PREC_F32}, {"fp64", MC_PT_PREC_FP64}, {"ds", MC_PT_PREC_DS}, {"df64", MC_PT_PREC_DF64}});
         }
+        else if (a == "--scene") { need(1); sceneFile = argv[++i]; }
+        else if (a == "--accel") { need(1); accel = choice(argv[++i], {{"linear", 0u}, {"bvh", 1u}}); }
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { printf("unknown option %s\n", a.c_str()); exit(EXIT_FAILURE); }
         else pos.push_back(argv[i]);
     }
@@ -168,7 +172,12 @@ int main(int argc, char* argv[]) {
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
     if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
-    (void)zoomSet; (void)denoise;
+    if (accel && (gpus > 1 || denoise)) { printf("--accel bvh: one GPU, and not with --denoise (the accelerated calls have no multi-GPU or denoised form)\n"); exit(EXIT_FAILURE); }
+    if (accel && spherePrec != MC_PT_PREC_F32) { printf("--accel bvh: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
+#if !defined(PATHTRACER_MODE)
+    if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
+#endif
+    (void)zoomSet; (void)denoise; (void)sceneFile; (void)accel;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -301,6 +310,14 @@ int main(int argc, char* argv[]) {
     if (largeSpheres) app.useLargeSphereWalls();
     app.setSpherePrecision(spherePrec);
     app.setDenoise(denoise);
+    if (sceneFile) {   // read and checked here, before a device is touched
+        const std::string err = app.loadScene(sceneFile);
+        if (!err.empty()) { printf("--scene %s: %s\n", sceneFile, err.c_str()); return EXIT_FAILURE; }
+    }
+    if (accel) {       // the BVH is built on the host, here
+        const std::string err = app.useAccel();
+        if (!err.empty()) { printf("--accel bvh: %s\n", err.c_str()); return EXIT_FAILURE; }
+    }
 #endif
     app.setNumGpus(gpus);
     app.setQuiet(quiet);
@@ -355,10 +372,10 @@ int main(int argc, char* argv[]) {
             printf("{\"timing_ms\": {\"init\": %.3f, \"alloc\": %.3f, \"run\": %.3f, \"kernel\": %.3f, \"copy\": %.3f, \"convert\": %.3f, "
                    "\"png\": %.3f, \"total\": %.3f, \"warmup\": %.3f, \"warmup_wait\": %.3f, \"streamed_bands\": %d, "
                    "\"png_join\": %.3f, \"png_assemble\": %.3f, \"png_write\": %.3f}, "
-                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, \"denoise\": %u, "
+                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, \"denoise\": %u, \"accel\": \"%s\", "
                    "\"main_at_ms\": %.3f, \"end_at_ms\": %.3f}\n",
                    initMs, t.allocMs, t.runMs, t.kernelMs, t.copyMs, t.convertMs, t.pngMs, since(tStart), t.warmupMs,
-                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false", denoise,
+                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false", denoise, accel ? "bvh" : "linear",
                    // CLOCK_MONOTONIC at main()'s first timed statement and now: a parent that reads the same clock around the process
                    // gets what `total` cannot contain — loading + static initialisers before main(), teardown after it
                    std::chrono::duration<double, std::milli>(tStart.time_since_epoch()).count(),

@@ -2,7 +2,9 @@
 #ifndef PATHTRACERAPP_H_
 #define PATHTRACERAPP_H_
 
+#include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "computeApp.h"
 #include "pngWriter.h"
@@ -63,6 +65,50 @@ struct PathtracerApp : public ComputeApp {
         spheres.assign(sp, sp + 12 * ns);
     }
 
+    // --scene FILE: a text file, one object per line, `plane` or `sphere` followed by the record's 12 floats (equation.xyzw or
+    // centre.xyz radius | emission.xyz 0 | colour.rgb material); blank lines and lines starting with # are skipped.  Returns "" or what is wrong.
+    std::string loadScene(const char* path) {
+        FILE* f = std::fopen(path, "r");
+        if (!f) return "cannot open the file";
+        std::vector<float> pl, sp;
+        char line[1024];
+        int lineNo = 0;
+        std::string err;
+        while (err.empty() && std::fgets(line, sizeof line, f)) {
+            lineNo++;
+            char kind[16] = {0};
+            float v[12];
+            int used = 0;
+            if (std::sscanf(line, " %15s%n", kind, &used) != 1 || kind[0] == '#') continue;
+            const bool plane = std::strcmp(kind, "plane") == 0;
+            if (!plane && std::strcmp(kind, "sphere") != 0) { err = "line " + std::to_string(lineNo) + ": neither `plane` nor `sphere`"; break; }
+            const char* at = line + used;
+            int k = 0;
+            for (; k < 12; k++) {
+                char* end = nullptr;
+                v[k] = std::strtof(at, &end);
+                if (end == at) break;
+                at = end;
+            }
+            while (*at == ' ' || *at == '\t' || *at == '\r' || *at == '\n') at++;
+            if (k != 12 || *at) { err = "line " + std::to_string(lineNo) + ": 12 numbers expected after `" + kind + "`"; break; }
+            (plane ? pl : sp).insert((plane ? pl : sp).end(), v, v + 12);
+        }
+        std::fclose(f);
+        if (!err.empty()) return err;
+        if ((pl.size() + sp.size()) / 12 > (1u << 20)) return "more than 2^20 objects";
+        planes.swap(pl);
+        spheres.swap(sp);
+        return "";
+    }
+    // --accel bvh: run() renders through mc_pathtrace_render_accel* (one GPU, no --denoise: main.cpp refuses those).  The tree is built
+    // here, on the host.  Returns "" or the library's refusal.
+    std::string useAccel() {
+        const int rc = mc_pathtrace_accel_create(planes.data(), (uint32_t)planes.size() / 12, spheres.data(), (uint32_t)spheres.size() / 12, &accel);
+        if (rc != MC_OK) return std::string(mc_error_string(rc)) + " (" + mc_last_error_detail() + ")";
+        return "";
+    }
+
     virtual void preRun() override {
         if (!quiet) { printf(" * before createBuffer()\n"); fflush(stdout); }
         createBuffer(bufferSize);   // output buffer; the two scene SSBOs of the reference (pathtracerApp.h:129-198)
@@ -86,6 +132,7 @@ struct PathtracerApp : public ComputeApp {
     }
 
     virtual std::function<int()> warmupCall() const override {   // what run() is going to ask for (the setters were called before init())
+        if (accel) return [] { return (int)MC_OK; };   // (the plain calls' warm-up would load the linear kernels and upload the tables for nothing)
         return [ctx = ctx, q = request(), planes = planes, spheres = spheres, rgba8 = gpuPostprocess ? 1 : 0] {
             return mc_context_warmup_pathtrace(ctx, &q, planes.data(), (uint32_t)planes.size() / 12, spheres.data(),
                                                (uint32_t)spheres.size() / 12, rgba8);
@@ -94,6 +141,11 @@ struct PathtracerApp : public ComputeApp {
 
     virtual void runCommandBuffer() override {
         const uint32_t np = (uint32_t)planes.size() / 12, ns = (uint32_t)spheres.size() / 12;
+        if (accel) {
+            if (gpuPostprocess) check(mc_pathtrace_render_accel_rgba8(ctx, accel, &params, rgba8.bytes()), "mc_pathtrace_render_accel_rgba8");
+            else check(mc_pathtrace_render_accel(ctx, accel, &params, buffer.data()), "mc_pathtrace_render_accel");
+            return;
+        }
         if (denoisePasses) {   // both routes: the storage buffer, or (--gpu-postprocess) the RGBA8 image converted and rotated on the device
             mc_pathtrace_denoise_params d;
             mc_pathtrace_denoise_default_params(params.width, params.height, &d);
@@ -136,6 +188,7 @@ private:
     uint32_t workgroupSize;
     mc_pathtrace_params params;
     uint32_t denoisePasses = 0;
+    mc_pathtrace_accel* accel = nullptr;   // --accel bvh (lives as long as the process: the app leaves through _Exit or its destructor-free end)
     std::vector<float> planes, spheres;
 };
 
