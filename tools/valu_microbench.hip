@@ -5,6 +5,8 @@
 //   valu_microbench opcodes   every transcendental opcode, f32 and f16, alone and in a mix (profiles/r04_valu_microbench8.txt)
 //   valu_microbench fp64      the fp64 rows of "classes": v_add/mul/fma_f64, v_cmp_gt_f64 — the issue cost and the fp64 peak of the
 //                             MC_PRECISION_F64 Mandelbrot kernel (profiles/f64_valu_microbench.txt)
+//   valu_microbench prio      a group of transcendentals issued at raised wave priority (s_setprio) against the same group at equal
+//                             priority (profiles/valu_microbench_prio.txt)
 // These are the measurements the path tracer's design rests on: add / mul / fmac / mov / logic issue in ~2.3 cycles
 // per wave64 instruction per SIMD, compare / select / min / max / convert / three-operand integer in ~4.2 alone but ~2.4 in a mix,
 // transcendentals in ~8.2 wherever they stand.  Each mode is the former file's code, unchanged, in a namespace of its own.
@@ -526,13 +528,119 @@ static int run() {
 #undef T_cvt
 #undef E
 
+// ======================================================================================================================
+// mode "prio" — does a wave that raises its priority get its transcendentals issued back to back?
+// "among" found that a transcendental among other instructions costs 11.5-12.7 cycles against 8.1 in a stream of its own, and that
+// putting a wave's four transcendentals next to each other changes nothing — but there six waves of EQUAL priority interleave on the
+// SIMD, so the group is not back to back in the SIMD's issue order.  Here the group of n = 2, 4, 7 independent transcendentals
+// (v_rsq / v_sqrt / v_sin / v_cos mixed as the path tracer's bounce mixes them) behind 12 v_add_f32 is issued once as it stands and
+// once bracketed by s_setprio 3 ... s_setprio 0, at 6 and 7 waves per SIMD, with all waves in phase and with every wave started
+// (wave id mod 13) adds late, as resident waves of the pool kernel are.  Cycles per transcendental = (trip - 12 x the F-only rate) / n.
+namespace prio {
+#define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
+constexpr int kIters = 2048;
+#define OPS : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b)
+#define F(k) "v_add_f32_e32 %" #k ", %" #k ", %8\n\t"
+#define R(k) "v_rsq_f32_e32 %" #k ", %" #k "\n\t"
+#define Q(k) "v_sqrt_f32_e32 %" #k ", %" #k "\n\t"
+#define N(k) "v_sin_f32_e32 %" #k ", %" #k "\n\t"
+#define O(k) "v_cos_f32_e32 %" #k ", %" #k "\n\t"
+#define UP "s_setprio 3\n\t"
+#define DOWN "s_setprio 0\n\t"
+// (the loop's scalar instructions stand between a trip's last transcendental and the next trip's first add, and no add reads the
+// transcendental directly before it: the wait state a transcendental's result needs is covered in every pattern)
+#define P_F12   F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(1) F(2) F(3) F(4) F(0)
+#define P_F16    F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+#define G2       N(1) O(2)
+#define G4       R(1) Q(2) N(3) O(4)
+#define G7       R(1) N(2) O(3) Q(4) N(5) O(6) Q(7)
+// the same instructions with every transcendental alone: what the kernel pays today
+#define P_LONE2  F(1) F(2) F(3) F(4) F(5) F(0) N(1) F(6) F(7) F(3) F(4) F(5) F(0) O(2)
+#define P_LONE4  F(5) F(6) F(0) R(1) F(7) F(5) F(0) Q(2) F(6) F(7) F(0) N(3) F(5) F(6) F(0) O(4)
+#define KERNEL(NAME, PAT)                                                                           \
+    __global__ void __launch_bounds__(256) NAME(float* out, float seed, int dephase) {               \
+        float a0 = seed, a1 = seed + 1, a2 = seed + 2, a3 = seed + 3, a4 = seed + 4, a5 = seed + 5, a6 = seed + 6, a7 = seed + 7; \
+        float b = seed * 0.5f + 1.0f;                                                               \
+        const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))); \
+        for (int j = dephase ? wave % 13 : 0; j > 0; j--) asm volatile(F(0) OPS);                   \
+        for (int i = 0; i < kIters; i++) asm volatile(PAT OPS);                                     \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;          \
+    }
+KERNEL(k_f16, P_F16)
+KERNEL(k_g2, P_F12 G2) KERNEL(k_g2p, P_F12 UP G2 DOWN) KERNEL(k_l2, P_LONE2)
+KERNEL(k_g4, P_F12 G4) KERNEL(k_g4p, P_F12 UP G4 DOWN) KERNEL(k_l4, P_LONE4)
+KERNEL(k_g7, P_F12 G7) KERNEL(k_g7p, P_F12 UP G7 DOWN)
+struct Entry { const char* name; void (*fn)(float*, float, int); int n; };
+static int run() {
+    CHECK(hipSetDevice(0));
+    hipDeviceProp_t prop; CHECK(hipGetDeviceProperties(&prop, 0));
+    const int cus = prop.multiProcessorCount;
+    float* out; CHECK(hipMalloc(&out, sizeof(float) * 256 * cus * 8));
+    std::vector<Entry> es = {
+        {"F x12, sin / F x6 cos ... lone", k_l2, 2}, {"F x12 (sin cos)", k_g2, 2}, {"F x12 prio3 (sin cos) prio0", k_g2p, 2},
+        {"(F F F T) x4          lone", k_l4, 4}, {"F x12 (rsq sqrt sin cos)", k_g4, 4}, {"F x12 prio3 (rsq sqrt sin cos) prio0", k_g4p, 4},
+        {"F x12 (rsq sin cos sqrt sin cos sqrt)", k_g7, 7}, {"F x12 prio3 (the same seven) prio0", k_g7p, 7},
+    };
+    hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    printf("cycles per SIMD @2.4 GHz; trip = one wave's pass over the pattern x waves per SIMD (the SIMD's time per trip of one wave);\n"
+           "per T = (trip - 12 x F) / n with F from the F x16 row of the same block; three timings of five launches each: min .. max\n");
+    for (int wps : {6, 7}) {   // 256-thread blocks (one wave per SIMD each), wps blocks per CU
+        const int blocks = cus * wps;
+        // cycles one SIMD spends on one trip of one of its waves
+        auto trip = [&](void (*fn)(float*, float, int), int dephase, double* lo, double* hi) {
+            hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, 0, out, 1.0f, dephase); CHECK(hipDeviceSynchronize());
+            *lo = 1e30; *hi = 0;
+            for (int t = 0; t < 3; t++) {
+                CHECK(hipEventRecord(e0));
+                for (int r = 0; r < 5; r++) hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, 0, out, 1.0f, dephase);
+                CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1));
+                float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); ms /= 5;
+                const double c = (ms * 1e-3) * 2.4e9 / ((double)wps * kIters);
+                if (c < *lo) *lo = c;
+                if (c > *hi) *hi = c;
+            }
+        };
+        for (int dephase : {0, 1}) {
+            double flo, fhi; trip(k_f16, dephase, &flo, &fhi);
+            const double f = 0.5 * (flo + fhi) / 16.0;
+            printf("---- %d waves per SIMD, %s\n%-40s %17s %s\n", wps, dephase ? "waves de-phased by (wave id mod 13) adds" : "waves in phase",
+                   "stream", "trip", "per T");
+            printf("%-40s %8.2f..%7.2f   F = %.3f per instruction\n", "F x16", flo, fhi, f);
+            for (auto& e : es) {
+                double lo, hi; trip(e.fn, dephase, &lo, &hi);
+                printf("%-40s %8.2f..%7.2f %7.2f..%5.2f\n", e.name, lo, hi, (lo - 12.0 * f) / e.n, (hi - 12.0 * f) / e.n);
+            }
+        }
+    }
+    return 0;
+}
+}  // namespace prio
+#undef CHECK
+#undef OPS
+#undef F
+#undef R
+#undef Q
+#undef N
+#undef O
+#undef UP
+#undef DOWN
+#undef P_F12
+#undef P_F16
+#undef G2
+#undef G4
+#undef G7
+#undef P_LONE2
+#undef P_LONE4
+#undef KERNEL
+
 int main(int argc, char** argv) {
     const std::string m = argc > 1 ? argv[1] : "";
+    if (m == "prio") return prio::run();
     if (m == "classes") return classes::run();
     if (m == "mix") return mix::run();
     if (m == "among") return among::run();
     if (m == "opcodes") return opcodes::run();
     if (m == "fp64") return classes::run_fp64();
-    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes | fp64\n");
+    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes | fp64 | prio\n");
     return 2;
 }

@@ -195,6 +195,45 @@ template <int Fast> __device__ __forceinline__ void sincos_angle(float angle, fl
     }
 }
 
+// ---- the fast tier's transcendentals as prioritised groups (the sample-pool kernel's bounce) ---------------------------
+// gfx950 prices a transcendental that stands alone among other instructions at 11 - 13 issue cycles and one issued directly behind
+// another at 8.3 - 9; with seven waves of EQUAL priority interleaving on a SIMD none ever is behind another, wherever the compiler
+// puts it, but a wave that raises its priority for the length of a group gets the group issued back to back
+// (profiles/valu_microbench_prio.txt: 10.0 - 13.1 cycles each as they stand, 8.3 - 9.8 between s_setprio 3 and s_setprio 0).
+// Each helper is ONE block: the independent transcendentals of one place in the bounce, the same opcodes on the same operands as
+// inversesqrt<1>, fsqrt<1> and sincos_angle<1> emit (v_rsq_f32, v_sqrt_f32, v_sin_f32 / v_cos_f32 on the random number in
+// revolutions) — every result keeps its bits.  The closing s_nop is the wait state a transcendental's result needs before an
+// ordinary instruction reads it: the compiler's hazard recogniser does not look inside a block.  Outputs that are not computed in
+// place are early-clobber: no result may land in the register of an operand another member of the group still reads.
+#ifdef MC_PT_TRANS_UNGROUPED   // diagnostic build only (tests/test_gpu_pool_trans_groups.py): the instruction order before the groups
+constexpr bool kTransGroups = false;
+#else
+constexpr bool kTransGroups = true;
+#endif
+// the light sample (:409, :412): 1 / |xc| and the sine and cosine of 2 pi u
+__device__ __forceinline__ void light_trans_group(float xcc, float u, float& inv_len, float& s, float& c) {
+    inv_len = xcc;
+    asm volatile("s_setprio 3\n\t"
+                 "v_rsq_f32_e32 %0, %0\n\t"
+                 "v_sin_f32_e32 %1, %3\n\t"
+                 "v_cos_f32_e32 %2, %3\n\t"
+                 "s_setprio 0\n\t"
+                 "s_nop 0"
+                 : "+v"(inv_len), "=&v"(s), "=&v"(c) : "v"(u));
+}
+// the cosine-weighted bounce (:426, :428): sqrt(u2), the sine and cosine of 2 pi u1, sqrt(1 - u2)
+__device__ __forceinline__ void bounce_trans_group(float u1, float u2, float& r2s, float& s1, float& c1, float& C) {
+    C = 1.0f - u2;
+    asm volatile("s_setprio 3\n\t"
+                 "v_sqrt_f32_e32 %0, %5\n\t"
+                 "v_sin_f32_e32 %1, %4\n\t"
+                 "v_cos_f32_e32 %2, %4\n\t"
+                 "v_sqrt_f32_e32 %3, %3\n\t"
+                 "s_setprio 0\n\t"
+                 "s_nop 0"
+                 : "=&v"(r2s), "=&v"(s1), "=&v"(c1), "+v"(C) : "v"(u1), "v"(u2));
+}
+
 // ---- strict log2 / exp2 / pow ------------------------------------------------------------------------
 __device__ __forceinline__ float mc_log2(float x) {
     if (x == 0.0f) return -__builtin_inff();

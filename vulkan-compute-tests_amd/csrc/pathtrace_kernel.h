@@ -606,8 +606,13 @@ template <int Fast> __device__ __forceinline__ v3 camera_ray(const PTArgs& a, ui
     return normalize<Fast>(a.lc - spos);                                  // :362
 }
 // Direction towards a point of the light's visible cap (:408-:413): xc = light centre - x, xcc = |xc|^2, lr2 = radius^2.
-template <int Fast> __device__ __forceinline__ v3 light_sample_direction(v3 xc, float xcc, float lr2, v3 rnd, float& cos_a_max) {
-    const float inv_len = dm::inversesqrt<Fast>(xcc);
+// Grouped (the fast sample-pool kernel): the three transcendentals whose operands are known on entry — 1 / |xc|, sin and cos of
+// 2 pi rnd.y — are issued as one prioritised group (dm::light_trans_group); the same values.
+template <int Fast, bool Grouped = false> __device__ __forceinline__ v3 light_sample_direction(v3 xc, float xcc, float lr2, v3 rnd, float& cos_a_max) {
+    static_assert(!Grouped || Fast == 1, "the grouped transcendentals are the fast tier's opcodes");
+    float inv_len, sphi, cphi;
+    if constexpr (Grouped) dm::light_trans_group(xcc, rnd.y, inv_len, sphi, cphi);
+    else inv_len = dm::inversesqrt<Fast>(xcc);
     v3 sw = xc * inv_len;                                     // :409 normalize(xc)
     if constexpr (Fast) {
         // The tangents are left UNNORMALISED — t1 = cross(axis, sw) (tangent_u before its scaling), t2 = cross(sw, t1), both of
@@ -621,8 +626,7 @@ template <int Fast> __device__ __forceinline__ v3 light_sample_direction(v3 xc, 
         const float cos_a = (1.0f - rnd.x) + rnd.x * cos_a_max;               // :411
         const float A = __builtin_fmaxf(1.0f - cos_a * cos_a, 1e-30f);
         const float g = A * dm::inversesqrt<Fast>(A * B);
-        float sphi, cphi;
-        dm::sincos_angle<Fast>(0.0f, rnd.y, sphi, cphi);                      // :412
+        if constexpr (!Grouped) dm::sincos_angle<Fast>(0.0f, rnd.y, sphi, cphi);   // :412
         // t1 = (z, 0, -x) or (0, -z, y) has a zero component and t2 = cross(sw, t1) = (-xy, B, -yz) or (B, -xy, -xz) carries B
         // itself, so a t1 + b t2 + c sw needs no cross product: with m = the axis component (y or x), q the other one,
         // cm = c - b m and sa = +-a:  special component = b B + c m,  the other two = sa z + q cm  and  -sa q + z cm.
@@ -642,7 +646,6 @@ template <int Fast> __device__ __forceinline__ v3 light_sample_direction(v3 xc, 
         float cos_a = (1.0f - rnd.x) + rnd.x * cos_a_max;         // :411
         float sin_a = dm::fsqrt<Fast>(1.0f - cos_a * cos_a);
         float phi = (2.0f * kPi) * rnd.y;                         // :412
-        float sphi, cphi;
         dm::sincos_angle<Fast>(phi, rnd.y, sphi, cphi);
         return normalize<Fast>(((su * cphi) * sin_a + (sv * sphi) * sin_a) + sw * cos_a);   // :413
     }
@@ -658,6 +661,19 @@ template <int Fast, bool Unit> __device__ __forceinline__ v3 cosine_bounce(v3 w,
     return Fast ? normalize_unit_combination<Fast, Unit>((u * (c1 * r2s) + v * (s1 * r2s)) + w * dm::fsqrt<Fast>(1.0f - r2))
                 : normalize_unit_combination<Fast, Unit>(((u * c1) * r2s + (v * s1) * r2s) + w * dm::fsqrt<Fast>(1.0f - r2));   // :428
 }
+// The fast sample-pool kernel issues the four transcendentals of the bounce that depend on the random numbers alone — sqrt(r2),
+// sin(r1), cos(r1), sqrt(1 - r2) — as one prioritised group (dm::bounce_trans_group) and hands them to the fast form of either bounce.
+struct BounceTrans { float r2s, s1, c1, C; };
+__device__ __forceinline__ BounceTrans bounce_trans_grouped(v3 rnd) {
+    BounceTrans q;
+    dm::bounce_trans_group(rnd.x, rnd.y, q.r2s, q.s1, q.c1, q.C);
+    return q;
+}
+template <bool Unit> __device__ __forceinline__ v3 cosine_bounce_grouped(v3 w, BounceTrans q) {
+    v3 u = tangent_u<1>(w);                                       // :427
+    v3 v = cross(w, u);
+    return normalize_unit_combination<1, Unit>((u * (q.c1 * q.r2s) + v * (q.s1 * q.r2s)) + w * q.C);   // :428
+}
 // The same bounce around the inward normal of an axis-aligned WALL of a slab scene: w = sigma * e_a, so the basis of :427 is two
 // signed axis vectors — u = normalize(cross(axis, w)) has one component -+sigma and two zeros, its length factor is the (correctly
 // rounded, or v_rsq_f32's) 1 / sqrt(1) = 1, v = cross(w, u) likewise — and :428's combination ((u*c1)*r2s + (v*s1)*r2s) + w*C is a
@@ -668,11 +684,7 @@ template <int Fast, bool Unit> __device__ __forceinline__ v3 cosine_bounce(v3 w,
 // form's; such a component multiplies t and is added to a non-zero coordinate, or fails the |d_a| > 1e-7 test of :119.)
 // `id` = the wall's slab id 2a + (normal is +e_a); a hit wall faces the ray (:119: dot(d, n) > 0), so nl = -n and sigma is
 // negative exactly for the odd ids.   a = 0: (sC, B, -sA)   a = 1: (B, sC, sA)   a = 2: (B, -sA, sC)   with sX = sigma * X.
-template <int Fast> __device__ __forceinline__ v3 cosine_bounce_wall(int id, v3 rnd) {
-    const float r1 = (2.0f * kPi) * rnd.x, r2 = rnd.y, r2s = dm::fsqrt<Fast>(r2);   // :426
-    float s1, c1;
-    dm::sincos_angle<Fast>(r1, rnd.x, s1, c1);
-    const float A = c1 * r2s, B = s1 * r2s, C = dm::fsqrt<Fast>(1.0f - r2);
+template <int Fast> __device__ __forceinline__ v3 cosine_bounce_wall(int id, float A, float B, float C) {
     const uint32_t sb = (uint32_t)id << 31;
     const float sC = dm::as_float(dm::as_uint(C) ^ sb), sA = dm::as_float(dm::as_uint(A) ^ sb);
     const float nsA = dm::as_float(dm::as_uint(sA) ^ 0x80000000u);
@@ -680,6 +692,14 @@ template <int Fast> __device__ __forceinline__ v3 cosine_bounce_wall(int id, v3 
     const v3 d{a0 ? sC : B, a0 ? B : (a1 ? sC : nsA), a0 ? nsA : (a1 ? sA : sC)};
     return normalize_unit_combination<Fast, true>(d);                                // :428
 }
+template <int Fast> __device__ __forceinline__ v3 cosine_bounce_wall(int id, v3 rnd) {
+    const float r1 = (2.0f * kPi) * rnd.x, r2 = rnd.y, r2s = dm::fsqrt<Fast>(r2);   // :426
+    float s1, c1;
+    dm::sincos_angle<Fast>(r1, rnd.x, s1, c1);
+    const float A = c1 * r2s, B = s1 * r2s, C = dm::fsqrt<Fast>(1.0f - r2);
+    return cosine_bounce_wall<Fast>(id, A, B, C);
+}
+__device__ __forceinline__ v3 cosine_bounce_wall_grouped(int id, BounceTrans q) { return cosine_bounce_wall<1>(id, q.c1 * q.r2s, q.s1 * q.r2s, q.C); }
 
 // Mirror / glass bounce in the fast slab form (:432-:447): every outcome is rd*alpha + n*beta — reflection (1, -2 dot(n, rd)),
 // refraction (nnt, -k) — so the scalars are selected and ONE direction is formed; cos of the leaving ray = sqrt(cos2t), c^5

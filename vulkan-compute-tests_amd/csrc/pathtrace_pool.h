@@ -32,6 +32,19 @@
 // the end — a reassociation, relative 1e-6 of the pixel value, far inside the fast-math tolerance; the strict variant
 // above keeps the reference's order.  It is deterministic: a wave's schedule depends on nothing outside the wave, and
 // the pixels a wave owns are the same for every tiling the host selects it for (pathtrace.hip).
+//
+// Transcendentals as prioritised groups (fast tier only).  4.9 % of the kernel's VALU instructions are hardware transcendentals and
+// take a quarter of its time: among other instructions one costs a SIMD 11 - 13 cycles, directly behind another one 8.3 - 9, and with
+// seven waves of equal priority interleaving none ever is behind another.  The two places of a diffuse bounce where several are
+// independent of each other and of everything computed there — the light sample's 1 / |xc| with sin and cos of its angle
+// (light_sample_direction<1, true>), the cosine bounce's sqrt(r2), sin, cos, sqrt(1 - r2) (bounce_trans_grouped) — issue them as ONE
+// block between s_setprio 3 and s_setprio 0 (mc_math.h): seven of a bounce's fourteen.  Same opcodes, same operands, same bits
+// (tests/test_gpu_pool_trans_groups.py renders with and without the groups: equal bit for bit); 71 VGPRs and 7 waves per SIMD as before.
+// Measured (profiles/valu_microbench_prio.txt, trans_groups_k2_ab.txt): a grouped transcendental costs 8.3 - 9.1 cycles in a group of
+// four, 8.6 - 9.8 in a pair; K2 14.01 -> 13.74 ms, 2.689 -> 2.643 cycles per VALU instruction on the same 1.2739e10 VALU instructions.
+// One light: the same instructions per iteration as before.  Every further light repeats the sine and cosine in its own group (the
+// compiler shared one pair between the unrolled light blocks before; a block cannot share out of another's).
+// -DMC_PT_TRANS_UNGROUPED (make exp; the shipped build never sets it) compiles the instruction order before the groups.
 #pragma once
 #include <type_traits>
 #include "pathtrace_kernel.h"
@@ -90,6 +103,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     // math does not execute, this one and the un-normalised directions are the two whose forked samples do not balance — more of them
     // lose radiance than gain it; with both in the reference's form gains and losses cancel: profiles/r05_fork_bias_identities.txt)
     constexpr bool kOccR2 = Fast == 1;
+    // fast tier: the bounce's transcendentals whose operands are known early are issued as prioritised groups (mc_math.h, "groups")
+    constexpr bool kGrouped = Fast == 1 && dm::kTransGroups;
     constexpr uint32_t TW = WaveTile<S>::w, TH = WaveTile<S>::h, Ring = 2u * (uint32_t)S, RRing = pool_result_batches<NS>() * (uint32_t)S;
     HotSlabN<NS> hot;
     hot.template load<false, true>(a.scene);   // (uniform operands but W_pos: this kernel has no vector registers to spare for copies)
@@ -317,7 +332,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         const float* ls = a.scene.obj + 12 * (6 + i);
                         v3 le{ls[4], ls[5], ls[6]};
                         float cos_a_max;
-                        v3 l = light_sample_direction<Fast>(xoc[i], xcc[i], hot.r2[i], rnd, cos_a_max);   // :408-:413
+                        v3 l = light_sample_direction<Fast, kGrouped>(xoc[i], xcc[i], hot.r2[i], rnd, cos_a_max);   // :408-:413
                         bool lit;                                                                          // :420
                         if constexpr (Fast && Disjoint) lit = shadow_visible_disjoint<kOccR2>(hot, l, i, xoc, occ);
                         else lit = shadow_reaches_sphere<Fast, kOccR2>(hot, x, l, i, xoc[i], occ);
@@ -333,7 +348,11 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         }
                     }
                     // :426-:428 (uniform: no lane of the wave bounces off a diffuse SPHERE — the light — in almost every iteration)
-                    if (__ballot(is_sphere) == 0ull) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
+                    if constexpr (kGrouped) {   // (the four transcendentals both forms share: one group in front of them)
+                        const BounceTrans bt = bounce_trans_grouped(rnd);
+                        if (__ballot(is_sphere) == 0ull) { MC_REGION(9); rd = cosine_bounce_wall_grouped(id, bt); }
+                        else { MC_REGION(10); rd = cosine_bounce_grouped<true>(nl, bt); }
+                    } else if (__ballot(is_sphere) == 0ull) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
                     else { MC_REGION(10); rd = cosine_bounce<Fast, true>(nl, rnd); }
                     emissive = 0.0f;                                              // :429
                 } else {                                                          // :432 mirror, :437 glass (box_ok: 2 or 3)
