@@ -1,4 +1,4 @@
-// VALU issue-cost surveys of gfx950 (MI355X) — ONE program with four modes (rounds 1-4 kept them as four files):
+// VALU issue-cost surveys of gfx950 (MI355X) — ONE program, one mode per survey (rounds 1-4 kept them as four files):
 //   valu_microbench classes   every opcode class in isolation (profiles/r01_valu_microbench.txt)
 //   valu_microbench mix       how the issue classes combine; instructions under EXEC = 0 (profiles/r03_valu_microbench3.txt)
 //   valu_microbench among     a transcendental among other instructions (profiles/r03_valu_microbench7.txt)
@@ -7,6 +7,8 @@
 //                             MC_PRECISION_F64 Mandelbrot kernel (profiles/f64_valu_microbench.txt)
 //   valu_microbench prio      a group of transcendentals issued at raised wave priority (s_setprio) against the same group at equal
 //                             priority (profiles/valu_microbench_prio.txt)
+//   valu_microbench ldsmov    a register filled by ds_read from a wave-uniform address against v_mov_b32 from an SGPR
+//                             (profiles/valu_microbench_ldsmov.txt)
 // These are the measurements the path tracer's design rests on: add / mul / fmac / mov / logic issue in ~2.3 cycles
 // per wave64 instruction per SIMD, compare / select / min / max / convert / three-operand integer in ~4.2 alone but ~2.4 in a mix,
 // transcendentals in ~8.2 wherever they stand.  Each mode is the former file's code, unchanged, in a namespace of its own.
@@ -633,14 +635,106 @@ static int run() {
 #undef P_LONE4
 #undef KERNEL
 
+// ======================================================================================================================
+// mode "ldsmov" — what does a register filled from LDS cost a SIMD against the same register filled by v_mov_b32 from an SGPR?
+// The pool kernel's stash pick-up and its plane test write wave-uniform values into vector registers with v_mov_b32: VALU issue
+// slots that compute nothing, in a kernel bound by VALU issue whose LDS pipe is idle.  A trip is 12 independent v_add_f32 plus
+//   four v_mov_b32 from SGPRs                 against   one ds_read_b128 from a wave-uniform address (a broadcast: no bank conflict),
+//   three v_mov_b32                           against   one ds_read_b96,
+// the load once issued in front of the adds with its s_waitcnt lgkmcnt(0) behind them (latency covered by the wave's own adds) and
+// once directly in front of its s_waitcnt (covered by the other waves only), at 6 and 7 waves per SIMD.  Cost of one v_mov =
+// (trip with n moves - trip of the 12 adds) / n; the load form's saving = trip with moves - trip with the load.
+namespace ldsmov {
+#define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
+constexpr int kIters = 2048;
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f3 __attribute__((ext_vector_type(3)));
+#define F(k, B) "v_add_f32_e32 %" #k ", %" #k ", %" #B "\n\t"
+#define P_F12(B) F(1, B) F(2, B) F(3, B) F(4, B) F(5, B) F(6, B) F(7, B) F(1, B) F(2, B) F(3, B) F(4, B) F(0, B)
+#define WAIT "s_waitcnt lgkmcnt(0)\n\t"
+#define ADDS : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b)
+// BODY: one trip.  m: the registers filled (summed into the result after the loop, so that the last trip's fill is live).
+#define KERNEL(NAME, BODY)                                                                          \
+    __global__ void __launch_bounds__(256) NAME(float* out, float seed) {                            \
+        __shared__ __attribute__((aligned(16))) float row[8];                                        \
+        if (threadIdx.x < 8u) row[threadIdx.x] = seed + (float)threadIdx.x;                          \
+        __syncthreads();                                                                             \
+        float a0 = seed, a1 = seed + 1, a2 = seed + 2, a3 = seed + 3, a4 = seed + 4, a5 = seed + 5, a6 = seed + 6, a7 = seed + 7; \
+        float b = seed * 0.5f + 1.0f;                                                               \
+        const unsigned addr = (unsigned)(size_t)row;   /* wave-uniform LDS byte address, in a vector register */ \
+        const int sb = __float_as_int(seed), s0 = __builtin_amdgcn_readfirstlane(sb + 8), s1 = __builtin_amdgcn_readfirstlane(sb + 9), s2 = __builtin_amdgcn_readfirstlane(sb + 10), s3 = __builtin_amdgcn_readfirstlane(sb + 11); \
+        f4 m = {0, 0, 0, 0}; f3 m3 = {0, 0, 0}; float q0 = 0, q1 = 0, q2 = 0, q3 = 0;                                                     \
+        for (int i = 0; i < kIters; i++) { BODY; }                                                   \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + m.x + m.y + m.z + m.w + m3.x + m3.y + m3.z + q0 + q1 + q2 + q3 + addr + (float)(s0 + s1 + s2 + s3); \
+    }
+KERNEL(k_f12, asm volatile(P_F12(8) ADDS))
+KERNEL(k_f16, asm volatile(P_F12(8) F(5, 8) F(6, 8) F(7, 8) F(0, 8) ADDS))
+#define FILL(M) : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(M)
+#define MOVS : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3) : "v"(b), "s"(s0), "s"(s1), "s"(s2), "s"(s3)
+KERNEL(k_mov4, asm volatile(P_F12(12) "v_mov_b32 %8, %13\n\tv_mov_b32 %9, %14\n\tv_mov_b32 %10, %15\n\tv_mov_b32 %11, %16\n\t" MOVS))
+KERNEL(k_mov3, asm volatile(P_F12(12) "v_mov_b32 %8, %13\n\tv_mov_b32 %9, %14\n\tv_mov_b32 %10, %15\n\t" MOVS))
+KERNEL(k_lds128_early, asm volatile("ds_read_b128 %8, %10\n\t" P_F12(9) WAIT FILL(m) : "v"(b), "v"(addr) : "memory"))
+KERNEL(k_lds128_late, asm volatile(P_F12(9) "ds_read_b128 %8, %10\n\t" WAIT FILL(m) : "v"(b), "v"(addr) : "memory"))
+KERNEL(k_lds96_early, asm volatile("ds_read_b96 %8, %10\n\t" P_F12(9) WAIT FILL(m3) : "v"(b), "v"(addr) : "memory"))
+KERNEL(k_lds96_late, asm volatile(P_F12(9) "ds_read_b96 %8, %10\n\t" WAIT FILL(m3) : "v"(b), "v"(addr) : "memory"))
+struct Entry { const char* name; void (*fn)(float*, float); };
+static int run() {
+    CHECK(hipSetDevice(0));
+    hipDeviceProp_t prop; CHECK(hipGetDeviceProperties(&prop, 0));
+    const int cus = prop.multiProcessorCount;
+    float* out; CHECK(hipMalloc(&out, sizeof(float) * 256 * cus * 8));
+    std::vector<Entry> es = {
+        {"F x12", k_f12}, {"F x16", k_f16}, {"F x12, v_mov x4 (sgpr)", k_mov4}, {"ds_read_b128, F x12, wait", k_lds128_early},
+        {"F x12, ds_read_b128, wait", k_lds128_late}, {"F x12, v_mov x3 (sgpr)", k_mov3}, {"ds_read_b96, F x12, wait", k_lds96_early},
+        {"F x12, ds_read_b96, wait", k_lds96_late},
+    };
+    hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    printf("cycles per SIMD @2.4 GHz per trip of one wave (time x clock / (waves per SIMD x trips)); three timings of five launches: min .. max\n");
+    for (int wps : {6, 7}) {   // 256-thread blocks (one wave per SIMD each), wps blocks per CU
+        const int blocks = cus * wps;
+        printf("---- %d waves per SIMD\n%-32s %17s\n", wps, "trip", "cycles");
+        std::vector<double> mid;
+        for (auto& e : es) {
+            hipLaunchKernelGGL(e.fn, dim3(blocks), dim3(256), 0, 0, out, 1.0f); CHECK(hipDeviceSynchronize());
+            double lo = 1e30, hi = 0;
+            for (int t = 0; t < 3; t++) {
+                CHECK(hipEventRecord(e0));
+                for (int r = 0; r < 5; r++) hipLaunchKernelGGL(e.fn, dim3(blocks), dim3(256), 0, 0, out, 1.0f);
+                CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1));
+                float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); ms /= 5;
+                const double c = (ms * 1e-3) * 2.4e9 / ((double)wps * kIters);
+                if (c < lo) lo = c;
+                if (c > hi) hi = c;
+            }
+            mid.push_back(0.5 * (lo + hi));
+            printf("%-32s %8.2f..%7.2f\n", e.name, lo, hi);
+        }
+        const double mov4 = (mid[2] - mid[0]) / 4.0, mov3 = (mid[5] - mid[0]) / 3.0;
+        printf("one v_mov: %.3f (of four), %.3f (of three); F: %.3f\n", mov4, mov3, (mid[1] - mid[0]) / 4.0);
+        printf("ds_read_b128 for four moves saves %.2f (early) %.2f (late) cycles per trip; gate: at least %.2f\n", mid[2] - mid[3], mid[2] - mid[4], 2.0 * mov4);
+        printf("ds_read_b96 for three moves saves %.2f (early) %.2f (late) cycles per trip; half of three moves: %.2f\n", mid[5] - mid[6], mid[5] - mid[7], 1.5 * mov3);
+    }
+    return 0;
+}
+}  // namespace ldsmov
+#undef CHECK
+#undef F
+#undef P_F12
+#undef WAIT
+#undef ADDS
+#undef FILL
+#undef MOVS
+#undef KERNEL
+
 int main(int argc, char** argv) {
     const std::string m = argc > 1 ? argv[1] : "";
     if (m == "prio") return prio::run();
+    if (m == "ldsmov") return ldsmov::run();
     if (m == "classes") return classes::run();
     if (m == "mix") return mix::run();
     if (m == "among") return among::run();
     if (m == "opcodes") return opcodes::run();
     if (m == "fp64") return classes::run_fp64();
-    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes | fp64 | prio\n");
+    fprintf(stderr, "usage: valu_microbench classes | mix | among | opcodes | fp64 | prio | ldsmov\n");
     return 2;
 }

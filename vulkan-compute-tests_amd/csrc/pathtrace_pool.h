@@ -45,6 +45,14 @@
 // One light: the same instructions per iteration as before.  Every further light repeats the sine and cosine in its own group (the
 // compiler shared one pair between the unrolled light blocks before; a block cannot share out of another's).
 // -DMC_PT_TRANS_UNGROUPED (make exp; the shipped build never sets it) compiles the instruction order before the groups.
+//
+// Loop predicates from lane masks the wave already holds (all tiers).  `__ballot(p)` of a bool that was merged across control flow is
+// compiled as v_cndmask_b32 v, 0, 1, s[..] + v_cmp_ne_u32 vcc, 0, v: a mask that lies in scalar registers is written into a vector
+// register and read back — two VALU instructions that compute nothing, in a kernel bound by VALU issue.  So: the termination test asks
+// the scalar `batch >= n_batches` first and takes its ballots only while the pool drains; "no diffuse lane is on a sphere" is read off
+// the mask the prologue's own compare `id >= 6` wrote; the emission of a path the roulette ends is added under the lanes' own condition.
+// Seven VALU instructions an iteration less, every bit kept (tests/test_gpu_pool_valu_diet.py; profiles/valu_diet_k2_ab.txt).  The
+// ballot at the top of the loop stays: its mask is data (gbits).  -DMC_PT_POOL_PARENT_FORMS (make exp) compiles the forms before.
 #pragma once
 #include <type_traits>
 #include "pathtrace_kernel.h"
@@ -52,6 +60,11 @@
 namespace mc {
 namespace pt {
 
+#ifdef MC_PT_POOL_PARENT_FORMS   // diagnostic build only (tests/test_gpu_pool_valu_diet.py): the loop predicates as ballots of carried bools
+constexpr bool kPoolParentForms = true;
+#else
+constexpr bool kPoolParentForms = false;
+#endif
 constexpr uint32_t kPoolEntryFloats = 8;     // {rd.x, rd.y, rd.z, t | id (-1: nothing to trace), key0 = samp * maxDepth, rnd.x, rnd.y of key0}
 constexpr uint32_t kPoolRecordStride = 16;   // floats per staged record: {geo.xyz, p (fast: 1 / p) | colour.rgb, material + 256 * emits | emission.xyz, RN(1 / p) (fast: p) | fast: colour.rgb / p, the same integer bits}
 template <int NS> constexpr uint32_t pool_record_floats() { return (6u + (uint32_t)NS) * kPoolRecordStride; }   // 6 planes + NS spheres
@@ -276,12 +289,21 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
             ghead += need < avail ? need : avail;
         }
         // pool exhausted and every path ended?  (no lane alive but entries left: only empty entries were taken — go round again)
+        // (the scalar test first: while batches are left — all but the last ten or so of a wave's ~294 iterations — no ballot is taken)
+#ifdef MC_PT_POOL_PARENT_FORMS
         if (__ballot(alive) == 0ull && batch >= n_batches && __ballot(ghead != batch * (uint32_t)S) == 0ull) { finished = true; break; }
+#else
+        if (batch >= n_batches && __ballot(alive) == 0ull && __ballot(ghead != batch * (uint32_t)S) == 0ull) { finished = true; break; }
+#endif
         // ---- one bounce of every live lane: prologue, material, intersection of the next depth (the rotated loop of trace_sample)
         // (structured ifs, no break / continue: every extra exit edge of this block cost a dozen register copies at its merge)
         if (alive) {
             {
                 MC_REGION(4);    // a bounce: prologue
+                // the live lanes on a sphere, as the compare's own lane mask (the diffuse branch asks whether any of ITS lanes, a subset
+                // of these, is on one)
+                unsigned long long sph_m = 0ull;
+                if constexpr (!kPoolParentForms) sph_m = __ballot(id >= 6);
                 v3 x = ro + rd * t;                                               // :374
                 v3 xoc[NS];                                                       // c_i - x (:317 at the next depth, :408 now)
 #pragma unroll
@@ -348,11 +370,15 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         }
                     }
                     // :426-:428 (uniform: no lane of the wave bounces off a diffuse SPHERE — the light — in almost every iteration)
+                    auto walls_only = [&]() {
+                        if constexpr (kPoolParentForms) return __ballot(is_sphere) == 0ull;
+                        else return (sph_m & __ballot(true)) == 0ull;
+                    };
                     if constexpr (kGrouped) {   // (the four transcendentals both forms share: one group in front of them)
                         const BounceTrans bt = bounce_trans_grouped(rnd);
-                        if (__ballot(is_sphere) == 0ull) { MC_REGION(9); rd = cosine_bounce_wall_grouped(id, bt); }
+                        if (walls_only()) { MC_REGION(9); rd = cosine_bounce_wall_grouped(id, bt); }
                         else { MC_REGION(10); rd = cosine_bounce_grouped<true>(nl, bt); }
-                    } else if (__ballot(is_sphere) == 0ull) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
+                    } else if (walls_only()) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
                     else { MC_REGION(10); rd = cosine_bounce<Fast, true>(nl, rnd); }
                     emissive = 0.0f;                                              // :429
                 } else {                                                          // :432 mirror, :437 glass (box_ok: 2 or 3)
@@ -376,9 +402,19 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         const float4* nobj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);
                         go = !(rn.z >= nobj[Fast ? 2 : 0].w);                     // :396
                         // a path the roulette ends has still gathered the emission of this hit (:391 precedes :396)
-                        if (__ballot(!go && dm::as_uint(nobj[1].w) >= 256u) != 0ull) {
+                        if constexpr (kPoolParentForms) {
+                            if (__ballot(!go && dm::as_uint(nobj[1].w) >= 256u) != 0ull) {
+                                const float4 o2 = nobj[2];
+                                if (!go) rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
+                            }
+                        } else if (!go && dm::as_uint(nobj[1].w) >= 256u) {
+                            // Only the emitters add.  The wave-wide form let every ended lane add whenever one of them had hit an
+                            // emitter: accmat * e * emissive with e = +-0, the emission of a record whose flag is clear.  accmat is finite
+                            // (box_ok: colours in [0, 1], divided by their own maximum; the glass factors are finite), so that product is a
+                            // zero of either sign, and rad + (+-0) = rad for every rad but -0 — which rad never is: it starts at +0 and
+                            // only ever receives sums, and a sum is -0 only when both operands are.  Leaving the addition out keeps every bit.
                             const float4 o2 = nobj[2];
-                            if (!go) rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
+                            rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
                         }
                     }
                 }
