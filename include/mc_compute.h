@@ -812,6 +812,65 @@ int mc_pathtrace_denoise_device_async(mc_context* ctx, const mc_pathtrace_denois
 int mc_pathtrace_render_denoised(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_denoise_params* d, const float* planes,
                                  uint32_t n_planes, const float* spheres, uint32_t n_spheres, float* out_rgba_f32, uint8_t* out_rgba8);
 
+/* ---- Path-tracer denoiser, colour tolerance from a measured noise plane (no reference counterpart; additions within ABI 3; DESIGN.md
+ *      section 3.19) ---------------------------------------------------------------------------------------------------------------
+ * The filter above uses one colour tolerance, sigma_colour, whatever noise the render still has: right for 16 spp, too wide for a cleaner
+ * render, which it goes on blurring.  The calls below take the tolerance per pixel from a MEASUREMENT of the noise.  Sample ranges compose
+ * bit for bit, so a render made as [0, h), a copy of the accumulator, then [h, spp) is the plain render plus the linear accumulator of its
+ * first h samples; the first part, encoded as if it were the whole, differs from the finished buffer by the noise that is left.
+ * Strict arithmetic whatever the render's math_mode, as above: one IEEE-754 fp32 operation per operation stated, in that order, no
+ * contraction, correctly rounded divide; host calls, device kernels and tests/pt_noise_ref.py agree bit for bit (one source: csrc/pt_noise.h).
+ *
+ * THE NOISE PLANE.  half: a vec4 plane in storage order, the linear accumulator a render leaves after sample_end = h < spp.  full: the
+ * finished, encoded buffer of the same render.  scale = (float)spp / (float)h, formed by the caller (exactly 2 for an even spp).  For each
+ * pixel q and c in r, g, b:
+ *     x = half[q].c * scale;   cl = min(max(x, 0), 1)   with max(x, 0) = x < 0 ? 0 : x and min(y, 1) = 1 < y ? 1 : y (GLSL's);
+ *     E = pow045(cl) * 255 + 0.5   (pathTracer.comp:453 as the strict kernels perform it: pow045(c) = exp2(0.45f * log2(c)), log2 and exp2
+ *                                   the library's strict ones; exp2 is the filter's);
+ *     e_c = E - full[q].c;         v_q = (e_r*e_r + e_g*e_g) + e_b*e_b.
+ *   V_p is the mean of v over the (2 radius + 1)^2 window around p = (x, y): sum = cnt = 0; taps q = (x + a, y + b) in row-major order
+ *   (b = -radius .. radius outer, a likewise inner), taps outside the image skipped: sum = sum + v_q, cnt = cnt + 1.0f; V_p = sum / cnt.
+ *   The window ignores the guide ids: noise is a property of the lighting, not of the surface.  radius is 0 .. 4.  out_variance: one float
+ *   per pixel, storage order, in units of the encoded buffer squared.  The planes are not checked for finiteness: finite planes give a
+ *   finite V >= 0 (or +inf where a sum overflows).
+ *
+ * THE NOISE-GUIDED FILTER.  Exactly THE FILTER above with one change: the per-pass constant kc_i = 4^i / sigma_colour^2 becomes the per-pixel
+ *     kc_i(p) = (float)4^i / ((k_noise * k_noise) * V_p + 1.0f)
+ *   taken at the CENTRE pixel p and used for all of p's taps.  The + 1 is one encoded unit squared: a noiseless pixel (the visible light)
+ *   gets a tolerance of one unit, not a division by zero.  Taps, ids, the other two terms of e, exp2, the sums, the divisions, miss pixels
+ *   copied, d_out == d_rgba: all as above.  d->sigma_colour must still be valid (it is checked as above) but is NOT USED.
+ *
+ * mc_pathtrace_noise_default_params: k_noise = 4, radius = 3 (DESIGN.md section 3.19 has the sweep they come from).
+ * mc_pathtrace_noise, mc_pathtrace_denoise_adaptive: host only, no device, usable without a GPU, the same source as the kernels.
+ * mc_pathtrace_noise_device_async, mc_pathtrace_denoise_adaptive_device_async: on device pointers (vec4 planes aligned to 16 bytes, the
+ *   variance plane to 4), asynchronous on `stream` (NULL: the context's); their scratch (one float plane; two vec4 planes between the
+ *   passes) is the context's, shared with every other call as the filter's is.  An output that overlaps an input is refused, d_out ==
+ *   d_rgba excepted.
+ * mc_pathtrace_render_denoised_adaptive (blocking), on the context's stream in this order: the guides; the render of [0, h), h = spp / 2
+ *   rounded down; a device copy of that plane; the render of [h, spp) continuing it; the noise plane with scale = (float)spp / (float)h;
+ *   the noise-guided filter in place; for out_rgba8 the conversion and rotation of mc_pathtrace_render_rgba8.  Outputs and d as in
+ *   mc_pathtrace_render_denoised.  In MC_PT_MATH_STRICT the plane the filter receives is mc_pathtrace_render's bit for bit (ranges
+ *   compose), so the result is the host filter applied to that render, the host noise plane of its [0, h) part and the host guides.  In
+ *   the fast modes the promise is the weaker one: the result is that of the same chain made from the separate public calls
+ *   (mc_pathtrace_render_device_async twice, a copy, the two calls above).  It is not tied to the one-call render because a fast-math
+ *   kernel is chosen per request, and two ranges need not be rendered by the kernel the whole would get, nor round like it (see
+ *   mc_pathtrace_select_kernel).  mc_context_last_timing covers all of it.
+ * Refused with MC_ERR_INVALID_ARGUMENT and a detail string: a NULL pointer, a zero size, radius above 4, a k_noise that is not finite and
+ *   above 0 or whose fp32 square is not finite, everything the filter above refuses (passes outside 1 .. 8, flags other than 0, ...), and in
+ *   mc_pathtrace_render_denoised_adaptive spp < 2, a row tile, an interleave, a sample range. */
+int mc_pathtrace_noise_default_params(float* k_noise, uint32_t* radius);
+int mc_pathtrace_noise(uint32_t width, uint32_t height, const float* half, float scale, const float* full, uint32_t radius, float* out_variance);
+int mc_pathtrace_noise_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_half, float scale, const void* d_full,
+                                    uint32_t radius, void* d_variance, void* stream);
+int mc_pathtrace_denoise_adaptive(const mc_pathtrace_denoise_params* d, float k_noise, const float* rgba, const float* normal_t,
+                                  const float* position_id, const float* variance, float* out);
+int mc_pathtrace_denoise_adaptive_device_async(mc_context* ctx, const mc_pathtrace_denoise_params* d, float k_noise, const void* d_rgba,
+                                               const void* d_normal_t, const void* d_position_id, const void* d_variance, void* d_out,
+                                               void* stream);
+int mc_pathtrace_render_denoised_adaptive(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_denoise_params* d, float k_noise,
+                                          uint32_t radius, const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres,
+                                          float* out_rgba_f32, uint8_t* out_rgba8);
+
 /* ---- Path tracer through a bounding-volume hierarchy over the spheres (no reference counterpart; additions within ABI 3; DESIGN.md
  *      section 3.18) ---------------------------------------------------------------------------------------------------------------
  * The plain calls test every object for every ray, as the shader's loop does (pathTracer.comp:112-131).  An mc_pathtrace_accel holds a

@@ -208,6 +208,14 @@ def lib():
             L.mc_pathtrace_denoise.argtypes = [dp, vp, vp, vp, vp]
             L.mc_pathtrace_denoise_device_async.argtypes = [vp, dp, vp, vp, vp, vp, vp]
             L.mc_pathtrace_render_denoised.argtypes = [vp, C.POINTER(PathtraceParams), dp, vp, u32, vp, u32, vp, vp]
+        if hasattr(L, "mc_pathtrace_noise"):   # the noise plane and the filter it steers
+            dp = C.POINTER(PathtraceDenoiseParams)
+            L.mc_pathtrace_noise_default_params.argtypes = [C.POINTER(f32), C.POINTER(u32)]
+            L.mc_pathtrace_noise.argtypes = [u32, u32, vp, f32, vp, u32, vp]
+            L.mc_pathtrace_noise_device_async.argtypes = [vp, u32, u32, vp, f32, vp, u32, vp, vp]
+            L.mc_pathtrace_denoise_adaptive.argtypes = [dp, f32, vp, vp, vp, vp, vp]
+            L.mc_pathtrace_denoise_adaptive_device_async.argtypes = [vp, dp, f32, vp, vp, vp, vp, vp, vp]
+            L.mc_pathtrace_render_denoised_adaptive.argtypes = [vp, C.POINTER(PathtraceParams), dp, f32, u32, vp, u32, vp, u32, vp, vp]
         if hasattr(L, "mc_pathtrace_accel_create"):   # the path tracer through a sphere BVH
             pp, u64 = C.POINTER(PathtraceParams), C.c_uint64
             L.mc_pathtrace_accel_create.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
@@ -474,6 +482,42 @@ def pathtrace_denoise(d, rgba, normal_t, position_id):
             raise ValueError(f"pathtrace_denoise: every plane is float32 of shape {shape}, got {a.shape}")
     out = np.empty(shape, np.float32)
     _check(lib().mc_pathtrace_denoise(C.byref(d), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(out)), "mc_pathtrace_denoise")
+    return out
+
+
+def pathtrace_noise_defaults():
+    """mc_pathtrace_noise_default_params: (k_noise, radius), 4.0 and 3."""
+    k, r = C.c_float(0.0), C.c_uint32(0)
+    _check(lib().mc_pathtrace_noise_default_params(C.byref(k), C.byref(r)), "mc_pathtrace_noise_default_params")
+    return k.value, r.value
+
+
+def pathtrace_noise(half, scale, full, radius=None):
+    """mc_pathtrace_noise (host only): the float32 (height, width) noise plane of a render from half, the linear accumulator after its
+    first h samples, and full, its finished buffer (float32 (height, width, 4) each); scale = spp / h."""
+    h, f = np.ascontiguousarray(half, np.float32), np.ascontiguousarray(full, np.float32)
+    if h.ndim != 3 or h.shape[2] != 4 or f.shape != h.shape:
+        raise ValueError("pathtrace_noise: half and full are float32 (height, width, 4) arrays of one shape")
+    if radius is None:
+        radius = pathtrace_noise_defaults()[1]
+    out = np.empty(h.shape[:2], np.float32)
+    _check(lib().mc_pathtrace_noise(h.shape[1], h.shape[0], _ptr(h), scale, _ptr(f), radius, _ptr(out)), "mc_pathtrace_noise")
+    return out
+
+
+def pathtrace_denoise_adaptive(d, rgba, normal_t, position_id, variance, k_noise=None):
+    """mc_pathtrace_denoise_adaptive (host only): pathtrace_denoise with the colour tolerance taken per pixel from the float32
+    (height, width) plane variance and k_noise (default: mc_pathtrace_noise_default_params'); d.sigma_colour is not used."""
+    shape = (d.height, d.width, 4)
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (rgba, normal_t, position_id)]
+    var = np.ascontiguousarray(variance, np.float32)
+    if any(a.shape != shape for a in arrs) or var.shape != shape[:2]:
+        raise ValueError(f"pathtrace_denoise_adaptive: the planes are float32 of shape {shape}, the variance of shape {shape[:2]}")
+    if k_noise is None:
+        k_noise = pathtrace_noise_defaults()[0]
+    out = np.empty(shape, np.float32)
+    _check(lib().mc_pathtrace_denoise_adaptive(C.byref(d), k_noise, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(var), _ptr(out)),
+           "mc_pathtrace_denoise_adaptive")
     return out
 
 
@@ -944,6 +988,31 @@ class Context:
         _check(lib().mc_pathtrace_render_denoised(self._h, C.byref(p), C.byref(d), _ptr(planes), planes.size // 12, _ptr(spheres),
                                                   spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None),
                "mc_pathtrace_render_denoised")
+        return out
+
+    def pathtrace_noise_device(self, width, height, d_half, scale, d_full, radius, d_variance, stream=0):
+        """mc_pathtrace_noise_device_async: the noise plane (one float per pixel) of the device vec4 planes d_half and d_full."""
+        _check(lib().mc_pathtrace_noise_device_async(self._h, width, height, d_half or None, scale, d_full or None, radius, d_variance or None,
+                                                     stream or None), "mc_pathtrace_noise_device_async")
+
+    def pathtrace_denoise_adaptive_device(self, d, k_noise, d_rgba, d_normal_t, d_position_id, d_variance, d_out, stream=0):
+        """mc_pathtrace_denoise_adaptive_device_async: the noise-guided filter from d_rgba into d_out (which may be d_rgba)."""
+        _check(lib().mc_pathtrace_denoise_adaptive_device_async(self._h, C.byref(d), k_noise, d_rgba or None, d_normal_t or None,
+                                                                d_position_id or None, d_variance or None, d_out or None, stream or None),
+               "mc_pathtrace_denoise_adaptive_device_async")
+
+    def pathtrace_denoised_adaptive(self, p, d=None, k_noise=None, radius=None, planes=None, spheres=None, rgba8=False):
+        """mc_pathtrace_render_denoised_adaptive: the render in two sample ranges, the guides, the noise plane and the noise-guided filter in
+        one blocking call; the outputs of pathtrace_denoised.  d, k_noise, radius: the defaults when None."""
+        planes, spheres = _scene_tables(planes, spheres)
+        if d is None:
+            d = pathtrace_denoise_params(p.width, p.height)
+        k0, r0 = pathtrace_noise_defaults()
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        _check(lib().mc_pathtrace_render_denoised_adaptive(self._h, C.byref(p), C.byref(d), k0 if k_noise is None else k_noise,
+                                                           r0 if radius is None else radius, _ptr(planes), planes.size // 12, _ptr(spheres),
+                                                           spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None),
+               "mc_pathtrace_render_denoised_adaptive")
         return out
 
     def pathtrace_accel(self, accel, p, acc=None):

@@ -26,6 +26,7 @@ namespace mc {
 namespace {
 
 using ptd::vec4;
+using namespace ptdh;
 
 __global__ void __launch_bounds__(256) pt_guides_kernel(ptd::Camera cam, uint32_t W, uint32_t H, const float* __restrict__ rec, uint32_t n_planes,
                                                         uint32_t n_spheres, vec4* __restrict__ normal_t, vec4* __restrict__ position_id) {
@@ -50,37 +51,6 @@ __global__ void __launch_bounds__(256) pt_denoise_pass_kernel(const vec4* __rest
         out[p] = ptd::filter_pixel(W, H, x, y, step, kc, kn, kx, in, normal_t, position_id, in[p], normal_t[p], position_id[p]);
     }
 }
-
-dim3 plane_grid(uint32_t W, uint32_t H) { return dim3((W + 63u) / 64u, std::min<uint32_t>((H + 3u) / 4u, 65535u)); }
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16u != 0u; }
-
-int refuse(const char* who, const std::string& what) {
-    set_error_detail(std::string(who) + ": " + what);
-    return MC_ERR_INVALID_ARGUMENT;
-}
-
-// A host plane as vec4: the caller's memory where it is 16-byte aligned, a copy in `store` otherwise.
-const vec4* aligned_in(const float* a, size_t npix, std::vector<vec4>& store) {
-    if (!misaligned(a)) return reinterpret_cast<const vec4*>(a);
-    store.resize(npix);
-    std::memcpy(store.data(), a, npix * 16);
-    return store.data();
-}
-// A host output plane: written in place where aligned, else through `store` (finish() copies it out).
-struct AlignedOut {
-    float* user;
-    size_t npix;
-    std::vector<vec4> store;
-    AlignedOut(float* u, size_t n) : user(u), npix(n) { if (misaligned(u)) store.resize(n); }
-    vec4* ptr() { return store.empty() ? reinterpret_cast<vec4*>(user) : store.data(); }
-    void finish() { if (!store.empty()) std::memcpy(user, store.data(), npix * 16); }
-};
 
 std::vector<float> scene_records(const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres) {
     std::vector<float> rec(12 * ((size_t)n_planes + n_spheres));

@@ -49,6 +49,9 @@ int main(int argc, char* argv[]) {
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
     uint32_t denoise = 0;               // --denoise [P]: the path tracer's a-trous filter with P passes (mc_pathtrace_render_denoised); 0 = off
+    float noiseGuided = 0.0f;           // --noise-guided [K]: with --denoise, the colour tolerance from a measured noise plane, k_noise = K
+                                        // (mc_pathtrace_render_denoised_adaptive); 0 = off
+    bool noiseGuidedSet = false;
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -146,6 +149,24 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--noise-guided" || a.rfind("--noise-guided=", 0) == 0) {   // K is optional, as --denoise's P is (default: the library's)
+            const char* v = nullptr;
+            if (a.size() > 14) v = argv[i] + 15;
+            else if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) v = argv[++i];
+            uint32_t radius = 0;
+            mc_pathtrace_noise_default_params(&noiseGuided, &radius);
+            char* end = nullptr;
+            if (v) noiseGuided = std::strtof(v, &end);
+            if (v && (end == v || *end || !(noiseGuided > 0.0f) || !(noiseGuided * noiseGuided < 3e38f))) {
+                printf("--noise-guided %s: k_noise is a number above 0 with a finite square\n", v);
+                exit(EXIT_FAILURE);
+            }
+            noiseGuidedSet = true;
+#if !defined(PATHTRACER_MODE)
+            printf("--noise-guided: a path tracer option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -171,13 +192,15 @@ int main(int argc, char* argv[]) {
         exit(EXIT_FAILURE);
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
+    if (noiseGuidedSet && (gpus > 1 || accel)) { printf("--noise-guided: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
     if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
+    if (noiseGuidedSet && !denoise) { printf("--noise-guided: only with --denoise (it steers that filter's colour tolerance)\n"); exit(EXIT_FAILURE); }
     if (accel && (gpus > 1 || denoise)) { printf("--accel bvh: one GPU, and not with --denoise (the accelerated calls have no multi-GPU or denoised form)\n"); exit(EXIT_FAILURE); }
     if (accel && spherePrec != MC_PT_PREC_F32) { printf("--accel bvh: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
 #if !defined(PATHTRACER_MODE)
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
-    (void)zoomSet; (void)denoise; (void)sceneFile; (void)accel;
+    (void)zoomSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -310,6 +333,7 @@ int main(int argc, char* argv[]) {
     if (largeSpheres) app.useLargeSphereWalls();
     app.setSpherePrecision(spherePrec);
     app.setDenoise(denoise);
+    app.setNoiseGuided(noiseGuided);
     if (sceneFile) {   // read and checked here, before a device is touched
         const std::string err = app.loadScene(sceneFile);
         if (!err.empty()) { printf("--scene %s: %s\n", sceneFile, err.c_str()); return EXIT_FAILURE; }
@@ -358,7 +382,10 @@ int main(int argc, char* argv[]) {
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
 #endif
-        if (denoise) printf("denoise: %u passes, %.3f ms device time (render + guides + filter)\n", denoise, app.timing().kernelMs);
+        if (denoise && noiseGuidedSet)
+            printf("denoise: %u passes, noise-guided (k_noise %g), %.3f ms device time (render in two halves + guides + noise plane + filter)\n",
+                   denoise, noiseGuided, app.timing().kernelMs);
+        else if (denoise) printf("denoise: %u passes, %.3f ms device time (render + guides + filter)\n", denoise, app.timing().kernelMs);
         auto t0 = std::chrono::steady_clock::now();
         if (outFile) app.saveRenderedImage(outFile);
         else app.saveRenderedImage();
@@ -372,10 +399,10 @@ int main(int argc, char* argv[]) {
             printf("{\"timing_ms\": {\"init\": %.3f, \"alloc\": %.3f, \"run\": %.3f, \"kernel\": %.3f, \"copy\": %.3f, \"convert\": %.3f, "
                    "\"png\": %.3f, \"total\": %.3f, \"warmup\": %.3f, \"warmup_wait\": %.3f, \"streamed_bands\": %d, "
                    "\"png_join\": %.3f, \"png_assemble\": %.3f, \"png_write\": %.3f}, "
-                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, \"denoise\": %u, \"accel\": \"%s\", "
+                   "\"gpu_postprocess\": %s, \"gpus\": %d, \"overlap_start\": %s, \"reference_png\": %s, \"denoise\": %u, \"noise_guided\": %g, \"accel\": \"%s\", "
                    "\"main_at_ms\": %.3f, \"end_at_ms\": %.3f}\n",
                    initMs, t.allocMs, t.runMs, t.kernelMs, t.copyMs, t.convertMs, t.pngMs, since(tStart), t.warmupMs,
-                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false", denoise, accel ? "bvh" : "linear",
+                   t.warmupWaitMs, t.streamedBands, t.pngJoinMs, t.pngAssembleMs, t.pngWriteMs, gpuPost ? "true" : "false", gpus, overlapStart ? "true" : "false", referencePng ? "true" : "false", denoise, noiseGuided, accel ? "bvh" : "linear",
                    // CLOCK_MONOTONIC at main()'s first timed statement and now: a parent that reads the same clock around the process
                    // gets what `total` cannot contain — loading + static initialisers before main(), teardown after it
                    std::chrono::duration<double, std::milli>(tStart.time_since_epoch()).count(),

@@ -60,6 +60,9 @@ struct PathtracerApp : public ComputeApp {
     // --denoise [P]: run() renders, makes the guide planes and filters on the device (mc_pathtrace_render_denoised) with the default
     // weights and P passes; 0 = off, and then run() is what it was.  One GPU (main.cpp refuses --gpus above 1).
     void setDenoise(uint32_t passes) { denoisePasses = passes; }
+    // --noise-guided [K]: the denoised run() takes its colour tolerance from a measured noise plane (mc_pathtrace_render_denoised_adaptive)
+    // with k_noise = K and the default radius; 0 = off.
+    void setNoiseGuided(float k) { noiseK = k; }
     void setScene(const float* pl, uint32_t np, const float* sp, uint32_t ns) {
         planes.assign(pl, pl + 12 * np);
         spheres.assign(sp, sp + 12 * ns);
@@ -150,6 +153,15 @@ struct PathtracerApp : public ComputeApp {
             mc_pathtrace_denoise_params d;
             mc_pathtrace_denoise_default_params(params.width, params.height, &d);
             d.passes = denoisePasses;
+            if (noiseK > 0.0f) {
+                float k = 0.0f;
+                uint32_t radius = 0;
+                mc_pathtrace_noise_default_params(&k, &radius);
+                check(mc_pathtrace_render_denoised_adaptive(ctx, &params, &d, noiseK, radius, planes.data(), np, spheres.data(), ns,
+                                                            gpuPostprocess ? nullptr : buffer.data(), gpuPostprocess ? rgba8.bytes() : nullptr),
+                      "mc_pathtrace_render_denoised_adaptive");
+                return;
+            }
             check(mc_pathtrace_render_denoised(ctx, &params, &d, planes.data(), np, spheres.data(), ns, gpuPostprocess ? nullptr : buffer.data(),
                                                gpuPostprocess ? rgba8.bytes() : nullptr),
                   "mc_pathtrace_render_denoised");
@@ -188,6 +200,7 @@ private:
     uint32_t workgroupSize;
     mc_pathtrace_params params;
     uint32_t denoisePasses = 0;
+    float noiseK = 0.0f;
     mc_pathtrace_accel* accel = nullptr;   // --accel bvh (lives as long as the process: the app leaves through _Exit or its destructor-free end)
     std::vector<float> planes, spheres;
 };
