@@ -69,6 +69,23 @@ int mc_test_ds_op(mc_context* ctx, int op, const float* a, const float* b, float
  * one runs a kernel of the product library on a caller's plane.) */
 int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_bytes, uint32_t width, uint32_t height, uint32_t* d_list,
                           uint32_t* d_count, void* stream);
+/* The per-lane audit of the Mandelbrot escape loop's fast block (csrc/mandel_block_audit.h).  Every state of the
+ * loop promises, per lane: when its needs_exact test of a block is false, no iteration of the block escaped and the state after the
+ * block's fast iterations equals the state after as many exact steps, bit for bit.  The audit runs each pixel (lane) alone: every block
+ * is stepped exactly, and every block after the first is also run fast from the saved state.  Four uint32_t per lane: n (the count the
+ * render gives), accepted_blocks (needs_exact false), raised_blocks, first_bad (i of the first accepted block in which a step escaped
+ * or the states differ; 0xffffffff if none).  sabotage != 0: needs_exact is taken as false for every block — only what counts as
+ * accepted changes, the lane still continues from the exact state — so first_bad then shows what the test is there to catch.  Blocking.
+ * mc_hook_mandel_block_audit: MC_PRECISION_F32 (MC_MANDEL_FMA honoured), _DS, _F64 on p's whole image or contiguous rows
+ *   [row_begin, row_end) with the c table of the render; out: (row_end - row_begin) x width x 4.  Any other precision or flag, or an
+ *   interleaved tile, is MC_ERR_INVALID_ARGUMENT.
+ * mc_hook_mandel_perturb_block_audit: the perturbation states on a caller's orbit table orbit_xy (Z_0 .. Z_L as L + 1 (re, im) pairs;
+ *   any values, not only a real centre's) and n_lanes lanes of offsets (ux[k], uy[k]).  deep == 0: the plain loop, offsets are dc.
+ *   deep != 0: the rescaled loop with E = exp2, offsets u * 2^exp2.  out: n_lanes x 4.  L == 0, n_lanes == 0 (or > 2^24), max_iter == 0
+ *   or a NULL pointer is MC_ERR_INVALID_ARGUMENT. */
+int mc_hook_mandel_block_audit(mc_context* ctx, const mc_mandelbrot_params* p, int sabotage, uint32_t* out);
+int mc_hook_mandel_perturb_block_audit(mc_context* ctx, const double* orbit_xy, uint32_t L, int deep, int32_t exp2, const double* ux,
+                                       const double* uy, size_t n_lanes, uint32_t max_iter, int sabotage, uint32_t* out);
 /* The arithmetic of mc_mandelbrot_orbit_create_device (csrc/mandel_orbit_fix.h), piece by piece.  Numbers are k + 1 uint64_t limbs, least
  * significant first: k fractional limbs and the integer limb, 1 <= k <= 130 (MC_ERR_INVALID_ARGUMENT otherwise).
  * mc_hook_orbit_mul_host: out = (a * b + 2^(64k - 1)) >> 64k, its low k + 1 limbs, by the shared header's columns and carry resolution run

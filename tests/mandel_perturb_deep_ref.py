@@ -209,9 +209,18 @@ def _fmax(a, b):
     return b if a != a else a if b != b else (a if a >= b else b)
 
 
+EVENTS = ("fresh_m0", "fresh_m_gt0", "renorm_hi", "renorm_lo", "to_plain", "rebase_near", "rebase_end", "rebase_to_plain",
+          "rebase_to_scaled", "rebase_to_zero", "escape_scaled", "escape_plain", "interior_scaled")
+
+
 def scalar_iters(Z, L, ux, uy, E, max_iter, stats=None):
     """The rescaled loop of include/mc_compute.h on Python floats, one pixel (Z a list of (re, im)).  stats (a dict), when given,
-    accumulates "iters" and "scaled" (the iterations begun in the scaled phase)."""
+    accumulates "iters" and "scaled" (the iterations begun in the scaled phase) and a count per event class of EVENTS: the branches
+    of the loop a lane can take (the census tests/test_mandel_block_audit_host.py asserts is complete over the audit's cases)."""
+    def note(key):
+        if stats is not None:
+            stats[key] = stats.get(key, 0) + 1
+
     wx = wy = dx = dy = 0.0
     S, scaled, m = E, True, 0
     for i in range(max_iter):
@@ -220,6 +229,7 @@ def scalar_iters(Z, L, ux, uy, E, max_iter, stats=None):
             stats["scaled"] = stats.get("scaled", 0) + scaled
         zmx, zmy = Z[m]
         if scaled and zmx == 0.0 and zmy == 0.0:
+            note("fresh_m0" if m == 0 else "fresh_m_gt0")
             nS = max(2 * S, E)
             px, pu = _ldexp(1.0, 2 * S - nS), _ldexp(1.0, E - nS)
             nwx = (((wx * wx) - (wy * wy)) * px) + (ux * pu)
@@ -237,25 +247,33 @@ def scalar_iters(Z, L, ux, uy, E, max_iter, stats=None):
         zy = Z[m][1] + ndy
         r = (zx * zx) + (zy * zy)
         if r > 2.0:
+            note("escape_scaled" if scaled else "escape_plain")
             return i
         if m == L or r < ((ndx * ndx) + (ndy * ndy)):
+            note("rebase_end" if m == L else "rebase_near")
             m, dx, dy = 0, zx, zy
             a = _fmax(abs(zx), abs(zy))
             if a >= T:
+                note("rebase_to_plain")
                 scaled, S, wx, wy = False, 0, zx, zy
             else:
+                note("rebase_to_zero" if a == 0.0 else "rebase_to_scaled")
                 scaled = True
                 S = E if a == 0.0 else math.frexp(a)[1]
                 wx, wy = _ldexp(zx, -S), _ldexp(zy, -S)
         else:
             wx, wy, dx, dy, S = nwx, nwy, ndx, ndy, nS
             if scaled and _fmax(abs(ndx), abs(ndy)) >= T:
+                note("to_plain")
                 scaled, S, wx, wy = False, 0, ndx, ndy
             elif scaled:
                 a = _fmax(abs(nwx), abs(nwy))
                 if a > WIN_HI or a < WIN_LO:
+                    note("renorm_hi" if a > WIN_HI else "renorm_lo")
                     e = math.frexp(a)[1]
                     wx, wy, S = _ldexp(nwx, -e), _ldexp(nwy, -e), nS + e
+    if scaled:
+        note("interior_scaled")
     return max_iter
 
 

@@ -80,8 +80,9 @@ def plane(Z, L, W, H, max_iter, scale, rows=None, cols=None):
     return iterate(Z, L, DX, DY, max_iter).reshape(rows.size, cols.size)
 
 
-def scalar_iters(Z, L, dcx, dcy, max_iter):
-    """The loop of include/mc_compute.h on Python floats, one pixel."""
+def scalar_iters(Z, L, dcx, dcy, max_iter, stats=None):
+    """The loop of include/mc_compute.h on Python floats, one pixel.  stats (a dict), when given, counts the rebases by kind:
+    "rebase_end" (the orbit's end, m == L) and "rebase_near" (|z| < |d|)."""
     dx = dy = 0.0
     m = 0
     for i in range(max_iter):
@@ -96,6 +97,9 @@ def scalar_iters(Z, L, dcx, dcy, max_iter):
         if r > 2.0:
             return i
         if m == L or r < ((ndx * ndx) + (ndy * ndy)):
+            if stats is not None:
+                key = "rebase_end" if m == L else "rebase_near"
+                stats[key] = stats.get(key, 0) + 1
             dx, dy, m = zx, zy, 0
         else:
             dx, dy = ndx, ndy

@@ -30,6 +30,15 @@ def test_test_hooks_live_in_their_own_library(B):
     assert not [n for n in names if not hasattr(T, n)]
     assert not [n for n in names if hasattr(B.lib(), n)], "test hooks exported by the product library"
     assert not [n for n in B.declared_symbols() if n.startswith("mc_test_")]
+    # ... and the mc_hook_* functions, which run kernels of the product library on a caller's data (the refine list, the device orbit's
+    # arithmetic, the fast-block audits mc_hook_mandel_block_audit and mc_hook_mandel_perturb_block_audit)
+    hooks = B.declared_hook_symbols()
+    assert len(hooks) == 7 and "mc_hook_mandel_block_audit" in hooks and "mc_hook_mandel_perturb_block_audit" in hooks
+    assert not [n for n in hooks if not hasattr(T, n)]
+    assert not [n for n in hooks if hasattr(B.lib(), n)], "hooks exported by the product library"
+    assert not [n for n in B.declared_symbols() if n.startswith("mc_hook_")]
+    pub = open(B.HEADER_PATH).read()
+    assert "block_audit" not in pub
 
 
 def test_public_header_offers_no_measurement_switch(B, tmp_path):

@@ -264,6 +264,9 @@ def test_lib():
             L.mc_hook_orbit_to_double_host.argtypes = [i32, vp, i32, C.POINTER(C.c_double)]
             L.mc_hook_orbit_create_lanes_host.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int32, C.c_uint32,
                                                           C.POINTER(vp)]
+        if hasattr(L, "mc_hook_mandel_block_audit"):   # the per-lane audit of the escape loop's fast block
+            L.mc_hook_mandel_block_audit.argtypes = [vp, C.POINTER(MandelbrotParams), i32, vp]
+            L.mc_hook_mandel_perturb_block_audit.argtypes = [vp, vp, C.c_uint32, i32, C.c_int32, vp, vp, C.c_size_t, C.c_uint32, i32, vp]
         _test_lib = L
     return _test_lib
 
@@ -272,6 +275,12 @@ def declared_test_symbols():
     """Every function name include/mc_compute_test.h declares."""
     text = re.sub(r"/\*.*?\*/", "", open(TEST_HEADER_PATH).read(), flags=re.S)
     return sorted(set(re.findall(r"\b(mc_test_[a-z0-9_]+)\s*\(", text)))
+
+
+def declared_hook_symbols():
+    """Every mc_hook_* function name include/mc_compute_test.h declares (kernels of the product library run on a caller's data)."""
+    text = re.sub(r"/\*.*?\*/", "", open(TEST_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(mc_hook_[a-z0-9_]+)\s*\(", text)))
 
 
 def _check(status, what):
@@ -1107,6 +1116,28 @@ class Context:
         """mc_hook_mandel_refine: the refine list of the W x H count plane at device pointer d_plane into d_list (device, W * H uint32), its
         length into d_count (device, one uint32).  Asynchronous on `stream`; the list's order is unspecified."""
         _check(test_lib().mc_hook_mandel_refine(self._h, d_plane, iters_bytes, width, height, d_list, d_count, stream), "mc_hook_mandel_refine")
+
+
+    def test_mandel_block_audit(self, p, sabotage=False):
+        """mc_hook_mandel_block_audit: the (tile rows, W, 4) uint32 array (n, accepted_blocks, raised_blocks, first_bad) of p's pixels,
+        each audited alone (F32, DS, F64; include/mc_compute_test.h).  sabotage: needs_exact taken as false."""
+        out = np.empty((tile_rows(p), p.width, 4), np.uint32)
+        _check(test_lib().mc_hook_mandel_block_audit(self._h, C.byref(p), int(bool(sabotage)), _ptr(out)), "mc_hook_mandel_block_audit")
+        return out
+
+    def test_mandel_perturb_block_audit(self, Z, ux, uy, max_iter, deep=False, exp2=0, sabotage=False):
+        """mc_hook_mandel_perturb_block_audit: the (lanes, 4) uint32 array (n, accepted_blocks, raised_blocks, first_bad) of the lanes with
+        offsets (ux[k], uy[k]) against the orbit table Z ((L + 1, 2) float64; any values).  deep: the rescaled loop with E = exp2."""
+        Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 2)
+        ux = np.ascontiguousarray(ux, np.float64).ravel()
+        uy = np.ascontiguousarray(uy, np.float64).ravel()
+        if ux.size != uy.size:
+            raise ValueError("Context.test_mandel_perturb_block_audit: ux and uy differ in length")
+        out = np.empty((ux.size, 4), np.uint32)
+        _check(test_lib().mc_hook_mandel_perturb_block_audit(self._h, _ptr(Z), Z.shape[0] - 1, int(bool(deep)), int(exp2), _ptr(ux), _ptr(uy),
+                                                             ux.size, int(max_iter), int(bool(sabotage)), _ptr(out)),
+               "mc_hook_mandel_perturb_block_audit")
+        return out
 
 
 class Zoom:

@@ -33,6 +33,15 @@ struct PerturbDeepArgs {
 };
 int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
 
+// The per-lane audit of the fast block (mandel_block_audit.h; mc_hook_mandel_block_audit and mc_hook_mandel_perturb_block_audit of
+// libmc_compute_test.so).  d_out: four uint32_t per pixel / lane (n, accepted blocks, raised blocks, first bad block).
+// mandelbrot.hip: F32 (MC_MANDEL_FMA honoured), DS, F64 on p's whole image or contiguous rows.  mandel_perturb.hip: StatePerturb, or
+// (deep) StateDeep with E = exp2, on a device orbit table of L + 1 entries and d_table = [ux[n_lanes] | uy[n_lanes]].
+int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p, bool sabotage, uint32_t* d_out, hipStream_t s);
+int perturb_block_audit_launch(const double2* d_orbit, uint32_t L, bool deep, int32_t exp2, bool has_zero, const double* d_table,
+                               uint32_t n_lanes, uint32_t max_iter, bool sabotage, uint32_t* d_out, hipStream_t s);
+int perturb_deep_block_audit_launch(const PerturbDeepArgs& a, dim3 grid, bool sabotage, uint32_t* d_out, hipStream_t s);
+
 // MC_PRECISION_PERTURB_BLA (mandel_perturb_bla.hip): PERTURB's loop with bilinear skips, for orbits rendered by the plain loop.
 // perturb_launch builds the arguments from the binding: the dc table is PERTURB's, the BLA table the orbit's (mc_mandelbrot_orbit_bla),
 // level-major with (A.x, A.y, B.x, B.y, R) per entry; level k starts at entry S(L-2) - S((L-2) >> k), S(n) = 2n - popcount(n)

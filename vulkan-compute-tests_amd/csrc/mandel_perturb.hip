@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
 #include "mandel_side_record.h"
@@ -128,6 +129,11 @@ struct StatePerturb {
         m = m + 1u;
     }
     static __device__ __forceinline__ bool needs_exact(const Acc& acc) { return acc.hi > 0x3fffffffu || acc.rebase; }
+    // every word the state iterates on, by bit pattern (mandel_block_audit.h)
+    __device__ __forceinline__ bool bits_equal(const StatePerturb& o) const {
+        return Z == o.Z && L == o.L && m == o.m && same_bits(dcx, o.dcx) && same_bits(dcy, o.dcy) && same_bits(dx, o.dx) &&
+               same_bits(dy, o.dy) && same_bits(zmx, o.zmx) && same_bits(zmy, o.zmy);
+    }
 };
 
 template <int U>
@@ -161,6 +167,18 @@ __global__ void __launch_bounds__(64) mandel_perturb_smooth_kernel(PerturbArgs a
     double cx, cy;
     st.escape_c(cx, cy);
     smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
+}
+
+// The per-lane audit of the fast block (mandel_block_audit.h) over a caller's lanes: lane k reads table[k] and table[W + k] (W = the
+// number of lanes), one thread per lane and nothing shared between them.  (After the kernels above, which keep their listings.)
+template <int U, bool Sabotage>
+__global__ void __launch_bounds__(64) mandel_perturb_block_audit_kernel(PerturbArgs a, uint32_t* __restrict__ out) {
+    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.t.W) return;
+    StatePerturb st;
+    st.init(k, k, a);
+    block_audit<StatePerturb, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
 }
 
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
@@ -258,6 +276,24 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     else hipLaunchKernelGGL((mandel_perturb_smooth_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, smooth.q);
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
+}
+
+// mc_hook_mandel_perturb_block_audit: a caller's orbit table and per-lane offsets, both already on the device.
+int perturb_block_audit_launch(const double2* d_orbit, uint32_t L, bool deep, int32_t exp2, bool has_zero, const double* d_table,
+                               uint32_t n_lanes, uint32_t max_iter, bool sabotage, uint32_t* d_out, hipStream_t s) {
+    if (!d_orbit || !d_table || !d_out || !L || !n_lanes || !max_iter) return MC_ERR_INVALID_ARGUMENT;
+    MandelTarget t{};
+    t.W = n_lanes; t.H = n_lanes; t.max_iter = max_iter; t.L = L;
+    t.row_begin = 0u; t.row_end = n_lanes;
+    t.table = d_table;
+    t.orbit = d_orbit;
+    const dim3 grid((n_lanes + 63u) / 64u);
+    if (deep) return perturb_deep_block_audit_launch({t, exp2, has_zero ? 1u : 0u}, grid, sabotage, d_out, s);   // mandel_perturb_deep.hip
+    const PerturbArgs a = {t};
+    if (sabotage) hipLaunchKernelGGL((mandel_perturb_block_audit_kernel<StatePerturb::kBlock, true>), grid, dim3(64), 0, s, a, d_out);
+    else hipLaunchKernelGGL((mandel_perturb_block_audit_kernel<StatePerturb::kBlock, false>), grid, dim3(64), 0, s, a, d_out);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
 }
 
 void perturb_release(mc_context* ctx) {

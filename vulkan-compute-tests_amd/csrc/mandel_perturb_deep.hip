@@ -9,6 +9,7 @@
 // The fast block runs U = 8 steps of the general formula with S fixed and the block's orbit entries fetched at its start; a lane that
 // would renormalise, change phase, rebase, meet a Z = 0 step or escape raises needs_exact, and the block is replayed by step().
 // IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
+#include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
 #include "mandel_smooth.h"
@@ -168,6 +169,12 @@ struct StateDeep {
         const double above = __longlong_as_double((long long)(((uint64_t)((acc.whi & 0x7ff00000u) + 0x00100000u)) << 32));
         return acc.whi >= 0x4ff00000u || acc.wlo < 0x2ff00000u || ldexp2(above, acc.S) >= kT;
     }
+    // every word the state iterates on, by bit pattern, with S, m and the phase (mandel_block_audit.h)
+    __device__ __forceinline__ bool bits_equal(const StateDeep& o) const {
+        return Z == o.Z && L == o.L && E == o.E && zeros == o.zeros && S == o.S && m == o.m && scaled == o.scaled &&
+               same_bits(ux, o.ux) && same_bits(uy, o.uy) && same_bits(wx, o.wx) && same_bits(wy, o.wy) && same_bits(dx, o.dx) &&
+               same_bits(dy, o.dy) && same_bits(zmx, o.zmx) && same_bits(zmy, o.zmy);
+    }
 };
 
 template <int U>
@@ -203,12 +210,32 @@ __global__ void __launch_bounds__(64) mandel_perturb_deep_smooth_kernel(PerturbD
     smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
 }
 
+// The per-lane audit of the fast block (mandel_block_audit.h) over a caller's lanes: lane k reads table[k] and table[W + k] (W = the
+// number of lanes).  (After the kernels above, which keep their listings.)
+template <int U, bool Sabotage>
+__global__ void __launch_bounds__(64) mandel_perturb_deep_block_audit_kernel(PerturbDeepArgs a, uint32_t* __restrict__ out) {
+    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.t.W) return;
+    StateDeep st;
+    st.init(k, k, a);
+    block_audit<StateDeep, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
+}
+
 }  // namespace
 
 int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
     if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
     else if (list) hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
     else hipLaunchKernelGGL((mandel_perturb_deep_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, smooth.q);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
+// (after perturb_deep_launch: the audit kernels are instantiated last, so the kernels above keep their place in the listing)
+int perturb_deep_block_audit_launch(const PerturbDeepArgs& a, dim3 grid, bool sabotage, uint32_t* d_out, hipStream_t s) {
+    if (sabotage) hipLaunchKernelGGL((mandel_perturb_deep_block_audit_kernel<StateDeep::kBlock, true>), grid, dim3(64), 0, s, a, d_out);
+    else hipLaunchKernelGGL((mandel_perturb_deep_block_audit_kernel<StateDeep::kBlock, false>), grid, dim3(64), 0, s, a, d_out);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }

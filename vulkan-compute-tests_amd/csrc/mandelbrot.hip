@@ -26,6 +26,7 @@
 
 #include "ds_arith.h"
 #include "mandel_adaptive.h"
+#include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
 #include "mandel_smooth.h"
@@ -92,6 +93,11 @@ struct StateF32 {
     __device__ __forceinline__ Acc acc_init() const { return 0u; }
     __device__ __forceinline__ void advance_fast(Acc& acc) { acc |= __float_as_uint(advance()); }
     static __device__ __forceinline__ bool needs_exact(Acc or_of_bits) { return or_of_bits > 0x40000000u; }
+    // every word the state iterates on, by bit pattern (mandel_block_audit.h)
+    __device__ __forceinline__ bool bits_equal(const StateF32& o) const {
+        return same_bits(cx, o.cx) && same_bits(cy, o.cy) && same_bits(zx, o.zx) && same_bits(zy, o.zy) && same_bits(sx, o.sx) &&
+               same_bits(sy, o.sy);
+    }
 };
 
 struct StateDS {
@@ -154,6 +160,10 @@ struct StateDS {
         sx = ds_sqr(zx); sy = ds_sqr(zy);
         return ds_greater(ds_add(sx, sy), ds_set(2.0f));
     }
+    __device__ __forceinline__ bool bits_equal(const StateDS& o) const {   // (mandel_block_audit.h)
+        auto eq = [](ds2 a, ds2 b) { return same_bits(a.hi, b.hi) && same_bits(a.lo, b.lo); };
+        return eq(cx, o.cx) && eq(cy, o.cy) && eq(zx, o.zx) && eq(zy, o.zy) && eq(sx, o.sx) && eq(sy, o.sy);
+    }
 };
 
 // Native IEEE double (MC_PRECISION_F64; the exact contract is in include/mc_compute.h).  The loop of StateF32<false> in
@@ -189,6 +199,10 @@ struct StateF64 {
     __device__ __forceinline__ Acc acc_init() const { return 0u; }
     __device__ __forceinline__ void advance_fast(Acc& acc) { acc |= (uint32_t)((uint64_t)__double_as_longlong(advance()) >> 32); }
     static __device__ __forceinline__ bool needs_exact(Acc or_of_high_words) { return or_of_high_words > 0x3fffffffu; }
+    __device__ __forceinline__ bool bits_equal(const StateF64& o) const {   // (mandel_block_audit.h)
+        return same_bits(cx, o.cx) && same_bits(cy, o.cy) && same_bits(zx, o.zx) && same_bits(zy, o.zy) && same_bits(sx, o.sx) &&
+               same_bits(sy, o.sy);
+    }
 };
 
 template <class State, int U>
@@ -225,6 +239,17 @@ __global__ void __launch_bounds__(64) mandelbrot_smooth_kernel(MandelArgs a, uin
     EscapeCapture cap;
     const uint32_t n = escape_time<State, U, EscapeCapture>(st, a.max_iter, ln.valid, &cap);
     smooth_tile_store(a, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
+}
+
+// The per-lane audit of the fast block (mandel_block_audit.h): the tile mapping of mandelbrot_kernel, one thread per pixel and nothing
+// shared between them; four words per pixel, tile-local.  (Last: the kernels above keep their listings.)
+template <class State, int U, bool Sabotage>
+__global__ void __launch_bounds__(64) mandelbrot_block_audit_kernel(MandelArgs a, uint32_t* __restrict__ out) {
+    const TileLane ln = tile_lane(a);
+    if (!ln.valid) return;
+    State st;
+    st.init(ln.gx, ln.gy, a);
+    block_audit<State, U, Sabotage>(st, a.max_iter, out + 4u * ((size_t)ln.ty * a.W + ln.gx));
 }
 
 }  // namespace
@@ -394,6 +419,39 @@ int mandelbrot_list_launch(mc_context* ctx, const mc_mandelbrot_params* grid, co
 
 int mandelbrot_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters_scratch, hipStream_t s) {
     return launch_impl(ctx, p, nullptr, d_iters_scratch, s, true);
+}
+
+// mc_hook_mandel_block_audit: F32 (MC_MANDEL_FMA honoured), DS and F64 with the block lengths the render launches, the c table built
+// as the render builds it; a whole image or a contiguous row range, no other flag.  d_out: tile rows x W x 4 uint32_t.
+int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p, bool sabotage, uint32_t* d_out, hipStream_t s) {
+    if (!ctx || !p || !d_out) return MC_ERR_INVALID_ARGUMENT;
+    if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end) return MC_ERR_INVALID_ARGUMENT;
+    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_DS && p->precision != MC_PRECISION_F64) return MC_ERR_INVALID_ARGUMENT;
+    if (p->row_stride || p->row_block) return MC_ERR_INVALID_ARGUMENT;
+    const bool fma = (p->flags & MC_MANDEL_FMA) != 0u;
+    if ((p->flags & ~(uint32_t)MC_MANDEL_FMA) || (fma && p->precision != MC_PRECISION_F32)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = ensure_c_table(ctx, p, s)) return rc;
+    MandelArgs a;
+    dim3 grid;
+    SampleList l{};
+    if (int rc = launch_geometry(p, nullptr, nullptr, false, nullptr, &a, &grid, &l)) return rc;
+    a.c_tab = (const float*)ctx->ctab.ptr;
+    a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
+    a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
+    a.lut = nullptr;
+    const dim3 block(64);
+#define MC_AUDIT_LAUNCH(State, U)                                                                                      \
+    do {                                                                                                               \
+        if (sabotage) hipLaunchKernelGGL((mandelbrot_block_audit_kernel<State, U, true>), grid, block, 0, s, a, d_out); \
+        else hipLaunchKernelGGL((mandelbrot_block_audit_kernel<State, U, false>), grid, block, 0, s, a, d_out);         \
+    } while (0)
+    if (p->precision == MC_PRECISION_DS) MC_AUDIT_LAUNCH(StateDS, 4);
+    else if (p->precision == MC_PRECISION_F64) MC_AUDIT_LAUNCH(StateF64, 8);
+    else if (fma) MC_AUDIT_LAUNCH(StateF32<true>, 8);
+    else MC_AUDIT_LAUNCH(StateF32<false>, 8);
+#undef MC_AUDIT_LAUNCH
+    MC_HIP_TRY(hipGetLastError());
+    return ctx->note_launch(s);
 }
 
 }  // namespace mc

@@ -227,6 +227,49 @@ int mc_hook_mandel_refine(mc_context* ctx, const void* d_plane, uint32_t iters_b
     return mandelbrot_refine_launch(ctx, d_plane, iters_bytes, width, height, d_list, d_count, s);
 }
 
+// The per-lane audit of the escape-time loop's fast block (mandel_block_audit.h): the kernels live beside the states they audit, in
+// libmc_compute.so's translation units; these hooks stage the buffers.  Blocking.
+int mc_hook_mandel_block_audit(mc_context* ctx, const mc_mandelbrot_params* p, int sabotage, uint32_t* out) {
+    if (!ctx || !p || !out) return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    DeviceBuffer dout;
+    struct Release { DeviceBuffer& b; ~Release() { b.release(); } } release{dout};
+    if (!p->width || p->row_begin >= p->row_end || p->row_end > p->height) return MC_ERR_INVALID_ARGUMENT;
+    const size_t bytes = (size_t)(p->row_end - p->row_begin) * p->width * 4u * sizeof(uint32_t);
+    if (int rc = dout.reserve(bytes)) return rc;
+    if (int rc = mandelbrot_block_audit_launch(ctx, p, sabotage != 0, (uint32_t*)dout.ptr, ctx->stream)) return rc;
+    MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    MC_HIP_TRY(hipMemcpy(out, dout.ptr, bytes, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+int mc_hook_mandel_perturb_block_audit(mc_context* ctx, const double* orbit_xy, uint32_t L, int deep, int32_t exp2, const double* ux,
+                                       const double* uy, size_t n_lanes, uint32_t max_iter, int sabotage, uint32_t* out) {
+    if (!ctx || !orbit_xy || !ux || !uy || !out || !L || !n_lanes || n_lanes > (1u << 24) || !max_iter) return MC_ERR_INVALID_ARGUMENT;
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    DeviceBuffer dorbit, dtab, dout;
+    struct Release {
+        DeviceBuffer &a, &b, &c;
+        ~Release() { a.release(); b.release(); c.release(); }
+    } release{dorbit, dtab, dout};
+    bool has_zero = false;   // some Z_j = 0 exactly, 1 <= j < L (mc_context_bind_mandelbrot_orbit)
+    for (uint32_t j = 1; j < L; j++)
+        if (orbit_xy[2 * (size_t)j] == 0.0 && orbit_xy[2 * (size_t)j + 1] == 0.0) { has_zero = true; break; }
+    const size_t orbit_bytes = ((size_t)L + 1) * 2 * sizeof(double), lane_bytes = n_lanes * sizeof(double);
+    const size_t out_bytes = n_lanes * 4 * sizeof(uint32_t);
+    int rc;
+    if ((rc = dorbit.reserve(orbit_bytes)) || (rc = dtab.reserve(2 * lane_bytes)) || (rc = dout.reserve(out_bytes))) return rc;
+    MC_HIP_TRY(hipMemcpy(dorbit.ptr, orbit_xy, orbit_bytes, hipMemcpyHostToDevice));
+    MC_HIP_TRY(hipMemcpy(dtab.ptr, ux, lane_bytes, hipMemcpyHostToDevice));
+    MC_HIP_TRY(hipMemcpy((char*)dtab.ptr + lane_bytes, uy, lane_bytes, hipMemcpyHostToDevice));
+    if ((rc = perturb_block_audit_launch((const double2*)dorbit.ptr, L, deep != 0, exp2, has_zero, (const double*)dtab.ptr,
+                                         (uint32_t)n_lanes, max_iter, sabotage != 0, (uint32_t*)dout.ptr, ctx->stream)))
+        return rc;
+    MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    MC_HIP_TRY(hipMemcpy(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
 // ---- the device orbit's arithmetic (mandel_orbit_fix.h) ------------------------------------------------------------------------------
 namespace {
 
