@@ -38,7 +38,9 @@ extern "C" {
  * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour; then MC_MANDEL_COLOUR_DISTANCE with
  * mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour; then
  * zoom sequences: mc_mandelbrot_zoom_ratio, mc_mandelbrot_zoom_compose, mc_mandelbrot_zoom_compose_device_async and mc_mandelbrot_zoom_create,
- * _push, _frame and _destroy.
+ * _push, _frame and _destroy; then the path tracer's denoiser, noise plane and BVH calls (their sections say so); then per-pixel sample
+ * budgets: mc_pathtrace_budget_params with mc_pathtrace_budget_default_params, _levels, _resolve, their _device_async forms and
+ * mc_pathtrace_budget_lists_device_async, mc_pathtrace_render_list_device_async, mc_pathtrace_render_budgeted, mc_context_last_budget.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -870,6 +872,87 @@ int mc_pathtrace_denoise_adaptive_device_async(mc_context* ctx, const mc_pathtra
 int mc_pathtrace_render_denoised_adaptive(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_denoise_params* d, float k_noise,
                                           uint32_t radius, const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres,
                                           float* out_rgba_f32, uint8_t* out_rgba8);
+
+/* ---- Path tracer, per-pixel sample budgets from the measured noise plane (no reference counterpart; additions within ABI 3; DESIGN.md
+ *      section 3.20) ---------------------------------------------------------------------------------------------------------------
+ * Every render above gives every pixel the same spp.  The calls below spend samples where the noise plane says the noise is: a pilot of
+ * n0 samples per pixel, one noise plane, a LEVEL l per pixel, then l doublings for the pixels that need them, so that a pixel of level l
+ * ends with n0 << l samples.  Three facts make the result exact (checked in the CPU oracle, tests/test_pt_budget_host.py):
+ *   1. A sample does not depend on spp but for the divisor (pathTracer.comp:357,393,452), and dividing by 2 n instead of n is an exact
+ *      scaling by 1/2 that IEEE addition commutes with.  So the plane a render with spp = 2 n0 leaves after samples [0, n0) is exactly half
+ *      the plain spp = n0 linear accumulator, encode_strict(2 * plane) is the finished plain n0 render, and its [0, n0 / 2) part gives the
+ *      plain render's noise plane, bit for bit.
+ *   2. A doubling continues exactly: the accumulator at divisor 2 n after samples [0, n), plus samples [n, 2 n) at divisor 2 n, is the plain
+ *      spp = 2 n accumulator; times 0.5 it is the start of the next doubling.
+ *   3. The noise plane's V compares half of the samples with all of them: the variance of the n0-sample estimate, halving per doubling.
+ * THE ONE CONDITION: no accumulator component may be a non-zero value below 2^(-126 + max_level + 1) in magnitude, so that every halving
+ *   stays exact (nothing becomes subnormal).  The reference scene's smallest non-zero component is of the order of 1e-2.
+ * Strict arithmetic whatever the render's math_mode: one IEEE-754 fp32 operation per operation stated, in that order, no contraction; host
+ * calls, device kernels and tests/pt_budget_ref.py agree bit for bit (one source: csrc/pt_budget.h).
+ *
+ * LEVELS.  tau2 = target * target in fp32.  Per pixel, from its V_p (mc_pathtrace_noise's plane):
+ *     t = V_p;  l = 0;  while (l < max_level && t > tau2) { t = t * 0.5f;  l = l + 1; }
+ *   One uint8_t per pixel, storage order.  NaN gives 0 (no comparison holds), +inf gives max_level.  The pixel's budget is n0 << l.
+ *   max_level is 0 .. 8; target must be finite and above 0 with a finite fp32 square.  target is in units of the encoded buffer, as
+ *   sqrt(V) is: the noise a pixel may keep.
+ * LISTS.  A uint32_t list of the W * H storage indices bucketed by level, HIGHEST LEVEL FIRST, and the count of every level 0 .. max_level
+ *   in counts[0 .. max_level] (counts: room for 9).  The pixels of level >= r are then the prefix [0, C_r), C_r = counts[r] + ... +
+ *   counts[max_level].  The order inside a bucket is unspecified.  A level byte above max_level counts as max_level.
+ * LIST RENDER (the hot kernel).  mc_pathtrace_render_list_device_async: for every entry idx of d_list[0 .. n_list), with row = idx / width,
+ *   gx = idx % width, gy = height - 1 - row:  acc = d_acc[idx] * prescale, all four components (sample_begin == 0: acc = 0 and the plane
+ *   is not read); then samples [sample_begin, sample_end) are added in sample order as accrad / spp, exactly as the plain render folds
+ *   them (pathTracer.comp:451-452); d_acc[idx] = acc.  NEVER the final encode (:453), even when sample_end == spp: the plane stays
+ *   linear.  Pixels that are not listed are not touched.  Entries must be distinct; an entry >= width * height is skipped, so a bad list
+ *   cannot reach memory outside the plane.  An S-lane group (S = 1, 4, 16) takes one entry.  The kernels are the round-synchronous
+ *   families (slab for six axis-aligned planes + 1 .. 8 spheres, generic with the records in LDS or in memory otherwise) in the tier
+ *   mc_pathtrace_select_kernel reports for the request; S is MC_PT_FORCE_S's if given, else the plain render's rule applied to n_list
+ *   entries.  In MC_PT_MATH_STRICT every sample is the oracle's, so the result does not depend on S or the family.  Whole-image addressing
+ *   only (a row tile or an interleave: MC_ERR_INVALID_ARGUMENT); MC_PT_PRECISION variants and more than 2^31 pixels are refused;
+ *   n_list == 0 launches nothing and returns MC_OK.  d_acc aligned to 16 bytes, d_list to 4.
+ * RESOLVE.  out[p].rgb = encode_strict(acc[p].rgb * (level[p] == 0 ? 2.0f : 1.0f)), out[p].w = acc[p].w; encode_strict is the noise plane's
+ *   E (above) of one component.  A pixel of level 0 still holds the pilot's plane, half its n0 accumulator (fact 1).  out may be acc.
+ * THE CHAIN.  mc_pathtrace_render_budgeted (blocking), p->spp = n0, on the context's stream in this order: the render of [0, n0 / 2) with
+ *   the spp field set to 2 n0; a device copy of that plane; the render of [n0 / 2, n0) continuing it (plane A); a scratch plane
+ *   encode_strict(2 A); the noise plane of the two with scale = (float)(2 n0) / (float)(n0 / 2) and radius b->radius; levels; lists; a
+ *   read-back of the counts; for r = 1 .. max_level with C_r > 0 a list render over the prefix C_r with spp = n0 << r, samples
+ *   [n0 << (r - 1), n0 << r) and prescale 1 for r = 1, 0.5 after (a round with C_r = 0 launches nothing); the resolve in place; for
+ *   out_rgba8 the conversion and rotation of mc_pathtrace_render_rgba8.  Exactly one of out_rgba_f32 and out_rgba8; out_levels (one byte
+ *   per pixel, storage order) may be NULL.  mc_context_last_timing covers all of it, the read-back included; mc_context_last_budget
+ *   reports the pixels per level and the mean samples per pixel of the last call.
+ *   THE PROMISE.  In MC_PT_MATH_STRICT out[p] is mc_pathtrace_render at spp = n0 << level[p], bit for bit, and level is
+ *   mc_pathtrace_budget_levels of mc_pathtrace_noise of the plain n0 render.  No pilot sample is thrown away.  In the fast modes the
+ *   promise is the weaker one of the noise-guided filter: the bits of the same chain made from the separate public calls; the encode is
+ *   the strict one in every mode.  Levels come from the same samples they extend, the usual bias of adaptive sampling.
+ *   Refused with MC_ERR_INVALID_ARGUMENT and a detail string: n0 odd or below 2, n0 << max_level above 2^20, max_level above 8, a row
+ *   tile, an interleave, a sample range, radius above 4, a bad target, flags other than 0, NULL pointers, both or neither image output.
+ *   Not offered: mc_pathtrace_accel scenes, mc_multi_*, budgets other than n0 times a power of two.
+ * mc_pathtrace_budget_default_params: max_level = 4, target = 32, radius = 3 (mc_pathtrace_noise_default_params'), flags = 0.
+ * mc_pathtrace_budget_levels, mc_pathtrace_budget_resolve: host only, usable without a GPU, the same source as the kernels.
+ * The _device_async forms of levels, lists and resolve: on device pointers (vec4 planes aligned to 16 bytes, float and uint32_t planes
+ *   to 4), asynchronous on `stream` (NULL: the context's); the lists' cursors are scratch of the context, shared with every other call.
+ *   An output that overlaps an input is refused, d_out == d_acc of the resolve excepted. */
+typedef struct mc_pathtrace_budget_params {
+    uint32_t max_level;   /* 0 .. 8: a pixel gets at most spp << max_level samples                          */
+    float target;         /* the noise a pixel may keep, in units of the encoded buffer (compare sqrt(V_p)) */
+    uint32_t radius;      /* of the noise plane's window, 0 .. 4                                            */
+    uint32_t flags;       /* 0                                                                              */
+} mc_pathtrace_budget_params;
+int mc_pathtrace_budget_default_params(mc_pathtrace_budget_params* b);
+int mc_pathtrace_budget_levels(uint32_t width, uint32_t height, const float* variance, float target, uint32_t max_level, uint8_t* out_levels);
+int mc_pathtrace_budget_resolve(uint32_t width, uint32_t height, const float* acc, const uint8_t* levels, float* out);
+int mc_pathtrace_budget_levels_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_variance, float target,
+                                            uint32_t max_level, void* d_levels, void* stream);
+int mc_pathtrace_budget_lists_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_levels, uint32_t max_level,
+                                           void* d_list, void* d_counts, void* stream);
+int mc_pathtrace_budget_resolve_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_acc, const void* d_levels,
+                                             void* d_out, void* stream);
+int mc_pathtrace_render_list_device_async(mc_context* ctx, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes,
+                                          const float* spheres, uint32_t n_spheres, const void* d_list, uint32_t n_list, float prescale,
+                                          void* d_acc, void* stream);
+int mc_pathtrace_render_budgeted(mc_context* ctx, const mc_pathtrace_params* p, const mc_pathtrace_budget_params* b, const float* planes,
+                                 uint32_t n_planes, const float* spheres, uint32_t n_spheres, float* out_rgba_f32, uint8_t* out_rgba8,
+                                 uint8_t* out_levels);
+int mc_context_last_budget(mc_context* ctx, uint64_t per_level[9], double* mean_spp);
 
 /* ---- Path tracer through a bounding-volume hierarchy over the spheres (no reference counterpart; additions within ABI 3; DESIGN.md
  *      section 3.18) ---------------------------------------------------------------------------------------------------------------

@@ -91,6 +91,11 @@ class PathtraceDenoiseParams(C.Structure):
                 ("k_normal", C.c_float), ("k_position", C.c_float), ("flags", C.c_uint32)]
 
 
+class PathtraceBudgetParams(C.Structure):
+    """mc_pathtrace_budget_params (include/mc_compute.h): the deepest level, the noise a pixel may keep, the noise window's radius."""
+    _fields_ = [("max_level", C.c_uint32), ("target", C.c_float), ("radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
 def declared_symbols():
     """Every function name include/mc_compute.h declares (used by the export test)."""
     text = open(HEADER_PATH).read()
@@ -216,6 +221,17 @@ def lib():
             L.mc_pathtrace_denoise_adaptive.argtypes = [dp, f32, vp, vp, vp, vp, vp]
             L.mc_pathtrace_denoise_adaptive_device_async.argtypes = [vp, dp, f32, vp, vp, vp, vp, vp, vp]
             L.mc_pathtrace_render_denoised_adaptive.argtypes = [vp, C.POINTER(PathtraceParams), dp, f32, u32, vp, u32, vp, u32, vp, vp]
+        if hasattr(L, "mc_pathtrace_render_budgeted"):   # per-pixel sample budgets
+            bp = C.POINTER(PathtraceBudgetParams)
+            L.mc_pathtrace_budget_default_params.argtypes = [bp]
+            L.mc_pathtrace_budget_levels.argtypes = [u32, u32, vp, f32, u32, vp]
+            L.mc_pathtrace_budget_resolve.argtypes = [u32, u32, vp, vp, vp]
+            L.mc_pathtrace_budget_levels_device_async.argtypes = [vp, u32, u32, vp, f32, u32, vp, vp]
+            L.mc_pathtrace_budget_lists_device_async.argtypes = [vp, u32, u32, vp, u32, vp, vp, vp]
+            L.mc_pathtrace_budget_resolve_device_async.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+            L.mc_pathtrace_render_list_device_async.argtypes = [vp, C.POINTER(PathtraceParams), vp, u32, vp, u32, vp, u32, f32, vp, vp]
+            L.mc_pathtrace_render_budgeted.argtypes = [vp, C.POINTER(PathtraceParams), bp, vp, u32, vp, u32, vp, vp, vp]
+            L.mc_context_last_budget.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         if hasattr(L, "mc_pathtrace_accel_create"):   # the path tracer through a sphere BVH
             pp, u64 = C.POINTER(PathtraceParams), C.c_uint64
             L.mc_pathtrace_accel_create.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
@@ -527,6 +543,43 @@ def pathtrace_denoise_adaptive(d, rgba, normal_t, position_id, variance, k_noise
     out = np.empty(shape, np.float32)
     _check(lib().mc_pathtrace_denoise_adaptive(C.byref(d), k_noise, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(var), _ptr(out)),
            "mc_pathtrace_denoise_adaptive")
+    return out
+
+
+def pathtrace_budget_params(max_level=None, target=None, radius=None, flags=0):
+    """mc_pathtrace_budget_default_params (max_level 4, target 32, radius 3), then the values given."""
+    b = PathtraceBudgetParams()
+    _check(lib().mc_pathtrace_budget_default_params(C.byref(b)), "mc_pathtrace_budget_default_params")
+    if max_level is not None:
+        b.max_level = max_level
+    if target is not None:
+        b.target = target
+    if radius is not None:
+        b.radius = radius
+    b.flags = flags
+    return b
+
+
+def pathtrace_budget_levels(variance, target, max_level):
+    """mc_pathtrace_budget_levels (host only): the uint8 (height, width) level plane of the float32 (height, width) noise plane; a pixel of
+    level l is worth n0 << l samples."""
+    v = np.ascontiguousarray(variance, np.float32)
+    if v.ndim != 2:
+        raise ValueError("pathtrace_budget_levels: variance is a float32 (height, width) array")
+    out = np.empty(v.shape, np.uint8)
+    _check(lib().mc_pathtrace_budget_levels(v.shape[1], v.shape[0], _ptr(v), target, max_level, _ptr(out)), "mc_pathtrace_budget_levels")
+    return out
+
+
+def pathtrace_budget_resolve(acc, levels, in_place=False):
+    """mc_pathtrace_budget_resolve (host only): the encoded float32 (height, width, 4) buffer of the linear accumulator plane acc and the
+    uint8 (height, width) level plane.  in_place: acc (a contiguous float32 array) is overwritten and returned."""
+    a = acc if in_place else np.ascontiguousarray(acc, np.float32)
+    lv = np.ascontiguousarray(levels, np.uint8)
+    if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 3 or a.shape[2] != 4 or lv.shape != a.shape[:2]:
+        raise ValueError("pathtrace_budget_resolve: acc is a contiguous float32 (height, width, 4) array, levels uint8 (height, width)")
+    out = a if in_place else np.empty(a.shape, np.float32)
+    _check(lib().mc_pathtrace_budget_resolve(a.shape[1], a.shape[0], _ptr(a), _ptr(lv), _ptr(out)), "mc_pathtrace_budget_resolve")
     return out
 
 
@@ -1023,6 +1076,51 @@ class Context:
                                                            spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None),
                "mc_pathtrace_render_denoised_adaptive")
         return out
+
+    def pathtrace_budget_levels_device(self, width, height, d_variance, target, max_level, d_levels, stream=0):
+        """mc_pathtrace_budget_levels_device_async: the level plane (one byte per pixel) of the device noise plane d_variance."""
+        _check(lib().mc_pathtrace_budget_levels_device_async(self._h, width, height, d_variance or None, target, max_level, d_levels or None,
+                                                             stream or None), "mc_pathtrace_budget_levels_device_async")
+
+    def pathtrace_budget_lists_device(self, width, height, d_levels, max_level, d_list, d_counts, stream=0):
+        """mc_pathtrace_budget_lists_device_async: the storage indices bucketed by level, highest first, into d_list (width * height uint32)
+        and the pixels of every level into d_counts (nine uint32)."""
+        _check(lib().mc_pathtrace_budget_lists_device_async(self._h, width, height, d_levels or None, max_level, d_list or None, d_counts or None,
+                                                            stream or None), "mc_pathtrace_budget_lists_device_async")
+
+    def pathtrace_budget_resolve_device(self, width, height, d_acc, d_levels, d_out, stream=0):
+        """mc_pathtrace_budget_resolve_device_async: the encoded buffer of the accumulator plane d_acc into d_out (which may be d_acc)."""
+        _check(lib().mc_pathtrace_budget_resolve_device_async(self._h, width, height, d_acc or None, d_levels or None, d_out or None,
+                                                              stream or None), "mc_pathtrace_budget_resolve_device_async")
+
+    def pathtrace_list_device(self, p, d_list, n_list, prescale, d_acc, planes=None, spheres=None, stream=0):
+        """mc_pathtrace_render_list_device_async: samples [sample_begin, sample_end) of p added to the listed pixels of the linear accumulator
+        plane d_acc, each first scaled by prescale; no final encode."""
+        planes, spheres = _scene_tables(planes, spheres)
+        _check(lib().mc_pathtrace_render_list_device_async(self._h, C.byref(p), _ptr(planes), planes.size // 12, _ptr(spheres), spheres.size // 12,
+                                                           d_list or None, n_list, prescale, d_acc or None, stream or None),
+               "mc_pathtrace_render_list_device_async")
+
+    def pathtrace_budgeted(self, p, b=None, planes=None, spheres=None, rgba8=False, want_levels=False):
+        """mc_pathtrace_render_budgeted: the pilot of p.spp samples, the noise plane, levels, lists, the doubling rounds and the resolve in one
+        blocking call; the outputs of pathtrace_denoised, with want_levels the pair (image, uint8 (height, width) levels).  b: the defaults
+        when None."""
+        planes, spheres = _scene_tables(planes, spheres)
+        if b is None:
+            b = pathtrace_budget_params()
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        levels = np.empty((p.height, p.width), np.uint8) if want_levels else None
+        _check(lib().mc_pathtrace_render_budgeted(self._h, C.byref(p), C.byref(b), _ptr(planes), planes.size // 12, _ptr(spheres),
+                                                  spheres.size // 12, None if rgba8 else _ptr(out), _ptr(out) if rgba8 else None, _ptr(levels)),
+               "mc_pathtrace_render_budgeted")
+        return (out, levels) if want_levels else out
+
+    def last_budget(self):
+        """mc_context_last_budget: (pixels per level 0 .. 8, mean samples per pixel) of the last pathtrace_budgeted."""
+        per = (C.c_uint64 * 9)()
+        mean = C.c_double(0.0)
+        _check(lib().mc_context_last_budget(self._h, per, C.byref(mean)), "mc_context_last_budget")
+        return [int(x) for x in per], mean.value
 
     def pathtrace_accel(self, accel, p, acc=None):
         """mc_pathtrace_render_accel: Context.pathtrace through a PathtraceAccel (acc: the accumulator a sample range continues)."""

@@ -66,6 +66,8 @@ struct mc_context {
     // before its first launch and fills it once its stream is idle, from events on the context's stream: t[0] before the first launch,
     // t[1] after the last kernel, t[2] after the copy (the banded render: t[0] and its band events).
     struct Timing { bool valid = false; double kernel_ms = 0.0, copy_ms = 0.0; } timing;
+    // What the last mc_pathtrace_render_budgeted spent (mc_context_last_budget, which only reads it): pixels per level, mean samples per pixel.
+    struct Budget { bool valid = false; uint64_t per_level[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; double mean_spp = 0.0; } budget;
     hipEvent_t t_ev[3] = {nullptr, nullptr, nullptr};
     int create_events();  // t_ev, on first use (the warm-ups make them ahead of the first render)
     int mark(int k);      // records t_ev[k] on the context's stream
@@ -84,6 +86,8 @@ int pathtrace_select_kernel(const mc_pathtrace_params* p, const float* planes, u
                             uint32_t n_spheres, mc_pathtrace_kernel_info* out);
 int pathtrace_launch(mc_context* ctx, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes,
                      const float* spheres, uint32_t n_spheres, void* d_rgba, hipStream_t s);
+int pathtrace_list_launch(mc_context* ctx, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes, const float* spheres,
+                          uint32_t n_spheres, const uint32_t* d_list, uint32_t n_list, float prescale, void* d_acc, hipStream_t s);
 // postprocess.hip
 int convert_rgba8_launch(mc_context* ctx, const void* d_rgba_f32, uint32_t W, uint32_t H, float scale, int rotate180,
                          void* d_rgba8, hipStream_t s);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pathtrace_kernel.h"
+#include "pt_budget_kernel.h"   // (declarations only: the list kernels are instantiated by pt_budget_strict / _fast / _careful.hip)
 
 namespace mc {
 
@@ -409,6 +410,44 @@ void fill_args(const mc_pathtrace_params* p, const SceneFacts& f, const PTPlan& 
     sc.box_ok = box_ok(p, f) ? 1u : 0u;
 }
 
+// A scene the slab kernels do not take: device buffer [records | emissive sphere indices | records with the derived slots], staged into
+// LDS by the kernel — or, for large scenes, read where they lie (the third part).  Uploaded when it differs from the context's copy.
+int upload_scene(mc_context* ctx, const SceneFacts& f, const float* planes, uint32_t n_planes, const float* spheres, uint32_t n_spheres, PTArgs& a,
+                 hipStream_t s) {
+    int rc;
+    const size_t n_rec = (size_t)(n_planes + n_spheres) * 12;
+    const uint32_t n_em = (uint32_t)f.lights.size();
+    std::vector<float> host(n_rec + n_em);
+    if (n_planes) std::memcpy(host.data(), planes, sizeof(float) * 12 * n_planes);
+    if (n_spheres) std::memcpy(host.data() + 12 * (size_t)n_planes, spheres, sizeof(float) * 12 * n_spheres);
+    if (n_em) std::memcpy(host.data() + n_rec, f.lights.data(), sizeof(uint32_t) * n_em);
+    const size_t derived_at = n_rec + ((n_em + 3u) & ~(size_t)3u);   // 16-byte aligned like the records: the kernels read (centre, radius) as one float4
+    host.resize(derived_at + n_rec);   // the staged copy's derived slots (pathtrace_kernel.h, stage_records): the same fp32 operations
+    for (size_t k = 0; k < (size_t)(n_planes + n_spheres); k++) {
+        float* o = host.data() + derived_at + 12 * k;
+        std::memcpy(o, host.data() + 12 * k, 12 * sizeof(float));
+        const float m01 = (o[8] < o[9]) ? o[9] : o[8];        // dm::gmax
+        o[7] = (m01 < o[10]) ? o[10] : m01;
+        o[11] = material_code(o);
+    }
+    if (host != ctx->scene_host || !ctx->scene_buf.ptr) {            // upload only when the scene changed
+        // Earlier launches of THIS context may still read the old copy: wait for the streams it has launched on
+        // (never the whole device — other contexts and streams keep running), then upload in stream order.
+        rc = ctx->drain_launch_streams();
+        if (rc) return rc;
+        if ((rc = ctx->scene_buf.reserve(host.size() * sizeof(float) + 16))) return rc;
+        ctx->scene_host.clear();   // the cache key is only valid once the upload has succeeded
+        MC_HIP_TRY(hipMemcpyAsync(ctx->scene_buf.ptr, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        MC_HIP_TRY(hipStreamSynchronize(s));   // pageable source `host` (a local): staged before the call returns
+        ctx->scene_host = std::move(host);
+    }
+    a.scene.d_obj = (const float*)ctx->scene_buf.ptr;
+    a.scene.d_emissive = (const uint32_t*)((const float*)ctx->scene_buf.ptr + n_rec);
+    a.scene.d_obj_derived = (const float*)ctx->scene_buf.ptr + derived_at;
+    a.scene.n_emissive = n_em;
+    return MC_OK;
+}
+
 }  // namespace
 
 // Host-side scene analysis behind mc_pathtrace_scene_class (no device involved): bit 0 = the scene takes the slab
@@ -444,39 +483,7 @@ int pathtrace_launch(mc_context* ctx, const mc_pathtrace_params* p, const float*
     PTArgs a;
     fill_args(p, f, plan, a);
     a.out = (float4*)d_rgba;
-    if (!plan.slab) {   // any other scene: device buffer [records | emissive sphere indices | records with the derived slots], staged
-                        // into LDS by the kernel — or, for large scenes, read where they lie (the third part)
-        const size_t n_rec = (size_t)(n_planes + n_spheres) * 12;
-        const uint32_t n_em = (uint32_t)f.lights.size();
-        std::vector<float> host(n_rec + n_em);
-        if (n_planes) std::memcpy(host.data(), planes, sizeof(float) * 12 * n_planes);
-        if (n_spheres) std::memcpy(host.data() + 12 * (size_t)n_planes, spheres, sizeof(float) * 12 * n_spheres);
-        if (n_em) std::memcpy(host.data() + n_rec, f.lights.data(), sizeof(uint32_t) * n_em);
-        const size_t derived_at = n_rec + ((n_em + 3u) & ~(size_t)3u);   // 16-byte aligned like the records: the kernels read (centre, radius) as one float4
-        host.resize(derived_at + n_rec);   // the staged copy's derived slots (pathtrace_kernel.h, stage_records): the same fp32 operations
-        for (size_t k = 0; k < (size_t)(n_planes + n_spheres); k++) {
-            float* o = host.data() + derived_at + 12 * k;
-            std::memcpy(o, host.data() + 12 * k, 12 * sizeof(float));
-            const float m01 = (o[8] < o[9]) ? o[9] : o[8];        // dm::gmax
-            o[7] = (m01 < o[10]) ? o[10] : m01;
-            o[11] = material_code(o);
-        }
-        if (host != ctx->scene_host || !ctx->scene_buf.ptr) {            // upload only when the scene changed
-            // Earlier launches of THIS context may still read the old copy: wait for the streams it has launched on
-            // (never the whole device — other contexts and streams keep running), then upload in stream order.
-            rc = ctx->drain_launch_streams();
-            if (rc) return rc;
-            if ((rc = ctx->scene_buf.reserve(host.size() * sizeof(float) + 16))) return rc;
-            ctx->scene_host.clear();   // the cache key is only valid once the upload has succeeded
-            MC_HIP_TRY(hipMemcpyAsync(ctx->scene_buf.ptr, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, s));
-            MC_HIP_TRY(hipStreamSynchronize(s));   // pageable source `host` (a local): staged before the call returns
-            ctx->scene_host = std::move(host);
-        }
-        a.scene.d_obj = (const float*)ctx->scene_buf.ptr;
-        a.scene.d_emissive = (const uint32_t*)((const float*)ctx->scene_buf.ptr + n_rec);
-        a.scene.d_obj_derived = (const float*)ctx->scene_buf.ptr + derived_at;
-        a.scene.n_emissive = n_em;
-    }
+    if (!plan.slab && (rc = upload_scene(ctx, f, planes, n_planes, spheres, n_spheres, a, s))) return rc;
     const uint32_t rows = tile_rows(p->row_begin, p->row_end, a.row_block, a.row_stride);
     // The sample-pool kernels bound their scheduling loop; a tripped bound (a scheduling defect, never seen) sets a bit of the
     // context's status word instead of storing an incomplete image silently: the blocking entry points and
@@ -501,6 +508,31 @@ int pathtrace_launch(mc_context* ctx, const mc_pathtrace_params* p, const float*
     }
     MC_HIP_TRY(hipGetLastError());
     return plan.slab ? MC_OK : ctx->note_launch(s);   // only the generic kernels read a cached device table
+}
+
+// The list render (pt_budget_kernel.h; the entry point and its own checks are pt_budget.hip's): the request planned as a render of forced
+// width is — the round-synchronous family of its scene, in the tier choose_kernel reports — over `n_list` > 0 entries instead of the image.
+// Width: the caller's MC_PT_FORCE_S, else choose_S over the ENTRIES and the range's samples, the rule of the plain render (a round's
+// work is uniform over its list, so the rule that fills the card with an image of that many pixels fills it with the list).
+int pathtrace_list_launch(mc_context* ctx, const mc_pathtrace_params* p, const float* planes, uint32_t n_planes, const float* spheres,
+                          uint32_t n_spheres, const uint32_t* d_list, uint32_t n_list, float prescale, void* d_acc, hipStream_t s) {
+    if (!ctx || !d_acc || !d_list || !n_list) return MC_ERR_INVALID_ARGUMENT;
+    int rc = validate(p, planes, n_planes, spheres, n_spheres);
+    if (rc) return rc;
+    mc_pathtrace_params q = *p;
+    if (((q.flags >> 8) & 0xffu) == 0u) q.flags |= MC_PT_FORCE_S(choose_S(n_list, q.sample_end - q.sample_begin));
+    q.flags |= MC_PT_NO_BOX_KERNEL;   // (a forced width never selects the pool kernel)
+    const SceneFacts f = analyse_scene(planes, n_planes, spheres, n_spheres, fast_guard(&q));
+    const PTPlan plan = choose_kernel(&q, f);
+    PTArgs a;
+    fill_args(&q, f, plan, a);
+    a.out = (float4*)d_acc;
+    if (!plan.slab && (rc = upload_scene(ctx, f, planes, n_planes, spheres, n_spheres, a, s))) return rc;
+    const pt::ListArgs l{d_list, n_list, prescale};
+    constexpr decltype(&pt::launch_list_tier<0>) kTier[] = {pt::launch_list_tier<0>, pt::launch_list_tier<1>, pt::launch_list_tier<2>};
+    if ((rc = kTier[plan.math_mode](a, l, plan.kernel, plan.S, s))) return rc;
+    MC_HIP_TRY(hipGetLastError());
+    return plan.slab ? MC_OK : ctx->note_launch(s);
 }
 
 }  // namespace mc

@@ -52,6 +52,9 @@ int main(int argc, char* argv[]) {
     float noiseGuided = 0.0f;           // --noise-guided [K]: with --denoise, the colour tolerance from a measured noise plane, k_noise = K
                                         // (mc_pathtrace_render_denoised_adaptive); 0 = off
     bool noiseGuidedSet = false;
+    mc_pathtrace_budget_params budget;  // --budget [L] [--noise-target T]: per-pixel sample budgets (mc_pathtrace_render_budgeted), the pilot = spp
+    mc_pathtrace_budget_default_params(&budget);
+    bool budgetSet = false, noiseTargetSet = false;
     const char* outFile = nullptr;
     uint32_t width = 2000, height = 2000, maxIter = 128, precision = MC_PRECISION_F32, mathMode = MC_PT_MATH_STRICT;
     double cx = -0.445, cy = 0.0, sx = 2.34, sy = 2.34;
@@ -167,6 +170,37 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--budget" || a.rfind("--budget=", 0) == 0) {   // L is optional, as --denoise's P is (default: the library's)
+            const char* v = nullptr;
+            if (a.size() > 8) v = argv[i] + 9;
+            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') v = argv[++i];
+            const int level = v ? atoi(v) : (int)budget.max_level;
+            if (level < 0 || level > 8 || (v && (!*v || std::strspn(v, "0123456789") != std::strlen(v)))) {
+                printf("--budget %s: the deepest level is 0 .. 8 (a pixel gets at most spp << level samples)\n", v ? v : "");
+                exit(EXIT_FAILURE);
+            }
+            budget.max_level = (uint32_t)level;
+            budgetSet = true;
+#if !defined(PATHTRACER_MODE)
+            printf("--budget: a path tracer option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
+        else if (a == "--noise-target") {   // with --budget: the noise a pixel may keep, in units of the encoded buffer
+            need(1);
+            const char* v = argv[++i];
+            char* end = nullptr;
+            budget.target = std::strtof(v, &end);
+            if (end == v || *end || !(budget.target > 0.0f) || !(budget.target * budget.target < 3e38f)) {
+                printf("--noise-target %s: a number above 0 with a finite square\n", v);
+                exit(EXIT_FAILURE);
+            }
+            noiseTargetSet = true;
+#if !defined(PATHTRACER_MODE)
+            printf("--noise-target: a path tracer option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--math") {   // strict (the default: bit-identical to the oracle) | fast | careful (mc_compute.h MC_PT_MATH_*)
             need(1);
             mathMode = choice(argv[++i], {{"strict", MC_PT_MATH_STRICT}, {"fast", MC_PT_MATH_FAST}, {"careful", MC_PT_MATH_FAST_CAREFUL}});
@@ -195,12 +229,19 @@ int main(int argc, char* argv[]) {
     if (noiseGuidedSet && (gpus > 1 || accel)) { printf("--noise-guided: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
     if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
     if (noiseGuidedSet && !denoise) { printf("--noise-guided: only with --denoise (it steers that filter's colour tolerance)\n"); exit(EXIT_FAILURE); }
+    if (noiseTargetSet && !budgetSet) { printf("--noise-target: only with --budget (it is the noise a budgeted pixel may keep)\n"); exit(EXIT_FAILURE); }
+    if (budgetSet && denoise) {
+        printf("--budget: not with --denoise (a budgeted-then-filtered chain is not offered: the noise-guided filter needs a half / full pair per pixel)\n");
+        exit(EXIT_FAILURE);
+    }
+    if (budgetSet && (gpus > 1 || accel)) { printf("--budget: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
+    if (budgetSet && spherePrec != MC_PT_PREC_F32) { printf("--budget: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
     if (accel && (gpus > 1 || denoise)) { printf("--accel bvh: one GPU, and not with --denoise (the accelerated calls have no multi-GPU or denoised form)\n"); exit(EXIT_FAILURE); }
     if (accel && spherePrec != MC_PT_PREC_F32) { printf("--accel bvh: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
 #if !defined(PATHTRACER_MODE)
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
-    (void)zoomSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
+    (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -334,6 +375,7 @@ int main(int argc, char* argv[]) {
     app.setSpherePrecision(spherePrec);
     app.setDenoise(denoise);
     app.setNoiseGuided(noiseGuided);
+    if (budgetSet) app.setBudget(budget);
     if (sceneFile) {   // read and checked here, before a device is touched
         const std::string err = app.loadScene(sceneFile);
         if (!err.empty()) { printf("--scene %s: %s\n", sceneFile, err.c_str()); return EXIT_FAILURE; }
@@ -381,6 +423,9 @@ int main(int argc, char* argv[]) {
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
+#endif
+#if defined(PATHTRACER_MODE)
+        if (budgetSet) app.printBudget();
 #endif
         if (denoise && noiseGuidedSet)
             printf("denoise: %u passes, noise-guided (k_noise %g), %.3f ms device time (render in two halves + guides + noise plane + filter)\n",

@@ -63,6 +63,18 @@ struct PathtracerApp : public ComputeApp {
     // --noise-guided [K]: the denoised run() takes its colour tolerance from a measured noise plane (mc_pathtrace_render_denoised_adaptive)
     // with k_noise = K and the default radius; 0 = off.
     void setNoiseGuided(float k) { noiseK = k; }
+    // --budget [L] [--noise-target T]: run() is mc_pathtrace_render_budgeted — a pilot of spp samples, then up to L doublings where the measured
+    // noise is above T — with the default radius.  One GPU, no --denoise, no --accel bvh (main.cpp refuses those).
+    void setBudget(const mc_pathtrace_budget_params& b) { budget = b; budgeted = true; }
+    // "budget: <pixels of level 0 .. L> mean <m> spp" (mc_context_last_budget), after run()
+    void printBudget() const {
+        uint64_t per[9];
+        double mean = 0.0;
+        if (mc_context_last_budget(ctx, per, &mean) != MC_OK) return;
+        printf("budget:");
+        for (uint32_t l = 0; l <= budget.max_level; l++) printf(" %llu", (unsigned long long)per[l]);
+        printf(" mean %.4f spp\n", mean);
+    }
     void setScene(const float* pl, uint32_t np, const float* sp, uint32_t ns) {
         planes.assign(pl, pl + 12 * np);
         spheres.assign(sp, sp + 12 * ns);
@@ -149,6 +161,12 @@ struct PathtracerApp : public ComputeApp {
             else check(mc_pathtrace_render_accel(ctx, accel, &params, buffer.data()), "mc_pathtrace_render_accel");
             return;
         }
+        if (budgeted) {   // both routes, as the denoised calls
+            check(mc_pathtrace_render_budgeted(ctx, &params, &budget, planes.data(), np, spheres.data(), ns, gpuPostprocess ? nullptr : buffer.data(),
+                                               gpuPostprocess ? rgba8.bytes() : nullptr, nullptr),
+                  "mc_pathtrace_render_budgeted");
+            return;
+        }
         if (denoisePasses) {   // both routes: the storage buffer, or (--gpu-postprocess) the RGBA8 image converted and rotated on the device
             mc_pathtrace_denoise_params d;
             mc_pathtrace_denoise_default_params(params.width, params.height, &d);
@@ -201,6 +219,8 @@ private:
     mc_pathtrace_params params;
     uint32_t denoisePasses = 0;
     float noiseK = 0.0f;
+    bool budgeted = false;
+    mc_pathtrace_budget_params budget = {0, 0.0f, 0, 0};
     mc_pathtrace_accel* accel = nullptr;   // --accel bvh (lives as long as the process: the app leaves through _Exit or its destructor-free end)
     std::vector<float> planes, spheres;
 };
