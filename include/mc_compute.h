@@ -34,7 +34,9 @@ extern "C" {
  * then MC_MANDEL_COLOUR_EQUALISED with mc_mandelbrot_histogram_device_async, mc_mandelbrot_equalise_map and
  * mc_mandelbrot_recolour_device_async; then MC_MANDEL_SUPERSAMPLE with mc_mandelbrot_supersample_params and
  * mc_mandelbrot_resolve_device_async; then MC_MANDEL_SUPERSAMPLE_ADAPTIVE with mc_context_last_refined; then
- * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing; then MC_MANDEL_COLOUR_SMOOTH with mc_mandelbrot_render_smooth,
+ * mc_mandelbrot_orbit_create_device with mc_context_last_orbit_timing; then MC_MANDEL_COLOUR_SMOOTH_EQUALISED with
+ * mc_mandelbrot_render_smooth_equalised, mc_mandelbrot_smooth_histogram_device_async, mc_mandelbrot_smooth_equalise_map,
+ * mc_mandelbrot_smooth_remap and mc_mandelbrot_smooth_remap_device_async (the newest); before it MC_MANDEL_COLOUR_SMOOTH with mc_mandelbrot_render_smooth,
  * mc_mandelbrot_render_smooth_device_async, mc_mandelbrot_smooth_count and mc_mandelbrot_smooth_colour; then MC_MANDEL_COLOUR_DISTANCE with
  * mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_distance_plane and mc_mandelbrot_distance_colour; then
  * zoom sequences: mc_mandelbrot_zoom_ratio, mc_mandelbrot_zoom_compose, mc_mandelbrot_zoom_compose_device_async and mc_mandelbrot_zoom_create,
@@ -322,9 +324,11 @@ enum {
                                   /* get their s x s samples (the contract is below, at mc_context_last_refined)            */
     MC_MANDEL_COLOUR_SMOOTH = 1u << 6,/* smooth colouring by a fractional escape count (the contract is below, at           */
                                   /* mc_mandelbrot_render_smooth)                                                           */
-    MC_MANDEL_COLOUR_DISTANCE = 1u << 7 /* the smooth colour shaded by a boundary distance estimate, of a WHOLE image (the      */
+    MC_MANDEL_COLOUR_DISTANCE = 1u << 7,/* the smooth colour shaded by a boundary distance estimate, of a WHOLE image (the      */
                                   /* contract is below, at mc_mandelbrot_render_distance); set WITHOUT MC_MANDEL_COLOUR_SMOOTH */
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
+    MC_MANDEL_COLOUR_SMOOTH_EQUALISED = 1u << 12 /* the smooth count ranked among a WHOLE image's escaped pixels (the contract is   */
+                                  /* below, at mc_mandelbrot_render_smooth_equalised); set WITHOUT MC_MANDEL_COLOUR_SMOOTH     */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
  * 2, 4, 8: valid; 3, 5, 6, 7, 9 .. 15: MC_ERR_INVALID_ARGUMENT.  The contract is below, at mc_mandelbrot_resolve_device_async. */
@@ -445,7 +449,8 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
  * receives n), mc_mandelbrot_render_device_async, mc_mandelbrot_render_rgba8 (whole images and bands), mc_mandelbrot_render_banded, row
  * tiles and interleaved tiles, MC_MANDEL_ITERS_U16 for the n plane, and mc_context_warmup_mandelbrot, which makes the smooth
  * instantiation resident.  Together with MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_SUPERSAMPLE(s >= 2) or MC_MANDEL_SUPERSAMPLE_ADAPTIVE it is
- * MC_ERR_INVALID_ARGUMENT (mc_last_error_detail says which: a rank map or a resolve over fractional counts does not exist yet); so it is
+ * MC_ERR_INVALID_ARGUMENT (mc_last_error_detail says which: the rank map over fractional counts is MC_MANDEL_COLOUR_SMOOTH_EQUALISED, a flag
+ * of its own, below; a resolve over fractional counts does not exist yet); so it is
  * together with the measurement switch MC_MANDEL_FMA of mc_compute_test.h (the contraction switch has no smooth kernel).  The calls
  * that build colours from a plane of integer counts refuse it with MC_ERR_INVALID_ARGUMENT: mc_mandelbrot_recolour_device_async,
  * mc_mandelbrot_resolve_device_async, mc_mandelbrot_assemble_device_async (mc_mandelbrot_histogram_device_async takes no params and so
@@ -517,6 +522,65 @@ int mc_mandelbrot_distance_device_async(mc_context* ctx, const mc_mandelbrot_par
 int mc_mandelbrot_distance_plane(uint32_t width, uint32_t height, uint32_t max_iter, const uint32_t* q, float* out_distance);
 int mc_mandelbrot_distance_colour(uint32_t max_iter, const float k_color[4], const uint32_t* q, const float* distance, uint64_t count,
                                   float threshold_px, float* out_rgba_f32);
+
+/* ---- smooth equalised colouring (the project's own addition; what tests/mandel_smooth_equalise_ref.py restates).
+ *      MC_MANDEL_COLOUR_SMOOTH_EQUALISED in mc_mandelbrot_params.flags.  MC_MANDEL_COLOUR_EQUALISED uses the whole palette on a deep frame
+ *      but draws one flat colour per count; MC_MANDEL_COLOUR_SMOOTH removes the steps but colours by q / (256 M), a sliver of the palette
+ *      on such a frame.  This is the rank map over FRACTIONAL counts: the piecewise-linear cumulative distribution of the smooth plane with
+ *      knots at the integer counts.  A function of the q plane alone, for every precision at once.  With M = max_iter <= 2^24 - 1 and q the
+ *      smooth plane (256 M = interior, an escaped pixel has q <= 256 M - 1):
+ *  - hist[j], j in [0, M]: the number of pixels of the WHOLE image with min(q >> 8, M) = j; uint32_t (width * height > 2^32 - 1 is
+ *    MC_ERR_INVALID_ARGUMENT).  A q above 256 M counts in bin M.  This is NOT the histogram of n: the continuation's k iterations and a
+ *    fraction F = 256 move pixels up, so q >> 8 is the key.
+ *  - E = hist[0] + ... + hist[M-1] (the escaped pixels); C(j) = hist[0] + ... + hist[j-1], C(0) = 0.
+ *  - the knot map, uint32_t qmap[M + 1]: qmap[M] = 256 M; for j < M: qmap[j] = (256 * M * C(j)) / E in unsigned 64-bit integer arithmetic,
+ *    rounded down (256 * (2^24 - 1) * (2^32 - 1) < 2^64: the product cannot overflow); if E = 0, qmap[j] = 0 for j < M.
+ *  - the remap q -> q': q >= 256 M gives q' = 256 M.  Otherwise j = q >> 8, f = q & 255, and
+ *      q' = qmap[j] + (uint32_t)(((uint64_t)(qmap[j + 1] - qmap[j]) * f) >> 8).
+ *  - CONSEQUENCES: q' is non-decreasing in q; an escaped pixel never reaches 256 M (bin j is occupied, so C(j) < E and qmap[j] < 256 M, and
+ *    f <= 255 keeps q' below a larger next knot); qmap[j] >> 8 == mc_mandelbrot_equalise_map(hist)[j]; the share of escaped pixels below
+ *    knot j is C(j) / E, and qmap[j] / (256 M) is within 1 / (256 M) of it.
+ *  - colour: mc_mandelbrot_smooth_colour's expression applied to q'; no new floating-point expression exists, everything new is integer
+ *    arithmetic.  RGBA8 is mc_convert_rgba8's conversion of that vec4, as everywhere.
+ * The flag is a colouring of its own: it implies the smooth count and is set WITHOUT MC_MANDEL_COLOUR_SMOOTH
+ * (MC_MANDEL_COLOUR_SMOOTH | MC_MANDEL_COLOUR_EQUALISED stays MC_ERR_INVALID_ARGUMENT).  mc_mandelbrot_render (out_iters still receives n)
+ * and mc_mandelbrot_render_rgba8 honour it for WHOLE images only (row_begin = 0, row_end = height, no interleave), in all six precisions:
+ * the smooth render of the q plane through the existing kernels (no vec4 leaves the render kernel), the histogram, the table's round trip
+ * (4 (M + 1) bytes), the knot map on the host, the remap and its colour, for _rgba8 the conversion; n, q and q' are scratch of the context;
+ * mc_context_last_timing spans the chain.  MC_ERR_INVALID_ARGUMENT, mc_last_error_detail naming the flag and the calls to use: a row tile
+ * or band of those two; the flag passed to mc_mandelbrot_render_device_async, mc_mandelbrot_render_banded, mc_mandelbrot_render_smooth /
+ * _device_async, mc_mandelbrot_render_distance, mc_mandelbrot_distance_device_async, mc_mandelbrot_recolour_device_async,
+ * mc_mandelbrot_resolve_device_async or mc_mandelbrot_assemble_device_async; the flag together with MC_MANDEL_COLOUR_SMOOTH,
+ * MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_COLOUR_DISTANCE, MC_MANDEL_SUPERSAMPLE(s >= 2), MC_MANDEL_SUPERSAMPLE_ADAPTIVE or the measurement
+ * switch MC_MANDEL_FMA; max_iter > 2^24 - 1.  mc_multi_* refuse it with MC_ERR_UNSUPPORTED.  mc_context_warmup_mandelbrot accepts it and
+ * makes the smooth instantiation and the two kernels below resident; mc_mandelbrot_supersample_params copies the bit like any other.
+ *
+ * mc_mandelbrot_render_smooth_equalised: the blocking whole-image call with all four planes (colours, n, q, q'); any output may be NULL, at
+ * least one must be given; p must carry the flag.
+ * By hand (tiles, one palette over a zoom sequence), three calls:
+ * mc_mandelbrot_smooth_histogram_device_async ADDS the counts of n_pixels smooth counts at d_smooth (uint32_t, aligned to 4; any such
+ * alignment) to d_hist, uint32_t[max_iter + 1] on the device, which the caller has zeroed: tiles and bands accumulate into one table.
+ * n_pixels > 2^32 - 1 or max_iter > 2^24 - 1: MC_ERR_INVALID_ARGUMENT.  The table is the same whatever order the adds arrive in.
+ * mc_mandelbrot_smooth_equalise_map (host only, no device): qmap from hist by the formula above.  NULL pointers, max_iter = 0 or above
+ * 2^24 - 1: MC_ERR_INVALID_ARGUMENT.  The total is NOT compared with any image's size; it is summed in 64 bits, and a total above 2^32 - 1
+ * is MC_ERR_INVALID_ARGUMENT.
+ * mc_mandelbrot_smooth_remap (host only, no device): out_ranked[i] = q' of q[i] for count values.  A q above 256 max_iter, or a qmap that
+ * decreases, has an entry above 256 max_iter or has qmap[max_iter] != 256 max_iter: MC_ERR_INVALID_ARGUMENT.
+ * mc_mandelbrot_smooth_remap_device_async: q' (d_ranked, uint32_t, aligned to 4) and / or its colour (d_rgba_f32, aligned to 16) for the
+ * tile p describes (contiguous or interleaved rows, stored compactly, as mc_mandelbrot_recolour_device_async); at least one output; p
+ * carries the flag; `qmap` is a HOST pointer to max_iter + 1 knots, checked as mc_mandelbrot_smooth_remap checks them; a q above
+ * 256 max_iter on the device is taken as interior.  The pairs (qmap[j], qmap[j + 1] - qmap[j]) are composed on the host and kept as a
+ * device table of the context, like the colour table: one 8-byte gather per pixel. */
+int mc_mandelbrot_render_smooth_equalised(mc_context* ctx, const mc_mandelbrot_params* p, float* out_rgba_f32, uint32_t* out_iters,
+                                          uint32_t* out_smooth, uint32_t* out_ranked);
+int mc_mandelbrot_smooth_histogram_device_async(mc_context* ctx, const void* d_smooth, uint64_t n_pixels, uint32_t max_iter,
+                                                void* d_hist /* uint32_t[max_iter + 1] */, void* stream);
+int mc_mandelbrot_smooth_equalise_map(uint32_t max_iter, const uint32_t* hist /* max_iter + 1 */, uint32_t* qmap /* max_iter + 1 */);
+int mc_mandelbrot_smooth_remap(uint32_t max_iter, const uint32_t* qmap /* max_iter + 1 */, const uint32_t* q, uint64_t count,
+                               uint32_t* out_ranked);
+int mc_mandelbrot_smooth_remap_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth,
+                                            const uint32_t* qmap /* HOST, max_iter + 1 */, void* d_ranked /* or NULL */,
+                                            void* d_rgba_f32 /* or NULL */, void* stream);
 
 /* ---- s x s supersampling (the project's own addition: the reference takes ONE sample per pixel, at its corner, mandelbrot.comp:29-30;
  *      DESIGN.md section 3.11; what tests/mandel_supersample_ref.py restates).  MC_MANDEL_SUPERSAMPLE(s) in flags, s = 2, 4 or 8:
@@ -630,7 +694,7 @@ int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels
  * would write, bit for bit, kept on the device with no host copy (the plain colouring renders straight into the slot; every other mode's
  * chain ends in the context's scratch and is copied device to device).  p is a whole image of the sequence's size (row_begin = 0,
  * row_end = height, no interleave, no MC_MANDEL_ITERS_U16: MC_ERR_INVALID_ARGUMENT otherwise) with any flag combination the blocking
- * whole-image render accepts with colours (plain, equalised, smooth, distance, supersample, adaptive), in any precision - the three
+ * whole-image render accepts with colours (plain, equalised, smooth, distance, smooth equalised, supersample, adaptive), in any precision - the three
  * perturbation precisions use the context's bound orbit - and the precision may change from one keyframe to the next.  The blocking
  * render's own refusals pass through unchanged.  The slots rotate: wide <- the previous keyframe, deep <- the new one.  From the second
  * push on the keyframe's scale must be EXACTLY half the previous keyframe's on both axes: for F32 / DS / F64 the view words read as

@@ -27,6 +27,7 @@ MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTU
 MANDEL_SUPERSAMPLE_ADAPTIVE = 32   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE: with MANDEL_SUPERSAMPLE(s), only pixels whose count differs from a neighbour's are sampled s x s
 MANDEL_COLOUR_SMOOTH = 64       # MC_MANDEL_COLOUR_SMOOTH: smooth colouring by a fractional escape count, 24.8 fixed point (include/mc_compute.h)
 MANDEL_COLOUR_DISTANCE = 128    # MC_MANDEL_COLOUR_DISTANCE: the smooth colour shaded by a boundary distance estimate, whole images; set without MANDEL_COLOUR_SMOOTH
+MANDEL_COLOUR_SMOOTH_EQUALISED = 4096   # MC_MANDEL_COLOUR_SMOOTH_EQUALISED: the smooth count ranked among a whole image's escaped pixels; set without MANDEL_COLOUR_SMOOTH
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
@@ -196,6 +197,12 @@ def lib():
             L.mc_mandelbrot_distance_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, f32, vp, vp, vp]
             L.mc_mandelbrot_distance_plane.argtypes = [u32, u32, u32, vp, vp]
             L.mc_mandelbrot_distance_colour.argtypes = [u32, C.POINTER(f32), vp, vp, C.c_uint64, f32, vp]
+        if hasattr(L, "mc_mandelbrot_smooth_equalise_map"):   # MC_MANDEL_COLOUR_SMOOTH_EQUALISED
+            L.mc_mandelbrot_render_smooth_equalised.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
+            L.mc_mandelbrot_smooth_histogram_device_async.argtypes = [vp, vp, C.c_uint64, u32, vp, vp]
+            L.mc_mandelbrot_smooth_equalise_map.argtypes = [u32, vp, vp]
+            L.mc_mandelbrot_smooth_remap.argtypes = [u32, vp, vp, C.c_uint64, vp]
+            L.mc_mandelbrot_smooth_remap_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp, vp]
         if hasattr(L, "mc_mandelbrot_zoom_compose"):   # zoom sequences
             dbl = C.c_double
             L.mc_mandelbrot_zoom_ratio.argtypes = [u32, u32, C.POINTER(dbl)]
@@ -371,6 +378,27 @@ def equalise_map(max_iter, hist):
         raise ValueError(f"equalise_map: the histogram has {h.size} bins, max_iter + 1 = {max_iter + 1} expected")
     out = np.empty(max(h.size, 1), np.uint32)
     _check(lib().mc_mandelbrot_equalise_map(max_iter, _ptr(h), _ptr(out)), "mc_mandelbrot_equalise_map")
+    return out
+
+
+def smooth_equalise_map(max_iter, hist):
+    """mc_mandelbrot_smooth_equalise_map (host only): the knot map uint32[max_iter + 1] of a histogram uint32[max_iter + 1] of q >> 8."""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if max_iter and h.size != max_iter + 1:
+        raise ValueError(f"smooth_equalise_map: the histogram has {h.size} bins, max_iter + 1 = {max_iter + 1} expected")
+    out = np.empty(max(h.size, 1), np.uint32)
+    _check(lib().mc_mandelbrot_smooth_equalise_map(max_iter, _ptr(h), _ptr(out)), "mc_mandelbrot_smooth_equalise_map")
+    return out
+
+
+def smooth_remap(max_iter, qmap, q):
+    """mc_mandelbrot_smooth_remap (host only): q' of each smooth count q (q <= 256 * max_iter) under the knot map qmap, uint32 of q's shape."""
+    m = np.ascontiguousarray(qmap, np.uint32).reshape(-1)
+    if max_iter and m.size != max_iter + 1:
+        raise ValueError(f"smooth_remap: the map has {m.size} knots, max_iter + 1 = {max_iter + 1} expected")
+    qa = np.ascontiguousarray(q, np.uint32)
+    out = np.empty(qa.shape, np.uint32)
+    _check(lib().mc_mandelbrot_smooth_remap(max_iter, _ptr(m), _ptr(qa), qa.size, _ptr(out)), "mc_mandelbrot_smooth_remap")
     return out
 
 
@@ -934,6 +962,18 @@ class Context:
                "mc_mandelbrot_render_distance")
         return rgba, iters, smooth, dist
 
+    def mandelbrot_smooth_equalised(self, p, want_rgba=True, want_iters=True, want_smooth=True, want_ranked=True):
+        """mc_mandelbrot_render_smooth_equalised (p carries MANDEL_COLOUR_SMOOTH_EQUALISED, a whole image): (rgba float32, n uint32,
+        q uint32, q' uint32), None where not wanted.  q' is the smooth count ranked among the image's escaped pixels."""
+        shape = (p.height, p.width)
+        rgba = np.empty(shape + (4,), np.float32) if want_rgba else None
+        iters = np.empty(shape, np.uint32) if want_iters else None
+        smooth = np.empty(shape, np.uint32) if want_smooth else None
+        ranked = np.empty(shape, np.uint32) if want_ranked else None
+        _check(lib().mc_mandelbrot_render_smooth_equalised(self._h, C.byref(p), _ptr(rgba), _ptr(iters), _ptr(smooth), _ptr(ranked)),
+               "mc_mandelbrot_render_smooth_equalised")
+        return rgba, iters, smooth, ranked
+
     def mandelbrot_banded(self, p, band_rows, rgba8=False):
         """mc_mandelbrot_render_banded: the image (rows [row_begin, row_end)) rendered in pipelined row bands; returns the image — the fp32
         storage buffer, or RGBA8 converted on the device — and the rows_done values the callback heard, in the order it heard them."""
@@ -992,6 +1032,21 @@ class Context:
         from d_smooth, the WHOLE image's uint32 smooth plane."""
         _check(lib().mc_mandelbrot_distance_device_async(self._h, C.byref(p), d_smooth or None, threshold_px, d_distance or None,
                                                          d_rgba or None, stream or None), "mc_mandelbrot_distance_device_async")
+
+    def mandelbrot_smooth_histogram_device(self, d_smooth, n_pixels, max_iter, d_hist, stream=0):
+        """mc_mandelbrot_smooth_histogram_device_async: ADDS the counts of min(q >> 8, max_iter) over n_pixels uint32 smooth counts to the
+        device table uint32[max_iter + 1]."""
+        _check(lib().mc_mandelbrot_smooth_histogram_device_async(self._h, d_smooth or None, n_pixels, max_iter, d_hist or None,
+                                                                 stream or None), "mc_mandelbrot_smooth_histogram_device_async")
+
+    def mandelbrot_smooth_remap_device(self, p, d_smooth, qmap, d_ranked=0, d_rgba=0, stream=0):
+        """mc_mandelbrot_smooth_remap_device_async: q' (uint32) and / or its colour for the tile p describes; qmap is a host array of
+        max_iter + 1 knots."""
+        m = np.ascontiguousarray(qmap, np.uint32).reshape(-1)
+        if m.size != p.max_iter + 1:
+            raise ValueError(f"Context.mandelbrot_smooth_remap_device: the map has {m.size} knots, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_smooth_remap_device_async(self._h, C.byref(p), d_smooth or None, _ptr(m), d_ranked or None,
+                                                             d_rgba or None, stream or None), "mc_mandelbrot_smooth_remap_device_async")
 
     def mandelbrot_histogram_device(self, d_iters, iters_bytes, n_pixels, max_iter, d_hist, stream=0):
         """mc_mandelbrot_histogram_device_async: ADDS the counts of n_pixels values (2 or 4 B each) to the device table

@@ -30,7 +30,7 @@ inline int distance_refuse_flag(const mc_mandelbrot_params* p, const char* who) 
 inline int distance_refuse_combination(const mc_mandelbrot_params* p, const char* who) {
     if (!distance_flag(p)) return MC_OK;
     const char* other = (p->flags & MC_MANDEL_COLOUR_SMOOTH)          ? "MC_MANDEL_COLOUR_SMOOTH (the flag implies the smooth count and is set without it)"
-                        : (p->flags & MC_MANDEL_COLOUR_EQUALISED)     ? "MC_MANDEL_COLOUR_EQUALISED (a rank map over fractional counts does not exist)"
+                        : (p->flags & MC_MANDEL_COLOUR_EQUALISED)     ? "MC_MANDEL_COLOUR_EQUALISED (the rank map over fractional counts is MC_MANDEL_COLOUR_SMOOTH_EQUALISED, a colouring of its own)"
                         : (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) ? "MC_MANDEL_SUPERSAMPLE_ADAPTIVE (a resolve over fractional counts does not exist)"
                         : ((p->flags >> 8) & 15u) > 1u                ? "MC_MANDEL_SUPERSAMPLE (a resolve over fractional counts does not exist)"
                         : (p->flags & MC_MANDEL_FMA)                  ? "MC_MANDEL_FMA (the contraction switch has no smooth kernel)"

@@ -22,115 +22,18 @@
 
 #include "mandel_distance_host.h"
 #include "mandel_equalise.h"
+#include "mandel_histogram_kernel.h"
 #include "mandel_side_record.h"
+#include "mandel_smooth_equalise_host.h"
 #include "mandel_smooth_host.h"
 
 namespace mc {
 
 namespace {
 
-constexpr int kCombineRounds = 4;
-
-template <bool LDS>
-__device__ __forceinline__ void table_add(uint32_t* tab, uint32_t bin, uint32_t count) {
-    if (LDS)
-        (void)__hip_atomic_fetch_add(tab + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else
-        (void)__hip_atomic_fetch_add(tab + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One word per lane (pending == false: the lane has none), called by the whole wave.
-template <bool LDS>
-__device__ __forceinline__ void wave_combine_add(uint32_t* tab, uint32_t v, bool pending, uint32_t lane) {
-#pragma unroll
-    for (int r = 0; r < kCombineRounds; r++) {
-        const unsigned long long act = __ballot(pending);
-        if (!act) return;   // wave-uniform
-        const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
-        const uint32_t lv = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)leader);
-        const bool mine = pending && v == lv;
-        const unsigned long long same = __ballot(mine);
-        if (lane == leader) table_add<LDS>(tab, lv, (uint32_t)__popcll(same));
-        pending = pending && !mine;
-    }
-    if (pending) table_add<LDS>(tab, v, 1u);
-}
-
-template <class T>
-struct Words;
-template <>
-struct Words<uint32_t> {
-    static constexpr int kPer = 4;
-    static __device__ __forceinline__ uint32_t get(const uint4& q, int j) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; }
-};
-template <>
-struct Words<uint16_t> {
-    static constexpr int kPer = 8;
-    static __device__ __forceinline__ uint32_t get(const uint4& q, int j) {
-        const uint32_t w = (j >> 1) == 0 ? q.x : (j >> 1) == 1 ? q.y : (j >> 1) == 2 ? q.z : q.w;
-        return (j & 1) ? (w >> 16) : (w & 0xffffu);
-    }
-};
-
-// head: values in front of the first 16-B boundary, nvec: whole 16-B vectors, tail: values behind them (head, tail < kPer).
-// Block b owns the bins [lo, lo + bins) of range b % n_ranges and share b / n_ranges of the plane (gridDim.x is a multiple of n_ranges);
-// LDS == false: one range, the global table itself.
-template <class T, bool LDS>
-__global__ void __launch_bounds__(256) mandel_histogram_kernel(const T* __restrict__ in, uint32_t head, uint64_t nvec, uint32_t tail,
-                                                               uint32_t max_iter, uint32_t range_bins, uint32_t n_ranges,
-                                                               uint32_t* __restrict__ hist) {
-    extern __shared__ uint32_t lds_tab[];
-    constexpr int kPer = Words<T>::kPer;
-    const uint32_t range = blockIdx.x % n_ranges, share = blockIdx.x / n_ranges, shares = gridDim.x / n_ranges;
-    const uint32_t lo = range * range_bins;
-    const uint32_t bins = max_iter - lo < range_bins ? max_iter - lo + 1u : range_bins;
-    uint32_t* tab = LDS ? lds_tab : hist;
-    if (LDS) {
-        for (uint32_t i = threadIdx.x; i < bins; i += 256u) lds_tab[i] = 0u;
-        __syncthreads();
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint4* __restrict__ vec = reinterpret_cast<const uint4*>(in + head);
-    const uint64_t stride = (uint64_t)shares * 256u;
-    // (the loop's trip count is the same for every lane of a wave: the ballots below see whole waves)
-    for (uint64_t base = (uint64_t)share * 256u + (threadIdx.x & ~63u); base < nvec; base += stride) {
-        const uint64_t i = base + lane;
-        const bool active = i < nvec;
-        uint4 q = make_uint4(0u, 0u, 0u, 0u);
-        if (active) q = vec[i];
-        uint32_t w[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const uint32_t v = Words<T>::get(q, j);
-            w[j] = (v > max_iter ? max_iter : v) - lo;   // the clamp of mandelbrot_assemble_kernel; in this block's range: w[j] < bins
-        }
-        // lane 0 of the wave is active here (base < nvec), and inactive lanes sit above the active ones
-        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)w[0]);
-        bool flat = true;
-#pragma unroll
-        for (int j = 0; j < kPer; j++) flat = flat && w[j] == first;
-        const unsigned long long act = __ballot(active);
-        if (__ballot(active && !flat) == 0ull) {   // the whole wave holds one value: one add
-            if (lane == 0u && first < bins) table_add<LDS>(tab, first, (uint32_t)__popcll(act) * (uint32_t)kPer);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < kPer; j++) wave_combine_add<LDS>(tab, w[j], active && w[j] < bins, lane);
-    }
-    if (share == 0u && threadIdx.x < head + tail) {   // fewer than 2 * kPer values, one per lane, by the first block of every range
-        const uint64_t at = threadIdx.x < head ? (uint64_t)threadIdx.x : (uint64_t)head + nvec * kPer + (threadIdx.x - head);
-        uint32_t v = (uint32_t)in[at];
-        v = (v > max_iter ? max_iter : v) - lo;
-        if (v < bins) table_add<LDS>(tab, v, 1u);
-    }
-    if (LDS) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < bins; i += 256u) {
-            const uint32_t c = lds_tab[i];
-            if (c) table_add<false>(hist, lo + i, c);
-        }
-    }
-}
+// mandel_histogram_kernel<T, LDS>: the kernel of mandel_histogram_kernel.h (one text, shared with the smooth plane's histogram); a count's
+// key is the count itself.
+MC_HISTOGRAM_KERNEL(mandel_histogram_kernel, hist::KeyCount)
 
 // d_rgba[i] = table[min(n[i], M)], table = lut[map[.]] composed on the host: ONE gather per pixel, as mandelbrot_assemble_kernel's.
 // 2-4 B read + 16 B written per pixel, one pixel per lane (the float4 stores of a wave are 1 KB contiguous).
@@ -178,25 +81,12 @@ int mandelbrot_histogram_launch(mc_context* ctx, const void* d_iters, uint32_t i
     if (addr % iters_bytes || reinterpret_cast<uintptr_t>(d_hist) % 4u) return MC_ERR_INVALID_ARGUMENT;
     if (max_iter == 0xffffffffu) return MC_ERR_INVALID_ARGUMENT;   // (max_iter + 1 bins must be countable in 32 bits)
     if (!n_pixels) return MC_OK;
-    const uint64_t all_bins = (uint64_t)max_iter + 1u;
-    const uint32_t range_bins = (uint32_t)std::min<uint64_t>(all_bins, kHistRangeBins);
-    const uint32_t n_ranges = (uint32_t)((all_bins + range_bins - 1u) / range_bins);
-    const bool lds = n_ranges <= kHistMaxRanges;
-    const uint32_t per = 16u / iters_bytes;
-    uint32_t head = (uint32_t)(((16u - addr % 16u) % 16u) / iters_bytes);
-    if (head > n_pixels) head = (uint32_t)n_pixels;
-    const uint64_t nvec = (n_pixels - head) / per;
-    const uint32_t tail = (uint32_t)(n_pixels - head - nvec * per);
-    // 8 blocks of 4 waves per CU for the global table; an LDS range's size bounds the blocks a CU holds (160 KB of LDS).  Every range
-    // gets the same number of blocks (its shares of the plane), at least one.
-    const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount;
-    const size_t shared = lds ? (size_t)range_bins * 4u : 0;
-    const uint32_t per_cu = lds ? std::max<uint32_t>(1u, std::min<uint32_t>(8u, (uint32_t)((160u << 10) / shared))) : 8u;
-    const uint32_t ranges = lds ? n_ranges : 1u;
-    uint64_t shares = std::min<uint64_t>((nvec + 255u) / 256u, std::max<uint64_t>(1u, (uint64_t)cus * per_cu / ranges));
-    if (!shares) shares = 1;
-    const dim3 grid((uint32_t)(shares * ranges)), block(256);
-    const uint32_t rb = lds ? range_bins : (uint32_t)std::min<uint64_t>(all_bins, 0xffffffffull);
+    const hist::Geometry g = hist::geometry(addr, iters_bytes, n_pixels, max_iter, (uint32_t)ctx->props.multiProcessorCount);
+    const dim3 grid(g.grid), block(256);
+    const bool lds = g.lds;
+    const size_t shared = g.shared;
+    const uint32_t head = g.head, tail = g.tail, rb = g.range_bins, ranges = g.ranges;
+    const uint64_t nvec = g.nvec;
     uint32_t* h = (uint32_t*)d_hist;
     if (iters_bytes == 4u) {
         const uint32_t* in = (const uint32_t*)d_iters;
@@ -359,6 +249,7 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
                                         const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_iters || !map || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u))
         return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = smooth_equalised_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     if (int rc = distance_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     MC_HIP_TRY(hipSetDevice(ctx->device));

@@ -17,6 +17,7 @@
 
 #include "mandel_equalise.h"
 #include "mandel_distance_host.h"
+#include "mandel_smooth_equalise_host.h"
 #include "mandel_smooth_host.h"
 
 namespace mc {
@@ -202,6 +203,7 @@ int mc_mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbro
 int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes,
                                        const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_samples || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = smooth_equalised_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (int rc = distance_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) {

@@ -236,6 +236,10 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
         set_error_detail("mc_multi_*: MC_MANDEL_COLOUR_DISTANCE is single-device only");
         return MC_ERR_UNSUPPORTED;
     }
+    if (p->flags & MC_MANDEL_COLOUR_SMOOTH_EQUALISED) {   // likewise: a histogram of the whole image's smooth plane
+        set_error_detail("mc_multi_*: MC_MANDEL_COLOUR_SMOOTH_EQUALISED is single-device only");
+        return MC_ERR_UNSUPPORTED;
+    }
     if (p->flags & MC_MANDEL_COLOUR_EQUALISED) {   // likewise: the histogram of the whole image is taken on one device
         set_error_detail("mc_multi_*: MC_MANDEL_COLOUR_EQUALISED is single-device only");
         return MC_ERR_UNSUPPORTED;

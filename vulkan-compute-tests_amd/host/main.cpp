@@ -3,7 +3,7 @@
 // Mandelbrot app renders 2000x2000; lifecycle init() -> preRun() -> run() -> saveRenderedImage();
 // std::runtime_error -> message + EXIT_FAILURE.  Options (never reinterpreting the two positional
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
-// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised|smooth|distance (equalised: histogram-equalised colouring of the whole image; smooth: fractional escape counts, no bands; distance: the smooth colour darkened where the boundary is closer than a pixel), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
+// --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised|smooth|distance|smooth-equalised (smooth-equalised: the smooth count ranked among the image's escaped pixels; equalised: histogram-equalised colouring of the whole image; smooth: fractional escape counts, no bands; distance: the smooth colour darkened where the boundary is closer than a pixel), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
 // --zoom K F (the Mandelbrot app: --centre / --scale is the DEEPEST of K + 1 keyframes one octave apart; K * F + 1 frames, each composed on
 // the device from the two keyframes that bracket it and written as <out>_%05u.<ext>),
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
@@ -40,7 +40,7 @@ int main(int argc, char* argv[]) {
     bool quiet = false, gpuPost = false, timingJson = false, referencePng = false, overlapStart = true, fullTeardown = false;
     int streamedSave = ComputeApp::kStreamAuto;
     int pngThreads = 0;
-    uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED) | smooth (MC_MANDEL_COLOUR_SMOOTH) | distance (MC_MANDEL_COLOUR_DISTANCE)
+    uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED) | smooth (MC_MANDEL_COLOUR_SMOOTH) | distance (MC_MANDEL_COLOUR_DISTANCE) | smooth-equalised (MC_MANDEL_COLOUR_SMOOTH_EQUALISED)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
     bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
@@ -95,7 +95,8 @@ int main(int argc, char* argv[]) {
                                       // | smooth: the fractional escape count, interpolated between neighbouring palette entries
             need(1);
             colour = choice(argv[++i], {{"reference", 0u}, {"equalised", (uint32_t)MC_MANDEL_COLOUR_EQUALISED},
-                                        {"smooth", (uint32_t)MC_MANDEL_COLOUR_SMOOTH}, {"distance", (uint32_t)MC_MANDEL_COLOUR_DISTANCE}});
+                                        {"smooth", (uint32_t)MC_MANDEL_COLOUR_SMOOTH}, {"distance", (uint32_t)MC_MANDEL_COLOUR_DISTANCE},
+                                        {"smooth-equalised", (uint32_t)MC_MANDEL_COLOUR_SMOOTH_EQUALISED}});
 #if !defined(MANDELBROT_MODE)
             printf("--colour: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
@@ -256,6 +257,11 @@ int main(int argc, char* argv[]) {
         if (supersample > 1u) { printf("--colour distance: does not combine with --supersample (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
         app.setColourFlags(colour);
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour distance renders the whole image in one call; --streamed-save has no effect\n");
+        streamedSave = ComputeApp::kStreamOff;
+    } else if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED) {   // the rank over the whole image's smooth plane: the whole-image calls, as equalised
+        if (supersample > 1u) { printf("--colour smooth-equalised: does not combine with --supersample (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
+        app.setColourFlags(colour);
+        if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour smooth-equalised renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     } else if (colour) {   // the histogram needs the whole image: one mc_mandelbrot_render(_rgba8), never the banded, streamed save
         app.setColourFlags(colour);
@@ -423,6 +429,7 @@ int main(int argc, char* argv[]) {
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
+        if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1) app.printSmoothEqualisedStats();
 #endif
 #if defined(PATHTRACER_MODE)
         if (budgetSet) app.printBudget();

@@ -27,7 +27,7 @@ struct MandelbrotApp : public ComputeApp {
         split(sx, params.scale_x_hi, params.scale_x_lo);
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
-    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, _SMOOTH, _DISTANCE (main.cpp --colour)
+    void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, _SMOOTH, _DISTANCE, _SMOOTH_EQUALISED (main.cpp --colour)
     void setSupersample(uint32_t s) { params.flags |= MC_MANDEL_SUPERSAMPLE(s); }   // 2, 4 or 8 (main.cpp --supersample)
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
     // MC_PRECISION_PERTURB / _BLA / _BLA_DEEP: the view is this orbit's (the app owns it; for the BLA precisions main() has built the
@@ -189,6 +189,24 @@ struct MandelbrotApp : public ComputeApp {
         for (float d : distance) below += d < 1.0f ? 1u : 0u;
         printf("distance below 1 pixel: %llu of %llu pixels (%.2f %%)\n", (unsigned long long)below, (unsigned long long)distance.size(),
                100.0 * (double)below / (double)distance.size());
+    }
+
+    // --colour smooth-equalised: how many pixels escaped and how many of the histogram's bins (integer parts of the smooth count) they
+    // occupy, the knots the palette is spread over.  The image came through the whole-image calls, which keep no plane: q is rendered
+    // once more.
+    void printSmoothEqualisedStats() {
+        std::vector<uint32_t> q((size_t)resx * resy);
+        check(mc_mandelbrot_render_smooth_equalised(ctx, &params, nullptr, nullptr, q.data(), nullptr), "mc_mandelbrot_render_smooth_equalised");
+        const uint32_t M = params.max_iter;
+        std::vector<uint8_t> seen(M, 0);
+        uint64_t escaped = 0, occupied = 0;
+        for (uint32_t v : q)
+            if (v < 256u * M) {
+                escaped++;
+                if (!seen[v >> 8]) { seen[v >> 8] = 1; occupied++; }
+            }
+        printf("smooth equalised: %llu of %llu pixels escaped, %llu of %u bins occupied\n", (unsigned long long)escaped,
+               (unsigned long long)q.size(), (unsigned long long)occupied, M);
     }
 
 private:
