@@ -42,7 +42,9 @@ extern "C" {
  * zoom sequences: mc_mandelbrot_zoom_ratio, mc_mandelbrot_zoom_compose, mc_mandelbrot_zoom_compose_device_async and mc_mandelbrot_zoom_create,
  * _push, _frame and _destroy; then the path tracer's denoiser, noise plane and BVH calls (their sections say so); then per-pixel sample
  * budgets: mc_pathtrace_budget_params with mc_pathtrace_budget_default_params, _levels, _resolve, their _device_async forms and
- * mc_pathtrace_budget_lists_device_async, mc_pathtrace_render_list_device_async, mc_pathtrace_render_budgeted, mc_context_last_budget.
+ * mc_pathtrace_budget_lists_device_async, mc_pathtrace_render_list_device_async, mc_pathtrace_render_budgeted, mc_context_last_budget;
+ * then zoom sequences from count keyframes: mc_mandelbrot_zoom_blend_map, mc_mandelbrot_zoom_compose_counts,
+ * mc_mandelbrot_zoom_compose_counts_device_async and mc_mandelbrot_zoom_counts_create, _push, _frame, _maps and _destroy.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -678,7 +680,8 @@ int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels
  *    exceeds 1.0, so the byte conversion cannot wrap.
  *  - STATED LIMIT: the central region is `deep` minified by up to 2 x through one bilinear tap, which aliases; keyframes rendered with
  *    MC_MANDEL_SUPERSAMPLE are the documented answer (a wider filter is a later step).  MC_MANDEL_COLOUR_EQUALISED ranks each keyframe by
- *    itself, so the palette shifts between octaves (one map over a sequence: the by-hand histogram calls above).
+ *    itself, so the palette shifts between octaves (one map over a sequence: the by-hand histogram calls above; one map per FRAME that
+ *    moves with the zoom: the count keyframes below, mc_mandelbrot_zoom_counts_*).
  *
  * mc_mandelbrot_zoom_ratio (host only): r = exp2(-(double)step / (double)steps_per_octave); exactly 1.0 at step 0 and exactly 0.5 at
  * step == steps_per_octave.  step > steps_per_octave or steps_per_octave == 0: MC_ERR_INVALID_ARGUMENT.  It exists so that an
@@ -718,6 +721,85 @@ int mc_mandelbrot_zoom_create(mc_context* ctx, uint32_t width, uint32_t height, 
 int mc_mandelbrot_zoom_push(mc_mandelbrot_zoom* z, const mc_mandelbrot_params* p);
 int mc_mandelbrot_zoom_frame(mc_mandelbrot_zoom* z, double r, float* out_rgba_f32, uint8_t* out_rgba8);
 int mc_mandelbrot_zoom_destroy(mc_mandelbrot_zoom* z);
+
+/* ---- zoom sequences from COUNT keyframes (the project's own addition; what tests/mandel_zoom_counts_ref.py
+ *      restates).  The sequence above keeps a keyframe as colours, so with the two equalised colourings an in-between frame shows two rank
+ *      maps side by side, along the rectangle of the deep keyframe.  Here a keyframe is a plane of uint32_t - the count n, or for the two
+ *      smooth colourings the smooth count q - and a frame colours the taps of BOTH keyframes through ONE map that moves with the zoom.  A
+ *      count keyframe is 4 bytes per pixel instead of 16, so the same calls also serve the plain and the smooth colouring.
+ *  - M = max_iter.  The colouring is the colour bits of p->flags: exactly one of 0 (plain), MC_MANDEL_COLOUR_EQUALISED,
+ *    MC_MANDEL_COLOUR_SMOOTH, MC_MANDEL_COLOUR_SMOOTH_EQUALISED.
+ *  - the moving map, mc_mandelbrot_zoom_blend_map (host only, no device): with s = step, S = steps_per_octave, S >= 1, s <= S,
+ *      out[j] = (map_wide[j] * (S - s) + map_deep[j] * s) / S    in unsigned 64-bit arithmetic, rounded down, j < entries.
+ *    Every entry must be <= 256 * (2^24 - 1) (MC_ERR_INVALID_ARGUMENT otherwise): entries and weights are below 2^32 and the weights sum
+ *    to S, so no product and no sum can reach 2^64.  It serves the rank map (entries <= M) and the knot map (entries <= 256 M).
+ *    Consequences: s = 0 gives map_wide and s = S gives map_deep, exactly; non-decreasing inputs give a non-decreasing output; out[j] lies
+ *    between the two inputs; an entry equal in both (map[M] = M, qmap[M] = 256 M) is kept; for 0 < s < S a count that is occupied in
+ *    either keyframe maps BELOW the top entry, because one of the two inputs is below it and its weight is at least 1, so an escaped tap
+ *    never takes the interior colour.  STATED, not corrected: at s = 0 with a deep keyframe present, a deep tap whose count no wide pixel
+ *    reaches may take the interior colour (the applications never compose that frame: step 0 is the previous octave's last frame).
+ *  - a tap's colour, from a plane of uint32_t, lut being mc_mandelbrot_colour_lut(M, k_color):
+ *      plain             lut[min(n, M)]
+ *      equalised         lut[map[min(n, M)]]
+ *      smooth            mc_mandelbrot_smooth_colour's expression of q
+ *      smooth equalised  that expression of mc_mandelbrot_smooth_remap's q'
+ *    No new floating-point expression exists.  `map` is NULL for plain and smooth and required for the other two (M + 1 entries, a HOST
+ *    table), checked as mc_mandelbrot_recolour_device_async (no entry above M) and mc_mandelbrot_smooth_remap (non-decreasing knots, the
+ *    last one 256 M) check theirs.  A q above 256 M is MC_ERR_INVALID_ARGUMENT on the host and is taken as interior on the device, as in
+ *    mc_mandelbrot_smooth_remap_device_async.
+ *  - a frame is mc_mandelbrot_zoom_compose's contract, unchanged, applied to those tap colours (positions, source test, taps, mix with
+ *    its f == 0 case, alpha 1, the RGBA8 conversion).  Bit for bit:
+ *      frame = mc_mandelbrot_zoom_compose(colour(wide), colour(deep), r).
+ *
+ * mc_mandelbrot_zoom_compose_counts (host only, the same source as the kernel) and mc_mandelbrot_zoom_compose_counts_device_async (the
+ * stage by hand; asynchronous on `stream`, NULL: the context's).  p supplies width, height, max_iter, k_color and the colouring; it is a
+ * whole image (row_begin = 0, row_end = height) with no interleave and no MC_MANDEL_ITERS_U16; precision and view words are not read.
+ * Refusals, all MC_ERR_INVALID_ARGUMENT with mc_last_error_detail naming the call: mc_mandelbrot_zoom_compose_device_async's (here the
+ * keyframes and d_rgba8 4-byte aligned, d_rgba_f32 16-byte aligned; an output that overlaps a keyframe or the other output; r outside
+ * [0.5, 1] or NaN; no output); more than one colour bit; MC_MANDEL_COLOUR_DISTANCE, MC_MANDEL_SUPERSAMPLE(s >= 2),
+ * MC_MANDEL_SUPERSAMPLE_ADAPTIVE or the measurement switch of mc_compute_test.h that contracts the fp32 render; a map where none belongs,
+ * or none where one does; max_iter above 2^24 - 1 for the two smooth colourings.
+ *
+ * The sequence object.  mc_mandelbrot_zoom_counts_create allocates two slots of 4 bytes per pixel on ctx's device (a failure:
+ * MC_ERR_OUT_OF_MEMORY; width * height above 2^32 - 1: MC_ERR_INVALID_ARGUMENT); the context must outlive it.
+ * mc_mandelbrot_zoom_counts_push renders p's count plane straight into a slot through the device forms (the n plane alone, or for the two
+ * smooth colourings the q plane alone; no vec4 leaves the render kernel), in all six precisions - the perturbation precisions use the
+ * context's bound orbit.  For the two equalised colourings it then runs the histogram kernel over the slot, reads the table back
+ * (4 (M + 1) bytes) and builds the rank map (mc_mandelbrot_equalise_map) or the knot map (mc_mandelbrot_smooth_equalise_map) on the host;
+ * the map is kept with the slot, on the host and on the device.  mc_mandelbrot_zoom_push's rules carry over: a whole image of the
+ * sequence's size, the exact-halving test on (frexp mantissa, exponent) pairs from the second push on, the slots' rotation, and the state
+ * after a refusal (the sequence as it was) or any other failure (the newest keyframe alone).  The first push fixes the colouring,
+ * max_iter and k_color; a later push that differs in one of them is MC_ERR_INVALID_ARGUMENT.  The precision may change between keyframes.
+ * mc_context_last_timing spans the chain, copy_ms = 0.
+ * mc_mandelbrot_zoom_counts_frame (blocking) composes the frame at r = mc_mandelbrot_zoom_ratio(step, steps_per_octave) into either or
+ * both host outputs.  With two keyframes the frame's map is the blend above at (step, steps_per_octave), built ON THE DEVICE from the two
+ * device maps by a table kernel (one thread per entry) that writes lut[map_f[.]] or the (knot, step) pairs the remap gathers from; then
+ * the compose kernel and the copy to the host, with no other host round trip.  With one keyframe: that keyframe alone with its own map, at
+ * any step.  With none: MC_ERR_INVALID_ARGUMENT.
+ * mc_mandelbrot_zoom_counts_maps copies the maps of the keyframes held, M + 1 entries each (either pointer may be NULL; with one keyframe
+ * held it is both the wide and the deep one).  MC_ERR_INVALID_ARGUMENT for the plain or the smooth colouring, or before a push.
+ * Identities: frame(step = steps_per_octave) is the deep keyframe's own mc_mandelbrot_render image with that colouring, bit for bit;
+ * frame(0) with one keyframe is that keyframe's image; in EVERY frame a pixel whose four taps share one count n gets exactly the tap
+ * colour of n under the frame's map, whichever keyframe it read (no seam: the vec4 sequence violates this wherever the two keyframes' maps
+ * differ).
+ * STATED LIMITS: a palette position still changes over time at a fixed point of the plane, continuously, through the blend; the blend is
+ * linear in step, not in the histograms; one bilinear tap still aliases the minified centre and count keyframes cannot be supersampled
+ * (distance shading, supersampling and adaptive supersampling stay with the vec4 sequence); one GPU. */
+int mc_mandelbrot_zoom_blend_map(uint32_t entries, const uint32_t* map_wide, const uint32_t* map_deep, uint32_t step,
+                                 uint32_t steps_per_octave, uint32_t* out);
+int mc_mandelbrot_zoom_compose_counts(const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep /* or NULL */,
+                                      const uint32_t* map /* or NULL */, double r, float* out_rgba_f32 /* or NULL */,
+                                      uint8_t* out_rgba8 /* or NULL */);
+int mc_mandelbrot_zoom_compose_counts_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide, const void* d_deep,
+                                                   const uint32_t* map /* HOST, or NULL */, double r, void* d_rgba_f32, void* d_rgba8,
+                                                   void* stream);
+typedef struct mc_mandelbrot_zoom_counts mc_mandelbrot_zoom_counts;
+int mc_mandelbrot_zoom_counts_create(mc_context* ctx, uint32_t width, uint32_t height, mc_mandelbrot_zoom_counts** out);
+int mc_mandelbrot_zoom_counts_push(mc_mandelbrot_zoom_counts* z, const mc_mandelbrot_params* p);
+int mc_mandelbrot_zoom_counts_frame(mc_mandelbrot_zoom_counts* z, uint32_t step, uint32_t steps_per_octave, float* out_rgba_f32,
+                                    uint8_t* out_rgba8);
+int mc_mandelbrot_zoom_counts_maps(mc_mandelbrot_zoom_counts* z, uint32_t* wide_map /* or NULL */, uint32_t* deep_map /* or NULL */);
+int mc_mandelbrot_zoom_counts_destroy(mc_mandelbrot_zoom_counts* z);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

@@ -212,6 +212,16 @@ def lib():
             L.mc_mandelbrot_zoom_push.argtypes = [vp, C.POINTER(MandelbrotParams)]
             L.mc_mandelbrot_zoom_frame.argtypes = [vp, dbl, vp, vp]
             L.mc_mandelbrot_zoom_destroy.argtypes = [vp]
+        if hasattr(L, "mc_mandelbrot_zoom_compose_counts"):   # zoom sequences from count keyframes
+            dbl, mp = C.c_double, C.POINTER(MandelbrotParams)
+            L.mc_mandelbrot_zoom_blend_map.argtypes = [u32, vp, vp, u32, u32, vp]
+            L.mc_mandelbrot_zoom_compose_counts.argtypes = [mp, vp, vp, vp, dbl, vp, vp]
+            L.mc_mandelbrot_zoom_compose_counts_device_async.argtypes = [vp, mp, vp, vp, vp, dbl, vp, vp, vp]
+            L.mc_mandelbrot_zoom_counts_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+            L.mc_mandelbrot_zoom_counts_push.argtypes = [vp, mp]
+            L.mc_mandelbrot_zoom_counts_frame.argtypes = [vp, u32, u32, vp, vp]
+            L.mc_mandelbrot_zoom_counts_maps.argtypes = [vp, vp, vp]
+            L.mc_mandelbrot_zoom_counts_destroy.argtypes = [vp]
         if hasattr(L, "mc_pathtrace_denoise"):   # the path-tracer denoiser
             dp = C.POINTER(PathtraceDenoiseParams)
             L.mc_pathtrace_denoise_default_params.argtypes = [u32, u32, dp]
@@ -478,6 +488,44 @@ def zoom_compose(wide, deep, r, want_rgba=True, want_rgba8=False):
     rgba = np.empty((H, W, 4), np.float32) if want_rgba else None
     rgba8 = np.empty((H, W, 4), np.uint8) if want_rgba8 else None
     _check(lib().mc_mandelbrot_zoom_compose(W, H, _ptr(w), _ptr(d), float(r), _ptr(rgba), _ptr(rgba8)), "mc_mandelbrot_zoom_compose")
+    return rgba, rgba8
+
+
+def zoom_blend_map(map_wide, map_deep, step, steps_per_octave):
+    """mc_mandelbrot_zoom_blend_map (host only): the moving map of a frame, (map_wide (S - s) + map_deep s) / S per entry in 64-bit integers,
+    rounded down; uint32 of the maps' length."""
+    a = np.ascontiguousarray(map_wide, np.uint32).reshape(-1)
+    b = np.ascontiguousarray(map_deep, np.uint32).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("zoom_blend_map: the two maps have one length")
+    out = np.empty(a.size, np.uint32)
+    _check(lib().mc_mandelbrot_zoom_blend_map(a.size, _ptr(a), _ptr(b), int(step), int(steps_per_octave), _ptr(out)),
+           "mc_mandelbrot_zoom_blend_map")
+    return out
+
+
+def _count_plane(a, p, what):
+    a = np.ascontiguousarray(a, np.uint32)
+    if a.shape != (p.height, p.width):
+        raise ValueError(f"{what}: a count keyframe is a uint32 (height, width) plane of the params' size")
+    return a
+
+
+def zoom_compose_counts(p, wide, deep, map, r, want_rgba=True, want_rgba8=False):
+    """mc_mandelbrot_zoom_compose_counts (host only): the frame at r from the count keyframes wide and deep (uint32 (H, W): n, or q for the
+    smooth colourings; deep may be None), coloured by p's colouring through map (uint32 (max_iter + 1), the equalised colourings; else
+    None).  Returns (rgba float32 (H, W, 4), rgba8 uint8 (H, W, 4)), None where not wanted."""
+    w = _count_plane(wide, p, "zoom_compose_counts")
+    d = None if deep is None else _count_plane(deep, p, "zoom_compose_counts")
+    m = None
+    if map is not None:
+        m = np.ascontiguousarray(map, np.uint32).reshape(-1)
+        if m.size != p.max_iter + 1:
+            raise ValueError(f"zoom_compose_counts: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+    rgba = np.empty((p.height, p.width, 4), np.float32) if want_rgba else None
+    rgba8 = np.empty((p.height, p.width, 4), np.uint8) if want_rgba8 else None
+    _check(lib().mc_mandelbrot_zoom_compose_counts(C.byref(p), _ptr(w), _ptr(d), _ptr(m), float(r), _ptr(rgba), _ptr(rgba8)),
+           "mc_mandelbrot_zoom_compose_counts")
     return rgba, rgba8
 
 
@@ -1083,6 +1131,23 @@ class Context:
         """mc_mandelbrot_zoom_create: a zoom sequence of width x height frames on this context (a context manager)."""
         return Zoom(self, width, height)
 
+    def zoom_compose_counts_device(self, p, d_wide, d_deep, map, r, d_rgba=0, d_rgba8=0, stream=0):
+        """mc_mandelbrot_zoom_compose_counts_device_async: the frame at r from the device count keyframes d_wide and d_deep (0: absent),
+        coloured by p's colouring through the HOST table map (None: plain, smooth), into the vec4 plane d_rgba and / or the RGBA8 plane
+        d_rgba8."""
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, np.uint32).reshape(-1)
+            if m.size != p.max_iter + 1:
+                raise ValueError(f"zoom_compose_counts_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_zoom_compose_counts_device_async(self._h, C.byref(p), d_wide or None, d_deep or None, _ptr(m), float(r),
+                                                                    d_rgba or None, d_rgba8 or None, stream or None),
+               "mc_mandelbrot_zoom_compose_counts_device_async")
+
+    def zoom_counts(self, width, height):
+        """mc_mandelbrot_zoom_counts_create: a zoom sequence from count keyframes on this context (a context manager)."""
+        return ZoomCounts(self, width, height)
+
     def pathtrace_guides_device(self, width, height, d_normal_t, d_position_id, planes=None, spheres=None, stream=0):
         """mc_pathtrace_guides_device_async: the guide planes of a width x height image into two device vec4 planes."""
         planes, spheres = _scene_tables(planes, spheres)
@@ -1318,6 +1383,57 @@ class Zoom:
     def close(self):
         if self._h:   # (the context is still open: Context.close closes its zooms before itself)
             lib().mc_mandelbrot_zoom_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ZoomCounts:
+    """mc_mandelbrot_zoom_counts: two count-keyframe slots on a context's device, each with its rank or knot map.  push(p) renders a
+    keyframe's count plane (each at exactly half the previous one's scale; the first fixes colouring, max_iter and k_color);
+    frame(step, steps_per_octave) composes a frame through ONE map, blended from the two keyframes' maps on the device.  Closing the
+    context closes the sequences made on it first."""
+
+    def __init__(self, ctx, width, height):
+        self._h = C.c_void_p()
+        self._ctx = ctx   # (kept alive: the slots are freed on its device)
+        self.width, self.height = int(width), int(height)
+        self._entries = 0
+        _check(lib().mc_mandelbrot_zoom_counts_create(ctx._h, self.width, self.height, C.byref(self._h)), "mc_mandelbrot_zoom_counts_create")
+        ctx._zooms = [r for r in ctx._zooms if r() is not None] + [weakref.ref(self)]
+
+    def push(self, p):
+        _check(lib().mc_mandelbrot_zoom_counts_push(self._h, C.byref(p)), "mc_mandelbrot_zoom_counts_push")
+        self._entries = int(p.max_iter) + 1
+
+    def frame(self, step, steps_per_octave, want_rgba=True, want_rgba8=False):
+        """(rgba float32 (H, W, 4), rgba8 uint8 (H, W, 4)), None where not wanted."""
+        rgba = np.empty((self.height, self.width, 4), np.float32) if want_rgba else None
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        _check(lib().mc_mandelbrot_zoom_counts_frame(self._h, int(step), int(steps_per_octave), _ptr(rgba), _ptr(rgba8)),
+               "mc_mandelbrot_zoom_counts_frame")
+        return rgba, rgba8
+
+    def maps(self):
+        """(wide map, deep map), uint32 (max_iter + 1) each: the rank or knot maps of the keyframes held (one held: twice that one's)."""
+        wide = np.empty(max(self._entries, 1), np.uint32)
+        deep = np.empty(max(self._entries, 1), np.uint32)
+        _check(lib().mc_mandelbrot_zoom_counts_maps(self._h, _ptr(wide), _ptr(deep)), "mc_mandelbrot_zoom_counts_maps")
+        return wide, deep
+
+    def close(self):
+        if self._h:   # (the context is still open: Context.close closes its sequences before itself)
+            lib().mc_mandelbrot_zoom_counts_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

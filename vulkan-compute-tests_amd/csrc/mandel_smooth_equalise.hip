@@ -96,6 +96,11 @@ int pairs_device(mc_context* ctx, uint32_t max_iter, const uint32_t* qmap, hipSt
 
 }  // namespace
 
+int smooth_equalise_check_knots(uint32_t max_iter, const uint32_t* qmap, const char* who) { return check_knots(max_iter, qmap, who); }
+int smooth_equalise_pairs_device(mc_context* ctx, uint32_t max_iter, const uint32_t* qmap, hipStream_t s, const void** d_pairs) {
+    return pairs_device(ctx, max_iter, qmap, s, d_pairs);
+}
+
 void smooth_equalise_release(mc_context* ctx) {
     g_sq_states.erase(ctx, [](SmoothEqualiseState& st) {
         st.hist.release();

@@ -22,6 +22,10 @@ int mandelbrot_smooth_equalise_whole(mc_context* ctx, const mc_mandelbrot_params
 // mc_context_warmup_mandelbrot with the flag: both kernels made resident on a 64-pixel plane at d_smooth, the side record's buffers
 // allocated.
 int mandelbrot_smooth_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_smooth, void* d_rgba, hipStream_t s);
+// A caller's knot table (non-decreasing, the last entry 256 * max_iter) and its pair table as a cached device table of the context: what
+// the remap stage checks and gathers from, for the count-keyframe compose (mandel_zoom_counts.hip), which gathers from the same table.
+int smooth_equalise_check_knots(uint32_t max_iter, const uint32_t* qmap, const char* who);
+int smooth_equalise_pairs_device(mc_context* ctx, uint32_t max_iter, const uint32_t* qmap, hipStream_t s, const void** d_pairs);
 // mc_context_destroy: the context's histogram and knot table, if any, are freed.
 void smooth_equalise_release(mc_context* ctx);
 

@@ -49,12 +49,6 @@ __global__ void __launch_bounds__(256) mandel_zoom_kernel(const float4* __restri
     }
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 int zoom_check_ratio(double r, const char* who) {
@@ -87,9 +81,9 @@ int mandelbrot_zoom_launch(mc_context* ctx, uint32_t W, uint32_t H, const void* 
         return MC_ERR_INVALID_ARGUMENT;
     }
     const size_t npix = (size_t)W * H;
-    if (overlaps(d_rgba_f32, npix * 16, d_wide, npix * 16) || overlaps(d_rgba_f32, npix * 16, d_deep, npix * 16) ||
-        overlaps(d_rgba8, npix * 4, d_wide, npix * 16) || overlaps(d_rgba8, npix * 4, d_deep, npix * 16) ||
-        overlaps(d_rgba8, npix * 4, d_rgba_f32, npix * 16)) {
+    if (zoom_overlaps(d_rgba_f32, npix * 16, d_wide, npix * 16) || zoom_overlaps(d_rgba_f32, npix * 16, d_deep, npix * 16) ||
+        zoom_overlaps(d_rgba8, npix * 4, d_wide, npix * 16) || zoom_overlaps(d_rgba8, npix * 4, d_deep, npix * 16) ||
+        zoom_overlaps(d_rgba8, npix * 4, d_rgba_f32, npix * 16)) {
         set_error_detail(std::string(who) + ": an output overlaps a keyframe or the other output (a pixel reads its neighbours' texels: "
                          "the frame cannot be composed in place)");
         return MC_ERR_INVALID_ARGUMENT;

@@ -10,6 +10,13 @@ namespace mc {
 // r of a frame: in [0.5, 1], not NaN.  who: the entry point's name for the refusal.
 int zoom_check_ratio(double r, const char* who);
 
+// Do the byte ranges [a, a + na) and [b, b + nb) meet?  A null pointer meets nothing.
+inline bool zoom_overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
 // mandel_zoom.hip: the frame at r from the W x H vec4 keyframes d_wide and d_deep (or null) into d_rgba_f32 (vec4) and / or d_rgba8
 // (4 bytes per pixel), on s.  Pointers are checked for alignment (16 bytes; d_rgba8: 4) and the outputs against every other buffer for
 // overlap.

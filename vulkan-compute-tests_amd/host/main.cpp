@@ -5,7 +5,8 @@
 // arguments) expose what the reference hard-codes: --gpus N, --out FILE, --quiet, and per mode
 // --width/--height/--max-iter/--centre X Y/--scale SX SY/--precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep (perturb, perturb-bla-deep: X Y are decimal text; SX SY may lie below the doubles, e.g. 1e-1000; perturb-bla: the same text, SX SY >= 2^-960), --colour reference|equalised|smooth|distance|smooth-equalised (smooth-equalised: the smooth count ranked among the image's escaped pixels; equalised: histogram-equalised colouring of the whole image; smooth: fractional escape counts, no bands; distance: the smooth colour darkened where the boundary is closer than a pixel), --supersample 1|2|4|8 (S x S samples per pixel, box-filtered on the device), --adaptive (with --supersample 2|4|8: only pixels whose count differs from a neighbour's are sampled S x S), --orbit host|device|auto (where the perturbation precisions compute their reference orbit)  or  --math strict|fast|careful,
 // --zoom K F (the Mandelbrot app: --centre / --scale is the DEEPEST of K + 1 keyframes one octave apart; K * F + 1 frames, each composed on
-// the device from the two keyframes that bracket it and written as <out>_%05u.<ext>),
+// the device from the two keyframes that bracket it and written as <out>_%05u.<ext>), --zoom-keyframes colours|counts
+// (counts: the keyframes are kept as count planes and every frame is coloured through one map blended from theirs),
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -48,6 +49,7 @@ int main(int argc, char* argv[]) {
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
+    bool zoomCounts = false;            // --zoom-keyframes colours | counts: count keyframes, one rank map per frame
     uint32_t denoise = 0;               // --denoise [P]: the path tracer's a-trous filter with P passes (mc_pathtrace_render_denoised); 0 = off
     float noiseGuided = 0.0f;           // --noise-guided [K]: with --denoise, the colour tolerance from a measured noise plane, k_noise = K
                                         // (mc_pathtrace_render_denoised_adaptive); 0 = off
@@ -133,6 +135,14 @@ int main(int argc, char* argv[]) {
             zoomSet = true;
 #if !defined(MANDELBROT_MODE)
             printf("--zoom: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
+        else if (a == "--zoom-keyframes") {   // what --zoom keeps of a keyframe: its colours (mc_mandelbrot_zoom_*) or its counts (mc_mandelbrot_zoom_counts_*)
+            need(1);
+            zoomCounts = choice(argv[++i], {{"colours", 0u}, {"counts", 1u}}) != 0u;
+#if !defined(MANDELBROT_MODE)
+            printf("--zoom-keyframes: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
 #endif
         }
@@ -227,6 +237,14 @@ int main(int argc, char* argv[]) {
         exit(EXIT_FAILURE);
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
+    if (zoomCounts) {   // count keyframes carry one count per pixel: the colourings and resolves that need more stay with --zoom-keyframes colours
+        const char* why = !zoomSet                                ? "needs --zoom K F (it chooses what a zoom sequence keeps of a keyframe)"
+                          : colour == MC_MANDEL_COLOUR_DISTANCE   ? "not with --colour distance (a stencil over a whole smooth plane; use --zoom-keyframes colours)"
+                          : adaptive                              ? "not with --adaptive (a supersampled pixel has no single count; use --zoom-keyframes colours)"
+                          : supersample > 1u                      ? "not with --supersample above 1 (a supersampled pixel has no single count; use --zoom-keyframes colours)"
+                                                                  : nullptr;
+        if (why) { printf("--zoom-keyframes counts: %s\n", why); exit(EXIT_FAILURE); }
+    }
     if (noiseGuidedSet && (gpus > 1 || accel)) { printf("--noise-guided: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
     if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
     if (noiseGuidedSet && !denoise) { printf("--noise-guided: only with --denoise (it steers that filter's colour tolerance)\n"); exit(EXIT_FAILURE); }
@@ -242,7 +260,7 @@ int main(int argc, char* argv[]) {
 #if !defined(PATHTRACER_MODE)
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
-    (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
+    (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -250,6 +268,7 @@ int main(int argc, char* argv[]) {
     app.setMaxIter(maxIter);
     if (viewSet) app.setView(cx, cy, sx, sy);
     app.setPrecision(precision);
+    app.setZoomCounts(zoomCounts);
     if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
         if (supersample > 1u) { printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
         app.setColourFlags(colour);

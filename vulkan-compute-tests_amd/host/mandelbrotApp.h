@@ -49,6 +49,9 @@ struct MandelbrotApp : public ComputeApp {
         zoomK = K; zoomF = F; zoomCx = cx; zoomCy = cy; zoomSx = sx; zoomSy = sy;
         zoomOrbit = std::move(keyOrbit);
     }
+    // --zoom-keyframes counts: runZoom() keeps the keyframes as count planes (mc_mandelbrot_zoom_counts_*) and every frame
+    // is coloured through one map blended from the two keyframes' maps; colours (the default): the vec4 sequence.
+    void setZoomCounts(bool counts) { zoomCounts = counts; }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
     MandelbrotApp(const MandelbrotApp&) = delete;
     MandelbrotApp& operator=(const MandelbrotApp&) = delete;
@@ -112,6 +115,7 @@ struct MandelbrotApp : public ComputeApp {
     // arrives under `out` with _%05u before its extension.  Frame 0 is keyframe 0 (composed from it alone at r = 1); once keyframe j >= 1
     // is pushed, frames (j - 1) F + 1 .. j F follow from keyframes j - 1 and j at r = mc_mandelbrot_zoom_ratio(1 .. F, F), the last of
     // them (r = 0.5) being keyframe j bit for bit.  --gpu-postprocess takes the RGBA8 form: the compose kernel writes the bytes itself.
+    // --zoom-keyframes counts: the same keyframes, frames and lines through mc_mandelbrot_zoom_counts_push / _frame with (step, F).
     void runZoom(const char* out) {
         using clock = std::chrono::steady_clock;
         auto ms = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
@@ -120,18 +124,31 @@ struct MandelbrotApp : public ComputeApp {
         waitWarmup();
         const auto tStart = clock::now();
         mc_mandelbrot_zoom* z = nullptr;
-        check(mc_mandelbrot_zoom_create(ctx, resx, resy, &z), "mc_mandelbrot_zoom_create");
-        struct Guard { mc_mandelbrot_zoom* z; ~Guard() { mc_mandelbrot_zoom_destroy(z); } } guard{z};
+        mc_mandelbrot_zoom_counts* zc = nullptr;
+        if (zoomCounts) check(mc_mandelbrot_zoom_counts_create(ctx, resx, resy, &zc), "mc_mandelbrot_zoom_counts_create");
+        else check(mc_mandelbrot_zoom_create(ctx, resx, resy, &z), "mc_mandelbrot_zoom_create");
+        struct Guard {
+            mc_mandelbrot_zoom* z;
+            mc_mandelbrot_zoom_counts* zc;
+            ~Guard() { mc_mandelbrot_zoom_destroy(z); mc_mandelbrot_zoom_counts_destroy(zc); }
+        } guard{z, zc};
         const std::string name(out);
         size_t dot = name.find_last_of('.');
         const size_t slash = name.find_last_of('/');
         if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) dot = name.size();
         double keyMs = 0.0, composeMs = 0.0, saveMs = 0.0;
         uint32_t frames = 0;
-        auto emit = [&](double r) {
+        auto emit = [&](uint32_t step) {
             auto t = clock::now();
-            check(mc_mandelbrot_zoom_frame(z, r, gpuPostprocess ? nullptr : buffer.data(), gpuPostprocess ? rgba8.bytes() : nullptr),
-                  "mc_mandelbrot_zoom_frame");
+            float* f32 = gpuPostprocess ? nullptr : buffer.data();
+            uint8_t* u8 = gpuPostprocess ? rgba8.bytes() : nullptr;
+            if (zoomCounts) {
+                check(mc_mandelbrot_zoom_counts_frame(zc, step, zoomF, f32, u8), "mc_mandelbrot_zoom_counts_frame");
+            } else {
+                double r = 0.0;
+                check(mc_mandelbrot_zoom_ratio(step, zoomF, &r), "mc_mandelbrot_zoom_ratio");
+                check(mc_mandelbrot_zoom_frame(z, r, f32, u8), "mc_mandelbrot_zoom_frame");
+            }
             composeMs += ms(t);
             char num[16];
             snprintf(num, sizeof num, "_%05u", frames);
@@ -151,20 +168,17 @@ struct MandelbrotApp : public ComputeApp {
             } else {
                 setView(zoomCx, zoomCy, std::ldexp(zoomSx, shift), std::ldexp(zoomSy, shift));
             }
-            check(mc_mandelbrot_zoom_push(z, &params), "mc_mandelbrot_zoom_push");
+            if (zoomCounts) check(mc_mandelbrot_zoom_counts_push(zc, &params), "mc_mandelbrot_zoom_counts_push");
+            else check(mc_mandelbrot_zoom_push(z, &params), "mc_mandelbrot_zoom_push");
             const double pushMs = ms(t);
             keyMs += pushMs;
             double kernel = 0.0;
             (void)mc_context_last_timing(ctx, &kernel, nullptr);
             printf("keyframe %u of %u: the view's scale x 2^%d, %.3f ms (kernels %.3f ms)\n", j, zoomK, shift, pushMs, kernel);
             if (j == 0) {
-                emit(1.0);
+                emit(0u);   // (r = 1: keyframe 0 alone)
             } else {
-                for (uint32_t s = 1; s <= zoomF; s++) {
-                    double r = 0.0;
-                    check(mc_mandelbrot_zoom_ratio(s, zoomF, &r), "mc_mandelbrot_zoom_ratio");
-                    emit(r);
-                }
+                for (uint32_t s = 1; s <= zoomF; s++) emit(s);
             }
         }
         printf("zoom: %u keyframes in %.3f ms, %u frames composed in %.3f ms and saved in %.3f ms, %.3f ms in all\n", zoomK + 1, keyMs, frames,
@@ -238,6 +252,7 @@ private:
     std::vector<float> distance;   // --colour distance: D of the last render
     std::function<std::string(mc_context*)> orbitFactory;
     uint32_t zoomK = 0, zoomF = 0;   // --zoom K F; 0: a still
+    bool zoomCounts = false;         // --zoom-keyframes counts
     double zoomCx = 0.0, zoomCy = 0.0, zoomSx = 0.0, zoomSy = 0.0;
     std::function<std::string(mc_context*, int)> zoomOrbit;
 };
