@@ -44,7 +44,10 @@ extern "C" {
  * budgets: mc_pathtrace_budget_params with mc_pathtrace_budget_default_params, _levels, _resolve, their _device_async forms and
  * mc_pathtrace_budget_lists_device_async, mc_pathtrace_render_list_device_async, mc_pathtrace_render_budgeted, mc_context_last_budget;
  * then zoom sequences from count keyframes: mc_mandelbrot_zoom_blend_map, mc_mandelbrot_zoom_compose_counts,
- * mc_mandelbrot_zoom_compose_counts_device_async and mc_mandelbrot_zoom_counts_create, _push, _frame, _maps and _destroy.
+ * mc_mandelbrot_zoom_compose_counts_device_async and mc_mandelbrot_zoom_counts_create, _push, _frame, _maps and _destroy; then the area
+ * filter of the minified deep keyframe: MC_MANDEL_ZOOM_FILTER_BILINEAR / _AREA with mc_mandelbrot_zoom_compose_filtered,
+ * mc_mandelbrot_zoom_compose_filtered_device_async, mc_mandelbrot_zoom_compose_counts_filtered,
+ * mc_mandelbrot_zoom_compose_counts_filtered_device_async, mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -679,7 +682,8 @@ int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels
  *    for bit on EVERY pixel (X2 = gx exactly); a linear ramp over the plane is reproduced to rounding.  On inputs in [0, 1] no component
  *    exceeds 1.0, so the byte conversion cannot wrap.
  *  - STATED LIMIT: the central region is `deep` minified by up to 2 x through one bilinear tap, which aliases; keyframes rendered with
- *    MC_MANDEL_SUPERSAMPLE are the documented answer (a wider filter is a later step).  MC_MANDEL_COLOUR_EQUALISED ranks each keyframe by
+ *    MC_MANDEL_SUPERSAMPLE are one answer, the area filter over the pixel's footprint the other (mc_mandelbrot_zoom_compose_filtered and
+ *    mc_mandelbrot_zoom_frame_filtered with MC_MANDEL_ZOOM_FILTER_AREA, below; these calls themselves are unchanged).  MC_MANDEL_COLOUR_EQUALISED ranks each keyframe by
  *    itself, so the palette shifts between octaves (one map over a sequence: the by-hand histogram calls above; one map per FRAME that
  *    moves with the zoom: the count keyframes below, mc_mandelbrot_zoom_counts_*).
  *
@@ -783,8 +787,10 @@ int mc_mandelbrot_zoom_destroy(mc_mandelbrot_zoom* z);
  * colour of n under the frame's map, whichever keyframe it read (no seam: the vec4 sequence violates this wherever the two keyframes' maps
  * differ).
  * STATED LIMITS: a palette position still changes over time at a fixed point of the plane, continuously, through the blend; the blend is
- * linear in step, not in the histograms; one bilinear tap still aliases the minified centre and count keyframes cannot be supersampled
- * (distance shading, supersampling and adaptive supersampling stay with the vec4 sequence); one GPU. */
+ * linear in step, not in the histograms; in these calls one bilinear tap still aliases the minified centre and count keyframes cannot be
+ * supersampled: mc_mandelbrot_zoom_compose_counts_filtered and mc_mandelbrot_zoom_counts_frame_filtered with MC_MANDEL_ZOOM_FILTER_AREA
+ * (below) filter it over the pixel's footprint (distance shading, supersampling and adaptive supersampling stay with the vec4
+ * sequence); one GPU. */
 int mc_mandelbrot_zoom_blend_map(uint32_t entries, const uint32_t* map_wide, const uint32_t* map_deep, uint32_t step,
                                  uint32_t steps_per_octave, uint32_t* out);
 int mc_mandelbrot_zoom_compose_counts(const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep /* or NULL */,
@@ -800,6 +806,67 @@ int mc_mandelbrot_zoom_counts_frame(mc_mandelbrot_zoom_counts* z, uint32_t step,
                                     uint8_t* out_rgba8);
 int mc_mandelbrot_zoom_counts_maps(mc_mandelbrot_zoom_counts* z, uint32_t* wide_map /* or NULL */, uint32_t* deep_map /* or NULL */);
 int mc_mandelbrot_zoom_counts_destroy(mc_mandelbrot_zoom_counts* z);
+
+/* ---- zoom sequences: the area filter of the minified deep keyframe (the project's own addition, additions within ABI 3; DESIGN.md section
+ *      3.23; what tests/mandel_zoom_filter_ref.py restates).  A frame at r reads the deep keyframe minified by r2 = 2 r in [1, 2]: an output
+ *      pixel's footprint there is a box of width r2, and one bilinear tap (a box of width 1) skips up to half of the texels.  Each call
+ *      below is its unfiltered namesake with one more argument, `filter`:
+ *        MC_MANDEL_ZOOM_FILTER_BILINEAR (0): exactly what the namesake returns - the same bits, the same statuses, the same detail text after
+ *          the function's name, the same kernel.
+ *        MC_MANDEL_ZOOM_FILTER_AREA (1): the box filter below on the pixels that read `deep`.
+ *      Any other value is MC_ERR_INVALID_ARGUMENT with the value in mc_last_error_detail.  Every refusal of the namesake carries over
+ *      (alignment, overlap, r outside [0.5, 1] or NaN, no output, the colouring rules of the count calls) and is checked before the filter.
+ *  - MC_MANDEL_ZOOM_FILTER_AREA.  Positions, r2, X2, Y2 and the source test are mc_mandelbrot_zoom_compose's, unchanged.  A pixel that reads
+ *    `wide` is computed exactly as there (wide is magnified: its footprint is under one texel, and a box of width 1 over texel cells is
+ *    the bilinear tap).  A pixel that reads `deep` takes the box of width r2 centred at (X2, Y2) over the texel cells [k - 0.5, k + 0.5].
+ *  - per axis (columns with X2 and W, rows with Y2 and H), in IEEE double, no contraction, source order:
+ *      h = 0.5 * r2;  a = X2 - h;  b = X2 + h;
+ *      fl = floor(a);  k0 = (int64)fl + (a >= fl + 0.5 ? 1 : 0);
+ *    (k0 is floor(a + 0.5) without that sum's rounding: fl and fl + 0.5 are exact, so k0 is exactly the cell that holds a, a lower end on
+ *    a cell boundary going to the cell above.)  Three cells k = k0, k0 + 1, k0 + 2 - an interval of length at most 2 that starts in cell
+ *    k0 touches no other - each with
+ *      lo = max(a, (double)k - 0.5);  hi = min(b, (double)k + 0.5);  d = hi - lo;  w_k = (float)(d > 0 ? d : 0)
+ *    converted round-to-nearest-even, and the tap index clamp(k, 0, W-1): the border replicates, because the footprint may reach half a
+ *    texel past the image (cell -1 or W).  A box that ends exactly on a cell boundary leaves the cell above at weight 0.
+ *  - value, per component in fp32, no contraction, a_yx the nine taps, wy_y and wx_x the weights above: visit the taps in row-major
+ *    order (y outer, x inner); p = wy_y * wx_x; a tap with p == 0.0f is skipped; the first tap kept sets acc = p * a_yx and sw = p, every
+ *    later one acc = acc + (p * a_yx) and sw = sw + p;  v = acc / sw, correctly rounded;  alpha is exactly 1.0f.  RGBA8 is
+ *    mc_convert_rgba8's conversion (scale 255, no rotation) of that vec4, as everywhere.  (The skip is what makes the identities hold for
+ *    EVERY input: 0 * inf is NaN, and -0.0f + 0.0f loses the sign.  A NaN tap of non-zero weight gives NaN; which NaN is not specified.)
+ *  - consequences, for every input, -0.0f, infinite and NaN taps included: r = 0.5 gives `deep` bit for bit on EVERY pixel (X2 = gx
+ *    exactly, a = gx - 0.5, one tap of weight 1.0f, (1 * a) / 1; a NaN tap comes back a NaN); r = 1 with deep absent gives `wide` bit
+ *    for bit; on no pixel outside the deep-sourced rectangle does the AREA frame differ from the BILINEAR frame.  A constant plane c is reproduced exactly where c is
+ *    0 or a power of two (every product p * c is exact, so acc = c * sw through the same roundings), and otherwise to within the
+ *    roundings of at most nine products, eight additions in each sum and one division: (1 + 2^-24)^19 - 1 < 2^-21 relative; the restatement
+ *    measures at most 6.3 x 2^-24.  On inputs in [0, 1] no component exceeds 1.0 (each p * a_yx is at most p, rounding and addition are
+ *    monotone, so acc <= sw), so the byte conversion cannot wrap.
+ *  - count keyframes: the tap colours are the count keyframes' own, unchanged (plain, equalised, smooth, smooth equalised through the
+ *    frame's one map), nine per deep-sourced pixel; no new floating-point expression exists beyond the filter above.  Bit for bit:
+ *      frame = mc_mandelbrot_zoom_compose_filtered(colour(wide), colour(deep), r, filter).
+ *
+ * mc_mandelbrot_zoom_compose_filtered and mc_mandelbrot_zoom_compose_counts_filtered are host only, the same source as the kernels.
+ * The _device_async forms are the stages by hand.  mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered compose
+ * from the existing sequence objects (nothing about push changes) and fill mc_context_last_timing as the _frame calls do; the RGBA8 form
+ * is written by the kernel itself.  frame_filtered(r = 0.5), or (step = steps_per_octave), is the deep keyframe's own render, bit for bit,
+ * with either filter.
+ * STATED LIMITS: one GPU; no filter wider than the footprint (a box, not a windowed kernel: it removes what one tap skips, it does not
+ * band-limit); with keyframes of one sample per pixel the sharpness of the centre still varies over an octave (the last frame before a
+ * keyframe is a box of width ~1, the first a box of width 2; DESIGN.md section 3.23 has the measured table); distance shading and
+ * supersampling stay with colour keyframes. */
+enum { MC_MANDEL_ZOOM_FILTER_BILINEAR = 0, MC_MANDEL_ZOOM_FILTER_AREA = 1 };
+int mc_mandelbrot_zoom_compose_filtered(uint32_t width, uint32_t height, const float* wide, const float* deep /* or NULL */, double r,
+                                        uint32_t filter, float* out_rgba_f32 /* or NULL */, uint8_t* out_rgba8 /* or NULL */);
+int mc_mandelbrot_zoom_compose_filtered_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d_wide, const void* d_deep,
+                                                     double r, uint32_t filter, void* d_rgba_f32, void* d_rgba8, void* stream);
+int mc_mandelbrot_zoom_compose_counts_filtered(const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep /* or NULL */,
+                                               const uint32_t* map /* or NULL */, double r, uint32_t filter,
+                                               float* out_rgba_f32 /* or NULL */, uint8_t* out_rgba8 /* or NULL */);
+int mc_mandelbrot_zoom_compose_counts_filtered_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide,
+                                                            const void* d_deep, const uint32_t* map /* HOST, or NULL */, double r,
+                                                            uint32_t filter, void* d_rgba_f32, void* d_rgba8, void* stream);
+int mc_mandelbrot_zoom_frame_filtered(mc_mandelbrot_zoom* z, double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8);
+int mc_mandelbrot_zoom_counts_frame_filtered(mc_mandelbrot_zoom_counts* z, uint32_t step, uint32_t steps_per_octave, uint32_t filter,
+                                             float* out_rgba_f32, uint8_t* out_rgba8);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

@@ -27,6 +27,8 @@ MANDEL_BLA_COUNT_TRIPS = 8      # test switch (include/mc_compute_test.h): PERTU
 MANDEL_SUPERSAMPLE_ADAPTIVE = 32   # MC_MANDEL_SUPERSAMPLE_ADAPTIVE: with MANDEL_SUPERSAMPLE(s), only pixels whose count differs from a neighbour's are sampled s x s
 MANDEL_COLOUR_SMOOTH = 64       # MC_MANDEL_COLOUR_SMOOTH: smooth colouring by a fractional escape count, 24.8 fixed point (include/mc_compute.h)
 MANDEL_COLOUR_DISTANCE = 128    # MC_MANDEL_COLOUR_DISTANCE: the smooth colour shaded by a boundary distance estimate, whole images; set without MANDEL_COLOUR_SMOOTH
+ZOOM_FILTER_BILINEAR = 0   # MC_MANDEL_ZOOM_FILTER_BILINEAR: the filtered zoom calls return what their unfiltered namesakes return
+ZOOM_FILTER_AREA = 1       # MC_MANDEL_ZOOM_FILTER_AREA: a box over the pixel's footprint in the minified deep keyframe
 MANDEL_COLOUR_SMOOTH_EQUALISED = 4096   # MC_MANDEL_COLOUR_SMOOTH_EQUALISED: the smooth count ranked among a whole image's escaped pixels; set without MANDEL_COLOUR_SMOOTH
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
@@ -222,6 +224,13 @@ def lib():
             L.mc_mandelbrot_zoom_counts_frame.argtypes = [vp, u32, u32, vp, vp]
             L.mc_mandelbrot_zoom_counts_maps.argtypes = [vp, vp, vp]
             L.mc_mandelbrot_zoom_counts_destroy.argtypes = [vp]
+        if hasattr(L, "mc_mandelbrot_zoom_compose_filtered"):   # the area filter of the minified deep keyframe
+            L.mc_mandelbrot_zoom_compose_filtered.argtypes = [u32, u32, vp, vp, dbl, u32, vp, vp]
+            L.mc_mandelbrot_zoom_compose_filtered_device_async.argtypes = [vp, u32, u32, vp, vp, dbl, u32, vp, vp, vp]
+            L.mc_mandelbrot_zoom_compose_counts_filtered.argtypes = [mp, vp, vp, vp, dbl, u32, vp, vp]
+            L.mc_mandelbrot_zoom_compose_counts_filtered_device_async.argtypes = [vp, mp, vp, vp, vp, dbl, u32, vp, vp, vp]
+            L.mc_mandelbrot_zoom_frame_filtered.argtypes = [vp, dbl, u32, vp, vp]
+            L.mc_mandelbrot_zoom_counts_frame_filtered.argtypes = [vp, u32, u32, u32, vp, vp]
         if hasattr(L, "mc_pathtrace_denoise"):   # the path-tracer denoiser
             dp = C.POINTER(PathtraceDenoiseParams)
             L.mc_pathtrace_denoise_default_params.argtypes = [u32, u32, dp]
@@ -491,6 +500,23 @@ def zoom_compose(wide, deep, r, want_rgba=True, want_rgba8=False):
     return rgba, rgba8
 
 
+def zoom_compose_filtered(wide, deep, r, filter, want_rgba=True, want_rgba8=False):
+    """mc_mandelbrot_zoom_compose_filtered (host only): zoom_compose with a filter, ZOOM_FILTER_BILINEAR (zoom_compose's own bits) or
+    ZOOM_FILTER_AREA (a box over the footprint of the pixels that read deep)."""
+    w = _keyframe(wide, "zoom_compose_filtered")
+    d = None
+    if deep is not None:
+        d = _keyframe(deep, "zoom_compose_filtered")
+        if d.shape != w.shape:
+            raise ValueError("zoom_compose_filtered: the two keyframes have one shape")
+    H, W = w.shape[:2]
+    rgba = np.empty((H, W, 4), np.float32) if want_rgba else None
+    rgba8 = np.empty((H, W, 4), np.uint8) if want_rgba8 else None
+    _check(lib().mc_mandelbrot_zoom_compose_filtered(W, H, _ptr(w), _ptr(d), float(r), int(filter), _ptr(rgba), _ptr(rgba8)),
+           "mc_mandelbrot_zoom_compose_filtered")
+    return rgba, rgba8
+
+
 def zoom_blend_map(map_wide, map_deep, step, steps_per_octave):
     """mc_mandelbrot_zoom_blend_map (host only): the moving map of a frame, (map_wide (S - s) + map_deep s) / S per entry in 64-bit integers,
     rounded down; uint32 of the maps' length."""
@@ -526,6 +552,22 @@ def zoom_compose_counts(p, wide, deep, map, r, want_rgba=True, want_rgba8=False)
     rgba8 = np.empty((p.height, p.width, 4), np.uint8) if want_rgba8 else None
     _check(lib().mc_mandelbrot_zoom_compose_counts(C.byref(p), _ptr(w), _ptr(d), _ptr(m), float(r), _ptr(rgba), _ptr(rgba8)),
            "mc_mandelbrot_zoom_compose_counts")
+    return rgba, rgba8
+
+
+def zoom_compose_counts_filtered(p, wide, deep, map, r, filter, want_rgba=True, want_rgba8=False):
+    """mc_mandelbrot_zoom_compose_counts_filtered (host only): zoom_compose_counts with a filter (ZOOM_FILTER_BILINEAR, ZOOM_FILTER_AREA)."""
+    w = _count_plane(wide, p, "zoom_compose_counts_filtered")
+    d = None if deep is None else _count_plane(deep, p, "zoom_compose_counts_filtered")
+    m = None
+    if map is not None:
+        m = np.ascontiguousarray(map, np.uint32).reshape(-1)
+        if m.size != p.max_iter + 1:
+            raise ValueError(f"zoom_compose_counts_filtered: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+    rgba = np.empty((p.height, p.width, 4), np.float32) if want_rgba else None
+    rgba8 = np.empty((p.height, p.width, 4), np.uint8) if want_rgba8 else None
+    _check(lib().mc_mandelbrot_zoom_compose_counts_filtered(C.byref(p), _ptr(w), _ptr(d), _ptr(m), float(r), int(filter), _ptr(rgba),
+                                                            _ptr(rgba8)), "mc_mandelbrot_zoom_compose_counts_filtered")
     return rgba, rgba8
 
 
@@ -1127,6 +1169,12 @@ class Context:
         _check(lib().mc_mandelbrot_zoom_compose_device_async(self._h, width, height, d_wide or None, d_deep or None, float(r), d_rgba or None,
                                                              d_rgba8 or None, stream or None), "mc_mandelbrot_zoom_compose_device_async")
 
+    def zoom_compose_filtered_device(self, width, height, d_wide, d_deep, r, filter, d_rgba=0, d_rgba8=0, stream=0):
+        """mc_mandelbrot_zoom_compose_filtered_device_async: zoom_compose_device with a filter (ZOOM_FILTER_BILINEAR, ZOOM_FILTER_AREA)."""
+        _check(lib().mc_mandelbrot_zoom_compose_filtered_device_async(self._h, width, height, d_wide or None, d_deep or None, float(r),
+                                                                      int(filter), d_rgba or None, d_rgba8 or None, stream or None),
+               "mc_mandelbrot_zoom_compose_filtered_device_async")
+
     def zoom(self, width, height):
         """mc_mandelbrot_zoom_create: a zoom sequence of width x height frames on this context (a context manager)."""
         return Zoom(self, width, height)
@@ -1143,6 +1191,19 @@ class Context:
         _check(lib().mc_mandelbrot_zoom_compose_counts_device_async(self._h, C.byref(p), d_wide or None, d_deep or None, _ptr(m), float(r),
                                                                     d_rgba or None, d_rgba8 or None, stream or None),
                "mc_mandelbrot_zoom_compose_counts_device_async")
+
+    def zoom_compose_counts_filtered_device(self, p, d_wide, d_deep, map, r, filter, d_rgba=0, d_rgba8=0, stream=0):
+        """mc_mandelbrot_zoom_compose_counts_filtered_device_async: zoom_compose_counts_device with a filter (ZOOM_FILTER_BILINEAR,
+        ZOOM_FILTER_AREA)."""
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, np.uint32).reshape(-1)
+            if m.size != p.max_iter + 1:
+                raise ValueError(f"zoom_compose_counts_filtered_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_zoom_compose_counts_filtered_device_async(self._h, C.byref(p), d_wide or None, d_deep or None, _ptr(m),
+                                                                             float(r), int(filter), d_rgba or None, d_rgba8 or None,
+                                                                             stream or None),
+               "mc_mandelbrot_zoom_compose_counts_filtered_device_async")
 
     def zoom_counts(self, width, height):
         """mc_mandelbrot_zoom_counts_create: a zoom sequence from count keyframes on this context (a context manager)."""
@@ -1380,6 +1441,14 @@ class Zoom:
         _check(lib().mc_mandelbrot_zoom_frame(self._h, float(r), _ptr(rgba), _ptr(rgba8)), "mc_mandelbrot_zoom_frame")
         return rgba, rgba8
 
+    def frame_filtered(self, r, filter, want_rgba=True, want_rgba8=False):
+        """mc_mandelbrot_zoom_frame_filtered: frame(r) with a filter (ZOOM_FILTER_BILINEAR: frame's own bits; ZOOM_FILTER_AREA)."""
+        rgba = np.empty((self.height, self.width, 4), np.float32) if want_rgba else None
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        _check(lib().mc_mandelbrot_zoom_frame_filtered(self._h, float(r), int(filter), _ptr(rgba), _ptr(rgba8)),
+               "mc_mandelbrot_zoom_frame_filtered")
+        return rgba, rgba8
+
     def close(self):
         if self._h:   # (the context is still open: Context.close closes its zooms before itself)
             lib().mc_mandelbrot_zoom_destroy(self._h)
@@ -1422,6 +1491,14 @@ class ZoomCounts:
         rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         _check(lib().mc_mandelbrot_zoom_counts_frame(self._h, int(step), int(steps_per_octave), _ptr(rgba), _ptr(rgba8)),
                "mc_mandelbrot_zoom_counts_frame")
+        return rgba, rgba8
+
+    def frame_filtered(self, step, steps_per_octave, filter, want_rgba=True, want_rgba8=False):
+        """mc_mandelbrot_zoom_counts_frame_filtered: frame(step, steps_per_octave) with a filter (ZOOM_FILTER_BILINEAR, ZOOM_FILTER_AREA)."""
+        rgba = np.empty((self.height, self.width, 4), np.float32) if want_rgba else None
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        _check(lib().mc_mandelbrot_zoom_counts_frame_filtered(self._h, int(step), int(steps_per_octave), int(filter), _ptr(rgba), _ptr(rgba8)),
+               "mc_mandelbrot_zoom_counts_frame_filtered")
         return rgba, rgba8
 
     def maps(self):

@@ -152,5 +152,99 @@ inline void compose_counts_host(uint32_t W, uint32_t H, uint32_t M, int mode, co
     }
 }
 
+// ---- the area filter (include/mc_compute.h, at mc_mandelbrot_zoom_compose_filtered): zoom::area over the colours of
+// the nine counts of a deep-sourced pixel's box; a wide-sourced pixel is pixel() above.  tap_colours9 is tap_colours for nine counts, the
+// same expressions per tap in the same order: every index first, then the gathers, then the colours.
+template <int kMode>
+MC_ZOOM_FN void tap_colours9(const uint32_t n[9], uint32_t M, const float* table, const uint32_t* pairs, float c[9][4]) {
+    if (kMode == Plain || kMode == Equalised) {
+        uint32_t i[9];
+        for (int k = 0; k < 9; k++) i[k] = n[k] < M ? n[k] : M;
+        for (int k = 0; k < 9; k++) load_rgb(table, i[k], c[k]);
+        for (int k = 0; k < 9; k++) c[k][3] = 1.0f;
+        return;
+    }
+    uint32_t q[9];
+    for (int k = 0; k < 9; k++) q[k] = n[k];
+    if (kMode == SmoothEqualised) {
+        const uint32_t top = 256u * M;
+        uint32_t knot[9], step[9];
+        for (int k = 0; k < 9; k++) {   // (an interior count reads the last pair and discards it)
+            const uint32_t j = q[k] < top ? (q[k] >> 8) : M - 1u;
+            knot[k] = pairs[2u * (size_t)j];
+            step[k] = pairs[2u * (size_t)j + 1u];
+        }
+        for (int k = 0; k < 9; k++) q[k] = q[k] < top ? smooth_equalise::remap_pair(q[k], knot[k], step[k]) : top;
+    }
+    SmoothTap t[9];
+    float a[9][3], b[9][3];
+    for (int k = 0; k < 9; k++) t[k] = smooth_tap(q[k], M);
+    for (int k = 0; k < 9; k++) {
+        load_rgb(table, t[k].i0, a[k]);
+        load_rgb(table, t[k].i1, b[k]);
+    }
+    for (int k = 0; k < 9; k++) smooth_tap_colour(t[k], a[k], b[k], c[k]);
+}
+
+template <int kMode>
+MC_ZOOM_FN void pixel_area(const zoom::AxisArea& ax, const zoom::AxisArea& ay, uint32_t W, uint32_t M, const uint32_t* wide, const uint32_t* deep,
+                           const float* table, const uint32_t* pairs, float v[4]) {
+    if (ax.bil.in_deep && ay.bil.in_deep) {
+        uint32_t n[9];
+        for (int y = 0; y < 3; y++)
+            for (int x = 0; x < 3; x++) n[3 * y + x] = deep[(size_t)ay.box.i[y] * W + ax.box.i[x]];
+        float c[9][4];
+        tap_colours9<kMode>(n, M, table, pairs, c);
+        zoom::area<4>(&c[0][0], ax.box.w, ay.box.w, v);
+    } else {
+        zoom::Axis bx = ax.bil, by = ay.bil;   // (pixel() chooses by in_deep: this pixel reads wide)
+        bx.in_deep = false;
+        by.in_deep = false;
+        pixel<kMode>(bx, by, W, M, wide, deep, table, pairs, v);
+    }
+}
+
+template <int kMode>
+inline void compose_counts_area_mode(uint32_t W, uint32_t H, uint32_t M, const uint32_t* wide, const uint32_t* deep, const float* table,
+                                     const uint32_t* pairs, double r, float* out_f32, uint8_t* out_u8) {
+    const bool have_deep = deep != nullptr;
+    for (uint32_t gy = 0; gy < H; gy++) {
+        const zoom::AxisArea ay = zoom::axis_area(gy, H, r, have_deep);
+        for (uint32_t gx = 0; gx < W; gx++) {
+            const zoom::AxisArea ax = zoom::axis_area(gx, W, r, have_deep);
+            float v[4];
+            pixel_area<kMode>(ax, ay, W, M, wide, deep, table, pairs, v);
+            const size_t o = (size_t)gy * W + gx;
+            if (out_f32)
+                for (int c = 0; c < 4; c++) out_f32[4 * o + c] = v[c];
+            if (out_u8) {
+                const uint32_t b = zoom::rgba8_of(v);
+                for (int c = 0; c < 4; c++) out_u8[4 * o + c] = (uint8_t)(b >> (8 * c));
+            }
+        }
+    }
+}
+
+// compose_counts_host with MC_MANDEL_ZOOM_FILTER_AREA: the same tables, the filtered frame.
+inline void compose_counts_area_host(uint32_t W, uint32_t H, uint32_t M, int mode, const uint32_t* wide, const uint32_t* deep, const float* lut,
+                                     const uint32_t* map, double r, float* out_f32, uint8_t* out_u8) {
+    switch (mode) {
+        case Plain: compose_counts_area_mode<Plain>(W, H, M, wide, deep, lut, nullptr, r, out_f32, out_u8); break;
+        case Equalised: {
+            std::vector<float> table(((size_t)M + 1) * 4);
+            composed_table(M, lut, map, table.data());
+            compose_counts_area_mode<Equalised>(W, H, M, wide, deep, table.data(), nullptr, r, out_f32, out_u8);
+            break;
+        }
+        case Smooth: compose_counts_area_mode<Smooth>(W, H, M, wide, deep, lut, nullptr, r, out_f32, out_u8); break;
+        default: {
+            std::vector<uint32_t> pairs((size_t)M * 2);
+            smooth_equalise::compose_pairs(M, map, pairs.data());
+            compose_counts_area_mode<SmoothEqualised>(W, H, M, wide, deep, lut, pairs.data(), r, out_f32, out_u8);
+            break;
+        }
+    }
+}
+
 }  // namespace zoom_counts
 }  // namespace mc

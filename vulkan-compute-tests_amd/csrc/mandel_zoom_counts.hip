@@ -66,6 +66,28 @@ __global__ void __launch_bounds__(256) mandel_zoom_table_kernel(const uint32_t* 
     }
 }
 
+// The filtered frame (MC_MANDEL_ZOOM_FILTER_AREA): the same mapping.  A deep-sourced pixel loads the nine counts of its box
+// together, then the gathers of all nine taps together (zoom_counts::tap_colours9), then zoom::area; a wide-sourced pixel is the four-tap
+// pixel of the kernel above.
+template <int kMode>
+__global__ void __launch_bounds__(256) mandel_zoom_counts_area_kernel(const uint32_t* __restrict__ wide, const uint32_t* __restrict__ deep,
+                                                                      const float* __restrict__ table, const uint32_t* __restrict__ pairs,
+                                                                      float4* __restrict__ out_rgba, uint32_t* __restrict__ out_u8,
+                                                                      uint32_t W, uint32_t H, uint32_t M, double r) {
+    const uint32_t gx = blockIdx.x * 64u + threadIdx.x;
+    if (gx >= W) return;
+    const bool have_deep = deep != nullptr;
+    const zoom::AxisArea ax = zoom::axis_area(gx, W, r, have_deep);
+    for (uint32_t gy = blockIdx.y * 4u + threadIdx.y; gy < H; gy += gridDim.y * 4u) {
+        const zoom::AxisArea ay = zoom::axis_area(gy, H, r, have_deep);   // (uniform over the wave: threadIdx.y is)
+        float v[4];
+        zoom_counts::pixel_area<kMode>(ax, ay, W, M, wide, deep, table, pairs, v);
+        const size_t o = (size_t)gy * W + gx;
+        if (out_rgba) out_rgba[o] = make_float4(v[0], v[1], v[2], v[3]);
+        if (out_u8) out_u8[o] = zoom::rgba8_of(v);
+    }
+}
+
 int refuse(const char* who, const std::string& what) {
     set_error_detail(std::string(who) + ": " + what);
     return MC_ERR_INVALID_ARGUMENT;
@@ -160,6 +182,30 @@ int mandelbrot_zoom_table_launch(mc_context* ctx, uint32_t max_iter, int mode, c
     return ctx->note_launch(s);   // (reads the cached colour table)
 }
 
+int mandelbrot_zoom_counts_filtered_launch(mc_context* ctx, uint32_t W, uint32_t H, uint32_t max_iter, int mode, const void* d_wide,
+                                           const void* d_deep, const void* d_table, const void* d_pairs, double r, uint32_t filter,
+                                           void* d_rgba_f32, void* d_rgba8, const char* who, hipStream_t s) {
+    if (!ctx || !d_table || !max_iter || (mode == zoom_counts::SmoothEqualised && !d_pairs)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = zoom_counts_check_args(W, H, d_wide, d_deep, r, d_rgba_f32, d_rgba8, who)) return rc;
+    if (int rc = zoom_check_filter(filter, who)) return rc;
+    if (filter == MC_MANDEL_ZOOM_FILTER_BILINEAR)
+        return mandelbrot_zoom_counts_launch(ctx, W, H, max_iter, mode, d_wide, d_deep, d_table, d_pairs, r, d_rgba_f32, d_rgba8, who, s);
+    const dim3 grid((W + 63u) / 64u, std::min<uint32_t>((H + 3u) / 4u, 65535u)), block(64, 4);
+#define MC_ZOOM_COUNTS_AREA_LAUNCH(kMode)                                                                                                  \
+    hipLaunchKernelGGL(mandel_zoom_counts_area_kernel<kMode>, grid, block, 0, s, (const uint32_t*)d_wide, (const uint32_t*)d_deep,           \
+                       (const float*)d_table, (const uint32_t*)d_pairs, (float4*)d_rgba_f32, (uint32_t*)d_rgba8, W, H, max_iter, r)
+    switch (mode) {
+        case zoom_counts::Plain: MC_ZOOM_COUNTS_AREA_LAUNCH(zoom_counts::Plain); break;
+        case zoom_counts::Equalised: MC_ZOOM_COUNTS_AREA_LAUNCH(zoom_counts::Equalised); break;
+        case zoom_counts::Smooth: MC_ZOOM_COUNTS_AREA_LAUNCH(zoom_counts::Smooth); break;
+        case zoom_counts::SmoothEqualised: MC_ZOOM_COUNTS_AREA_LAUNCH(zoom_counts::SmoothEqualised); break;
+        default: return MC_ERR_INVALID_ARGUMENT;
+    }
+#undef MC_ZOOM_COUNTS_AREA_LAUNCH
+    MC_HIP_TRY(hipGetLastError());
+    return ctx->note_launch(s);   // (reads the cached colour, composed or pair table)
+}
+
 }  // namespace mc
 
 using namespace mc;
@@ -181,6 +227,11 @@ int check_map(const mc_mandelbrot_params* p, int mode, const uint32_t* map, cons
     return MC_OK;
 }
 
+int compose_counts_host_call(const char* who, const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep, const uint32_t* map,
+                             double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8);
+int compose_counts_device_call(const char* who, mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide, const void* d_deep,
+                               const uint32_t* map, double r, uint32_t filter, void* d_rgba_f32, void* d_rgba8, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -201,13 +252,41 @@ int mc_mandelbrot_zoom_blend_map(uint32_t entries, const uint32_t* map_wide, con
 
 int mc_mandelbrot_zoom_compose_counts(const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep, const uint32_t* map, double r,
                                       float* out_rgba_f32, uint8_t* out_rgba8) {
-    const char* who = "mc_mandelbrot_zoom_compose_counts";
+    return compose_counts_host_call("mc_mandelbrot_zoom_compose_counts", p, wide, deep, map, r, MC_MANDEL_ZOOM_FILTER_BILINEAR, out_rgba_f32,
+                                    out_rgba8);
+}
+
+int mc_mandelbrot_zoom_compose_counts_filtered(const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep, const uint32_t* map,
+                                               double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8) {
+    return compose_counts_host_call("mc_mandelbrot_zoom_compose_counts_filtered", p, wide, deep, map, r, filter, out_rgba_f32, out_rgba8);
+}
+
+int mc_mandelbrot_zoom_compose_counts_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide, const void* d_deep,
+                                                   const uint32_t* map, double r, void* d_rgba_f32, void* d_rgba8, void* stream) {
+    return compose_counts_device_call("mc_mandelbrot_zoom_compose_counts_device_async", ctx, p, d_wide, d_deep, map, r,
+                                      MC_MANDEL_ZOOM_FILTER_BILINEAR, d_rgba_f32, d_rgba8, stream);
+}
+
+int mc_mandelbrot_zoom_compose_counts_filtered_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide,
+                                                            const void* d_deep, const uint32_t* map, double r, uint32_t filter,
+                                                            void* d_rgba_f32, void* d_rgba8, void* stream) {
+    return compose_counts_device_call("mc_mandelbrot_zoom_compose_counts_filtered_device_async", ctx, p, d_wide, d_deep, map, r, filter,
+                                      d_rgba_f32, d_rgba8, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int compose_counts_host_call(const char* who, const mc_mandelbrot_params* p, const uint32_t* wide, const uint32_t* deep, const uint32_t* map,
+                             double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8) {
     int mode = 0;
     if (int rc = zoom_counts_mode(p, who, &mode)) return rc;
     if (!wide) return refuse(who, "the wide keyframe is NULL");
     if (!out_rgba_f32 && !out_rgba8) return refuse(who, "at least one output must be given");
     if (int rc = zoom_check_ratio(r, who)) return rc;
     if (int rc = check_map(p, mode, map, who)) return rc;
+    if (int rc = zoom_check_filter(filter, who)) return rc;
     const uint32_t M = p->max_iter;
     const size_t npix = (size_t)p->width * p->height;
     if (mode >= zoom_counts::Smooth)
@@ -218,18 +297,21 @@ int mc_mandelbrot_zoom_compose_counts(const mc_mandelbrot_params* p, const uint3
                                            " is above 256 * max_iter");
     std::vector<float> lut(((size_t)M + 1) * 4);
     mandelbrot_build_lut(M, p->k_color, lut.data());
-    zoom_counts::compose_counts_host(p->width, p->height, M, mode, wide, deep, lut.data(), map, r, out_rgba_f32, out_rgba8);
+    if (filter == MC_MANDEL_ZOOM_FILTER_AREA)
+        zoom_counts::compose_counts_area_host(p->width, p->height, M, mode, wide, deep, lut.data(), map, r, out_rgba_f32, out_rgba8);
+    else
+        zoom_counts::compose_counts_host(p->width, p->height, M, mode, wide, deep, lut.data(), map, r, out_rgba_f32, out_rgba8);
     return MC_OK;
 }
 
-int mc_mandelbrot_zoom_compose_counts_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide, const void* d_deep,
-                                                   const uint32_t* map, double r, void* d_rgba_f32, void* d_rgba8, void* stream) {
-    const char* who = "mc_mandelbrot_zoom_compose_counts_device_async";
+int compose_counts_device_call(const char* who, mc_context* ctx, const mc_mandelbrot_params* p, const void* d_wide, const void* d_deep,
+                               const uint32_t* map, double r, uint32_t filter, void* d_rgba_f32, void* d_rgba8, void* stream) {
     if (!ctx) return MC_ERR_INVALID_ARGUMENT;
     int mode = 0;
     if (int rc = zoom_counts_mode(p, who, &mode)) return rc;
     if (int rc = zoom_counts_check_args(p->width, p->height, d_wide, d_deep, r, d_rgba_f32, d_rgba8, who)) return rc;
     if (int rc = check_map(p, mode, map, who)) return rc;
+    if (int rc = zoom_check_filter(filter, who)) return rc;
     MC_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const void* table = nullptr;
@@ -241,7 +323,8 @@ int mc_mandelbrot_zoom_compose_counts_device_async(mc_context* ctx, const mc_man
         if (mode == zoom_counts::SmoothEqualised)
             if (int rc = smooth_equalise_pairs_device(ctx, p->max_iter, map, s, &pairs)) return rc;
     }
-    return mandelbrot_zoom_counts_launch(ctx, p->width, p->height, p->max_iter, mode, d_wide, d_deep, table, pairs, r, d_rgba_f32, d_rgba8, who, s);
+    return mandelbrot_zoom_counts_filtered_launch(ctx, p->width, p->height, p->max_iter, mode, d_wide, d_deep, table, pairs, r, filter, d_rgba_f32,
+                                                  d_rgba8, who, s);
 }
 
-}  // extern "C"
+}  // namespace

@@ -22,6 +22,12 @@ int mandelbrot_zoom_counts_launch(mc_context* ctx, uint32_t W, uint32_t H, uint3
                                   const void* d_table, const void* d_pairs, double r, void* d_rgba_f32, void* d_rgba8, const char* who,
                                   hipStream_t s);
 
+// The filtered frame: mandelbrot_zoom_counts_launch's arguments and checks, then the filter's (zoom_check_filter).
+// MC_MANDEL_ZOOM_FILTER_BILINEAR launches that call's kernel as it does; MC_MANDEL_ZOOM_FILTER_AREA the area kernel of the mode.
+int mandelbrot_zoom_counts_filtered_launch(mc_context* ctx, uint32_t W, uint32_t H, uint32_t max_iter, int mode, const void* d_wide,
+                                           const void* d_deep, const void* d_table, const void* d_pairs, double r, uint32_t filter,
+                                           void* d_rgba_f32, void* d_rgba8, const char* who, hipStream_t s);
+
 // The frame's table from the two keyframes' DEVICE maps (max_iter + 1 entries each), blended at step of steps_per_octave, one thread per
 // entry, on s: lut[map_f[.]] ((max_iter + 1) vec4) for zoom_counts::Equalised, the (knot, step) pairs (max_iter uint2) for
 // zoom_counts::SmoothEqualised.  d_lut: the context's colour table.

@@ -23,4 +23,13 @@ inline bool zoom_overlaps(const void* a, size_t na, const void* b, size_t nb) {
 int mandelbrot_zoom_launch(mc_context* ctx, uint32_t W, uint32_t H, const void* d_wide, const void* d_deep, double r, void* d_rgba_f32,
                            void* d_rgba8, const char* who, hipStream_t s);
 
+// filter of a filtered call: MC_MANDEL_ZOOM_FILTER_BILINEAR or MC_MANDEL_ZOOM_FILTER_AREA; any other value is refused with the value in
+// the detail.  who: the entry point's name for the refusal.
+int zoom_check_filter(uint32_t filter, const char* who);
+
+// The filtered frame: mandelbrot_zoom_launch's arguments and checks, then the filter's.  MC_MANDEL_ZOOM_FILTER_BILINEAR launches
+// mandelbrot_zoom_launch's kernel as that call does; MC_MANDEL_ZOOM_FILTER_AREA the area kernel (nine taps per deep-sourced pixel).
+int mandelbrot_zoom_filtered_launch(mc_context* ctx, uint32_t W, uint32_t H, const void* d_wide, const void* d_deep, double r, uint32_t filter,
+                                    void* d_rgba_f32, void* d_rgba8, const char* who, hipStream_t s);
+
 }  // namespace mc

@@ -7,6 +7,7 @@
 // --zoom K F (the Mandelbrot app: --centre / --scale is the DEEPEST of K + 1 keyframes one octave apart; K * F + 1 frames, each composed on
 // the device from the two keyframes that bracket it and written as <out>_%05u.<ext>), --zoom-keyframes colours|counts
 // (counts: the keyframes are kept as count planes and every frame is coloured through one map blended from theirs),
+// --zoom-filter bilinear|area (area: the minified deep keyframe is filtered over each pixel's footprint),
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -49,6 +50,8 @@ int main(int argc, char* argv[]) {
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
+    uint32_t zoomFilter = MC_MANDEL_ZOOM_FILTER_BILINEAR;   // --zoom-filter bilinear | area: the area filter of the minified deep keyframe
+    bool zoomFilterSet = false;
     bool zoomCounts = false;            // --zoom-keyframes colours | counts: count keyframes, one rank map per frame
     uint32_t denoise = 0;               // --denoise [P]: the path tracer's a-trous filter with P passes (mc_pathtrace_render_denoised); 0 = off
     float noiseGuided = 0.0f;           // --noise-guided [K]: with --denoise, the colour tolerance from a measured noise plane, k_noise = K
@@ -146,6 +149,15 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--zoom-filter") {   // how --zoom's frames read the minified deep keyframe: one bilinear tap, or a box over the pixel's footprint
+            need(1);
+            zoomFilter = choice(argv[++i], {{"bilinear", (uint32_t)MC_MANDEL_ZOOM_FILTER_BILINEAR}, {"area", (uint32_t)MC_MANDEL_ZOOM_FILTER_AREA}});
+            zoomFilterSet = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--zoom-filter: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--denoise" || a.rfind("--denoise=", 0) == 0) {   // render + guide planes + a-trous filter on the device
             // P is optional (default 5): `--denoise=P`, or `--denoise P` where the next argument is a number (so the positional spp and
             // resy go in front of a bare --denoise)
@@ -237,6 +249,7 @@ int main(int argc, char* argv[]) {
         exit(EXIT_FAILURE);
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
+    if (zoomFilterSet && !zoomSet) { printf("--zoom-filter: needs --zoom K F (it chooses how a zoom sequence's frames read the deep keyframe)\n"); exit(EXIT_FAILURE); }
     if (zoomCounts) {   // count keyframes carry one count per pixel: the colourings and resolves that need more stay with --zoom-keyframes colours
         const char* why = !zoomSet                                ? "needs --zoom K F (it chooses what a zoom sequence keeps of a keyframe)"
                           : colour == MC_MANDEL_COLOUR_DISTANCE   ? "not with --colour distance (a stencil over a whole smooth plane; use --zoom-keyframes colours)"
@@ -260,7 +273,7 @@ int main(int argc, char* argv[]) {
 #if !defined(PATHTRACER_MODE)
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
-    (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
+    (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
     (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -269,6 +282,7 @@ int main(int argc, char* argv[]) {
     if (viewSet) app.setView(cx, cy, sx, sy);
     app.setPrecision(precision);
     app.setZoomCounts(zoomCounts);
+    app.setZoomFilter(zoomFilter);
     if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
         if (supersample > 1u) { printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
         app.setColourFlags(colour);

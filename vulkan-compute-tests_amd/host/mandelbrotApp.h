@@ -52,6 +52,9 @@ struct MandelbrotApp : public ComputeApp {
     // --zoom-keyframes counts: runZoom() keeps the keyframes as count planes (mc_mandelbrot_zoom_counts_*) and every frame
     // is coloured through one map blended from the two keyframes' maps; colours (the default): the vec4 sequence.
     void setZoomCounts(bool counts) { zoomCounts = counts; }
+    // --zoom-filter area: runZoom() composes every frame through the _frame_filtered calls with
+    // MC_MANDEL_ZOOM_FILTER_AREA; bilinear (the default): the unfiltered calls, as before the option existed.
+    void setZoomFilter(uint32_t filter) { zoomFilter = filter; }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
     MandelbrotApp(const MandelbrotApp&) = delete;
     MandelbrotApp& operator=(const MandelbrotApp&) = delete;
@@ -142,12 +145,15 @@ struct MandelbrotApp : public ComputeApp {
             auto t = clock::now();
             float* f32 = gpuPostprocess ? nullptr : buffer.data();
             uint8_t* u8 = gpuPostprocess ? rgba8.bytes() : nullptr;
+            const bool filtered = zoomFilter != MC_MANDEL_ZOOM_FILTER_BILINEAR;
             if (zoomCounts) {
-                check(mc_mandelbrot_zoom_counts_frame(zc, step, zoomF, f32, u8), "mc_mandelbrot_zoom_counts_frame");
+                if (filtered) check(mc_mandelbrot_zoom_counts_frame_filtered(zc, step, zoomF, zoomFilter, f32, u8), "mc_mandelbrot_zoom_counts_frame_filtered");
+                else check(mc_mandelbrot_zoom_counts_frame(zc, step, zoomF, f32, u8), "mc_mandelbrot_zoom_counts_frame");
             } else {
                 double r = 0.0;
                 check(mc_mandelbrot_zoom_ratio(step, zoomF, &r), "mc_mandelbrot_zoom_ratio");
-                check(mc_mandelbrot_zoom_frame(z, r, f32, u8), "mc_mandelbrot_zoom_frame");
+                if (filtered) check(mc_mandelbrot_zoom_frame_filtered(z, r, zoomFilter, f32, u8), "mc_mandelbrot_zoom_frame_filtered");
+                else check(mc_mandelbrot_zoom_frame(z, r, f32, u8), "mc_mandelbrot_zoom_frame");
             }
             composeMs += ms(t);
             char num[16];
@@ -253,6 +259,7 @@ private:
     std::function<std::string(mc_context*)> orbitFactory;
     uint32_t zoomK = 0, zoomF = 0;   // --zoom K F; 0: a still
     bool zoomCounts = false;         // --zoom-keyframes counts
+    uint32_t zoomFilter = MC_MANDEL_ZOOM_FILTER_BILINEAR;   // --zoom-filter
     double zoomCx = 0.0, zoomCy = 0.0, zoomSx = 0.0, zoomSy = 0.0;
     std::function<std::string(mc_context*, int)> zoomOrbit;
 };
