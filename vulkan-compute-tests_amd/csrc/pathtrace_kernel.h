@@ -704,9 +704,13 @@ __device__ __forceinline__ v3 cosine_bounce_wall_grouped(int id, BounceTrans q) 
 // Mirror / glass bounce in the fast slab form (:432-:447): every outcome is rd*alpha + n*beta — reflection (1, -2 dot(n, rd)),
 // refraction (nnt, -k) — so the scalars are selected and ONE direction is formed; cos of the leaving ray = sqrt(cos2t), c^5
 // through c^2.  mat is 2 or 3; dot_n_rd = dot(n, rd); rx = rnd.x; accmat receives :445's weight.
-template <int Fast> __device__ __forceinline__ v3 specular_bounce_fast(int mat, v3 rd, v3 n, float dot_n_rd, float rx, v3& accmat) {
+// OneAlpha (the pool kernels): alpha's 1.0f as an opaque register value — as a constant it was materialised twice, in front of the
+// glass branch and again inside it.
+template <int Fast, bool OneAlpha = false>
+__device__ __forceinline__ v3 specular_bounce_fast(int mat, v3 rd, v3 n, float dot_n_rd, float rx, v3& accmat) {
     MC_PT_DECISION_FP
     float alpha = 1.0f, beta = -2.0f * dot_n_rd;
+    if constexpr (OneAlpha) asm volatile("" : "+v"(alpha));
     if (mat == 3) {
         MC_REGION(6);
         const bool into = (dm::as_uint(dot_n_rd) >> 31) != 0u;            // :438 (nl == n)

@@ -51,8 +51,25 @@
 // register and read back — two VALU instructions that compute nothing, in a kernel bound by VALU issue.  So: the termination test asks
 // the scalar `batch >= n_batches` first and takes its ballots only while the pool drains; "no diffuse lane is on a sphere" is read off
 // the mask the prologue's own compare `id >= 6` wrote; the emission of a path the roulette ends is added under the lanes' own condition.
-// Seven VALU instructions an iteration less, every bit kept (tests/test_gpu_pool_valu_diet.py; profiles/valu_diet_k2_ab.txt).  The
-// ballot at the top of the loop stays: its mask is data (gbits).  -DMC_PT_POOL_PARENT_FORMS (make exp) compiles the forms before.
+// Seven VALU instructions an iteration less, every bit kept (tests/test_gpu_pool_valu_diet.py; profiles/valu_diet_k2_ab.txt).
+// -DMC_PT_POOL_PARENT_FORMS (make exp) compiles the forms before.
+//
+// Lane state in wave masks (profiles/valu_diet2_k2_ab.txt).  A lane's two one-bit facts were per-lane values: `alive`, whose ballot at the
+// top of the loop — its mask is data, the dead lanes of a pixel are counted — cost the same pair, and `emissive`, a 0.0f / 1.0f factor
+// set by a v_mov in the stash pick-up, after the specular merge and after the diffuse bounce of (nearly) every iteration.
+//   alive_m (fast, careful): a wave-uniform 64-bit mask in scalar registers.  It stays scalar only while no assignment to it stands under
+//     a lanes' branch, and a ballot is free only of a COMPARE.  So the bounce block ends after the material, and the depth limit, the
+//     intersection, the next bounce's random numbers and the roulette follow where all lanes pass: each compare's mask is and-ed into
+//     alive_m by the scalar unit, the blocks between are entered through the inverse ballot (a bare s_and_saveexec_b64).  The same
+//     instructions on the same operands in the live lanes; what a dead lane computes of them (key, rx, ry) the pick-up overwrites.
+//   emis (all tiers): a per-lane condition, only ever tested — the compiler keeps it as a mask by itself.  The three emission sites add
+//     accmat * e in the lanes where it holds (add_emission), leaving out multiplications by 1 and additions of +-0: the argument is beside
+//     the first of them.
+//   key is incremented in place (it went through a temporary and two copies), alpha = 1 of the mirror / glass bounce is one v_mov.
+// Fast <1, 16, 3, true>: 8.5 VALU instructions an iteration less (SQ_INSTS_VALU), 71 VGPRs, 7 waves, K2 13.51 -> 13.27 ms; every bit kept in
+// all tiers (tests/test_gpu_pool_lane_masks.py).  Where a form cost registers it is not taken (pool_lane_masks, pool_emis_cond): the strict
+// kernels keep `alive` per lane (the mask form spilled), fast with two spheres keeps the parent's forms (8 -> 7 waves).
+// -DMC_PT_POOL_FLOAT_STATE (make exp; implied by MC_PT_POOL_PARENT_FORMS) compiles the per-lane values: the parent's listing.
 #pragma once
 #include <type_traits>
 #include "pathtrace_kernel.h"
@@ -65,6 +82,25 @@ constexpr bool kPoolParentForms = true;
 #else
 constexpr bool kPoolParentForms = false;
 #endif
+// diagnostic builds only (tests/test_gpu_pool_lane_masks.py; the parent forms are older still): `alive` and `emissive` as per-lane values
+#if defined(MC_PT_POOL_FLOAT_STATE) || defined(MC_PT_POOL_PARENT_FORMS)
+constexpr bool kPoolFloatState = true;
+#else
+constexpr bool kPoolFloatState = false;
+#endif
+// A lane mask from a compare, and a mask as a per-lane condition.  (__ballot takes an int: a bool that was merged across control flow
+// reaches it as v_cndmask_b32 v, 0, 1 + v_cmp_ne_u32 — and so does the builtin's argument when it is anything but a compare.  Of a
+// compare it is the compare's own result in scalar registers; the inverse enters a branch with a bare s_and_saveexec_b64.)
+__device__ __forceinline__ unsigned long long lanes_where(bool cmp) { return __builtin_amdgcn_ballot_w64(cmp); }
+__device__ __forceinline__ bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// rad + accmat * e with the product rounded before the sum in every tier — what rad + (accmat * e) * 1.0f computes, contracted
+// (fma(p, 1, rad) rounds p + rad once) or not (p * 1 = p).  Written out under contract(off): the fast tier would otherwise fuse
+// accmat * e into the sum and round once where the form with the factor rounds twice.
+__device__ __forceinline__ v3 add_emission(v3 rad, v3 accmat, v3 e) {
+#pragma clang fp contract(off)
+    const float px = accmat.x * e.x, py = accmat.y * e.y, pz = accmat.z * e.z;
+    return v3{rad.x + px, rad.y + py, rad.z + pz};
+}
 constexpr uint32_t kPoolEntryFloats = 8;     // {rd.x, rd.y, rd.z, t | id (-1: nothing to trace), key0 = samp * maxDepth, rnd.x, rnd.y of key0}
 constexpr uint32_t kPoolRecordStride = 16;   // floats per staged record: {geo.xyz, p (fast: 1 / p) | colour.rgb, material + 256 * emits | emission.xyz, RN(1 / p) (fast: p) | fast: colour.rgb / p, the same integer bits}
 template <int NS> constexpr uint32_t pool_record_floats() { return (6u + (uint32_t)NS) * kPoolRecordStride; }   // 6 planes + NS spheres
@@ -83,6 +119,12 @@ template <int Fast, int NS> constexpr int pool_waves() {
     constexpr int kStrict3 = 6;   // 80 VGPRs (three values spilled, none reloaded inside an iteration), 6 blocks of 26 KB per CU
     return Fast ? (NS <= 3 ? kFast3 : NS <= 5 ? 6 : NS <= 6 ? 5 : 4) : (NS <= 3 ? kStrict3 : NS <= 6 ? 4 : 3);
 }
+
+// Which instantiations take the lane-mask forms (see the header): all would compute the same bits; these keep their occupancy and
+// add no scratch with them.
+template <int Fast, int NS> constexpr bool pool_parent_state() { return kPoolFloatState || (Fast == 1 && NS == 2); }   // (fast, two spheres: 8 -> 7 waves with any of them)
+template <int Fast, int NS> constexpr bool pool_lane_masks() { return !pool_parent_state<Fast, NS>() && Fast != 0 && !(Fast == 2 && NS == 7); }
+template <int Fast, int NS> constexpr bool pool_emis_cond() { return !pool_parent_state<Fast, NS>(); }
 
 // Disjoint (fast math): the host proved the spheres pairwise disjoint — shadow rays are decided without square roots
 // (shadow_visible_disjoint); false: overlapping spheres, the root form (shadow_reaches_sphere).  The strict kernel has one form.
@@ -116,6 +158,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     // math does not execute, this one and the un-normalised directions are the two whose forked samples do not balance — more of them
     // lose radiance than gain it; with both in the reference's form gains and losses cancel: profiles/r05_fork_bias_identities.txt)
     constexpr bool kOccR2 = Fast == 1;
+    // what of the lane-mask forms this instantiation takes (pool_lane_masks)
+    constexpr bool kLaneMasks = pool_lane_masks<Fast, NS>(), kEmisCond = pool_emis_cond<Fast, NS>(), kOneAlpha = kEmisCond;
     // fast tier: the bounce's transcendentals whose operands are known early are issued as prioritised groups (mc_math.h, "groups")
     constexpr bool kGrouped = Fast == 1 && dm::kTransGroups;
     constexpr uint32_t TW = WaveTile<S>::w, TH = WaveTile<S>::h, Ring = 2u * (uint32_t)S, RRing = pool_result_batches<NS>() * (uint32_t)S;
@@ -187,6 +231,12 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     // frees its lane at the end of an iteration, not a third of the way into the next one.
     float rx = 0.0f, ry = 0.0f;
     bool alive = false;
+    // The two facts as lane masks (kLaneMasks, kEmisCond: which of them this instantiation takes).  `alive_m`, the lanes that trace a path, is a
+    // wave-uniform 64-bit value in scalar registers: the refill needs it as DATA (the dead lanes of a pixel, counted), and every change
+    // of it is a scalar and / or of compares' masks taken where all lanes pass.  `emis` (:365: no diffuse surface met since the camera or
+    // the last specular bounce) is only ever tested, so it is a per-lane condition the compiler keeps as a mask by itself.
+    unsigned long long alive_m = 0ull;
+    bool emis = true;
     // every iteration either traces a bounce of a live lane, or consumes stash entries, or produces a batch: bounded
     unsigned long long max_iters = (unsigned long long)n_batches * S * (a.max_depth + 2ull) + 64ull;
 #ifdef MC_PT_POOL_TEST_BOUND   // diagnostic build only (tests/test_gpu_pool.py): a bound the loop must trip
@@ -197,7 +247,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
         // ---- lanes whose path ended take their pixel's next camera rays
         // (MC_REGION: diagnostic build only — make stats, tools/pool_region_stats.py — executions and active lanes per block)
         MC_REGION(0);    // an iteration
-        const unsigned long long deadm = __ballot(!alive);
+        const unsigned long long deadm = kLaneMasks ? ~alive_m & lanes_where(true) : __ballot(!alive);
         if (deadm != 0ull) {
             MC_REGION(1);    // refill bookkeeping
             const Lane me = my_lane(false);
@@ -273,7 +323,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 avail += (uint32_t)S;
             }
             const uint32_t rank = (uint32_t)__builtin_popcount(gbits & ((1u << me.sub) - 1u));   // dead lanes of my pixel below me
-            if (!alive && rank < avail) {
+            const unsigned long long take_m = kLaneMasks ? deadm & lanes_where(rank < avail) : 0ull;
+            if (kLaneMasks ? lane_in(take_m) : (!alive && rank < avail)) {
                 MC_REGION(3);    // lanes taking a stash entry
                 const float4* q = reinterpret_cast<const float4*>(gstash + ((ghead + rank) & (Ring - 1u)) * kPoolEntryFloats);
                 const float4 q0 = q[0], q1 = q[1];
@@ -283,9 +334,12 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 key = dm::as_uint(q1.y); kend = key + a.max_depth; krr = key + 5u;
                 rx = q1.z; ry = q1.w;
                 ro = a.lc;                                                  // :362
-                accmat = v3{1.0f, 1.0f, 1.0f}; emissive = 1.0f;             // :361, :365
-                alive = id >= 0;
+                accmat = v3{1.0f, 1.0f, 1.0f};                              // :361
+                if constexpr (kEmisCond) emis = true; else emissive = 1.0f;   // :365
+                if constexpr (!kLaneMasks) alive = id >= 0;
             }
+            // (where all lanes pass: set under the lanes' branch the mask would be a vector value)
+            if constexpr (kLaneMasks) alive_m |= take_m & lanes_where(id >= 0);
             ghead += need < avail ? need : avail;
         }
         // pool exhausted and every path ended?  (no lane alive but entries left: only empty entries were taken — go round again)
@@ -293,11 +347,15 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
 #ifdef MC_PT_POOL_PARENT_FORMS
         if (__ballot(alive) == 0ull && batch >= n_batches && __ballot(ghead != batch * (uint32_t)S) == 0ull) { finished = true; break; }
 #else
-        if (batch >= n_batches && __ballot(alive) == 0ull && __ballot(ghead != batch * (uint32_t)S) == 0ull) { finished = true; break; }
+        if (batch >= n_batches && (kLaneMasks ? alive_m : __ballot(alive)) == 0ull && __ballot(ghead != batch * (uint32_t)S) == 0ull) { finished = true; break; }
 #endif
         // ---- one bounce of every live lane: prologue, material, intersection of the next depth (the rotated loop of trace_sample)
         // (structured ifs, no break / continue: every extra exit edge of this block cost a dozen register copies at its merge)
-        if (alive) {
+        // kLaneMasks: the block ends after the material; the depth limit, the intersection, the next bounce's random numbers and the
+        // roulette follow where all lanes pass, each compare's mask and-ed into `alive_m` there — the same instructions (what a dead
+        // lane computes of them is never read: the pick-up rewrites id, key, rx, ry), and no mask is merged across a lanes' branch.
+        v3 xoc[NS];                                                               // c_i - x (:317 at the next depth, :408 now)
+        if (kLaneMasks ? lane_in(alive_m) : alive) {
             {
                 MC_REGION(4);    // a bounce: prologue
                 // the live lanes on a sphere, as the compare's own lane mask (the diffuse branch asks whether any of ITS lanes, a subset
@@ -305,7 +363,6 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 unsigned long long sph_m = 0ull;
                 if constexpr (!kPoolParentForms) sph_m = __ballot(id >= 6);
                 v3 x = ro + rd * t;                                               // :374
-                v3 xoc[NS];                                                       // c_i - x (:317 at the next depth, :408 now)
 #pragma unroll
                 for (int i = 0; i < NS; i++) { xoc[i] = v3{hot.c[i][0], hot.c[i][1], hot.c[i][2]} - x; occ[i] = dot(xoc[i], xoc[i]); }
                 float xcc[NS];                                                    // |c_i - x|^2 itself (:410 needs it)
@@ -314,6 +371,9 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 const float4* obj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);   // per-lane fetch
                 // (fast: past depth 5 the colour row is the one already divided by the roulette probability)
                 const float4 o0 = obj[0], o1 = obj[(Fast && key > krr) ? 3 : 1];
+                // (fast, careful: o0.w is not read and the compiler narrows row 0 to ds_read_b96.  Keeping the word in use for a
+                //  ds_read_b128 was measured: 13.220 against 13.223 ms at K2, a tenth of the run-to-run spread — not kept,
+                //  profiles/valu_diet2_k2_ab.txt)
                 const bool is_sphere = id >= 6;
                 v3 geo{o0.x, o0.y, o0.z};
                 v3 col{o1.x, o1.y, o1.z};
@@ -332,10 +392,23 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                     nl = dot_n_rd < 0.0f ? n : -n;
                 }
                 v3& rad = Fast ? acc : accrad;                                    // where gathered radiance goes (see the header)
+                if constexpr (!kEmisCond) {
                 if (__ballot(mbits >= 256u) != 0ull) {                            // :391 (non-emitters add a zero: box_ok)
                     MC_REGION(12);   // emission of a hit
                     const float4 o2 = obj[2];
                     rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
+                }
+                } else if (mbits >= 256u && emis) {                                      // :391
+                    // Only the emitters' lanes whose condition holds add, and they add accmat * e without a factor.  Every bit is kept:
+                    // the factor `emissive` was 1.0f or 0.0f and nothing else.  1: (accmat * e) * 1 = accmat * e, and contracted,
+                    // fma(accmat * e, 1, rad), is the product's rounded value plus rad, rounded once — add_emission's sum.  0:
+                    // (accmat * e) * 0 is a zero of either sign for the finite accmat of a closed box (colours in [0, 1] divided by their
+                    // own maximum, finite glass factors) and finite e, and rad + (+-0) = rad for every rad but -0, which rad never is
+                    // (it starts at +0 and only receives sums; a sum is -0 only when both operands are).  A lane that did not hit an
+                    // emitter read e = +0: a zero again.  (The argument of the roulette's emission below, applied to the factor too.)
+                    MC_REGION(12);   // emission of a hit
+                    const float4 o2 = obj[2];
+                    rad = add_emission(rad, accmat, v3{o2.x, o2.y, o2.z});
                 }
                 accmat = accmat * col;                                            // :392
                 const v3 rnd{rx, ry, 0.0f};                                       // :393 (drawn at the end of the previous bounce)
@@ -380,13 +453,14 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         else { MC_REGION(10); rd = cosine_bounce_grouped<true>(nl, bt); }
                     } else if (walls_only()) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
                     else { MC_REGION(10); rd = cosine_bounce<Fast, true>(nl, rnd); }
-                    emissive = 0.0f;                                              // :429
+                    if constexpr (kEmisCond) emis = false; else emissive = 0.0f;  // :429
                 } else {                                                          // :432 mirror, :437 glass (box_ok: 2 or 3)
                     MC_REGION(11);   // mirror / glass
-                    if constexpr (Fast) rd = specular_bounce_fast<Fast>(mat, rd, n, dot_n_rd, rnd.x, accmat);
+                    if constexpr (Fast) rd = specular_bounce_fast<Fast, kOneAlpha>(mat, rd, n, dot_n_rd, rnd.x, accmat);
                     else rd = specular_bounce_general<false, true>(mat, rd, n, nl, dot_n_rd, rnd.x, accmat);
-                    emissive = 1.0f;                                              // :447
+                    if constexpr (kEmisCond) emis = true; else emissive = 1.0f;   // :447
                 }
+                if constexpr (!kLaneMasks) {
                 key++;
                 go = key != kend;                                                 // :367 depth limit
                 if (go) {
@@ -407,6 +481,12 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                                 const float4 o2 = nobj[2];
                                 if (!go) rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
                             }
+                        } else if constexpr (kEmisCond) {
+                            // (as below, and without the factor: see the emission of a hit)
+                            if (!go && dm::as_uint(nobj[1].w) >= 256u && emis) {
+                                const float4 o2 = nobj[2];
+                                rad = add_emission(rad, accmat, v3{o2.x, o2.y, o2.z});
+                            }
                         } else if (!go && dm::as_uint(nobj[1].w) >= 256u) {
                             // Only the emitters add.  The wave-wide form let every ended lane add whenever one of them had hit an
                             // emitter: accmat * e * emissive with e = +-0, the emission of a record whose flag is clear.  accmat is finite
@@ -419,14 +499,49 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                     }
                 }
                 }
-                if constexpr (!Fast) {
+                }
+                if constexpr (!Fast && !kLaneMasks) {
                     if (!go) {   // the path has ended: :452's accrad / samps.y into the sample's slot of the result ring
                         const v3 q = divs_recip<Fast>(accrad, fspp, a.inv_spp);
                         const uint32_t slot = cur % RRing;
                         gres[slot] = q.x; gres[RRing + slot] = q.y; gres[2u * RRing + slot] = q.z;
                     }
                 }
-                alive = go;
+                if constexpr (!kLaneMasks) alive = go;
+            }
+        }
+        if constexpr (kLaneMasks) {
+            static_assert(Fast != 0 || !kLaneMasks, "the strict kernels keep `alive` per lane: the mask form spilled (pool_lane_masks)");
+            v3& rad = acc;
+            // (key of a dead lane is never read again: incremented in every lane, in place — the increment under the lanes' branch went
+            //  through a temporary, a copy of kend for the lanes at the depth limit and a copy of the temporary for the others)
+            key++;
+            alive_m &= lanes_where(key != kend);                                  // :367 depth limit
+            if (lane_in(alive_m)) {
+                MC_REGION(14);   // intersection of the next depth
+                id = intersect_slab<Fast, (Fast != 0), kOccR2, 16>(hot, ro, rd, t, false, occ, xoc);
+            }
+            // (:369: a closed box — every ray hits)
+            // the next bounce's random numbers and roulette
+            const v3 rn = rand01(gx, gy, key);                                    // :393 (key = samp * maxDepth + depth)
+            rx = rn.x; ry = rn.y;
+            const unsigned long long deep_m = alive_m & lanes_where(key > krr);   // :395 depth > 5
+            const float4* nobj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);   // (formed once, read under the masks)
+            float pn;                                                             // the hit's roulette probability, read by the deep lanes
+            asm volatile("" : "=v"(pn));                                          // (any value elsewhere, and no instruction: deep_m masks the compare)
+            if (lane_in(deep_m)) {
+                MC_REGION(15);   // roulette
+                pn = nobj[2].w;
+            }
+            const unsigned long long end_m = deep_m & lanes_where(rn.z >= pn);    // :396
+            alive_m &= ~end_m;
+            if (lane_in(end_m)) {
+                // a path the roulette ends has still gathered the emission of this hit (:391 precedes :396) — the emitters' lanes alone,
+                // and without the factor, as at the emission of a hit above
+                if (dm::as_uint(nobj[1].w) >= 256u && emis) {
+                    const float4 o2 = nobj[2];
+                    rad = add_emission(rad, accmat, v3{o2.x, o2.y, o2.z});
+                }
             }
         }
     }
