@@ -1138,7 +1138,7 @@ int mc_pathtrace_render_denoised_adaptive(mc_context* ctx, const mc_pathtrace_pa
  *   the strict one in every mode.  Levels come from the same samples they extend, the usual bias of adaptive sampling.
  *   Refused with MC_ERR_INVALID_ARGUMENT and a detail string: n0 odd or below 2, n0 << max_level above 2^20, max_level above 8, a row
  *   tile, an interleave, a sample range, radius above 4, a bad target, flags other than 0, NULL pointers, both or neither image output.
- *   Not offered: mc_pathtrace_accel scenes, mc_multi_*, budgets other than n0 times a power of two.
+ *   Not offered: mc_multi_*, budgets other than n0 times a power of two.  (mc_pathtrace_accel scenes: mc_pathtrace_render_accel_budgeted.)
  * mc_pathtrace_budget_default_params: max_level = 4, target = 32, radius = 3 (mc_pathtrace_noise_default_params'), flags = 0.
  * mc_pathtrace_budget_levels, mc_pathtrace_budget_resolve: host only, usable without a GPU, the same source as the kernels.
  * The _device_async forms of levels, lists and resolve: on device pointers (vec4 planes aligned to 16 bytes, float and uint32_t planes
@@ -1211,6 +1211,45 @@ int mc_pathtrace_render_accel(mc_context* ctx, const mc_pathtrace_accel* a, cons
 int mc_pathtrace_render_accel_device_async(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, void* d_rgba_f32,
                                            void* stream);
 int mc_pathtrace_render_accel_rgba8(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, uint8_t* out_rgba8);
+
+/* ---- What runs behind a render, for mc_pathtrace_accel scenes: guides, the denoised and noise-guided chains, the list render and the
+ *      budgeted chain (no reference counterpart; additions within ABI 3) -------------------------------------
+ * ONE DEFINITION for all six: a call returns what its table form returns for the tables the object was made from.  The walk returns the
+ * linear loop's (id, t) for every ray, the accelerated render is the plain render bit for bit in MC_PT_MATH_STRICT, and sample ranges
+ * compose; so each chain below is its table form's chain with the guides taken from the tree and every render made through the tree.
+ *
+ * mc_pathtrace_accel_guides, _guides_device_async  (mirror mc_pathtrace_guides, mc_pathtrace_guides_device_async): the two guide planes,
+ *   bit for bit — storage order, a miss as (0, 0, 0, 1e20) and (0, 0, 0, -1).  Strict in every math mode (IEEE divide and square root).
+ *   The host form needs no device.  The device form reads the object's cached device copy: nothing is uploaded per call, and
+ *   mc_pathtrace_accel_stats.device_copies stays at one per context.  Planes aligned to 16 bytes, not overlapping.
+ * mc_pathtrace_render_accel_denoised  (mirrors mc_pathtrace_render_denoised), mc_pathtrace_render_accel_denoised_adaptive  (mirrors
+ *   mc_pathtrace_render_denoised_adaptive): the same order and scratch layout, less the records' upload.  In MC_PT_MATH_STRICT the output
+ *   is the table form's, bit for bit, f32 and RGBA8.  In MC_PT_MATH_FAST and MC_PT_MATH_FAST_CAREFUL the careful BVH tier renders, as
+ *   mc_pathtrace_accel_select_kernel reports, and the promise is the table forms' weaker one: the bits of the same chain made from the
+ *   separate public accel calls — NOT the table form's bits, which may come from another tier for the same scene.
+ * mc_pathtrace_render_accel_list_device_async  (mirrors mc_pathtrace_render_list_device_async): that call's contract word for word — the
+ *   entry -> pixel mapping, acc * prescale with the plane not read when sample_begin == 0, samples added in sample order, never the
+ *   final encode, unlisted pixels untouched, an entry >= width * height skipped, n_list == 0 is MC_OK with no launch.  S is the plain
+ *   render's rule applied to n_list entries and the range's sample count; a ragged count takes the accelerated render's two launches
+ *   (the prescale belongs to the first).
+ * mc_pathtrace_render_accel_budgeted  (mirrors mc_pathtrace_render_budgeted): its chain and its promise — in MC_PT_MATH_STRICT out[p] is
+ *   mc_pathtrace_render_accel at spp = n0 << level[p], bit for bit; mc_context_last_budget and mc_context_last_timing report as there.
+ * Refused as the table forms refuse, with the same status and a detail string; and, as the accelerated render: a NULL or destroyed
+ *   object, p->flags other than 0 (MC_ERR_INVALID_ARGUMENT), an MC_PT_PRECISION variant (MC_ERR_UNSUPPORTED, named in the detail).  The
+ *   arguments are checked before the context is asked for: every such refusal shows on a machine without a device.
+ * Not offered: a warm-up form, mc_multi_*. */
+int mc_pathtrace_accel_guides(const mc_pathtrace_accel* a, uint32_t width, uint32_t height, float* out_normal_t, float* out_position_id);
+int mc_pathtrace_accel_guides_device_async(mc_context* ctx, const mc_pathtrace_accel* a, uint32_t width, uint32_t height, void* d_normal_t,
+                                           void* d_position_id, void* stream);
+int mc_pathtrace_render_accel_denoised(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p,
+                                       const mc_pathtrace_denoise_params* d, float* out_rgba_f32, uint8_t* out_rgba8);
+int mc_pathtrace_render_accel_denoised_adaptive(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p,
+                                                const mc_pathtrace_denoise_params* d, float k_noise, uint32_t radius, float* out_rgba_f32,
+                                                uint8_t* out_rgba8);
+int mc_pathtrace_render_accel_list_device_async(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, const void* d_list,
+                                                uint32_t n_list, float prescale, void* d_acc, void* stream);
+int mc_pathtrace_render_accel_budgeted(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p,
+                                       const mc_pathtrace_budget_params* b, float* out_rgba_f32, uint8_t* out_rgba8, uint8_t* out_levels);
 
 /* ---- cold start (no reference counterpart: vkCreateComputePipelines compiles the shader inside preRun, vulkanComputeApp.cpp:589-643,
  *      before anything is timed; here the runtime loads a kernel family's code object on its first launch, 8 - 12 ms, and the first

@@ -269,6 +269,14 @@ def lib():
             L.mc_pathtrace_render_accel.argtypes = [vp, vp, pp, vp]
             L.mc_pathtrace_render_accel_device_async.argtypes = [vp, vp, pp, vp, vp]
             L.mc_pathtrace_render_accel_rgba8.argtypes = [vp, vp, pp, vp]
+        if hasattr(L, "mc_pathtrace_accel_guides"):   # guides, the denoised chains, the list render and the budgeted chain through the BVH
+            pp, dp, bp = C.POINTER(PathtraceParams), C.POINTER(PathtraceDenoiseParams), C.POINTER(PathtraceBudgetParams)
+            L.mc_pathtrace_accel_guides.argtypes = [vp, u32, u32, vp, vp]
+            L.mc_pathtrace_accel_guides_device_async.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+            L.mc_pathtrace_render_accel_denoised.argtypes = [vp, vp, pp, dp, vp, vp]
+            L.mc_pathtrace_render_accel_denoised_adaptive.argtypes = [vp, vp, pp, dp, f32, u32, vp, vp]
+            L.mc_pathtrace_render_accel_list_device_async.argtypes = [vp, vp, pp, vp, u32, f32, vp, vp]
+            L.mc_pathtrace_render_accel_budgeted.argtypes = [vp, vp, pp, bp, vp, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -765,6 +773,13 @@ class PathtraceAccel:
         out = PathtraceKernelInfo()
         _check(lib().mc_pathtrace_accel_select_kernel(self._h, C.byref(p), C.byref(out)), "mc_pathtrace_accel_select_kernel")
         return out
+
+    def guides(self, width, height):
+        """mc_pathtrace_accel_guides: the planes of pathtrace_guides for the object's tables, through the tree (host only)."""
+        nt = np.empty((height, width, 4), np.float32)
+        pid = np.empty((height, width, 4), np.float32)
+        _check(lib().mc_pathtrace_accel_guides(self._h, width, height, _ptr(nt), _ptr(pid)), "mc_pathtrace_accel_guides")
+        return nt, pid
 
     def close(self):
         if self._h:
@@ -1318,6 +1333,47 @@ class Context:
     def pathtrace_accel_device(self, accel, p, d_rgba, stream=0):
         _check(lib().mc_pathtrace_render_accel_device_async(self._h, accel._h, C.byref(p), d_rgba or None, stream or None),
                "mc_pathtrace_render_accel_device_async")
+
+    def pathtrace_accel_guides_device(self, accel, width, height, d_normal_t, d_position_id, stream=0):
+        """mc_pathtrace_accel_guides_device_async: pathtrace_guides_device through a PathtraceAccel's cached device copy."""
+        _check(lib().mc_pathtrace_accel_guides_device_async(self._h, accel._h, width, height, d_normal_t or None, d_position_id or None,
+                                                            stream or None), "mc_pathtrace_accel_guides_device_async")
+
+    def pathtrace_accel_denoised(self, accel, p, d=None, rgba8=False):
+        """mc_pathtrace_render_accel_denoised: pathtrace_denoised through a PathtraceAccel."""
+        if d is None:
+            d = pathtrace_denoise_params(p.width, p.height)
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        _check(lib().mc_pathtrace_render_accel_denoised(self._h, accel._h, C.byref(p), C.byref(d), None if rgba8 else _ptr(out),
+                                                        _ptr(out) if rgba8 else None), "mc_pathtrace_render_accel_denoised")
+        return out
+
+    def pathtrace_accel_denoised_adaptive(self, accel, p, d=None, k_noise=None, radius=None, rgba8=False):
+        """mc_pathtrace_render_accel_denoised_adaptive: pathtrace_denoised_adaptive through a PathtraceAccel."""
+        if d is None:
+            d = pathtrace_denoise_params(p.width, p.height)
+        k0, r0 = pathtrace_noise_defaults()
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        _check(lib().mc_pathtrace_render_accel_denoised_adaptive(self._h, accel._h, C.byref(p), C.byref(d), k0 if k_noise is None else k_noise,
+                                                                 r0 if radius is None else radius, None if rgba8 else _ptr(out),
+                                                                 _ptr(out) if rgba8 else None),
+               "mc_pathtrace_render_accel_denoised_adaptive")
+        return out
+
+    def pathtrace_accel_list_device(self, accel, p, d_list, n_list, prescale, d_acc, stream=0):
+        """mc_pathtrace_render_accel_list_device_async: pathtrace_list_device through a PathtraceAccel."""
+        _check(lib().mc_pathtrace_render_accel_list_device_async(self._h, accel._h, C.byref(p), d_list or None, n_list, prescale, d_acc or None,
+                                                                 stream or None), "mc_pathtrace_render_accel_list_device_async")
+
+    def pathtrace_accel_budgeted(self, accel, p, b=None, rgba8=False, want_levels=False):
+        """mc_pathtrace_render_accel_budgeted: pathtrace_budgeted through a PathtraceAccel; last_budget reports it."""
+        if b is None:
+            b = pathtrace_budget_params()
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        levels = np.empty((p.height, p.width), np.uint8) if want_levels else None
+        _check(lib().mc_pathtrace_render_accel_budgeted(self._h, accel._h, C.byref(p), C.byref(b), None if rgba8 else _ptr(out),
+                                                        _ptr(out) if rgba8 else None, _ptr(levels)), "mc_pathtrace_render_accel_budgeted")
+        return (out, levels) if want_levels else out
 
     def pathtrace_device(self, p, d_rgba, planes=None, spheres=None, stream=0):
         if planes is None or spheres is None:

@@ -1,5 +1,6 @@
 // Host side of the BVH path tracer launch: the request's checks, the camera basis, the sample-parallel width, the device
-// copy of an mc_pathtrace_accel per context, and the device-form entry points.  Device code: pt_bvh_kernel.h; the structure: pt_bvh.h;
+// copy of an mc_pathtrace_accel per context, and the device-form entry points of the render and of the list render (§3.24; the guides
+// through the tree: pt_bvh_guides.hip).  Device code: pt_bvh_kernel.h; the structure: pt_bvh.h;
 // the build and the host-only entry points: pt_bvh_host.cpp; the blocking entry points: api.hip, beside the calls whose skeleton they use.
 #include <cmath>
 #include <cstring>
@@ -175,14 +176,10 @@ int pathtrace_accel_select(const mc_pathtrace_accel* a, const mc_pathtrace_param
     return MC_OK;
 }
 
-int pathtrace_accel_launch(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, void* d_rgba, hipStream_t s,
-                           const char* who) {
-    if (!ctx || !d_rgba) return refuse(who, "a NULL pointer");
-    Plan plan;
-    if (int rc = plan_request(a, p, who, plan)) return rc;
-    DeviceCopy copy{};
-    if (int rc = device_copy(ctx, a, s, copy)) return rc;
-    BvhArgs k;
+namespace {
+
+// The kernels' arguments of request p on the device copy `copy` (the output plane is the caller's to set).
+void fill_args(const mc_pathtrace_accel* a, const mc_pathtrace_params* p, const DeviceCopy& copy, BvhArgs& k) {
     std::memset(&k, 0, sizeof(k));
     PTArgs& args = k.a;
     args.W = p->width; args.H = p->height; args.spp = p->spp;
@@ -191,12 +188,33 @@ int pathtrace_accel_launch(mc_context* ctx, const mc_pathtrace_accel* a, const m
     args.row_block = p->row_stride ? p->row_block : 0u; args.row_stride = p->row_stride;
     set_camera(args);
     args.inv_W = 1.0f / (float)p->width; args.inv_H = 1.0f / (float)p->height; args.inv_spp = 1.0f / (float)p->spp;
-    args.out = (float4*)d_rgba;
     args.scene.n_planes = a->n_planes; args.scene.n_spheres = a->n_spheres;
     args.scene.n_emissive = (uint32_t)a->lights.size();
     args.scene.d_obj = args.scene.d_obj_derived = copy.view.rec;
     args.scene.d_emissive = copy.d_lights;
     k.view = copy.view;
+}
+
+}  // namespace
+
+int pt_accel_device_view(mc_context* ctx, const mc_pathtrace_accel* a, hipStream_t s, bvh::View& view) {
+    DeviceCopy copy{};
+    if (int rc = device_copy(ctx, a, s, copy)) return rc;
+    view = copy.view;
+    return MC_OK;
+}
+
+int pathtrace_accel_launch(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, void* d_rgba, hipStream_t s,
+                           const char* who) {
+    if (!ctx || !d_rgba) return refuse(who, "a NULL pointer");
+    Plan plan;
+    if (int rc = plan_request(a, p, who, plan)) return rc;
+    DeviceCopy copy{};
+    if (int rc = device_copy(ctx, a, s, copy)) return rc;
+    BvhArgs k;
+    fill_args(a, p, copy, k);
+    PTArgs& args = k.a;
+    args.out = (float4*)d_rgba;
     const uint32_t rows = tile_rows(p->row_begin, p->row_end, args.row_block, args.row_stride);
     auto launch = [&](const BvhArgs& ka, int width) {
         return plan.math_mode == MC_PT_MATH_STRICT ? pt::launch_bvh_tier<0>(ka, width, rows, s) : pt::launch_bvh_tier<2>(ka, width, rows, s);
@@ -215,6 +233,58 @@ int pathtrace_accel_launch(mc_context* ctx, const mc_pathtrace_accel* a, const m
     return ctx->note_launch(s);   // the kernels read the cached device copy
 }
 
+// The list render: pt_budget_list_render's checks in its order and words (the object's and plan_request's in place of the tables'), then
+// pathtrace_bvh_list_kernel at the width choose_S gives for n_list ENTRIES and the range's samples.  A ragged sample count takes the
+// two launches plan_request plans for a render; the prescale is the FIRST launch's alone: the tail continues (sample_begin > 0) what
+// the head has already scaled and stored, and gets 1.0f.
+int pathtrace_accel_list_render(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, const void* d_list, uint32_t n_list,
+                                float prescale, void* d_acc, const char* who, hipStream_t s) {
+    auto misaligned = [](const void* q, uintptr_t to) { return reinterpret_cast<uintptr_t>(q) % to != 0u; };
+    if (!p) return refuse(who, "the render parameters are NULL");
+    if (!p->width || !p->height) return refuse(who, "width and height must be above 0");
+    if ((uint64_t)p->width * p->height > (1ull << 31)) return refuse(who, "more than 2^31 pixels: a list holds 32-bit storage indices");
+    if (!whole_image(p) || p->row_block)
+        return refuse(who, "whole-image addressing only (row_begin = 0, row_end = height, no interleave): an entry is a storage index of the image");
+    Plan plan;
+    if (int rc = plan_request(a, p, who, plan)) return rc;   // (the object, the ranges, the math mode, the flags; an MC_PT_PRECISION variant by name)
+    if (!d_acc || (!d_list && n_list)) return refuse(who, "the accumulator plane or the list is NULL");
+    if (misaligned(d_acc, 16u)) return refuse(who, "the accumulator plane must be aligned to 16 bytes");
+    if (misaligned(d_list, 4u)) return refuse(who, "the list must be aligned to 4 bytes");
+    if (n_list > (1u << 31)) return refuse(who, "more than 2^31 entries");
+    {
+        const uintptr_t x = reinterpret_cast<uintptr_t>(d_acc), y = reinterpret_cast<uintptr_t>(d_list);
+        const size_t na = (size_t)p->width * p->height * 16, nb = (size_t)n_list * 4;
+        if (d_list && x < y + nb && y < x + na) return refuse(who, "the accumulator plane overlaps the list");
+    }
+    if (!ctx) return refuse(who, "the context is NULL");
+    if (!n_list) return MC_OK;
+    // the width for the ENTRIES (plan_request's is the image's), and its tail
+    const uint32_t n_samples = p->sample_end - p->sample_begin;
+    const int S = choose_S(n_list, n_samples);
+    const uint32_t rest = n_samples % (uint32_t)S;
+    const int tail_S = (S > 1 && rest != 0u && n_samples > (uint32_t)S) ? (rest >= 4u ? 4 : 1) : 0;
+    DeviceCopy copy{};
+    if (int rc = device_copy(ctx, a, s, copy)) return rc;
+    BvhArgs k;
+    fill_args(a, p, copy, k);
+    k.a.out = (float4*)d_acc;
+    auto launch = [&](const BvhArgs& ka, float scale, int width) {
+        const pt::BvhListArgs l{(const uint32_t*)d_list, n_list, scale};
+        return plan.math_mode == MC_PT_MATH_STRICT ? pt::launch_bvh_list_tier<0>(ka, l, width, s) : pt::launch_bvh_list_tier<2>(ka, l, width, s);
+    };
+    int rc;
+    if (tail_S) {
+        BvhArgs head = k, tail = k;
+        head.a.sample_end = tail.a.sample_begin = p->sample_end - rest;
+        if ((rc = launch(head, prescale, S))) return rc;
+        if ((rc = launch(tail, 1.0f, tail_S))) return rc;
+    } else {
+        if ((rc = launch(k, prescale, S))) return rc;
+    }
+    MC_HIP_TRY(hipGetLastError());
+    return ctx->note_launch(s);
+}
+
 }  // namespace mc
 
 extern "C" {
@@ -229,6 +299,14 @@ int mc_pathtrace_render_accel_device_async(mc_context* ctx, const mc_pathtrace_a
     if (!ctx) return mc::refuse(who, "the context is NULL");
     MC_HIP_TRY(hipSetDevice(ctx->device));
     return mc::pathtrace_accel_launch(ctx, a, p, d_rgba_f32, stream ? (hipStream_t)stream : ctx->stream, who);
+}
+
+int mc_pathtrace_render_accel_list_device_async(mc_context* ctx, const mc_pathtrace_accel* a, const mc_pathtrace_params* p, const void* d_list,
+                                                uint32_t n_list, float prescale, void* d_acc, void* stream) {
+    const char* who = "mc_pathtrace_render_accel_list_device_async";
+    // (a NULL context is refused after the arguments: every refusal of theirs shows on a machine without a device)
+    if (ctx) MC_HIP_TRY(hipSetDevice(ctx->device));
+    return mc::pathtrace_accel_list_render(ctx, a, p, d_list, n_list, prescale, d_acc, who, stream ? (hipStream_t)stream : ctx ? ctx->stream : nullptr);
 }
 
 }  // extern "C"

@@ -5,4 +5,5 @@
 
 namespace mc { namespace pt {
 template <> int launch_bvh_tier<2>(const BvhArgs& k, int S, uint32_t tile_rows, hipStream_t s) { return launch_bvh_tier_impl<2>(k, S, tile_rows, s); }
+template <> int launch_bvh_list_tier<2>(const BvhArgs& k, const BvhListArgs& l, int S, hipStream_t s) { return launch_bvh_list_tier_impl<2>(k, l, S, s); }
 } }

@@ -1,4 +1,5 @@
-// Path tracer BVH, host side: the build and the host-only entry points (mc_pathtrace_accel_create / _destroy / _info / _intersect).
+// Path tracer BVH, host side: the build and the host-only entry points (mc_pathtrace_accel_create / _destroy / _info / _intersect /
+// _guides).
 // Plain C++17, no HIP header; built with the library's floating-point flags (-ffp-contract=off), since intersect_bvh's results are
 // results.  The structure, the cull and its proof: pt_bvh.h.
 #include <algorithm>
@@ -8,6 +9,7 @@
 #include <new>
 #include <set>
 
+#include "pt_bvh_guides.h"
 #include "pt_bvh_host.h"
 
 namespace mc {
@@ -208,6 +210,30 @@ int mc_pathtrace_accel_intersect(const mc_pathtrace_accel* a, uint64_t n_rays, c
     for (uint64_t k = 0; k < n_rays; k++) {
         const mc::bvh::f3 o{origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]}, d{dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]};
         out_id[k] = mc::bvh::intersect_bvh<mc::bvh::IeeeOps>(v, o, d, out_t[k]);
+    }
+    return MC_OK;
+}
+
+// The guide planes of mc_pathtrace_guides for the object's tables, through the tree (pt_bvh_guides.h).
+int mc_pathtrace_accel_guides(const mc_pathtrace_accel* a, uint32_t width, uint32_t height, float* out_normal_t, float* out_position_id) {
+    using mc::ptd::vec4;
+    const char* who = "mc_pathtrace_accel_guides";
+    if (!a) return mc::refuse(who, "a NULL pointer");
+    if (!mc::pt_accel_live(a)) return mc::refuse(who, "not a live mc_pathtrace_accel (destroyed already?)");
+    if (!width || !height) return mc::refuse(who, "width and height must be above 0");
+    if (!out_normal_t || !out_position_id) return mc::refuse(who, "an output plane is NULL");
+    const size_t npix = (size_t)width * height;
+    // a plane of the caller's that is not aligned to 16 bytes is written through a copy (vec4 is alignas(16))
+    auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16u != 0u; };
+    try {
+        std::vector<vec4> s_nt(misaligned(out_normal_t) ? npix : 0u), s_pid(misaligned(out_position_id) ? npix : 0u);
+        vec4* nt = s_nt.empty() ? reinterpret_cast<vec4*>(out_normal_t) : s_nt.data();
+        vec4* pid = s_pid.empty() ? reinterpret_cast<vec4*>(out_position_id) : s_pid.data();
+        mc::ptd::guides_bvh_host(width, height, a->host_view(), nt, pid);
+        if (!s_nt.empty()) std::memcpy(out_normal_t, s_nt.data(), npix * 16);
+        if (!s_pid.empty()) std::memcpy(out_position_id, s_pid.data(), npix * 16);
+    } catch (const std::bad_alloc&) {
+        return mc::refuse(who, "out of host memory", MC_ERR_OUT_OF_MEMORY);
     }
     return MC_OK;
 }

@@ -11,6 +11,9 @@
 // loads); the walk is PER LANE — after the first bounce a wave's rays diverge — so a node is two 16-byte vector loads, a leaf sphere one 16-byte
 // and one 4-byte vector load.  The walk is stackless (depth-first order, one skip link per node): no private array, no scratch.  No LDS, no
 // atomics, no inline assembly beyond the empty register barriers the skeleton already uses.
+//
+// Two kernels share the sample body: pathtrace_bvh_kernel (a lane group per pixel of the launch grid; §3.18) and pathtrace_bvh_list_kernel
+// (a lane group per entry of a list of storage indices, the accumulator left linear: the budgeted chain's rounds; §3.24).
 #pragma once
 #include "pathtrace_kernel.h"
 #include "pt_bvh.h"
@@ -177,8 +180,93 @@ __global__ void __launch_bounds__(256) pathtrace_bvh_kernel(BvhArgs k) {
     if (c.valid && c.j == 0) a.out[c.idx] = acc;
 }
 
-// The launcher of one tier (Fast = 0 strict, 2 careful), instantiated by the tier's own translation unit.
+// ---- the LIST RENDER through the tree (include/mc_compute.h, mc_pathtrace_render_accel_list_device_async) -----------
+// pathtrace_list_kernel of pt_budget_kernel.h — an S-lane group takes one ENTRY of a list of storage indices, its accumulator is read
+// from the plane, scaled by `prescale`, continued over [sample_begin, sample_end) in sample order and stored back LINEAR (never :453) —
+// RESTATED with trace_sample_bvh as the sample, as pathtrace_bvh_kernel above restates pathtrace_kernel.  The scene stays in memory (the
+// NP = -2 family): nothing is staged, no LDS.  Bounds: an entry is read only below `count`; an entry >= W * H is skipped (no load, no
+// trace, no store).  Entries must be distinct.
+struct BvhListArgs {
+    const uint32_t* __restrict__ list;   // storage indices row * W + gx, any order, distinct
+    uint32_t count;                      // entries, > 0
+    float prescale;                      // the stored accumulator is multiplied by this before the range is added (sample_begin > 0)
+};
+
+// Waves per SIMD the list kernel's register budget is set for: what pathtrace_bvh_kernel of the same tier and width gets on its own (7 in the
+// careful tier and at S = 1, 6 in the strict tier at S = 4 and 16), so that a round never runs at a lower occupancy than the render it continues.
+// (Left to itself the strict S = 1 list kernel takes 73 VGPRs, one above the 72 that seven waves allow.)
+template <int Fast, int S> constexpr int bvh_list_waves() { return (Fast || S == 1) ? 7 : 6; }
+
+template <int Fast, int S>
+__global__ void __launch_bounds__(256, (bvh_list_waves<Fast, S>())) pathtrace_bvh_list_kernel(BvhArgs k, BvhListArgs l) {
+    const PTArgs& a = k.a;
+    // (a lane's entry, pixel and sample slot derived afresh where needed, through an opaque copy: see pathtrace_list_kernel)
+    struct LaneCoords { uint32_t j, gx, gy, idx; bool valid; };
+    auto lane_coords = [&]() {
+        uint32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        LaneCoords c;
+        c.j = tid % (uint32_t)S;                                                        // (S divides 64: the slot within the wave's group)
+        const uint32_t entry = blockIdx.x * (256u / (uint32_t)S) + tid / (uint32_t)S;   // a wave's groups are adjacent entries
+        const bool listed = entry < l.count;
+        const uint32_t idx = l.list[listed ? entry : 0u];
+        c.valid = listed && idx < a.W * a.H;            // (the host refuses images of more than 2^31 pixels)
+        c.idx = c.valid ? idx : 0u;
+        const uint32_t row = c.idx / a.W;
+        c.gx = c.idx - row * a.W;
+        c.gy = a.H - 1u - row;                          // pathTracer.comp:349
+        return c;
+    };
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (a.sample_begin > 0) {
+        const LaneCoords c = lane_coords();
+        if (c.valid) {
+            acc = a.out[c.idx];
+            acc.x = acc.x * l.prescale; acc.y = acc.y * l.prescale; acc.z = acc.z * l.prescale; acc.w = acc.w * l.prescale;
+        }
+    }
+    const float fspp = (float)a.spp;
+    for (uint32_t base = a.sample_begin; base < a.sample_end; base += (uint32_t)S) {
+        const LaneCoords c = lane_coords();
+        const uint32_t s = base + c.j;
+        v3 q{0.0f, 0.0f, 0.0f};
+        if (c.valid && s < a.sample_end) {
+            v3 rad = trace_sample_bvh<Fast>(k, c.gx, c.gy, s);
+            q = Fast ? rad * a.inv_spp : divs_recip<Fast>(rad, fspp, a.inv_spp);      // :452, as pathtrace_bvh_kernel
+        }
+        // the round's S samples into the accumulator in sample order (pathtrace_bvh_kernel's fold)
+        const uint32_t count = min((uint32_t)S, a.sample_end - base);
+        if (S == 1) {
+            acc.x += q.x; acc.y += q.y; acc.z += q.z; acc.w += 0.0f;
+        } else {
+            uint32_t tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            const uint32_t first = (tid & 63u) - (tid & 63u) % (uint32_t)S;
+            auto from_lane = [](float v, uint32_t src) {
+                return __int_as_float(__builtin_amdgcn_ds_bpermute((int)(src << 2), __float_as_int(v)));
+            };
+            for (uint32_t kk = 0; kk < count; kk++) {
+                const uint32_t src = first + kk;
+                acc.x += from_lane(q.x, src); acc.y += from_lane(q.y, src); acc.z += from_lane(q.z, src); acc.w += 0.0f;
+            }
+        }
+    }
+    const LaneCoords c = lane_coords();
+    if (c.valid && c.j == 0u) a.out[c.idx] = acc;   // linear: no :453 here, whatever sample_end is
+}
+
+// The launchers of one tier (Fast = 0 strict, 2 careful), instantiated by the tier's own translation unit.
 template <int Fast> int launch_bvh_tier(const BvhArgs& k, int S, uint32_t tile_rows, hipStream_t s);
+template <int Fast> int launch_bvh_list_tier(const BvhArgs& k, const BvhListArgs& l, int S, hipStream_t s);
+
+template <int Fast> int launch_bvh_list_tier_impl(const BvhArgs& k, const BvhListArgs& l, int S, hipStream_t s) {
+    return dispatch<1, 4, 16>(S, [&](auto W) {
+        constexpr int Sv = decltype(W)::value;
+        constexpr uint32_t per_block = 256u / (uint32_t)Sv;
+        hipLaunchKernelGGL((pathtrace_bvh_list_kernel<Fast, Sv>), dim3((l.count + per_block - 1u) / per_block), dim3(256), 0, s, k, l);
+        return (int)MC_OK;
+    });
+}
 
 template <int Fast> int launch_bvh_tier_impl(const BvhArgs& k, int S, uint32_t tile_rows, hipStream_t s) {
     return dispatch<1, 4, 16>(S, [&](auto W) {

@@ -98,16 +98,20 @@ inline Camera camera() {
     return c;
 }
 
-// The centre ray of pixel (gx, gy) against the records rec (12 floats each: n_planes planes, then n_spheres spheres).
-MC_PTD_FN void guide_pixel(const Camera& cam, uint32_t W, uint32_t H, uint32_t gx, uint32_t gy, const float* rec, uint32_t n_planes,
-                           uint32_t n_spheres, vec4& normal_t, vec4& position_id) {
+// A pixel's guides in three parts, so that a caller with another intersect() (pt_bvh_guides.h: the sphere BVH) shares the ray and the tail:
+// the centre ray of pixel (gx, gy) ...
+MC_PTD_FN void guide_ray(const Camera& cam, uint32_t W, uint32_t H, uint32_t gx, uint32_t gy, f3& o, f3& d) {
     const float sx = (((float)gx + 0.5f) / (float)W - 0.5f) * 0.036f;
     const float sy = (((float)gy + 0.5f) / (float)H - 0.5f) * 0.024f;
     const f3 spos = add(add(cam.o, muls(cam.cx, sx)), muls(cam.cy, sy));
-    const f3 o = cam.lc;
-    const f3 d = normalize(sub(cam.lc, spos));
-    float t = kInf;
-    int32_t id = -1;   // (the entry points refuse more than 2^20 objects)
+    o = cam.lc;
+    d = normalize(sub(cam.lc, spos));
+}
+
+// ... intersect() over the records rec (12 floats each: n_planes planes, then n_spheres spheres), every object in table order ...
+MC_PTD_FN void guide_intersect_linear(f3 o, f3 d, const float* rec, uint32_t n_planes, uint32_t n_spheres, float& t, int32_t& id) {
+    t = kInf;
+    id = -1;   // (the entry points refuse more than 2^20 objects)
     for (uint32_t i = 0; i < n_planes; i++) {
         const float* pl = rec + 12 * (size_t)i;
         const f3 n{pl[0], pl[1], pl[2]};
@@ -132,6 +136,10 @@ MC_PTD_FN void guide_pixel(const Camera& cam, uint32_t W, uint32_t H, uint32_t g
             if (dd < t) { t = dd; id = (int32_t)(n_planes + i); }
         }
     }
+}
+
+// ... and the two vec4s of the first hit (id, t): a miss is !(t < 1e20); rec[12 * id + 0 .. 2] is the plane's normal or the sphere's centre.
+MC_PTD_FN void guide_tail(f3 o, f3 d, float t, int32_t id, const float* rec, uint32_t n_planes, vec4& normal_t, vec4& position_id) {
     if (!(t < kInf)) {
         normal_t = vec4{0.0f, 0.0f, 0.0f, kInf};
         position_id = vec4{0.0f, 0.0f, 0.0f, -1.0f};
@@ -144,6 +152,17 @@ MC_PTD_FN void guide_pixel(const Camera& cam, uint32_t W, uint32_t H, uint32_t g
     const f3 nl = dot(n, d) < 0.0f ? n : neg(n);
     normal_t = vec4{nl.x, nl.y, nl.z, t};
     position_id = vec4{x.x, x.y, x.z, (float)id};
+}
+
+// The centre ray of pixel (gx, gy) against the records rec (12 floats each: n_planes planes, then n_spheres spheres).
+MC_PTD_FN void guide_pixel(const Camera& cam, uint32_t W, uint32_t H, uint32_t gx, uint32_t gy, const float* rec, uint32_t n_planes,
+                           uint32_t n_spheres, vec4& normal_t, vec4& position_id) {
+    f3 o, d;
+    guide_ray(cam, W, H, gx, gy, o, d);
+    float t;
+    int32_t id;
+    guide_intersect_linear(o, d, rec, n_planes, n_spheres, t, id);
+    guide_tail(o, d, t, id, rec, n_planes, normal_t, position_id);
 }
 
 inline void guides_host(uint32_t W, uint32_t H, const float* rec, uint32_t n_planes, uint32_t n_spheres, vec4* normal_t, vec4* position_id) {

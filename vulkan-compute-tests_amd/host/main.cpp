@@ -258,7 +258,7 @@ int main(int argc, char* argv[]) {
                                                                   : nullptr;
         if (why) { printf("--zoom-keyframes counts: %s\n", why); exit(EXIT_FAILURE); }
     }
-    if (noiseGuidedSet && (gpus > 1 || accel)) { printf("--noise-guided: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
+    if (noiseGuidedSet && gpus > 1) { printf("--noise-guided: one GPU (the chain has no multi-GPU form)\n"); exit(EXIT_FAILURE); }
     if (denoise && gpus > 1) { printf("--denoise: one GPU (the filter reads across the rows of the whole image)\n"); exit(EXIT_FAILURE); }
     if (noiseGuidedSet && !denoise) { printf("--noise-guided: only with --denoise (it steers that filter's colour tolerance)\n"); exit(EXIT_FAILURE); }
     if (noiseTargetSet && !budgetSet) { printf("--noise-target: only with --budget (it is the noise a budgeted pixel may keep)\n"); exit(EXIT_FAILURE); }
@@ -266,9 +266,14 @@ int main(int argc, char* argv[]) {
         printf("--budget: not with --denoise (a budgeted-then-filtered chain is not offered: the noise-guided filter needs a half / full pair per pixel)\n");
         exit(EXIT_FAILURE);
     }
-    if (budgetSet && (gpus > 1 || accel)) { printf("--budget: one GPU, and not with --accel bvh (the chain has no multi-GPU or BVH form)\n"); exit(EXIT_FAILURE); }
+    if (budgetSet && gpus > 1) { printf("--budget: one GPU (the chain has no multi-GPU form)\n"); exit(EXIT_FAILURE); }
     if (budgetSet && spherePrec != MC_PT_PREC_F32) { printf("--budget: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
-    if (accel && (gpus > 1 || denoise)) { printf("--accel bvh: one GPU, and not with --denoise (the accelerated calls have no multi-GPU or denoised form)\n"); exit(EXIT_FAILURE); }
+    if (accel && gpus > 1) { printf("--accel bvh: one GPU (the accelerated calls have no multi-GPU form)\n"); exit(EXIT_FAILURE); }
+    if (accel && denoise && !noiseGuidedSet) {
+        printf("--accel bvh --denoise: only with --noise-guided (the app runs the accelerated noise-guided chain; the fixed-tolerance one, "
+               "mc_pathtrace_render_accel_denoised, is a library call)\n");
+        exit(EXIT_FAILURE);
+    }
     if (accel && spherePrec != MC_PT_PREC_F32) { printf("--accel bvh: the fp32 sphere test only (--sphere-precision f32)\n"); exit(EXIT_FAILURE); }
 #if !defined(PATHTRACER_MODE)
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }

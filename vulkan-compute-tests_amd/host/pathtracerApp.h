@@ -64,7 +64,7 @@ struct PathtracerApp : public ComputeApp {
     // with k_noise = K and the default radius; 0 = off.
     void setNoiseGuided(float k) { noiseK = k; }
     // --budget [L] [--noise-target T]: run() is mc_pathtrace_render_budgeted — a pilot of spp samples, then up to L doublings where the measured
-    // noise is above T — with the default radius.  One GPU, no --denoise, no --accel bvh (main.cpp refuses those).
+    // noise is above T — with the default radius.  One GPU, no --denoise (main.cpp refuses those); with --accel bvh the accelerated chain.
     void setBudget(const mc_pathtrace_budget_params& b) { budget = b; budgeted = true; }
     // "budget: <pixels of level 0 .. L> mean <m> spp" (mc_context_last_budget), after run()
     void printBudget() const {
@@ -116,8 +116,9 @@ struct PathtracerApp : public ComputeApp {
         spheres.swap(sp);
         return "";
     }
-    // --accel bvh: run() renders through mc_pathtrace_render_accel* (one GPU, no --denoise: main.cpp refuses those).  The tree is built
-    // here, on the host.  Returns "" or the library's refusal.
+    // --accel bvh: run() renders through mc_pathtrace_render_accel* — the plain render, or with --denoise --noise-guided / --budget the
+    // accelerated noise-guided / budgeted chain (one GPU, no plain --denoise: main.cpp refuses those).  The tree is built here, on the
+    // host.  Returns "" or the library's refusal.
     std::string useAccel() {
         const int rc = mc_pathtrace_accel_create(planes.data(), (uint32_t)planes.size() / 12, spheres.data(), (uint32_t)spheres.size() / 12, &accel);
         if (rc != MC_OK) return std::string(mc_error_string(rc)) + " (" + mc_last_error_detail() + ")";
@@ -157,6 +158,23 @@ struct PathtracerApp : public ComputeApp {
     virtual void runCommandBuffer() override {
         const uint32_t np = (uint32_t)planes.size() / 12, ns = (uint32_t)spheres.size() / 12;
         if (accel) {
+            float* f32 = gpuPostprocess ? nullptr : buffer.data();   // both routes, as the table forms below
+            uint8_t* u8 = gpuPostprocess ? rgba8.bytes() : nullptr;
+            if (budgeted) {
+                check(mc_pathtrace_render_accel_budgeted(ctx, accel, &params, &budget, f32, u8, nullptr), "mc_pathtrace_render_accel_budgeted");
+                return;
+            }
+            if (denoisePasses) {   // (main.cpp lets only the noise-guided chain through)
+                mc_pathtrace_denoise_params d;
+                mc_pathtrace_denoise_default_params(params.width, params.height, &d);
+                d.passes = denoisePasses;
+                float k = 0.0f;
+                uint32_t radius = 0;
+                mc_pathtrace_noise_default_params(&k, &radius);
+                check(mc_pathtrace_render_accel_denoised_adaptive(ctx, accel, &params, &d, noiseK, radius, f32, u8),
+                      "mc_pathtrace_render_accel_denoised_adaptive");
+                return;
+            }
             if (gpuPostprocess) check(mc_pathtrace_render_accel_rgba8(ctx, accel, &params, rgba8.bytes()), "mc_pathtrace_render_accel_rgba8");
             else check(mc_pathtrace_render_accel(ctx, accel, &params, buffer.data()), "mc_pathtrace_render_accel");
             return;
