@@ -47,7 +47,8 @@ extern "C" {
  * mc_mandelbrot_zoom_compose_counts_device_async and mc_mandelbrot_zoom_counts_create, _push, _frame, _maps and _destroy; then the area
  * filter of the minified deep keyframe: MC_MANDEL_ZOOM_FILTER_BILINEAR / _AREA with mc_mandelbrot_zoom_compose_filtered,
  * mc_mandelbrot_zoom_compose_filtered_device_async, mc_mandelbrot_zoom_compose_counts_filtered,
- * mc_mandelbrot_zoom_compose_counts_filtered_device_async, mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered.
+ * mc_mandelbrot_zoom_compose_counts_filtered_device_async, mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered;
+ * then MC_MANDEL_SUPERSAMPLE_SMOOTH with mc_mandelbrot_resolve_smooth_device_async and mc_mandelbrot_resolve_smooth.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -332,8 +333,10 @@ enum {
     MC_MANDEL_COLOUR_DISTANCE = 1u << 7,/* the smooth colour shaded by a boundary distance estimate, of a WHOLE image (the      */
                                   /* contract is below, at mc_mandelbrot_render_distance); set WITHOUT MC_MANDEL_COLOUR_SMOOTH */
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
-    MC_MANDEL_COLOUR_SMOOTH_EQUALISED = 1u << 12 /* the smooth count ranked among a WHOLE image's escaped pixels (the contract is   */
+    MC_MANDEL_COLOUR_SMOOTH_EQUALISED = 1u << 12,/* the smooth count ranked among a WHOLE image's escaped pixels (the contract is  */
                                   /* below, at mc_mandelbrot_render_smooth_equalised); set WITHOUT MC_MANDEL_COLOUR_SMOOTH     */
+    MC_MANDEL_SUPERSAMPLE_SMOOTH = 1u << 13 /* with MC_MANDEL_SUPERSAMPLE(s) and ONE of the two smooth colourings: the s x s samples  */
+                                  /* are smooth counts (the contract is below, at mc_mandelbrot_resolve_smooth_device_async)   */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
  * 2, 4, 8: valid; 3, 5, 6, 7, 9 .. 15: MC_ERR_INVALID_ARGUMENT.  The contract is below, at mc_mandelbrot_resolve_device_async. */
@@ -455,7 +458,7 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
  * tiles and interleaved tiles, MC_MANDEL_ITERS_U16 for the n plane, and mc_context_warmup_mandelbrot, which makes the smooth
  * instantiation resident.  Together with MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_SUPERSAMPLE(s >= 2) or MC_MANDEL_SUPERSAMPLE_ADAPTIVE it is
  * MC_ERR_INVALID_ARGUMENT (mc_last_error_detail says which: the rank map over fractional counts is MC_MANDEL_COLOUR_SMOOTH_EQUALISED, a flag
- * of its own, below; a resolve over fractional counts does not exist yet); so it is
+ * of its own, below; the resolve over fractional counts is asked for with MC_MANDEL_SUPERSAMPLE_SMOOTH beside the factor, further below); so it is
  * together with the measurement switch MC_MANDEL_FMA of mc_compute_test.h (the contraction switch has no smooth kernel).  The calls
  * that build colours from a plane of integer counts refuse it with MC_ERR_INVALID_ARGUMENT: mc_mandelbrot_recolour_device_async,
  * mc_mandelbrot_resolve_device_async, mc_mandelbrot_assemble_device_async (mc_mandelbrot_histogram_device_async takes no params and so
@@ -614,7 +617,7 @@ int mc_mandelbrot_smooth_remap_device_async(mc_context* ctx, const mc_mandelbrot
  *
  * mc_mandelbrot_supersample_params (host only, no device): q = the plain-render parameters of p's sample grid: width, height, row_begin,
  * row_end, row_block and row_stride multiplied by s, the supersample bits, MC_MANDEL_COLOUR_EQUALISED and MC_MANDEL_SUPERSAMPLE_ADAPTIVE cleared, everything else copied
- * (q may be p).  A contiguous or interleaved tile of p is exactly the tile of q whose compact rows are, for each compact pixel row, its s
+ * (q may be p; with MC_MANDEL_SUPERSAMPLE_SMOOTH set, see that bit's section below: the grid's smooth-render parameters).  A contiguous or interleaved tile of p is exactly the tile of q whose compact rows are, for each compact pixel row, its s
  * sample rows in order.  s = 0 or 1 multiplies by 1.  An invalid s, a product above 2^32 - 1 or a NULL pointer: MC_ERR_INVALID_ARGUMENT.
  *
  * mc_mandelbrot_resolve_device_async writes the colours of p's compact tile (p carries MC_MANDEL_SUPERSAMPLE(s), s = 2, 4, 8) to
@@ -658,6 +661,57 @@ int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_para
  * mc_context_last_refined: the refined pixels and the image's pixels of the context's last successful adaptive render; either pointer may
  * be NULL; MC_ERR_INVALID_ARGUMENT before the first such render. */
 int mc_context_last_refined(mc_context* ctx, uint64_t* refined, uint64_t* pixels);
+
+/* ---- smooth supersampling: the resolve over fractional counts (the project's own addition; what
+ *      tests/mandel_smooth_supersample_ref.py restates).  MC_MANDEL_SUPERSAMPLE_SMOOTH in flags, valid only together with
+ *      MC_MANDEL_SUPERSAMPLE(s), s = 2, 4 or 8, and EXACTLY ONE of MC_MANDEL_COLOUR_SMOOTH and MC_MANDEL_COLOUR_SMOOTH_EQUALISED: the
+ *      anti-aliased, band-free image.  It composes two existing expressions and defines no new floating-point one.
+ *  - samples: the supersampling section's, unchanged: sample (s*y + i, s*x + j) of pixel (y, x) is the pixel at that position of the
+ *    plain smooth s*W x s*H render, and its smooth count q is whatever mc_mandelbrot_render_smooth gives there.
+ *  - a sample's colour: mc_mandelbrot_smooth_colour's expression applied to q (a q >= 256 M gives lut[M]); with a knot map qmap, that
+ *    expression applied to q', mc_mandelbrot_smooth_remap's expression of q.
+ *  - a pixel's colour: the supersampling section's tree over those s*s vec4: sums by adjacent pairs, level by level, first inside a
+ *    sample row, then over the row sums, then one multiply by 1.0f / (s*s); all fp32, round to nearest, no contraction; alpha is exactly
+ *    1.0f.
+ *  - CONSEQUENCES: (1) a pixel whose s*s samples share one q gets exactly the smooth colour of that q: interior and flat regions are
+ *    bit-identical to the plain smooth image; (2) a plane whose fractions are all 0 (q = 256 n) gives, bit for bit, what
+ *    mc_mandelbrot_resolve_device_async gives for the counts n; (3) the image does not depend on how pixels are grouped onto lanes.
+ *  - ranked form (MC_MANDEL_COLOUR_SMOOTH_EQUALISED): hist is the histogram of min(q >> 8, M) over ALL s*s*W*H samples (more than
+ *    2^32 - 1 samples: MC_ERR_INVALID_ARGUMENT), qmap is mc_mandelbrot_smooth_equalise_map of it, every sample is coloured through qmap.
+ *  - limits: s in {2, 4, 8}; max_iter <= 2^24 - 1.
+ * The pairs MC_MANDEL_COLOUR_SMOOTH | MC_MANDEL_SUPERSAMPLE(s) and MC_MANDEL_COLOUR_SMOOTH_EQUALISED | MC_MANDEL_SUPERSAMPLE(s) WITHOUT the
+ * bit stay MC_ERR_INVALID_ARGUMENT as before (mc_last_error_detail now names the bit).  The bit alone, with s <= 1, with neither or both
+ * colourings, or together with MC_MANDEL_SUPERSAMPLE_ADAPTIVE, MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_COLOUR_DISTANCE, MC_MANDEL_ITERS_U16
+ * or the measurement switch MC_MANDEL_FMA is MC_ERR_INVALID_ARGUMENT, mc_last_error_detail naming the bit and what it needs.
+ * mc_mandelbrot_render (out_rgba_f32; out_iters refused as for every s >= 2) and mc_mandelbrot_render_rgba8 honour it in all six
+ * precisions.  MC_MANDEL_COLOUR_SMOOTH form: whole images, contiguous row bands and, for mc_mandelbrot_render, interleaved row tiles —
+ * what plain supersampling serves; a band's bytes are the whole image's rows.  Ranked form: whole images only (the refusal is
+ * MC_MANDEL_COLOUR_SMOOTH_EQUALISED's own).  The chain: the smooth render of the sample grid's q plane only (no n plane and no vec4 leave
+ * the render kernel), [the smooth histogram over all samples, the table's round trip and the knot map when ranked,] the resolve, for
+ * _rgba8 the conversion.  mc_context_last_timing spans the chain.  The q plane is scratch of the context and always uint32_t: 4 bytes x
+ * s*s x the tile's pixels (7680 x 5120 at s = 4: 2.5 GB); bound it with row bands, or with the device call below.
+ * mc_context_warmup_mandelbrot accepts the bit and makes the resolve kernel resident too; mc_mandelbrot_zoom_push renders through
+ * mc_mandelbrot_render and so accepts it.  EVERY OTHER call that takes mc_mandelbrot_params refuses the bit by name with
+ * MC_ERR_INVALID_ARGUMENT: mc_mandelbrot_render_device_async, _render_banded, _render_smooth / _device_async, _render_distance,
+ * _distance_device_async, _render_smooth_equalised, _recolour_device_async, _resolve_device_async, _assemble_device_async,
+ * _smooth_remap_device_async and the count-keyframe zoom calls; mc_multi_* answer MC_ERR_UNSUPPORTED.
+ * mc_mandelbrot_supersample_params with the bit set clears it, keeps MC_MANDEL_COLOUR_SMOOTH and replaces
+ * MC_MANDEL_COLOUR_SMOOTH_EQUALISED by MC_MANDEL_COLOUR_SMOOTH: q is directly the argument of mc_mandelbrot_render_smooth_device_async
+ * for the sample grid.  Without the bit it behaves as before (the smooth bits are copied).
+ *
+ * mc_mandelbrot_resolve_smooth_device_async: the stage by hand, sibling of mc_mandelbrot_resolve_device_async.  p carries the bit, the
+ * factor and one of the two colourings; d_smooth holds the compact sample rows of p's tile (contiguous or interleaved), uint32_t,
+ * aligned to 4 (any such alignment); d_rgba_f32 is aligned to 16.  `qmap` is a HOST table of max_iter + 1 knots, checked as
+ * mc_mandelbrot_smooth_remap_device_async checks it and sharing that call's cached pair table; it must be given exactly when p carries
+ * MC_MANDEL_COLOUR_SMOOTH_EQUALISED.  The colour table is the context's cached one.  A q above 256 max_iter on the device is taken as
+ * interior: no gather can leave a table.
+ * mc_mandelbrot_resolve_smooth (host only, no device): the same source as the kernel.  q: (rows * s) x (s * width) smooth counts, dense;
+ * qmap: max_iter + 1 knots or NULL; out_rgba_f32: rows * width vec4.  A NULL pointer (qmap excepted), a zero size, s outside {2, 4, 8},
+ * max_iter = 0 or above 2^24 - 1, a q above 256 max_iter, or a qmap mc_mandelbrot_smooth_remap would refuse: MC_ERR_INVALID_ARGUMENT. */
+int mc_mandelbrot_resolve_smooth_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth,
+                                              const uint32_t* qmap /* HOST, max_iter + 1, or NULL */, void* d_rgba_f32, void* stream);
+int mc_mandelbrot_resolve_smooth(uint32_t max_iter, const float k_color[4], uint32_t s, uint32_t width, uint32_t rows, const uint32_t* q,
+                                 const uint32_t* qmap /* max_iter + 1, or NULL */, float* out_rgba_f32);
 
 /* ---- zoom sequences (the project's own addition: the reference renders one still; what tests/mandel_zoom_ref.py
  *      restates).  A zoom renders one KEYFRAME per octave (the scale halves from one to the next, the centre stays) and composes every

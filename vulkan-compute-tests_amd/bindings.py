@@ -30,6 +30,7 @@ MANDEL_COLOUR_DISTANCE = 128    # MC_MANDEL_COLOUR_DISTANCE: the smooth colour s
 ZOOM_FILTER_BILINEAR = 0   # MC_MANDEL_ZOOM_FILTER_BILINEAR: the filtered zoom calls return what their unfiltered namesakes return
 ZOOM_FILTER_AREA = 1       # MC_MANDEL_ZOOM_FILTER_AREA: a box over the pixel's footprint in the minified deep keyframe
 MANDEL_COLOUR_SMOOTH_EQUALISED = 4096   # MC_MANDEL_COLOUR_SMOOTH_EQUALISED: the smooth count ranked among a whole image's escaped pixels; set without MANDEL_COLOUR_SMOOTH
+MANDEL_SUPERSAMPLE_SMOOTH = 8192   # MC_MANDEL_SUPERSAMPLE_SMOOTH: with MANDEL_SUPERSAMPLE(s) and one smooth colouring, the s x s samples are smooth counts
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
@@ -205,6 +206,9 @@ def lib():
             L.mc_mandelbrot_smooth_equalise_map.argtypes = [u32, vp, vp]
             L.mc_mandelbrot_smooth_remap.argtypes = [u32, vp, vp, C.c_uint64, vp]
             L.mc_mandelbrot_smooth_remap_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp, vp]
+        if hasattr(L, "mc_mandelbrot_resolve_smooth"):   # MC_MANDEL_SUPERSAMPLE_SMOOTH
+            L.mc_mandelbrot_resolve_smooth_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
+            L.mc_mandelbrot_resolve_smooth.argtypes = [u32, C.POINTER(f32), u32, u32, u32, vp, vp, vp]
         if hasattr(L, "mc_mandelbrot_zoom_compose"):   # zoom sequences
             dbl = C.c_double
             L.mc_mandelbrot_zoom_ratio.argtypes = [u32, u32, C.POINTER(dbl)]
@@ -366,11 +370,14 @@ def split_double(d):
 
 def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, centre=(-0.445, 0.0), scale=(2.34, 2.34),
                       k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0, supersample=0,
-                      adaptive=False):
-    """adaptive: MANDEL_SUPERSAMPLE_ADAPTIVE beside supersample= (only pixels whose count differs from a neighbour's are sampled s x s)."""
+                      adaptive=False, smooth_samples=False):
+    """adaptive: MANDEL_SUPERSAMPLE_ADAPTIVE beside supersample= (only pixels whose count differs from a neighbour's are sampled s x s).
+    smooth_samples: MANDEL_SUPERSAMPLE_SMOOTH beside supersample= and one of MANDEL_COLOUR_SMOOTH / MANDEL_COLOUR_SMOOTH_EQUALISED in
+    flags= (the samples are smooth counts, resolved over fractional counts)."""
     p = MandelbrotParams()
     _check(lib().mc_mandelbrot_default_params(width, height, C.byref(p)), "mc_mandelbrot_default_params")
     p.max_iter, p.precision, p.flags = max_iter, precision, flags | MANDEL_SUPERSAMPLE(supersample) | (MANDEL_SUPERSAMPLE_ADAPTIVE if adaptive else 0)
+    p.flags |= MANDEL_SUPERSAMPLE_SMOOTH if smooth_samples else 0
     p.centre_x_hi, p.centre_x_lo = split_double(centre[0])
     p.centre_y_hi, p.centre_y_lo = split_double(centre[1])
     p.scale_x_hi, p.scale_x_lo = split_double(scale[0])
@@ -384,7 +391,8 @@ def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, cent
 
 def supersample_params(p):
     """mc_mandelbrot_supersample_params (host only): the plain-render params of p's sample grid (s times the width, height and rows; the
-    supersample bits, MANDEL_COLOUR_EQUALISED and MANDEL_SUPERSAMPLE_ADAPTIVE cleared)."""
+    supersample bits, MANDEL_COLOUR_EQUALISED and MANDEL_SUPERSAMPLE_ADAPTIVE cleared; with MANDEL_SUPERSAMPLE_SMOOTH that bit cleared too and
+    the colouring MANDEL_COLOUR_SMOOTH: the params of the grid's smooth render)."""
     q = MandelbrotParams()
     _check(lib().mc_mandelbrot_supersample_params(C.byref(p), C.byref(q)), "mc_mandelbrot_supersample_params")
     return q
@@ -426,6 +434,24 @@ def smooth_remap(max_iter, qmap, q):
     qa = np.ascontiguousarray(q, np.uint32)
     out = np.empty(qa.shape, np.uint32)
     _check(lib().mc_mandelbrot_smooth_remap(max_iter, _ptr(m), _ptr(qa), qa.size, _ptr(out)), "mc_mandelbrot_smooth_remap")
+    return out
+
+
+def resolve_smooth(max_iter, s, q, qmap=None, k_color=(0.1, 0.7, 0.6, 0.0)):
+    """mc_mandelbrot_resolve_smooth (host only): float32 (rows, width, 4), the s x s resolve over fractional counts of the dense smooth
+    sample plane q, uint32 (rows * s, width * s), each q <= 256 * max_iter; qmap: max_iter + 1 knots for the ranked form, or None."""
+    qa = np.ascontiguousarray(q, np.uint32)
+    if qa.ndim != 2 or not s or qa.shape[0] % s or qa.shape[1] % s:
+        raise ValueError("resolve_smooth: q is a (rows * s, width * s) plane")
+    m = None
+    if qmap is not None:
+        m = np.ascontiguousarray(qmap, np.uint32).reshape(-1)
+        if max_iter and m.size != max_iter + 1:
+            raise ValueError(f"resolve_smooth: the map has {m.size} knots, max_iter + 1 = {max_iter + 1} expected")
+    rows, width = qa.shape[0] // s, qa.shape[1] // s
+    k = (C.c_float * 4)(*k_color)
+    out = np.empty((rows, width, 4), np.float32)
+    _check(lib().mc_mandelbrot_resolve_smooth(max_iter, k, s, width, rows, _ptr(qa), _ptr(m), _ptr(out)), "mc_mandelbrot_resolve_smooth")
     return out
 
 
@@ -1177,6 +1203,18 @@ class Context:
                 raise ValueError(f"Context.mandelbrot_resolve_device: the map has {m.size} entries, max_iter + 1 = {p.max_iter + 1} expected")
         _check(lib().mc_mandelbrot_resolve_device_async(self._h, C.byref(p), d_samples or None, iters_bytes, _ptr(m), d_rgba or None,
                                                         stream or None), "mc_mandelbrot_resolve_device_async")
+
+    def mandelbrot_resolve_smooth_device(self, p, d_smooth, qmap, d_rgba, stream=0):
+        """mc_mandelbrot_resolve_smooth_device_async: the colours of p's tile (p carries MANDEL_SUPERSAMPLE_SMOOTH, MANDEL_SUPERSAMPLE(s) and
+        one smooth colouring) from the smooth sample plane that mandelbrot_smooth_device(supersample_params(p)) wrote; qmap is a host array
+        of max_iter + 1 knots for MANDEL_COLOUR_SMOOTH_EQUALISED, None otherwise."""
+        m = None
+        if qmap is not None:
+            m = np.ascontiguousarray(qmap, np.uint32).reshape(-1)
+            if m.size != p.max_iter + 1:
+                raise ValueError(f"Context.mandelbrot_resolve_smooth_device: the map has {m.size} knots, max_iter + 1 = {p.max_iter + 1} expected")
+        _check(lib().mc_mandelbrot_resolve_smooth_device_async(self._h, C.byref(p), d_smooth or None, _ptr(m), d_rgba or None, stream or None),
+               "mc_mandelbrot_resolve_smooth_device_async")
 
     def zoom_compose_device(self, width, height, d_wide, d_deep, r, d_rgba=0, d_rgba8=0, stream=0):
         """mc_mandelbrot_zoom_compose_device_async: the frame at r from the device keyframes d_wide and d_deep (0: absent) into the vec4

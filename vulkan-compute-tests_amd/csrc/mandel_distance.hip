@@ -20,6 +20,7 @@
 
 #include "mandel_distance.h"
 #include "mandel_distance_host.h"
+#include "mandel_resolve_smooth_host.h"
 #include "mandel_smooth_equalise_host.h"
 
 namespace mc {
@@ -106,6 +107,7 @@ int refuse_threshold(const char* who) {
 int mandelbrot_distance_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth, float threshold_px, void* d_distance,
                                void* d_rgba, const char* who, hipStream_t s) {
     if (!ctx || !p || !d_smooth || (!d_distance && !d_rgba) || !p->height || !p->max_iter || !rows_ok(p)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = smooth_samples_refuse_flag(p, who)) return rc;
     if (int rc = smooth_equalised_refuse_flag(p, who)) return rc;
     if (!distance_flag(p)) {
         set_error_detail(std::string(who) + ": the params must carry MC_MANDEL_COLOUR_DISTANCE");

@@ -23,6 +23,7 @@
 #include "mandel_distance_host.h"
 #include "mandel_equalise.h"
 #include "mandel_histogram_kernel.h"
+#include "mandel_resolve_smooth_host.h"
 #include "mandel_side_record.h"
 #include "mandel_smooth_equalise_host.h"
 #include "mandel_smooth_host.h"
@@ -249,6 +250,7 @@ int mc_mandelbrot_recolour_device_async(mc_context* ctx, const mc_mandelbrot_par
                                         const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_iters || !map || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u))
         return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = smooth_samples_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     if (int rc = smooth_equalised_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;
     if (int rc = distance_refuse_flag(p, "mc_mandelbrot_recolour_device_async")) return rc;

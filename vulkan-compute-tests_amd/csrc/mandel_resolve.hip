@@ -17,6 +17,7 @@
 
 #include "mandel_equalise.h"
 #include "mandel_distance_host.h"
+#include "mandel_resolve_smooth_host.h"
 #include "mandel_smooth_equalise_host.h"
 #include "mandel_smooth_host.h"
 
@@ -159,6 +160,11 @@ int mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_p
     out.row_begin = p->row_begin * s; out.row_end = p->row_end * s;
     out.row_block = p->row_block * s; out.row_stride = p->row_stride * s;
     out.flags &= ~((uint32_t)MC_MANDEL_SUPERSAMPLE(15) | (uint32_t)MC_MANDEL_COLOUR_EQUALISED | (uint32_t)MC_MANDEL_SUPERSAMPLE_ADAPTIVE);
+    if (out.flags & MC_MANDEL_SUPERSAMPLE_SMOOTH) {   // the samples are smooth counts: q renders the grid's q plane (mandel_resolve_smooth.hip)
+        if (out.flags & MC_MANDEL_COLOUR_SMOOTH_EQUALISED)
+            out.flags = (out.flags & ~(uint32_t)MC_MANDEL_COLOUR_SMOOTH_EQUALISED) | (uint32_t)MC_MANDEL_COLOUR_SMOOTH;
+        out.flags &= ~(uint32_t)MC_MANDEL_SUPERSAMPLE_SMOOTH;
+    }
     *q = out;
     return MC_OK;
 }
@@ -203,6 +209,7 @@ int mc_mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbro
 int mc_mandelbrot_resolve_device_async(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_samples, uint32_t iters_bytes,
                                        const uint32_t* map, void* d_rgba_f32, void* stream) {
     if (!ctx || !p || !d_samples || !d_rgba_f32 || !p->max_iter || (iters_bytes != 2u && iters_bytes != 4u)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = smooth_samples_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (int rc = smooth_equalised_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (int rc = smooth_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;
     if (int rc = distance_refuse_flag(p, "mc_mandelbrot_resolve_device_async")) return rc;

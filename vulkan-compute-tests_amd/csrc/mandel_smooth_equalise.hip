@@ -15,6 +15,7 @@
 
 #include "mandel_distance_host.h"
 #include "mandel_histogram_kernel.h"
+#include "mandel_resolve_smooth_host.h"
 #include "mandel_side_record.h"
 #include "mandel_smooth_equalise.h"
 #include "mandel_smooth_equalise_host.h"
@@ -144,6 +145,7 @@ int mandelbrot_smooth_histogram_launch(mc_context* ctx, const void* d_smooth, ui
 
 // The remap stage's params: the flag, alone among the colourings.
 static int smooth_remap_check(const mc_mandelbrot_params* p, const char* who) {
+    if (int rc = smooth_samples_refuse_flag(p, who)) return rc;
     if (!smooth_equalised_flag(p)) {
         set_error_detail(std::string(who) + ": the params must carry MC_MANDEL_COLOUR_SMOOTH_EQUALISED");
         return MC_ERR_INVALID_ARGUMENT;
@@ -175,6 +177,23 @@ int mandelbrot_smooth_remap_launch(mc_context* ctx, const mc_mandelbrot_params* 
     return ctx->note_launch(s);   // (reads the cached pair and colour tables)
 }
 
+int mandelbrot_smooth_equalise_plane_map(mc_context* ctx, uint32_t max_iter, const void* d_smooth, uint64_t n, hipStream_t s,
+                                         const uint32_t** qmap) {
+    SmoothEqualiseState* st = g_sq_states.get(ctx);
+    const size_t entries = (size_t)max_iter + 1;
+    int rc = st->hist.reserve(entries * 4);
+    if (rc) return rc;
+    st->hist_host.resize(entries);
+    st->qmap_host.resize(entries);
+    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
+    if ((rc = mandelbrot_smooth_histogram_launch(ctx, d_smooth, n, max_iter, st->hist.ptr, s))) return rc;
+    MC_HIP_TRY(hipMemcpyAsync(st->hist_host.data(), st->hist.ptr, entries * 4, hipMemcpyDeviceToHost, s));
+    MC_HIP_TRY(hipStreamSynchronize(s));
+    if (!smooth_equalise::knot_map(max_iter, st->hist_host.data(), st->qmap_host.data())) return MC_ERR_INVALID_ARGUMENT;   // (n < 2^32: cannot happen)
+    *qmap = st->qmap_host.data();
+    return MC_OK;
+}
+
 int mandelbrot_smooth_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth, void* d_ranked, void* d_rgba,
                                      const char* who, hipStream_t s) {
     const uint64_t npix = (uint64_t)p->width * p->height;
@@ -183,18 +202,9 @@ int mandelbrot_smooth_equalise_whole(mc_context* ctx, const mc_mandelbrot_params
                          "below 2^32");
         return MC_ERR_INVALID_ARGUMENT;
     }
-    SmoothEqualiseState* st = g_sq_states.get(ctx);
-    const size_t entries = (size_t)p->max_iter + 1;
-    int rc = st->hist.reserve(entries * 4);
-    if (rc) return rc;
-    st->hist_host.resize(entries);
-    st->qmap_host.resize(entries);
-    MC_HIP_TRY(hipMemsetAsync(st->hist.ptr, 0, entries * 4, s));
-    if ((rc = mandelbrot_smooth_histogram_launch(ctx, d_smooth, npix, p->max_iter, st->hist.ptr, s))) return rc;
-    MC_HIP_TRY(hipMemcpyAsync(st->hist_host.data(), st->hist.ptr, entries * 4, hipMemcpyDeviceToHost, s));
-    MC_HIP_TRY(hipStreamSynchronize(s));
-    if (!smooth_equalise::knot_map(p->max_iter, st->hist_host.data(), st->qmap_host.data())) return MC_ERR_INVALID_ARGUMENT;   // (npix < 2^32: cannot happen)
-    return mandelbrot_smooth_remap_launch(ctx, p, d_smooth, st->qmap_host.data(), d_ranked, d_rgba, who, s);
+    const uint32_t* qmap = nullptr;
+    if (int rc = mandelbrot_smooth_equalise_plane_map(ctx, p->max_iter, d_smooth, npix, s, &qmap)) return rc;
+    return mandelbrot_smooth_remap_launch(ctx, p, d_smooth, qmap, d_ranked, d_rgba, who, s);
 }
 
 int mandelbrot_smooth_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_smooth, void* d_rgba, hipStream_t s) {

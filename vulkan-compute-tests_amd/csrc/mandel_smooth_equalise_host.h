@@ -19,6 +19,10 @@ int mandelbrot_smooth_remap_launch(mc_context* ctx, const mc_mandelbrot_params* 
 // d_ranked and / or d_rgba.  Synchronises s once (the table round trip).
 int mandelbrot_smooth_equalise_whole(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth, void* d_ranked, void* d_rgba,
                                      const char* who, hipStream_t s);
+// The knot map of the n smooth counts at d_smooth on s: the histogram into the side record's table, its round trip (s is synchronised once)
+// and knot_map on the host.  *qmap: max_iter + 1 knots in the side record, valid until the context's next call of this kind.
+int mandelbrot_smooth_equalise_plane_map(mc_context* ctx, uint32_t max_iter, const void* d_smooth, uint64_t n, hipStream_t s,
+                                         const uint32_t** qmap);
 // mc_context_warmup_mandelbrot with the flag: both kernels made resident on a 64-pixel plane at d_smooth, the side record's buffers
 // allocated.
 int mandelbrot_smooth_equalise_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_smooth, void* d_rgba, hipStream_t s);
@@ -49,8 +53,8 @@ inline int smooth_equalised_refuse_combination(const mc_mandelbrot_params* p, co
     const char* other = (p->flags & MC_MANDEL_COLOUR_SMOOTH)          ? "MC_MANDEL_COLOUR_SMOOTH (the flag implies the smooth count and is set without it)"
                         : (p->flags & MC_MANDEL_COLOUR_EQUALISED)     ? "MC_MANDEL_COLOUR_EQUALISED (the flag is the rank map over fractional counts and is set without it)"
                         : (p->flags & MC_MANDEL_COLOUR_DISTANCE)      ? "MC_MANDEL_COLOUR_DISTANCE (two colourings of one smooth plane: choose one)"
-                        : (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) ? "MC_MANDEL_SUPERSAMPLE_ADAPTIVE (a resolve over fractional counts does not exist)"
-                        : ((p->flags >> 8) & 15u) > 1u                ? "MC_MANDEL_SUPERSAMPLE (a resolve over fractional counts does not exist)"
+                        : (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) ? "MC_MANDEL_SUPERSAMPLE_ADAPTIVE (adaptive refinement of fractional counts does not exist; the full resolve is MC_MANDEL_SUPERSAMPLE_SMOOTH)"
+                        : ((p->flags >> 8) & 15u) > 1u                ? "MC_MANDEL_SUPERSAMPLE (the resolve over fractional counts is asked for by name: add MC_MANDEL_SUPERSAMPLE_SMOOTH)"
                         : (p->flags & MC_MANDEL_FMA)                  ? "MC_MANDEL_FMA (the contraction switch has no smooth kernel)"
                                                                       : nullptr;
     if (other) {

@@ -18,8 +18,8 @@ int mandelbrot_smooth_launch(mc_context* ctx, const mc_mandelbrot_params* p, voi
 inline int smooth_refuse_combination(const mc_mandelbrot_params* p, const char* who) {
     if (!p || !(p->flags & MC_MANDEL_COLOUR_SMOOTH)) return MC_OK;
     const char* other = (p->flags & MC_MANDEL_COLOUR_EQUALISED)       ? "MC_MANDEL_COLOUR_EQUALISED (the rank map over fractional counts is MC_MANDEL_COLOUR_SMOOTH_EQUALISED, set on its own)"
-                        : (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) ? "MC_MANDEL_SUPERSAMPLE_ADAPTIVE (a resolve over fractional counts does not exist yet)"
-                        : ((p->flags >> 8) & 15u) > 1u                ? "MC_MANDEL_SUPERSAMPLE (a resolve over fractional counts does not exist yet)"
+                        : (p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) ? "MC_MANDEL_SUPERSAMPLE_ADAPTIVE (adaptive refinement of fractional counts does not exist; the full resolve is MC_MANDEL_SUPERSAMPLE_SMOOTH)"
+                        : ((p->flags >> 8) & 15u) > 1u                ? "MC_MANDEL_SUPERSAMPLE (the resolve over fractional counts is asked for by name: add MC_MANDEL_SUPERSAMPLE_SMOOTH)"
                         : (p->flags & MC_MANDEL_FMA)                  ? "MC_MANDEL_FMA (the contraction switch measures the plain fp32 kernel only)"
                                                                       : nullptr;
     if (other) {

@@ -16,6 +16,7 @@
 
 #include "mandel_distance_host.h"
 #include "mandel_equalise.h"
+#include "mandel_resolve_smooth_host.h"
 #include "mandel_smooth_equalise_host.h"
 #include "mandel_zoom_counts.h"
 #include "mandel_zoom_counts_host.h"
@@ -104,6 +105,7 @@ int zoom_counts_mode(const mc_mandelbrot_params* p, const char* who, int* mode) 
     if (p->flags & MC_MANDEL_COLOUR_DISTANCE)
         return refuse(who, "MC_MANDEL_COLOUR_DISTANCE shades by a stencil over a whole smooth plane: a count keyframe cannot carry it (the vec4 "
                            "sequence, mc_mandelbrot_zoom_push, does)");
+    if (int rc = smooth_samples_refuse_flag(p, who)) return rc;
     if ((p->flags & MC_MANDEL_SUPERSAMPLE_ADAPTIVE) || ((p->flags >> 8) & 15u) > 1u)
         return refuse(who, "MC_MANDEL_SUPERSAMPLE / MC_MANDEL_SUPERSAMPLE_ADAPTIVE: a supersampled pixel has no single count (the vec4 sequence, "
                            "mc_mandelbrot_zoom_push, takes such keyframes)");

@@ -8,6 +8,7 @@
 // the device from the two keyframes that bracket it and written as <out>_%05u.<ext>), --zoom-keyframes colours|counts
 // (counts: the keyframes are kept as count planes and every frame is coloured through one map blended from theirs),
 // --zoom-filter bilinear|area (area: the minified deep keyframe is filtered over each pixel's footprint),
+// --supersample-smooth (with --supersample 2|4|8 and --colour smooth|smooth-equalised: the samples are smooth counts),
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -45,6 +46,7 @@ int main(int argc, char* argv[]) {
     uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED) | smooth (MC_MANDEL_COLOUR_SMOOTH) | distance (MC_MANDEL_COLOUR_DISTANCE) | smooth-equalised (MC_MANDEL_COLOUR_SMOOTH_EQUALISED)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
     bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
+    bool supersampleSmooth = false;   // --supersample-smooth (MC_MANDEL_SUPERSAMPLE_SMOOTH): with --supersample 2 | 4 | 8 and --colour smooth | smooth-equalised
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
     uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
@@ -119,6 +121,13 @@ int main(int argc, char* argv[]) {
             adaptive = true;
 #if !defined(MANDELBROT_MODE)
             printf("--adaptive: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
+        else if (a == "--supersample-smooth") {   // the samples are smooth counts: the resolve over fractional counts
+            supersampleSmooth = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--supersample-smooth: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
 #endif
         }
@@ -244,6 +253,14 @@ int main(int argc, char* argv[]) {
         else pos.push_back(argv[i]);
     }
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
+    if (supersampleSmooth) {
+        const char* why = supersample <= 1u ? "needs --supersample 2 | 4 | 8"
+                          : colour != MC_MANDEL_COLOUR_SMOOTH && colour != MC_MANDEL_COLOUR_SMOOTH_EQUALISED ? "needs --colour smooth | smooth-equalised"
+                          : adaptive ? "not with --adaptive (adaptive refinement compares integer counts)"
+                          : gpus > 1 ? "one GPU (the resolve runs on the device that holds the samples)"
+                                     : nullptr;
+        if (why) { printf("--supersample-smooth: %s\n", why); exit(EXIT_FAILURE); }
+    }
     if (zoomSet && (zoomK < 1 || zoomF < 1)) {
         printf("usage: --zoom K F: K octaves (keyframes K + 1, the given view the deepest) of F frames each, both at least 1; got %d %d\n", zoomK, zoomF);
         exit(EXIT_FAILURE);
@@ -279,7 +296,7 @@ int main(int argc, char* argv[]) {
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
     (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
-    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
+    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
@@ -289,7 +306,10 @@ int main(int argc, char* argv[]) {
     app.setZoomCounts(zoomCounts);
     app.setZoomFilter(zoomFilter);
     if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
-        if (supersample > 1u) { printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
+        if (supersample > 1u && !supersampleSmooth) {
+            printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts) unless --supersample-smooth asks for it\n");
+            return EXIT_FAILURE;
+        }
         app.setColourFlags(colour);
     } else if (colour == MC_MANDEL_COLOUR_DISTANCE) {   // a stencil over the whole image's smooth plane: the whole-image calls, as equalised
         if (supersample > 1u) { printf("--colour distance: does not combine with --supersample (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
@@ -297,7 +317,10 @@ int main(int argc, char* argv[]) {
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour distance renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     } else if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED) {   // the rank over the whole image's smooth plane: the whole-image calls, as equalised
-        if (supersample > 1u) { printf("--colour smooth-equalised: does not combine with --supersample (a resolve over fractional counts)\n"); return EXIT_FAILURE; }
+        if (supersample > 1u && !supersampleSmooth) {
+            printf("--colour smooth-equalised: does not combine with --supersample (a resolve over fractional counts) unless --supersample-smooth asks for it\n");
+            return EXIT_FAILURE;
+        }
         app.setColourFlags(colour);
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour smooth-equalised renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
@@ -309,6 +332,7 @@ int main(int argc, char* argv[]) {
     if (supersample > 1u) {   // the sample plane is resolved by the whole-image calls: never the banded, streamed save
         app.setSupersample(supersample);
         if (adaptive) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_ADAPTIVE);   // (whole-image calls as well: the save is never streamed)
+        if (supersampleSmooth) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_SMOOTH);
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --supersample renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     }
@@ -467,7 +491,7 @@ int main(int argc, char* argv[]) {
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
-        if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1) app.printSmoothEqualisedStats();
+        if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1 && !supersampleSmooth) app.printSmoothEqualisedStats();
 #endif
 #if defined(PATHTRACER_MODE)
         if (budgetSet) app.printBudget();
