@@ -25,6 +25,28 @@ namespace dm {
 
 __device__ __forceinline__ float as_float(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t as_uint(float f) { return __float_as_uint(f); }
+// v, negated where the sign bit of s is CLEAR: bits(v) ^ (~bits(s) & 0x80000000) as ONE v_bitop3_b32 (truth table 0xc6: b ^ (~a & c)).
+// Written with the builtin so that the three inputs stay one instruction at every use: from the spelled-out form the compiler forms
+// the flip word ~bits(s) & 0x80000000 once, holds it in a register and pays a v_xor per use besides.
+__device__ __forceinline__ float flip_where_sign_clear(float v, float s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return as_float(__builtin_amdgcn_bitop3_b32(as_uint(s), as_uint(v), 0x80000000u, 0xc6));
+#else
+    return as_float(as_uint(v) ^ (~as_uint(s) & 0x80000000u));
+#endif
+}
+
+// max(v, 0) as the single v_max_f32 the compiler emits for fmaxf(v, 0.0f) of an arithmetic result — for a v it cannot see the origin of.
+// Why it is written out: in front of fmaxf of a value that comes out of a bit operation (flip_where_sign_clear) the compiler puts a
+// canonicalising v_max_f32 v, v, v — seen with AMD clang 22.0.0git (roc-7.2.0, HIP 7.2.26015); __builtin_amdgcn_fmed3f(v, 0, inf) was
+// folded back into the same pair.  The optimiser cannot see through the asm: when a compiler emits the single instruction for
+// fmaxf(flip_where_sign_clear(..), 0.0f) by itself (`make asm`, the light contribution of pathtrace_pool_kernel), this goes.
+// Device code only (its one caller is the sample-pool kernel).
+__device__ __forceinline__ float max_zero_as_is(float v) {
+    float r;
+    asm("v_max_f32_e32 %0, 0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
 
 // ---- IEEE primitives ------------------------------------------------------------------------------
 // hipcc's default for HIP is correctly-rounded fp32 divide and sqrt (-fhip-fp32-correctly-rounded-divide-sqrt);

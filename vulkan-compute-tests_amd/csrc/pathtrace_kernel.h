@@ -151,8 +151,9 @@ __device__ __forceinline__ v3 reflect(v3 I, v3 N) { return I - N * (2.0f * dot(N
 __device__ __forceinline__ v3 select(bool c, v3 a, v3 b) { return v3{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
 __device__ __forceinline__ float comp(v3 a, int axis) { return axis == 0 ? a.x : (axis == 1 ? a.y : a.z); }
 
-// rand01 — pathTracer.comp:107-110 (float(0xffffffffU) rounds to 2^32: the scale is exactly 2^-32)
-__device__ __forceinline__ v3 rand01(uint32_t x, uint32_t y, uint32_t z) {
+// rand01 — pathTracer.comp:107-110 (float(0xffffffffU) rounds to 2^32: the scale is exactly 2^-32).  The three rounds of the integer
+// hash, converted to float and not yet scaled: the one copy of the generator, which rand01 and rand01_zraw scale.
+__device__ __forceinline__ v3 rand_hash_unscaled(uint32_t x, uint32_t y, uint32_t z) {
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         uint32_t nx = ((x >> 8) ^ y) * 1103515245u;
@@ -160,8 +161,19 @@ __device__ __forceinline__ v3 rand01(uint32_t x, uint32_t y, uint32_t z) {
         uint32_t nz = ((z >> 8) ^ x) * 1103515245u;
         x = nx; y = ny; z = nz;
     }
-    const float s = 2.3283064365386963e-10f;   // 2^-32
-    return v3{(float)x * s, (float)y * s, (float)z * s};
+    return v3{(float)x, (float)y, (float)z};
+}
+constexpr float kRandScale = 2.3283064365386963e-10f;   // 2^-32
+__device__ __forceinline__ v3 rand01(uint32_t x, uint32_t y, uint32_t z) {
+    const v3 h = rand_hash_unscaled(x, y, z);
+    return v3{h.x * kRandScale, h.y * kRandScale, h.z * kRandScale};
+}
+// The same draw with z left as the converted integer, float(z) in [0, 2^32]: the sample-pool kernels compare the roulette's draw (:396)
+// with p * 2^32 from the staged record instead of scaling it.  float(z) * 2^-32 >= p and float(z) >= p * 2^32 are the same decision for
+// every p: both scalings are by a power of two and exact (float(z) is 0 or at least 1, so its scaled value is no denormal; p <= 1).
+__device__ __forceinline__ v3 rand01_zraw(uint32_t x, uint32_t y, uint32_t z) {
+    const v3 h = rand_hash_unscaled(x, y, z);
+    return v3{h.x * kRandScale, h.y * kRandScale, h.z};
 }
 
 // Diagnostic build only (make stats -> lib/libmc_compute_stats.so, tools/pool_region_stats.py): how often each code
@@ -286,10 +298,15 @@ template <int NS> struct HotSlabN {
     // InVgpr = false leaves the values to the compiler (SGPR operands): for kernels without the register headroom.
     // WPosInVgpr: only W_pos in vector registers — the select `d_a > 0 ? W_pos : W_negm` then is ONE v_cndmask (SGPR, VGPR, vcc)
     // instead of two v_mov and a v_cndmask (a VOP3 select reads its mask and one more scalar at most).
-    template <bool InVgpr = true, bool WPosInVgpr = false> __device__ __forceinline__ void load(const SceneArgs& sc) {
+    // WNegInVgpr: this many of the W_negm as well (the sample-pool kernels: as many as fit under the instantiation's register budget) —
+    // each spares the v_mov that brings it out of its scalar register in every intersection.
+    template <bool InVgpr = true, bool WPosInVgpr = false, int WNegInVgpr = 0> __device__ __forceinline__ void load(const SceneArgs& sc) {
         auto put = [](float u) { return InVgpr ? to_vgpr(u) : u; };
 #pragma unroll
-        for (int a = 0; a < 3; a++) { W_pos[a] = (InVgpr || WPosInVgpr) ? to_vgpr(sc.slab_w_pos[a]) : sc.slab_w_pos[a]; W_negm[a] = put(-sc.slab_w_neg[a]); }
+        for (int a = 0; a < 3; a++) {
+            W_pos[a] = (InVgpr || WPosInVgpr) ? to_vgpr(sc.slab_w_pos[a]) : sc.slab_w_pos[a];
+            W_negm[a] = (InVgpr || a < WNegInVgpr) ? to_vgpr(-sc.slab_w_neg[a]) : -sc.slab_w_neg[a];
+        }
 #pragma unroll
         for (int i = 0; i < NS; i++) {
 #pragma unroll

@@ -70,6 +70,23 @@
 // all tiers (tests/test_gpu_pool_lane_masks.py).  Where a form cost registers it is not taken (pool_lane_masks, pool_emis_cond): the strict
 // kernels keep `alive` per lane (the mask form spilled), fast with two spheres keeps the parent's forms (8 -> 7 waves).
 // -DMC_PT_POOL_FLOAT_STATE (make exp; implied by MC_PT_POOL_PARENT_FORMS) compiles the per-lane values: the parent's listing.
+//
+// Third diet (profiles/valu_diet3_listing.txt): what an iteration still computed although the wave had it, or held in a costlier place.
+//   1  `key > krr` of the prologue's row select is the roulette's own mask of the iteration before: deep_m & ~end_m stays in scalar
+//      registers over the loop edge (deep_row_m).
+//   2  nl = +-n is read once per light, in max(dot(l, nl), 0): dot(l, n) with the flip applied to the sum by one v_bitop3
+//      (dm::flip_where_sign_clear); the vector is formed only where a lane bounces off a diffuse sphere (nl_of).  The argument for the
+//      one case that differs — an exactly cancelling sum, -0 for +0 — stands where nl was formed.
+//   3  the three -w_neg of the slab intersection in vector registers (HotSlabN::load: a v_cndmask reads one scalar, and that is its mask).
+//      The registers are the ones the staged record wasted: its "emits" flag shared a word with the material code, whose byte-selecting
+//      compares need their constants in VGPRs.  The flag has slot 3 now (fast, careful), the code is the whole word (pool_flag_apart).
+//   4  the roulette compares the unscaled draw with p * 2^32 from the record (rand01_zraw).
+//   5  `id >= 0` of the stash entries taken is asked only while a wave can take an empty one: a pixel outside the image or the tile,
+//      the ragged last batch.  (`lane & 48` of the refill stays re-derived: held it costs a register.)
+// Fast <1, 16, 3, true>: 6.1 VALU instructions an iteration less by the listing, 71 VGPRs, 7 waves.  Taken per instantiation (pool_diet3):
+// fast and careful with eight spheres keep the parent's loop (scratch); the strict kernels take nothing (item 4 measured no gain there).
+// -DMC_PT_POOL_DIET3_PARENT (make exp; implied by the two older switches) compiles the forms before: the parent's listing
+// (tests/test_gpu_pool_diet3.py renders with both: equal bit for bit).
 #pragma once
 #include <type_traits>
 #include "pathtrace_kernel.h"
@@ -101,8 +118,17 @@ __device__ __forceinline__ v3 add_emission(v3 rad, v3 accmat, v3 e) {
     const float px = accmat.x * e.x, py = accmat.y * e.y, pz = accmat.z * e.z;
     return v3{rad.x + px, rad.y + py, rad.z + pz};
 }
+// nl = dot(n, rd) < 0 ? n : -n (:390) in the fast tiers' form: the sign bit of the dot product, inverted, flips n
+__device__ __forceinline__ v3 nl_of(v3 n, float dot_n_rd) {
+    return v3{dm::flip_where_sign_clear(n.x, dot_n_rd), dm::flip_where_sign_clear(n.y, dot_n_rd), dm::flip_where_sign_clear(n.z, dot_n_rd)};
+}
 constexpr uint32_t kPoolEntryFloats = 8;     // {rd.x, rd.y, rd.z, t | id (-1: nothing to trace), key0 = samp * maxDepth, rnd.x, rnd.y of key0}
-constexpr uint32_t kPoolRecordStride = 16;   // floats per staged record: {geo.xyz, p (fast: 1 / p) | colour.rgb, material + 256 * emits | emission.xyz, RN(1 / p) (fast: p) | fast: colour.rgb / p, the same integer bits}
+// floats per staged record, four rows of four (the packing at the top of the kernel is the definition):
+//   row 0   geo.xyz | strict: p.  fast, careful: 1 / p — or, where pool_flag_apart holds, the "emits" flag (256 or 0, integer bits)
+//   row 1   colour.rgb | the material code as integer bits, + 256 * emits unless pool_flag_apart (then the bare code)
+//   row 2   emission.xyz | strict: RN(1 / p).  fast, careful: p — or, where pool_rr_unscaled holds, p * 2^32
+//   row 3   fast, careful: colour.rgb / p | the same word as row 1's.  strict: unused
+constexpr uint32_t kPoolRecordStride = 16;
 template <int NS> constexpr uint32_t pool_record_floats() { return (6u + (uint32_t)NS) * kPoolRecordStride; }   // 6 planes + NS spheres
 constexpr uint32_t kPoolStashFloats = 128u * kPoolEntryFloats;     // per wave: 64/S pixels x 2 batches x S entries
 // Strict: the result ring holds this many batches per pixel (3 planes x, y, z).  Three for the reference's scene: with the 23 + 3 KB of a
@@ -126,6 +152,29 @@ template <int Fast, int NS> constexpr bool pool_parent_state() { return kPoolFlo
 template <int Fast, int NS> constexpr bool pool_lane_masks() { return !pool_parent_state<Fast, NS>() && Fast != 0 && !(Fast == 2 && NS == 7); }
 template <int Fast, int NS> constexpr bool pool_emis_cond() { return !pool_parent_state<Fast, NS>(); }
 
+// The third diet (see the header), item by item and per instantiation as above: what an instantiation takes costs it neither a wave of
+// occupancy nor a scratch instruction.  -DMC_PT_POOL_DIET3_PARENT (make exp; implied by the two older switches) compiles the forms before.
+#if defined(MC_PT_POOL_DIET3_PARENT) || defined(MC_PT_POOL_FLOAT_STATE) || defined(MC_PT_POOL_PARENT_FORMS)
+constexpr bool kPoolDiet3Parent = true;
+#else
+constexpr bool kPoolDiet3Parent = false;
+#endif
+// (fast and careful with eight spheres, at four and five waves: 16 B more scratch with items 1, 4 and 5 alone — they keep the parent's loop)
+template <int Fast, int NS> constexpr bool pool_diet3() { return !kPoolDiet3Parent && !pool_parent_state<Fast, NS>() && !(Fast != 0 && NS == 8); }
+// 1: the depth-over-5 mask carried over the loop edge (a lane mask: the kernels that hold alive_m)
+template <int Fast, int NS> constexpr bool pool_deep_carry() { return pool_diet3<Fast, NS>() && pool_lane_masks<Fast, NS>(); }
+// 2: dot(l, nl) as dot(l, n) with its sign flipped (the fast and careful tiers' flip; the strict kernel selects n or -n)
+template <int Fast, int NS> constexpr bool pool_nl_dot() { return pool_diet3<Fast, NS>() && Fast != 0; }
+// 3: how many of the three -w_neg the intersection holds in vector registers — all three wherever the flag below made the room
+template <int Fast, int NS> constexpr int pool_wneg_vgprs() { return pool_diet3<Fast, NS>() && Fast != 0 ? 3 : 0; }
+// 4: the roulette compares the unscaled draw with p * 2^32 from the record (strict: measured, 32.47 -> 32.52 ms at K2, inside the spread
+// of 0.10 — not taken, the strict kernels are the parent's: profiles/valu_diet3_k2_ab.txt)
+template <int Fast, int NS> constexpr bool pool_rr_unscaled() { return pool_diet3<Fast, NS>() && Fast != 0; }
+// 5: no `id >= 0` of the entries taken while every entry the wave can take holds a path (the closed-box tiers' lane-mask kernels)
+template <int Fast, int NS> constexpr bool pool_live_entries() { return pool_diet3<Fast, NS>() && pool_lane_masks<Fast, NS>(); }
+// what makes the room for 3: a record's "emits" flag in a word of its own, the material code a whole word (fast, careful: slot 3 is free)
+template <int Fast, int NS> constexpr bool pool_flag_apart() { return pool_diet3<Fast, NS>() && Fast != 0; }
+
 // Disjoint (fast math): the host proved the spheres pairwise disjoint — shadow rays are decided without square roots
 // (shadow_visible_disjoint); false: overlapping spheres, the root form (shadow_reaches_sphere).  The strict kernel has one form.
 template <int Fast, int S, int NS, bool Disjoint = true>
@@ -143,13 +192,20 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
         const float* o = a.scene.obj + 12u * threadIdx.x;
         float* r = lds_obj + kPoolRecordStride * threadIdx.x;
         const float p = dm::gmax(dm::gmax(o[8], o[9]), o[10]);
-        r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = Fast ? dm::fdiv<Fast>(1.0f, p) : p;
+        const float r3 = Fast ? dm::fdiv<Fast>(1.0f, p) : p;
+        r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = r3;
         r[4] = o[8]; r[5] = o[9]; r[6] = o[10];
         const uint32_t emits = (o[4] != 0.0f || o[5] != 0.0f || o[6] != 0.0f) ? 256u : 0u;
-        r[7] = dm::as_float((uint32_t)(int)__builtin_floorf(o[11] + 0.5f) | emits);
-        r[8] = o[4]; r[9] = o[5]; r[10] = o[6]; r[11] = Fast ? p : dm::rcp_short(p);
+        // (pool_flag_apart: the flag in slot 3, which 1 / p leaves free once the colour rows below are formed — the material code then is
+        // the whole word: no byte select, and no vector registers that hold the constants a byte-selecting compare needs)
+        constexpr bool kFlagApart = pool_flag_apart<Fast, NS>();
+        const uint32_t mcode = (uint32_t)(int)__builtin_floorf(o[11] + 0.5f);
+        r[7] = dm::as_float(kFlagApart ? mcode : (mcode | emits));
+        // (pool_rr_unscaled: p * 2^32, what the roulette compares the unscaled draw with — rand01_zraw; p has no other reader)
+        r[8] = o[4]; r[9] = o[5]; r[10] = o[6]; r[11] = Fast ? (pool_rr_unscaled<Fast, NS>() ? p * 4294967296.0f : p) : dm::rcp_short(p);
         // fast math: the colour already divided by p (:392 and :397 as ONE multiplication past depth 5), with the same integer bits
-        if constexpr (Fast) { r[12] = o[8] * r[3]; r[13] = o[9] * r[3]; r[14] = o[10] * r[3]; r[15] = r[7]; }
+        if constexpr (Fast) { r[12] = o[8] * r3; r[13] = o[9] * r3; r[14] = o[10] * r3; r[15] = r[7]; }
+        if constexpr (kFlagApart) r[3] = dm::as_float(emits);
     }
     __syncthreads();
     // fast math: the sphere tests of a bounce (three of the shadow ray, three of the next ray, all from the hit point x) read
@@ -162,9 +218,13 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     constexpr bool kLaneMasks = pool_lane_masks<Fast, NS>(), kEmisCond = pool_emis_cond<Fast, NS>(), kOneAlpha = kEmisCond;
     // fast tier: the bounce's transcendentals whose operands are known early are issued as prioritised groups (mc_math.h, "groups")
     constexpr bool kGrouped = Fast == 1 && dm::kTransGroups;
+    // what of the third diet it takes (pool_deep_carry ...)
+    constexpr bool kDeepCarry = pool_deep_carry<Fast, NS>(), kNlDot = pool_nl_dot<Fast, NS>(), kRrUnscaled = pool_rr_unscaled<Fast, NS>(),
+                   kLiveEntries = pool_live_entries<Fast, NS>(), kFlagApart = pool_flag_apart<Fast, NS>();
     constexpr uint32_t TW = WaveTile<S>::w, TH = WaveTile<S>::h, Ring = 2u * (uint32_t)S, RRing = pool_result_batches<NS>() * (uint32_t)S;
     HotSlabN<NS> hot;
-    hot.template load<false, true>(a.scene);   // (uniform operands but W_pos: this kernel has no vector registers to spare for copies)
+    // (uniform operands but W_pos — and as many of W_negm as pool_wneg_vgprs finds room for: this kernel has no vector registers to spare for copies)
+    hot.template load<false, true, pool_wneg_vgprs<Fast, NS>()>(a.scene);
     // A lane's pixel (pix = lane / S of the wave tile) and slot of a batch (sub = lane % S) never change.  What derives from them
     // and is needed only now and then — the stash base, the tile row, the validity — is derived afresh from an opaque copy of
     // the thread id where it is used, so that it does not occupy registers across the bounce loop (80 VGPRs = 6 waves per SIMD).
@@ -237,6 +297,20 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
     // the last specular bounce) is only ever tested, so it is a per-lane condition the compiler keeps as a mask by itself.
     unsigned long long alive_m = 0ull;
     bool emis = true;
+    // kDeepCarry: the lanes that go on past depth 5 — the roulette's own mask less the paths it ended, kept in scalar registers over the
+    // loop edge.  The next prologue picks the colour row by it instead of comparing key with krr again: for a lane that goes on it is that
+    // compare on the same two values, and a lane that takes a stash entry in between was not in alive_m, so its bit is clear — as its
+    // compare would be (key = key0 <= krr).
+    unsigned long long deep_row_m = 0ull;
+    // kLiveEntries: every stash entry this wave's lanes can take holds a path (closed box: every camera ray hits) — all four pixels lie in
+    // the image and the tile, and no batch produced so far is a ragged last one.  Wave-uniform; while it holds, `id >= 0` of the entries
+    // taken is not asked.
+    bool pixels_live = false;
+    uint32_t full_batches = 0u;   // (batches before a ragged last one: every batch when the sample range is a multiple of S)
+    if constexpr (kLiveEntries) {
+        pixels_live = __ballot(!pixel_valid) == 0ull;
+        full_batches = (a.sample_end - a.sample_begin) % (uint32_t)S == 0u ? n_batches : n_batches - 1u;
+    }
     // every iteration either traces a bounce of a live lane, or consumes stash entries, or produces a batch: bounded
     unsigned long long max_iters = (unsigned long long)n_batches * S * (a.max_depth + 2ull) + 64ull;
 #ifdef MC_PT_POOL_TEST_BOUND   // diagnostic build only (tests/test_gpu_pool.py): a bound the loop must trip
@@ -339,7 +413,10 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 if constexpr (!kLaneMasks) alive = id >= 0;
             }
             // (where all lanes pass: set under the lanes' branch the mask would be a vector value)
-            if constexpr (kLaneMasks) alive_m |= take_m & lanes_where(id >= 0);
+            if constexpr (kLiveEntries) {
+                if (pixels_live && batch <= full_batches) alive_m |= take_m;   // (uniform)
+                else alive_m |= take_m & lanes_where(id >= 0);
+            } else if constexpr (kLaneMasks) alive_m |= take_m & lanes_where(id >= 0);
             ghead += need < avail ? need : avail;
         }
         // pool exhausted and every path ended?  (no lane alive but entries left: only empty entries were taken — go round again)
@@ -370,7 +447,9 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 for (int i = 0; i < NS; i++) { xcc[i] = occ[i]; if constexpr (kOccR2) occ[i] = occ[i] - hot.r2[i]; }
                 const float4* obj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);   // per-lane fetch
                 // (fast: past depth 5 the colour row is the one already divided by the roulette probability)
-                const float4 o0 = obj[0], o1 = obj[(Fast && key > krr) ? 3 : 1];
+                // (kDeepCarry: the mask the previous iteration's roulette left — see deep_row_m)
+                const bool deep_row = kDeepCarry ? lane_in(deep_row_m) : (Fast && key > krr);
+                const float4 o0 = obj[0], o1 = obj[deep_row ? 3 : 1];
                 // (fast, careful: o0.w is not read and the compiler narrows row 0 to ds_read_b96.  Keeping the word in use for a
                 //  ds_read_b128 was measured: 13.220 against 13.223 ms at K2, a tenth of the run-to-run spread — not kept,
                 //  profiles/valu_diet2_k2_ab.txt)
@@ -378,14 +457,27 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                 v3 geo{o0.x, o0.y, o0.z};
                 v3 col{o1.x, o1.y, o1.z};
                 const uint32_t mbits = dm::as_uint(o1.w);
-                const int mat = (int)(mbits & 255u);                              // :378/:384
+                const int mat = kFlagApart ? (int)mbits : (int)(mbits & 255u);    // :378/:384
+                const bool hit_emits = kFlagApart ? dm::as_uint(o0.w) != 0u : mbits >= 256u;
 #ifdef MC_PT_REGION_STATS
                 if (is_sphere) MC_REGION(5);    // sphere normal
 #endif
                 v3 n = is_sphere ? normalize<Fast>(x - geo) : geo;                // :381/:387
                 const float dot_n_rd = dot(n, rd);
                 v3 nl;                                                            // :390 nl = dot(n, rd) < 0 ? n : -n
-                if constexpr (Fast) {   // (the sign bit of the dot product, inverted, flips n — trace_sample)
+                // kNlDot: the vector nl is formed only where a lane bounces off a diffuse sphere (the general basis); the light's cosine is
+                // dot(l, n) with the flip applied to the sum.  Negating every component of n negates every product and every partial sum
+                // of the dot product exactly (rounding to nearest is symmetric, contracted or not), so the flipped sum IS dot(l, -n) —
+                // but for a sum that cancels exactly: +0 in either order, hence -0 once flipped where dot(l, -n) gives +0.  max(., 0) and
+                // the multiplication by the solid angle's finite factor make that a scale of +-0, and (accmat * le) * (+-0) is a zero
+                // added to a sum that is never -0 (the argument beside add_emission's first use): every bit of rad is kept.
+                // (dm::flip_where_sign_clear: one v_bitop3 of dot_n_rd, the value and the sign mask at each use — no flip word is held)
+                if constexpr (kNlDot) {
+                    // (nl is not read: the light's cosine flips its sum, the general bounce forms nl_of(n, dot_n_rd) — in the fast tiers.
+                    //  The strict kernel hands nl to specular_bounce_general and must never get here with an unflipped normal.)
+                    static_assert(!kNlDot || Fast != 0, "the flipped dot product is the fast and careful tiers' form: strict reads nl");
+                    nl = n;
+                } else if constexpr (Fast) {   // (the sign bit of the dot product, inverted, flips n — trace_sample)
                     const uint32_t flip = ~dm::as_uint(dot_n_rd) & 0x80000000u;
                     nl = v3{dm::as_float(dm::as_uint(n.x) ^ flip), dm::as_float(dm::as_uint(n.y) ^ flip), dm::as_float(dm::as_uint(n.z) ^ flip)};
                 } else {
@@ -398,7 +490,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                     const float4 o2 = obj[2];
                     rad = rad + (accmat * v3{o2.x, o2.y, o2.z}) * emissive;
                 }
-                } else if (mbits >= 256u && emis) {                                      // :391
+                } else if (hit_emits && emis) {                                      // :391
                     // Only the emitters' lanes whose condition holds add, and they add accmat * e without a factor.  Every bit is kept:
                     // the factor `emissive` was 1.0f or 0.0f and nothing else.  1: (accmat * e) * 1 = accmat * e, and contracted,
                     // fma(accmat * e, 1, rad), is the product's rounded value plus rad, rounded once — add_emission's sum.  0:
@@ -434,7 +526,11 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                         if (lit) {
                             MC_REGION(8);    // light contribution
                             if constexpr (Fast) {
-                                const float scale = __builtin_fmaxf(dot(l, nl), 0.0f) * (2.0f - (cos_a_max + cos_a_max));   // :421-:422
+                                const float l_nl = kNlDot ? dm::flip_where_sign_clear(dot(l, n), dot_n_rd) : dot(l, nl);
+                                // (kNlDot: the same v_max_f32 v, 0, v, written out — fmaxf of a value that comes out of a bit operation gets
+                                //  a v_max_f32 v, v, v in front of it, which quiets a signalling NaN that no flipped sum can be)
+                                const float cosine = kNlDot ? dm::max_zero_as_is(l_nl) : __builtin_fmaxf(l_nl, 0.0f);
+                                const float scale = cosine * (2.0f - (cos_a_max + cos_a_max));   // :421-:422
                                 rad = rad + (accmat * le) * scale;
                             } else {
                                 const float omega = (2.0f * kPi) * (1.0f - cos_a_max);                     // :421
@@ -450,9 +546,9 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                     if constexpr (kGrouped) {   // (the four transcendentals both forms share: one group in front of them)
                         const BounceTrans bt = bounce_trans_grouped(rnd);
                         if (walls_only()) { MC_REGION(9); rd = cosine_bounce_wall_grouped(id, bt); }
-                        else { MC_REGION(10); rd = cosine_bounce_grouped<true>(nl, bt); }
+                        else { MC_REGION(10); rd = cosine_bounce_grouped<true>(kNlDot ? nl_of(n, dot_n_rd) : nl, bt); }
                     } else if (walls_only()) { MC_REGION(9); rd = cosine_bounce_wall<Fast>(id, rnd); }
-                    else { MC_REGION(10); rd = cosine_bounce<Fast, true>(nl, rnd); }
+                    else { MC_REGION(10); rd = cosine_bounce<Fast, true>(kNlDot ? nl_of(n, dot_n_rd) : nl, rnd); }
                     if constexpr (kEmisCond) emis = false; else emissive = 0.0f;  // :429
                 } else {                                                          // :432 mirror, :437 glass (box_ok: 2 or 3)
                     MC_REGION(11);   // mirror / glass
@@ -469,7 +565,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                     go = id >= 0;                                                 // :369
                 }
                 if (go) {                                                         // the next bounce's random numbers and roulette
-                    const v3 rn = rand01(gx, gy, key);                            // :393 (key = samp * maxDepth + depth)
+                    // (kRrUnscaled: z as the converted integer, compared with p * 2^32 — rand01_zraw)
+                    const v3 rn = kRrUnscaled ? rand01_zraw(gx, gy, key) : rand01(gx, gy, key);   // :393 (key = samp * maxDepth + depth)
                     rx = rn.x; ry = rn.y;
                     if (key > krr) {                                              // :395 depth > 5
                         MC_REGION(15);   // roulette
@@ -483,7 +580,7 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
                             }
                         } else if constexpr (kEmisCond) {
                             // (as below, and without the factor: see the emission of a hit)
-                            if (!go && dm::as_uint(nobj[1].w) >= 256u && emis) {
+                            if (!go && (kFlagApart ? dm::as_uint(nobj[0].w) != 0u : dm::as_uint(nobj[1].w) >= 256u) && emis) {
                                 const float4 o2 = nobj[2];
                                 rad = add_emission(rad, accmat, v3{o2.x, o2.y, o2.z});
                             }
@@ -523,7 +620,8 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
             }
             // (:369: a closed box — every ray hits)
             // the next bounce's random numbers and roulette
-            const v3 rn = rand01(gx, gy, key);                                    // :393 (key = samp * maxDepth + depth)
+            // (kRrUnscaled: z as the converted integer, compared with p * 2^32 — rand01_zraw)
+            const v3 rn = kRrUnscaled ? rand01_zraw(gx, gy, key) : rand01(gx, gy, key);   // :393 (key = samp * maxDepth + depth)
             rx = rn.x; ry = rn.y;
             const unsigned long long deep_m = alive_m & lanes_where(key > krr);   // :395 depth > 5
             const float4* nobj = reinterpret_cast<const float4*>(lds_obj + kPoolRecordStride * (uint32_t)id);   // (formed once, read under the masks)
@@ -531,14 +629,15 @@ __global__ void __launch_bounds__(256, (pool_waves<Fast, NS>())) pathtrace_pool_
             asm volatile("" : "=v"(pn));                                          // (any value elsewhere, and no instruction: deep_m masks the compare)
             if (lane_in(deep_m)) {
                 MC_REGION(15);   // roulette
-                pn = nobj[2].w;
+                pn = nobj[2].w;   // (kRrUnscaled: p * 2^32)
             }
             const unsigned long long end_m = deep_m & lanes_where(rn.z >= pn);    // :396
             alive_m &= ~end_m;
+            if constexpr (kDeepCarry) deep_row_m = deep_m & ~end_m;
             if (lane_in(end_m)) {
                 // a path the roulette ends has still gathered the emission of this hit (:391 precedes :396) — the emitters' lanes alone,
                 // and without the factor, as at the emission of a hit above
-                if (dm::as_uint(nobj[1].w) >= 256u && emis) {
+                if ((kFlagApart ? dm::as_uint(nobj[0].w) != 0u : dm::as_uint(nobj[1].w) >= 256u) && emis) {
                     const float4 o2 = nobj[2];
                     rad = add_emission(rad, accmat, v3{o2.x, o2.y, o2.z});
                 }
