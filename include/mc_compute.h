@@ -48,7 +48,9 @@ extern "C" {
  * filter of the minified deep keyframe: MC_MANDEL_ZOOM_FILTER_BILINEAR / _AREA with mc_mandelbrot_zoom_compose_filtered,
  * mc_mandelbrot_zoom_compose_filtered_device_async, mc_mandelbrot_zoom_compose_counts_filtered,
  * mc_mandelbrot_zoom_compose_counts_filtered_device_async, mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered;
- * then MC_MANDEL_SUPERSAMPLE_SMOOTH with mc_mandelbrot_resolve_smooth_device_async and mc_mandelbrot_resolve_smooth.
+ * then MC_MANDEL_SUPERSAMPLE_SMOOTH with mc_mandelbrot_resolve_smooth_device_async and mc_mandelbrot_resolve_smooth; then the Buddhabrot:
+ * mc_buddhabrot_params and mc_buddhabrot_stats with mc_buddhabrot_default_params, _density, _density_device_async, _render, _sqrt_map,
+ * _tonemap and _tonemap_device_async.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -921,6 +923,91 @@ int mc_mandelbrot_zoom_compose_counts_filtered_device_async(mc_context* ctx, con
 int mc_mandelbrot_zoom_frame_filtered(mc_mandelbrot_zoom* z, double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8);
 int mc_mandelbrot_zoom_counts_frame_filtered(mc_mandelbrot_zoom_counts* z, uint32_t step, uint32_t steps_per_octave, uint32_t filter,
                                              float* out_rgba_f32, uint8_t* out_rgba8);
+
+/* ---- Buddhabrot: the orbit-density plane of the same iteration (the project's own addition: the reference has no counterpart and no
+ *      picture to match; additions within ABI 3; what tests/buddhabrot_ref.py restates).  Every point of every
+ *      ESCAPING orbit of pseudo-randomly sampled c adds one to the bin of the plane it lands in: a scatter through atomic integer adds,
+ *      where every other render of this library is a gather.  Integer adds commute, so the plane and the statistics do not depend on
+ *      which lane takes which sample nor on the order the adds arrive in: every call below is exact to the bit, host and device alike.
+ *      Everything is IEEE double in the order written, no contraction, denormals kept, unless stated otherwise.
+ *
+ *  SAMPLE k (k in [sample_begin, sample_end), a 64-bit index):
+ *   - x = (uint32_t)k, y = (uint32_t)(k >> 32), z = seed;
+ *   - three rounds of the integer hash of the path tracer's generator (pathTracer.comp:107-110), all three words at once per round:
+ *       x' = ((x >> 8) ^ y) * 1103515245,  y' = ((y >> 8) ^ z) * 1103515245,  z' = ((z >> 8) ^ x) * 1103515245   (mod 2^32);
+ *   - the INTEGERS are kept: ux = x, uy = y after the rounds (the generator's conversion to float is not used);
+ *   - tx = ((double)ux + 0.5) * 2^-32,  cx = sample_centre_x + ((tx - 0.5) * sample_scale_x);  cy likewise from uy with
+ *     sample_centre_y and sample_scale_y.
+ *  INTERIOR SKIP (part of the contract, not a shortcut): with xm = cx - 0.25, y2 = cy * cy, q = (xm * xm) + y2, xp = cx + 1.0 the
+ *     sample is skipped and contributes nothing when (q * (q + xm)) <= (0.25 * y2) [the main cardioid] or ((xp * xp) + y2) <= 0.0625
+ *     [the period-2 disc].
+ *  CLASSIFY: zx = zy = sx = sy = 0; for i in [0, M), M = max_iter:
+ *       nzx = (sx - sy) + cx;  nzy = ((2 * zx) * zy) + cy;  zx = nzx;  zy = nzy;  sx = zx * zx;  sy = zy * zy;
+ *       if (sx + sy > 4.0) { n = i; escaped; stop }
+ *     The step is MC_PRECISION_F64's, operation for operation.  The radius is 4.0 (|z|^2 > 4), NOT the 2.0 the Mandelbrot renders
+ *     inherit from the reference: points with |z|^2 in (2, 4] belong to bounded orbits too, and this picture is the project's own with no
+ *     reference image to match.  A sample that never escapes within M steps contributes nothing.
+ *  PLOT, only for an escaped sample with n >= min_iter: the same steps again from z = 0, and for each of z_1 .. z_n (the n points that
+ *     did not escape; the escaping point z_(n+1) is not plotted):
+ *       fx = ((zx - view_centre_x) * kx) + ox,  kx = (double)width / view_scale_x (ONE IEEE division, on the host),  ox = 0.5 * (double)width;
+ *       fy = ((zy - view_centre_y) * ky) + oy,  ky = (double)height / view_scale_y,  oy = 0.5 * (double)height;
+ *       inside iff fx >= 0 && fx < (double)width && fy >= 0 && fy < (double)height (a NaN is outside);
+ *       if inside: plane[(uint32_t)fy * width + (uint32_t)fx] += 1.
+ *     The plane is uint32_t[height][width], storage rows as everywhere.  Counts WRAP modulo 2^32; they do not saturate.
+ *  The calls ADD to the plane (and to the device statistics) they are given: sample ranges, seeds and devices compose by plain addition,
+ *  as the histogram call's tiles do, and a progressive render is a loop of calls.
+ *  STATISTICS (all order-independent, so exact): samples = the k in range; skipped = removed by the interior test; contributing =
+ *  samples that escaped with min_iter <= n; points = the sum of n over the contributing samples; added = the points inside the view.
+ *  VALIDATION: MC_ERR_INVALID_ARGUMENT, mc_last_error_detail naming the field, for NULL pointers; width or height = 0 or
+ *  width * height > 2^32 - 1; max_iter = 0 or > 2^24; a scale that is not finite or is zero; a centre that is not finite (negative scales
+ *  are allowed: they mirror); sample_end < sample_begin or more than 2^40 samples in one call; unknown flag bits.  min_iter >= max_iter
+ *  is valid and adds nothing.
+ *  FLAGS: measurement bits only, as bits 0 - 15 of the path tracer's flags are: MC_BUDDHA_KERNEL_PLAIN runs the device call's plain form
+ *  (one sample per lane, a grid-stride loop, classify then replay), MC_BUDDHA_KERNEL_POOLED its pooled form (each wave owns a run of
+ *  sample indices; a lane that has finished its sample takes the wave's next one; classification and plotting share one loop body).
+ *  Neither bit: the shipped choice (DESIGN.md section 3.26 says which and on what measurement); both: MC_ERR_INVALID_ARGUMENT.  The
+ *  plane and the statistics are the same bits either way; the host call ignores the two bits.
+ *  STATED LIMITS: uint32 counts that wrap; one GPU (ranges compose, so a multi-GPU render is an addition of planes by the caller;
+ *  mc_multi_* has no form of it); uniform sampling only, no importance sampling. */
+enum { MC_BUDDHA_KERNEL_PLAIN = 1u << 0, MC_BUDDHA_KERNEL_POOLED = 1u << 1 };
+typedef struct mc_buddhabrot_params {
+    double view_centre_x, view_centre_y, view_scale_x, view_scale_y;         /* the window the density plane covers */
+    double sample_centre_x, sample_centre_y, sample_scale_x, sample_scale_y; /* the window c is drawn from */
+    uint64_t sample_begin, sample_end;   /* sample indices k in [begin, end) */
+    uint32_t width, height;              /* the plane: uint32_t[height][width] */
+    uint32_t max_iter, min_iter;         /* M; an orbit contributes iff it escapes after n iterations, min_iter <= n < M */
+    uint32_t seed, flags;
+} mc_buddhabrot_params;                  /* 104 bytes */
+typedef struct mc_buddhabrot_stats {
+    uint64_t samples, skipped, contributing, points, added;
+} mc_buddhabrot_stats;                   /* 40 bytes: the device form is uint64_t[5] in this order */
+/* View centre (-0.5, 0), view scale (3, 3 * height / width), sample window centre (-0.5, 0) and scale (4, 4), max_iter 1000, min_iter 0,
+ * seed 1, flags 0, the range [0, samples). */
+int mc_buddhabrot_default_params(uint32_t width, uint32_t height, uint64_t samples, mc_buddhabrot_params* out);
+/* Host only, usable without a GPU: the same __host__ __device__ body the kernels are built from, in a translation unit without HIP.  ADDS
+ * to plane, and to *stats_or_NULL. */
+int mc_buddhabrot_density(const mc_buddhabrot_params* p, uint32_t* plane, mc_buddhabrot_stats* stats_or_NULL);
+/* ADDS to d_plane (uint32_t[height][width], 4-byte aligned) and to d_stats (uint64_t[5], 8-byte aligned; may be NULL) on the device. */
+int mc_buddhabrot_density_device_async(mc_context* ctx, const mc_buddhabrot_params* p, void* d_plane, void* d_stats, void* stream);
+/* Blocking: zeroes a device plane of the context, launches, copies the plane (and the statistics) out: out_plane RECEIVES the density
+ * of p's range, it is not added to.  mc_context_last_timing spans it. */
+int mc_buddhabrot_render(mc_context* ctx, const mc_buddhabrot_params* p, uint32_t* out_plane, mc_buddhabrot_stats* out_stats_or_NULL);
+/* Tone mapping, deliberately small: a density d becomes map[min(d, L)] / L through a table of L + 1 entries, L = levels in 1 .. 2^20.
+ *  - mc_buddhabrot_sqrt_map (host only): map[j] = (uint32_t)((double)L * sqrt((double)j / (double)L)), clamped to L.
+ *  - mc_buddhabrot_tonemap (host) and mc_buddhabrot_tonemap_device_async: per pixel and channel c the output is
+ *    (float)m_c[min(d_c, L)] / (float)L — exact conversions and one IEEE fp32 division — and alpha is 1.  The three planes may be the
+ *    same pointer (grey: one plane three times) or three renders of different max_iter (the "Nebulabrot"); a map entry above L is
+ *    MC_ERR_INVALID_ARGUMENT.  The device form takes three DEVICE planes and three HOST maps; the quotients are formed on the host and
+ *    kept as a device table of the context, the way mc_mandelbrot_recolour_device_async keeps its table.
+ *  - the rank map needs no new call: a density plane is a count plane, so mc_mandelbrot_histogram_device_async(ctx, d_plane, 4,
+ *    width * height, L, d_hist) (densities above L count in bin L) followed by mc_mandelbrot_equalise_map(L, hist, map) yields a valid
+ *    map (map[L] = L; lower densities by their rank among the bins below L). */
+int mc_buddhabrot_sqrt_map(uint32_t levels, uint32_t* map /* levels + 1 */);
+int mc_buddhabrot_tonemap(uint32_t width, uint32_t height, const uint32_t* d0, const uint32_t* d1, const uint32_t* d2, uint32_t levels,
+                          const uint32_t* m0, const uint32_t* m1, const uint32_t* m2, float* out_rgba_f32);
+int mc_buddhabrot_tonemap_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d0, const void* d1, const void* d2,
+                                       uint32_t levels, const uint32_t* m0 /* HOST, levels + 1 */, const uint32_t* m1, const uint32_t* m2,
+                                       void* d_rgba_f32, void* stream);
 
 /* ---- Path tracer: replaces shaders/pathTracer.comp:343-458 and the spp-dispatch loop of
  *      PathtracerApp::createCommandBuffer (src/pathtracerApp.h:358-378), fused into one launch ------ */

@@ -34,6 +34,10 @@ MANDEL_SUPERSAMPLE_SMOOTH = 8192   # MC_MANDEL_SUPERSAMPLE_SMOOTH: with MANDEL_S
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
 
+BUDDHA_KERNEL_PLAIN = 1    # MC_BUDDHA_KERNEL_PLAIN: measurement bit, the device call's plain form (one sample per lane, classify then replay)
+BUDDHA_KERNEL_POOLED = 2   # MC_BUDDHA_KERNEL_POOLED: measurement bit, the pooled form (a wave owns a run of samples, one loop body for both phases)
+
+
 def MANDEL_SUPERSAMPLE(s):
     """MC_MANDEL_SUPERSAMPLE(s): s x s samples per pixel, resolved on the device (bits 8-11 of flags; 2, 4 or 8; 0 and 1: off)."""
     return (int(s) & 15) << 8
@@ -98,6 +102,23 @@ class PathtraceDenoiseParams(C.Structure):
 class PathtraceBudgetParams(C.Structure):
     """mc_pathtrace_budget_params (include/mc_compute.h): the deepest level, the noise a pixel may keep, the noise window's radius."""
     _fields_ = [("max_level", C.c_uint32), ("target", C.c_float), ("radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BuddhabrotParams(C.Structure):
+    """mc_buddhabrot_params (include/mc_compute.h): the view, the sample window, the sample range, the plane's size, M, min_iter, seed."""
+    _fields_ = [("view_centre_x", C.c_double), ("view_centre_y", C.c_double), ("view_scale_x", C.c_double), ("view_scale_y", C.c_double),
+                ("sample_centre_x", C.c_double), ("sample_centre_y", C.c_double), ("sample_scale_x", C.c_double),
+                ("sample_scale_y", C.c_double), ("sample_begin", C.c_uint64), ("sample_end", C.c_uint64), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("max_iter", C.c_uint32), ("min_iter", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BuddhabrotStats(C.Structure):
+    """mc_buddhabrot_stats (include/mc_compute.h); the device form is uint64[5] in this order."""
+    _fields_ = [("samples", C.c_uint64), ("skipped", C.c_uint64), ("contributing", C.c_uint64), ("points", C.c_uint64),
+                ("added", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.samples, self.skipped, self.contributing, self.points, self.added)
 
 
 def declared_symbols():
@@ -281,6 +302,15 @@ def lib():
             L.mc_pathtrace_render_accel_denoised_adaptive.argtypes = [vp, vp, pp, dp, f32, u32, vp, vp]
             L.mc_pathtrace_render_accel_list_device_async.argtypes = [vp, vp, pp, vp, u32, f32, vp, vp]
             L.mc_pathtrace_render_accel_budgeted.argtypes = [vp, vp, pp, bp, vp, vp, vp]
+        if hasattr(L, "mc_buddhabrot_density"):   # the Buddhabrot
+            bp, u64 = C.POINTER(BuddhabrotParams), C.c_uint64
+            L.mc_buddhabrot_default_params.argtypes = [u32, u32, u64, bp]
+            L.mc_buddhabrot_density.argtypes = [bp, vp, C.POINTER(BuddhabrotStats)]
+            L.mc_buddhabrot_density_device_async.argtypes = [vp, bp, vp, vp, vp]
+            L.mc_buddhabrot_render.argtypes = [vp, bp, vp, C.POINTER(BuddhabrotStats)]
+            L.mc_buddhabrot_sqrt_map.argtypes = [u32, vp]
+            L.mc_buddhabrot_tonemap.argtypes = [u32, u32, vp, vp, vp, u32, vp, vp, vp, vp]
+            L.mc_buddhabrot_tonemap_device_async.argtypes = [vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -413,6 +443,63 @@ def equalise_map(max_iter, hist):
         raise ValueError(f"equalise_map: the histogram has {h.size} bins, max_iter + 1 = {max_iter + 1} expected")
     out = np.empty(max(h.size, 1), np.uint32)
     _check(lib().mc_mandelbrot_equalise_map(max_iter, _ptr(h), _ptr(out)), "mc_mandelbrot_equalise_map")
+    return out
+
+
+def buddhabrot_params(width, height, samples, max_iter=1000, min_iter=0, seed=1, view=None, sample_window=None, sample_begin=0, flags=0):
+    """mc_buddhabrot_default_params, then the overrides: view and sample_window are (centre_x, centre_y, scale_x, scale_y); the range is
+    [sample_begin, sample_begin + samples)."""
+    p = BuddhabrotParams()
+    _check(lib().mc_buddhabrot_default_params(width, height, samples, C.byref(p)), "mc_buddhabrot_default_params")
+    p.max_iter, p.min_iter, p.seed, p.flags = max_iter, min_iter, seed, flags
+    p.sample_begin, p.sample_end = sample_begin, sample_begin + samples
+    if view is not None:
+        p.view_centre_x, p.view_centre_y, p.view_scale_x, p.view_scale_y = view
+    if sample_window is not None:
+        p.sample_centre_x, p.sample_centre_y, p.sample_scale_x, p.sample_scale_y = sample_window
+    return p
+
+
+def buddhabrot_density(p, plane=None, stats=None):
+    """mc_buddhabrot_density (host only): ADDS p's samples to plane (uint32 (height, width); a zeroed one when None) and to stats (a
+    BuddhabrotStats; a zeroed one when None).  Returns (plane, stats)."""
+    if plane is None:
+        plane = np.zeros((p.height, p.width), np.uint32)
+    if plane.dtype != np.uint32 or not plane.flags["C_CONTIGUOUS"] or plane.size != p.width * p.height:
+        raise ValueError("buddhabrot_density: plane must be a C-contiguous uint32 array of height x width")
+    if stats is None:
+        stats = BuddhabrotStats()
+    _check(lib().mc_buddhabrot_density(C.byref(p), _ptr(plane), C.byref(stats)), "mc_buddhabrot_density")
+    return plane, stats
+
+
+def buddhabrot_sqrt_map(levels):
+    """mc_buddhabrot_sqrt_map (host only): uint32[levels + 1], map[j] = floor(levels * sqrt(j / levels)) clamped to levels."""
+    out = np.empty(max(int(levels), 0) + 1, np.uint32)
+    _check(lib().mc_buddhabrot_sqrt_map(levels, _ptr(out)), "mc_buddhabrot_sqrt_map")
+    return out
+
+
+def _tone_maps(levels, maps, what):
+    out = []
+    for m in maps:
+        a = np.ascontiguousarray(m, np.uint32).reshape(-1)
+        if a.size != levels + 1:
+            raise ValueError(f"{what}: a map has {a.size} entries, levels + 1 = {levels + 1} expected")
+        out.append(a)
+    return out
+
+
+def buddhabrot_tonemap(d0, d1, d2, levels, m0, m1, m2):
+    """mc_buddhabrot_tonemap (host): float32 (height, width, 4) from three uint32 planes (which may be one array) and three maps."""
+    planes = [np.ascontiguousarray(d, np.uint32) for d in (d0, d1, d2)]
+    H, W = planes[0].shape
+    if any(d.shape != (H, W) for d in planes):
+        raise ValueError("buddhabrot_tonemap: the three planes differ in shape")
+    maps = _tone_maps(levels, (m0, m1, m2), "buddhabrot_tonemap")
+    out = np.empty((H, W, 4), np.float32)
+    _check(lib().mc_buddhabrot_tonemap(W, H, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), levels, _ptr(maps[0]), _ptr(maps[1]),
+                                       _ptr(maps[2]), _ptr(out)), "mc_buddhabrot_tonemap")
     return out
 
 
@@ -1142,7 +1229,26 @@ class Context:
         _check(lib().mc_convert_rgba8(self._h, _ptr(a), W, H, scale, int(rotate180), _ptr(out)), "mc_convert_rgba8")
         return out
 
+    def buddhabrot(self, p):
+        """mc_buddhabrot_render: (plane uint32 (height, width), BuddhabrotStats) of p's sample range."""
+        plane = np.empty((p.height, p.width), np.uint32)
+        stats = BuddhabrotStats()
+        _check(lib().mc_buddhabrot_render(self._h, C.byref(p), _ptr(plane), C.byref(stats)), "mc_buddhabrot_render")
+        return plane, stats
+
     # ---- device-buffer forms (pointers are ints, e.g. torch.Tensor.data_ptr()) ------------------------
+    def buddhabrot_device(self, p, d_plane, d_stats=0, stream=0):
+        """mc_buddhabrot_density_device_async: ADDS p's samples to the device plane uint32[height][width] and to d_stats (uint64[5]; 0: none)."""
+        _check(lib().mc_buddhabrot_density_device_async(self._h, C.byref(p), d_plane or None, d_stats or None, stream or None),
+               "mc_buddhabrot_density_device_async")
+
+    def buddhabrot_tonemap_device(self, width, height, d0, d1, d2, levels, m0, m1, m2, d_rgba, stream=0):
+        """mc_buddhabrot_tonemap_device_async: three device planes (which may be one pointer), three host maps of levels + 1 entries."""
+        maps = _tone_maps(levels, (m0, m1, m2), "Context.buddhabrot_tonemap_device")
+        _check(lib().mc_buddhabrot_tonemap_device_async(self._h, width, height, d0 or None, d1 or None, d2 or None, levels, _ptr(maps[0]),
+                                                        _ptr(maps[1]), _ptr(maps[2]), d_rgba or None, stream or None),
+               "mc_buddhabrot_tonemap_device_async")
+
     def mandelbrot_device(self, p, d_rgba=0, d_iters=0, stream=0):
         _check(lib().mc_mandelbrot_render_device_async(self._h, C.byref(p), d_rgba or None, d_iters or None, stream or None),
                "mc_mandelbrot_render_device_async")

@@ -9,6 +9,12 @@
 // (counts: the keyframes are kept as count planes and every frame is coloured through one map blended from theirs),
 // --zoom-filter bilinear|area (area: the minified deep keyframe is filtered over each pixel's footprint),
 // --supersample-smooth (with --supersample 2|4|8 and --colour smooth|smooth-equalised: the samples are smooth counts),
+// --buddhabrot SAMPLES (the Mandelbrot app: the orbit-density plane of SAMPLES pseudo-random c instead of the set, DESIGN.md §3.26;
+// --centre / --scale / --width / --height / --max-iter / --out / --gpu-postprocess mean what they mean without it, the defaults being the
+// library's view (-0.5, 0, 3, 3 H / W) and max_iter 1000), with --min-iter m, --seed s, --sample-window CX CY SX SY (where c is drawn
+// from; default -0.5 0 4 4), --nebula MR MG MB (three renders of those max_iter, one per colour channel), --tone sqrt|equalised
+// (default sqrt) and --white PCT (default 99.9: the white level L is the density not exceeded by PCT % of the non-empty bins, read from
+// one histogram capped at 2^20 - 1 — the app's policy, not the library's); --help prints this list,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -69,10 +75,25 @@ int main(int argc, char* argv[]) {
     const char* cyText = "0";
     const char* sxText = "2.34";     // --precision perturb: the scale as text too (strtold reaches about 1e-4951; atof stops at 1e-308)
     const char* syText = "2.34";
-    bool viewSet = false, largeSpheres = false;
+    bool viewSet = false, centreSet = false, scaleSet = false, largeSpheres = false;
     uint32_t spherePrec = MC_PT_PREC_F32;
     const char* sceneFile = nullptr;    // --scene FILE: the path tracer's tables from a text file, one `plane` or `sphere` and 12 floats per line
     uint32_t accel = 0;                 // --accel linear | bvh: the plain calls (every ray tests every object) or mc_pathtrace_render_accel*
+    // --buddhabrot SAMPLES with --min-iter, --seed, --sample-window, --nebula, --tone, --white (mc_buddhabrot_*)
+    unsigned long long buddhaSamples = 0, buddhaMinIter = 0, buddhaSeed = 1;
+    bool buddhaSet = false, buddhaOptions = false, buddhaWindowSet = false, buddhaNebula = false, buddhaEqualised = false, maxIterSet = false;
+    double buddhaWindow[4] = {-0.5, 0.0, 4.0, 4.0}, buddhaWhite = 99.9;
+    unsigned long long buddhaNebulaIter[3] = {0, 0, 0};
+    // a whole non-negative number up to `most`, or the run ends
+    auto count = [](const std::string& opt, const char* v, unsigned long long most) -> unsigned long long {
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(v, &end, 10);
+        if (!*v || std::strspn(v, "0123456789") != std::strlen(v) || n > most) {
+            printf("%s %s: a whole number from 0 to %llu\n", opt.c_str(), v, most);
+            exit(EXIT_FAILURE);
+        }
+        return n;
+    };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](int n) { if (i + n >= argc) { printf("missing value for %s\n", a.c_str()); exit(EXIT_FAILURE); } };
@@ -94,9 +115,40 @@ int main(int argc, char* argv[]) {
                    "codec's exact file bytes come from a reference tree that calls this library, INTEGRATION.md route B)\n");
         else if (a == "--width") { need(1); width = (uint32_t)atoi(argv[++i]); }
         else if (a == "--height") { need(1); height = (uint32_t)atoi(argv[++i]); }
-        else if (a == "--max-iter") { need(1); maxIter = (uint32_t)atoi(argv[++i]); }
-        else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = true; }
-        else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = true; }
+        else if (a == "--max-iter") { need(1); maxIter = (uint32_t)atoi(argv[++i]); maxIterSet = true; }
+        else if (a == "--help") {
+            printf("options: --gpus N, --out FILE, --quiet, --gpu-postprocess, --png-threads T, --timing-json, --width W, --height H, --max-iter M,\n"
+                   "  --centre X Y, --scale SX SY, --precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep,\n"
+                   "  --colour reference|equalised|smooth|distance|smooth-equalised, --supersample 1|2|4|8, --adaptive, --supersample-smooth,\n"
+                   "  --orbit host|device|auto, --zoom K F, --zoom-keyframes colours|counts, --zoom-filter bilinear|area,\n"
+                   "  --math strict|fast|careful, --denoise [P], --noise-guided [K], --budget [L], --noise-target T, --scene FILE, --accel linear|bvh,\n"
+                   "  --buddhabrot SAMPLES  the orbit-density plane of SAMPLES pseudo-random c (the Mandelbrot app); --centre / --scale default to\n"
+                   "      the view -0.5 0 / 3 3H/W and --max-iter to 1000; with it:\n"
+                   "    --min-iter m            only orbits that escape after at least m iterations are plotted (default 0)\n"
+                   "    --seed s                the sample sequence (default 1)\n"
+                   "    --sample-window CX CY SX SY   the window c is drawn from (default -0.5 0 4 4)\n"
+                   "    --nebula MR MG MB       three renders of those max_iter, one per colour channel\n"
+                   "    --tone sqrt|equalised   the map from density to brightness (default sqrt)\n"
+                   "    --white PCT             the white level: the density not exceeded by PCT %% of the non-empty bins, read from one\n"
+                   "                            histogram capped at 2^20 - 1 (default 99.9)\n");
+            return EXIT_SUCCESS;
+        }
+        else if (a == "--buddhabrot") { need(1); buddhaSamples = count(a, argv[++i], 1ull << 40); buddhaSet = true; }
+        else if (a == "--min-iter") { need(1); buddhaMinIter = count(a, argv[++i], 0xffffffffull); buddhaOptions = true; }
+        else if (a == "--seed") { need(1); buddhaSeed = count(a, argv[++i], 0xffffffffull); buddhaOptions = true; }
+        else if (a == "--sample-window") { need(4); for (double& w : buddhaWindow) w = atof(argv[++i]); buddhaWindowSet = buddhaOptions = true; }
+        else if (a == "--nebula") { need(3); for (unsigned long long& n : buddhaNebulaIter) n = count(a, argv[++i], 1ull << 24); buddhaNebula = buddhaOptions = true; }
+        else if (a == "--tone") { need(1); buddhaEqualised = choice(argv[++i], {{"sqrt", 0u}, {"equalised", 1u}}) != 0u; buddhaOptions = true; }
+        else if (a == "--white") {
+            need(1);
+            const char* v = argv[++i];
+            char* end = nullptr;
+            buddhaWhite = std::strtod(v, &end);
+            if (end == v || *end || !(buddhaWhite > 0.0) || !(buddhaWhite <= 100.0)) { printf("--white %s: a percentage above 0, at most 100\n", v); exit(EXIT_FAILURE); }
+            buddhaOptions = true;
+        }
+        else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = centreSet = true; }
+        else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = scaleSet = true; }
         else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}, {"perturb-bla", MC_PRECISION_PERTURB_BLA}, {"perturb-bla-deep", MC_PRECISION_PERTURB_BLA_DEEP}}); }
         else if (a == "--colour") {   // reference: t = n / M (mandelbrot.comp:50-56) | equalised: the count's rank among the image's escaped pixels
                                       // | smooth: the fractional escape count, interpolated between neighbouring palette entries
@@ -252,6 +304,23 @@ int main(int argc, char* argv[]) {
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { printf("unknown option %s\n", a.c_str()); exit(EXIT_FAILURE); }
         else pos.push_back(argv[i]);
     }
+    if (buddhaOptions && !buddhaSet) { printf("--min-iter / --seed / --sample-window / --nebula / --tone / --white: only with --buddhabrot SAMPLES\n"); exit(EXIT_FAILURE); }
+    if (buddhaSet) {
+        const char* why = !buddhaSamples                    ? "SAMPLES is at least 1"
+                          : maxIterSet && !maxIter          ? "--max-iter is at least 1"
+                          : gpus > 1                        ? "one GPU (sample ranges compose: add the planes of several processes)"
+                          : colour                          ? "not with --colour (the density has its own tone maps: --tone)"
+                          : supersample > 1u || adaptive    ? "not with --supersample / --adaptive"
+                          : zoomSet                         ? "not with --zoom"
+                          : precision != MC_PRECISION_F32   ? "not with --precision (the orbits are iterated in fp64)"
+                          : orbitSet                        ? "not with --orbit"
+                                                            : nullptr;
+        if (why) { printf("--buddhabrot: %s\n", why); exit(EXIT_FAILURE); }
+    }
+#if !defined(MANDELBROT_MODE)
+    if (buddhaSet) { printf("--buddhabrot: a Mandelbrot option\n"); exit(EXIT_FAILURE); }
+#endif
+    (void)maxIterSet; (void)centreSet; (void)scaleSet; (void)buddhaMinIter; (void)buddhaSeed; (void)buddhaWindowSet; (void)buddhaNebula; (void)buddhaEqualised; (void)buddhaWindow; (void)buddhaWhite; (void)buddhaNebulaIter;
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
     if (supersampleSmooth) {
         const char* why = supersample <= 1u ? "needs --supersample 2 | 4 | 8"
@@ -305,6 +374,25 @@ int main(int argc, char* argv[]) {
     app.setPrecision(precision);
     app.setZoomCounts(zoomCounts);
     app.setZoomFilter(zoomFilter);
+    if (buddhaSet) {   // one blocking render per channel, then the tone map: never the banded, streamed save
+        MandelbrotApp::Buddhabrot b;
+        b.samples = buddhaSamples;
+        b.maxIter = maxIterSet ? maxIter : 0u;
+        b.minIter = (uint32_t)buddhaMinIter;
+        b.seed = (uint32_t)buddhaSeed;
+        b.viewSet = viewSet;   // --centre or --scale alone: the other half is the library's default view, not the set's
+        b.view[0] = centreSet ? cx : -0.5; b.view[1] = centreSet ? cy : 0.0;
+        b.view[2] = scaleSet ? sx : 3.0; b.view[3] = scaleSet ? sy : (3.0 * (double)height) / (double)width;
+        b.windowSet = buddhaWindowSet;
+        for (int k = 0; k < 4; k++) b.window[k] = buddhaWindow[k];
+        b.nebula = buddhaNebula;
+        for (int k = 0; k < 3; k++) b.nebulaIter[k] = (uint32_t)buddhaNebulaIter[k];
+        b.equalised = buddhaEqualised;
+        b.whitePct = buddhaWhite;
+        app.setBuddhabrot(b);
+        if (streamedSave == ComputeApp::kStreamOn) printf("note: --buddhabrot renders whole planes; --streamed-save has no effect\n");
+        streamedSave = ComputeApp::kStreamOff;
+    }
     if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
         if (supersample > 1u && !supersampleSmooth) {
             printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts) unless --supersample-smooth asks for it\n");

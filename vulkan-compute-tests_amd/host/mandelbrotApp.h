@@ -2,6 +2,7 @@
 #ifndef MANDELBROTAPP_H_
 #define MANDELBROTAPP_H_
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 
@@ -55,6 +56,19 @@ struct MandelbrotApp : public ComputeApp {
     // --zoom-filter area: runZoom() composes every frame through the _frame_filtered calls with
     // MC_MANDEL_ZOOM_FILTER_AREA; bilinear (the default): the unfiltered calls, as before the option existed.
     void setZoomFilter(uint32_t filter) { zoomFilter = filter; }
+    // --buddhabrot SAMPLES: run() renders the orbit-density plane(s) through mc_buddhabrot_render instead of the
+    // Mandelbrot set, tone-maps them into the storage buffer and the save goes on as ever.  view: --centre / --scale when given (else the
+    // library's default view); maxIter: --max-iter when given (else the library's 1000); nebula: three renders of max_iter MR MG MB, one
+    // per colour channel, instead of one grey plane; equalised: the rank map of each plane's histogram instead of the square-root map.
+    struct Buddhabrot {
+        uint64_t samples = 0;   // 0: off
+        uint32_t maxIter = 0, minIter = 0, seed = 1;
+        bool viewSet = false, windowSet = false, nebula = false, equalised = false;
+        double view[4] = {0, 0, 0, 0}, window[4] = {0, 0, 0, 0};
+        uint32_t nebulaIter[3] = {0, 0, 0};
+        double whitePct = 99.9;
+    };
+    void setBuddhabrot(const Buddhabrot& b) { buddha = b; }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
     MandelbrotApp(const MandelbrotApp&) = delete;
     MandelbrotApp& operator=(const MandelbrotApp&) = delete;
@@ -82,11 +96,12 @@ struct MandelbrotApp : public ComputeApp {
     }
 
     virtual std::function<int()> warmupCall() const override {   // tables + code object of that request (bit 1: the banded render's second stream)
-        if (zoomK) return [] { return (int)MC_OK; };
+        if (zoomK || buddha.samples) return [] { return (int)MC_OK; };
         return [ctx = ctx, q = request(), how = (gpuPostprocess ? 1 : 0) | (streaming() ? 2 : 0)] { return mc_context_warmup_mandelbrot(ctx, &q, how); };
     }
 
     virtual void runCommandBuffer() override {
+        if (buddha.samples) { runBuddhabrot(); return; }
         if (streaming()) { runStreamed(); return; }
         if (gpuPostprocess) {   // render + float->u8 on the device: 4 B/pixel cross PCIe instead of 16
             if (multi) check(mc_multi_mandelbrot_render_rgba8(multi, &params, rgba8.bytes()), "mc_multi_mandelbrot_render_rgba8");
@@ -230,6 +245,70 @@ struct MandelbrotApp : public ComputeApp {
     }
 
 private:
+    // --buddhabrot: one render per channel, the stats line of each, the white level, the maps, the tone map, [the conversion on the device].
+    // The white level L is APP POLICY, not part of the ABI: the density not exceeded by whitePct % of the non-empty bins — the smallest
+    // v >= 1 with (double)#{bins: 1 <= d <= v} >= (whitePct / 100) * (double)#{bins: d >= 1} — read from ONE histogram of min(d, 2^20 - 1)
+    // over all the planes; 1 when every bin is empty.  --tone equalised ranks each plane's densities among its NON-EMPTY bins (the empty
+    // bin's count is dropped from the histogram before mc_mandelbrot_equalise_map, so the background does not spend the palette).
+    void runBuddhabrot() {
+        const uint32_t channels = buddha.nebula ? 3u : 1u;
+        const size_t npix = (size_t)resx * resy;
+        mc_buddhabrot_params bp;
+        check(mc_buddhabrot_default_params(resx, resy, buddha.samples, &bp), "mc_buddhabrot_default_params");
+        if (buddha.viewSet) { bp.view_centre_x = buddha.view[0]; bp.view_centre_y = buddha.view[1]; bp.view_scale_x = buddha.view[2]; bp.view_scale_y = buddha.view[3]; }
+        if (buddha.windowSet) { bp.sample_centre_x = buddha.window[0]; bp.sample_centre_y = buddha.window[1]; bp.sample_scale_x = buddha.window[2]; bp.sample_scale_y = buddha.window[3]; }
+        bp.min_iter = buddha.minIter;
+        bp.seed = buddha.seed;
+        std::vector<uint32_t> planes[3];
+        for (uint32_t c = 0; c < channels; c++) {
+            bp.max_iter = buddha.nebula ? buddha.nebulaIter[c] : (buddha.maxIter ? buddha.maxIter : bp.max_iter);
+            planes[c].resize(npix);
+            mc_buddhabrot_stats st;
+            check(mc_buddhabrot_render(ctx, &bp, planes[c].data(), &st), "mc_buddhabrot_render");
+            double kernel = 0.0;
+            (void)mc_context_last_timing(ctx, &kernel, nullptr);
+            printf("buddhabrot: max_iter %u, min_iter %u, seed %u: samples %llu, skipped %llu, contributing %llu, points %llu, added %llu (kernel %.3f ms)\n",
+                   bp.max_iter, bp.min_iter, bp.seed, (unsigned long long)st.samples, (unsigned long long)st.skipped,
+                   (unsigned long long)st.contributing, (unsigned long long)st.points, (unsigned long long)st.added, kernel);
+        }
+        constexpr uint32_t kCap = (1u << 20) - 1u;
+        std::vector<uint64_t> hist((size_t)kCap + 1, 0);
+        for (uint32_t c = 0; c < channels; c++)
+            for (uint32_t d : planes[c]) hist[std::min(d, kCap)]++;
+        uint64_t nonEmpty = 0;
+        for (uint32_t v = 1; v <= kCap; v++) nonEmpty += hist[v];
+        uint32_t L = 1;
+        if (nonEmpty) {
+            const double need = (buddha.whitePct / 100.0) * (double)nonEmpty;
+            uint64_t run = 0;
+            for (uint32_t v = 1; v <= kCap; v++) {
+                run += hist[v];
+                if ((double)run >= need) { L = v; break; }
+            }
+        }
+        printf("buddhabrot: white level %u (%g %% of %llu non-empty bins), tone %s\n", L, buddha.whitePct, (unsigned long long)nonEmpty,
+               buddha.equalised ? "equalised" : "sqrt");
+        std::vector<uint32_t> maps[3];
+        for (uint32_t c = 0; c < channels; c++) {
+            maps[c].resize((size_t)L + 1);
+            if (!buddha.equalised) {
+                check(mc_buddhabrot_sqrt_map(L, maps[c].data()), "mc_buddhabrot_sqrt_map");
+                continue;
+            }
+            std::vector<uint32_t> h((size_t)L + 1, 0);
+            for (uint32_t d : planes[c]) h[std::min(d, L)]++;
+            h[0] = 0;
+            check(mc_mandelbrot_equalise_map(L, h.data(), maps[c].data()), "mc_mandelbrot_equalise_map");
+        }
+        const uint32_t* d[3] = {planes[0].data(), planes[channels > 1 ? 1 : 0].data(), planes[channels > 1 ? 2 : 0].data()};
+        const uint32_t* m[3] = {maps[0].data(), maps[channels > 1 ? 1 : 0].data(), maps[channels > 1 ? 2 : 0].data()};
+        std::vector<float> staged;   // --gpu-postprocess: the storage buffer was not allocated, only the RGBA8 image
+        float* rgba = buffer.data();
+        if (gpuPostprocess) { staged.resize(npix * 4); rgba = staged.data(); }
+        check(mc_buddhabrot_tonemap(resx, resy, d[0], d[1], d[2], L, m[0], m[1], m[2], rgba), "mc_buddhabrot_tonemap");
+        if (gpuPostprocess) check(mc_convert_rgba8(ctx, rgba, resx, resy, 255.0f, 0, rgba8.bytes()), "mc_convert_rgba8");
+    }
+    Buddhabrot buddha;
     // The image in row bands of kBandRows through mc_mandelbrot_render_banded: band k + 1 is launched on a second stream before band k has
     // finished, and every band is handed to the PNG workers as it arrives.  At K4 (5120 rows: 8 bands) the 50 ms of filter + deflate run
     // beside the 60 ms of rendering instead of after them.  (A blocking render per band was measured first: every band's last tiles then
