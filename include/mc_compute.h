@@ -50,7 +50,9 @@ extern "C" {
  * mc_mandelbrot_zoom_compose_counts_filtered_device_async, mc_mandelbrot_zoom_frame_filtered and mc_mandelbrot_zoom_counts_frame_filtered;
  * then MC_MANDEL_SUPERSAMPLE_SMOOTH with mc_mandelbrot_resolve_smooth_device_async and mc_mandelbrot_resolve_smooth; then the Buddhabrot:
  * mc_buddhabrot_params and mc_buddhabrot_stats with mc_buddhabrot_default_params, _density, _density_device_async, _render, _sqrt_map,
- * _tonemap and _tonemap_device_async.
+ * _tonemap and _tonemap_device_async; then its importance map and guided sampling: mc_buddhabrot_guide_params and _guide_info with
+ * mc_buddhabrot_importance, _importance_device_async, _importance_cells, _density_guided, _density_guided_device_async,
+ * _guide_default_params and _render_guided.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -968,7 +970,8 @@ int mc_mandelbrot_zoom_counts_frame_filtered(mc_mandelbrot_zoom_counts* z, uint3
  *  Neither bit: the shipped choice (DESIGN.md section 3.26 says which and on what measurement); both: MC_ERR_INVALID_ARGUMENT.  The
  *  plane and the statistics are the same bits either way; the host call ignores the two bits.
  *  STATED LIMITS: uint32 counts that wrap; one GPU (ranges compose, so a multi-GPU render is an addition of planes by the caller;
- *  mc_multi_* has no form of it); uniform sampling only, no importance sampling. */
+ *  mc_multi_* has no form of it).  The calls of this block sample the window uniformly; a zoomed view, which few c reach, is what the
+ *  importance map and the guided calls further down (mc_buddhabrot_importance*, _density_guided*, _render_guided) are for. */
 enum { MC_BUDDHA_KERNEL_PLAIN = 1u << 0, MC_BUDDHA_KERNEL_POOLED = 1u << 1 };
 typedef struct mc_buddhabrot_params {
     double view_centre_x, view_centre_y, view_scale_x, view_scale_y;         /* the window the density plane covers */
@@ -992,6 +995,77 @@ int mc_buddhabrot_density_device_async(mc_context* ctx, const mc_buddhabrot_para
 /* Blocking: zeroes a device plane of the context, launches, copies the plane (and the statistics) out: out_plane RECEIVES the density
  * of p's range, it is not added to.  mc_context_last_timing spans it. */
 int mc_buddhabrot_render(mc_context* ctx, const mc_buddhabrot_params* p, uint32_t* out_plane, mc_buddhabrot_stats* out_stats_or_NULL);
+/* Importance map and guided sampling, for views that few c reach (additions within ABI 3; what
+ * tests/buddhabrot_guided_ref.py restates).  Everything stays integer adds and a deterministic function of k, so every call below is
+ * exact to the bit, independent of the schedule, and composes by addition, as the calls above do.
+ *  CELLS: grid_log2 = g in 1 .. 12, G = 2^g.  The sample window is cut into G x G cells by the top g bits of the hash words:
+ *       cell = (uy >> (32 - g)) * G + (ux >> (32 - g)),
+ *     ux, uy the integers SAMPLE k keeps.  Row-major; the cell rows follow cy (uy), the columns cx (ux).
+ *  IMPORTANCE MAP (mc_buddhabrot_importance, host; mc_buddhabrot_importance_device_async): the samples, the statistics and the plane of
+ *     mc_buddhabrot_density / _density_device_async for the same p, bit for bit, and in addition a map uint32_t[G * G]: every
+ *     contributing sample k whose added_k (its points inside the view) is above 0 does map[cell(k)] += added_k — on the device one
+ *     relaxed agent-scope atomic per such sample, at the end of its plot phase.  The map WRAPS modulo 2^32.  The calls ADD to the map, so
+ *     ranges and seeds compose by addition; sum(map) == the added the same calls report (mod 2^32), and the map of g is the map of g + 1
+ *     summed 2 x 2.  plane / d_plane may be NULL: then no plane add is issued at all and the statistics, added included, are still
+ *     exact (a pilot's normal use).  Both kernel forms honour it through the MC_BUDDHA_KERNEL_* bits.
+ *  CELL LIST (mc_buddhabrot_importance_cells, host only, deterministic): the cells with map[cell] >= threshold (threshold >= 1), grown by
+ *     `dilate` (0 .. 8) rings of the 8-neighbourhood clipped at the grid's edge, in ASCENDING index order.  flags bit 0,
+ *     MC_BUDDHA_CELLS_COMPLEMENT: the cells NOT in that set instead (list and complement partition the grid).  *n_cells receives the
+ *     count; cells_out may be NULL to query it, else it has room for that many (G * G always suffices).  An empty result is valid.
+ *  GUIDED DENSITY (mc_buddhabrot_density_guided, host; mc_buddhabrot_density_guided_device_async): for sample k in [sample_begin,
+ *     sample_end):
+ *       j = k mod n_cells (k the 64-bit index),  cell = cells[j];
+ *       ux, uy = SAMPLE k's hash words, exactly as above;
+ *       ux' = ((cell mod G) << (32 - g)) | (ux >> g),   uy' = ((cell / G) << (32 - g)) | (uy >> g)
+ *     — the hash's HIGH bits, shifted down, fill the cell — and everything after that is the contract above applied to ux', uy': tx, cx,
+ *     INTERIOR SKIP, CLASSIFY, PLOT.  Each plotted point adds `weight` (>= 1) instead of 1, modulo 2^32; the statistics count samples and
+ *     points as ever (added counts POINTS, not weight).  A range that is a multiple of n_cells gives every listed cell the same number of
+ *     samples; a list may repeat a cell.  A cell index >= G * G is MC_ERR_INVALID_ARGUMENT: the host call checks its list; the async
+ *     device form takes a DEVICE list (4-byte aligned, caller-owned, alive until the launch has run) and cannot, so there it is the
+ *     caller's precondition — its kernels clamp the index to G * G - 1, so that a broken list gives wrong samples, never a wild access.
+ *     WEIGHT makes an unbiased picture a sum of two calls: the list at N samples per cell and weight 1, plus its complement at N / B
+ *     samples per cell and weight B, have in their sum the expectation of the uniform density of N * G * G samples (every cell's orbits
+ *     at the same expected weight per unit of sample area; the complement's at B times the variance).  The list ALONE is biased by
+ *     whatever the pilot missed: orbits from cells outside the list are absent from it (DESIGN.md section 3.27 has measured shares).
+ *  THE CHAIN (mc_buddhabrot_render_guided, blocking): (1) zero a map of the context; (2) the pilot: the uniform samples
+ *     [0, pilot_samples) of p->seed with p's view, window, M, min_iter and flags, no plane; (3) copy the map out; (4) the list by
+ *     mc_buddhabrot_importance_cells(g, map, threshold, dilate, 0), uploaded; (5) the guided render of p's range over it at weight 1 into
+ *     a zeroed plane; (6) if complement_weight B > 0 and the complement is not empty: a second guided call over the complement list,
+ *     range [sample_end, sample_end + ceil(samples * n_complement / (n_cells * B))), samples = sample_end - sample_begin, at weight B,
+ *     into the same plane.  out_plane receives the plane, out_stats the statistics of step 5 alone; out_info the two counts, the pilot's
+ *     statistics and the complement pass's (zeros when it did not run).  An EMPTY list is MC_OK with a zero plane, zero statistics and
+ *     n_cells = 0.  mc_context_last_timing spans the chain.
+ *  VALIDATION beyond p's: grid_log2 outside 1 .. 12; NULL map, cells, n_cells, guide; threshold = 0; dilate > 8; unknown flags;
+ *     n_cells = 0; weight = 0; pilot_samples > 2^40; a complement range above 2^40 samples or past 2^64. */
+enum { MC_BUDDHA_CELLS_COMPLEMENT = 1u << 0 };
+typedef struct mc_buddhabrot_guide_params {
+    uint32_t grid_log2, dilate;          /* g; rings of dilation */
+    uint64_t pilot_samples;              /* the pilot's range is [0, pilot_samples) */
+    uint32_t threshold;                  /* a cell is listed when its map word is at least this */
+    uint32_t complement_weight;          /* B; 0: no complement pass */
+} mc_buddhabrot_guide_params;            /* 24 bytes */
+typedef struct mc_buddhabrot_guide_info {
+    uint32_t n_cells, n_complement;
+    mc_buddhabrot_stats pilot, complement;
+} mc_buddhabrot_guide_info;              /* 88 bytes */
+/* ADDS to map (uint32_t[G * G]), to plane_or_NULL and to *stats_or_NULL.  Host only, usable without a GPU. */
+int mc_buddhabrot_importance(const mc_buddhabrot_params* p, uint32_t grid_log2, uint32_t* map, uint32_t* plane_or_NULL,
+                             mc_buddhabrot_stats* stats_or_NULL);
+/* ADDS to d_map (4-byte aligned), to d_plane (may be NULL) and to d_stats (uint64_t[5], 8-byte aligned; may be NULL) on the device. */
+int mc_buddhabrot_importance_device_async(mc_context* ctx, const mc_buddhabrot_params* p, uint32_t grid_log2, void* d_map, void* d_plane,
+                                          void* d_stats, void* stream);
+int mc_buddhabrot_importance_cells(uint32_t grid_log2, const uint32_t* map, uint32_t threshold, uint32_t dilate, uint32_t flags,
+                                   uint32_t* cells_out_or_NULL, uint32_t* n_cells);
+/* ADDS to plane and to *stats_or_NULL.  Host only, usable without a GPU. */
+int mc_buddhabrot_density_guided(const mc_buddhabrot_params* p, const uint32_t* cells, uint32_t n_cells, uint32_t grid_log2,
+                                 uint32_t weight, uint32_t* plane, mc_buddhabrot_stats* stats_or_NULL);
+/* d_cells: a DEVICE list of n_cells words.  ADDS to d_plane and to d_stats (may be NULL) on the device. */
+int mc_buddhabrot_density_guided_device_async(mc_context* ctx, const mc_buddhabrot_params* p, const void* d_cells, uint32_t n_cells,
+                                              uint32_t grid_log2, uint32_t weight, void* d_plane, void* d_stats, void* stream);
+/* g = 8, pilot_samples = 2^24, threshold 1, dilate 1, complement_weight 0. */
+int mc_buddhabrot_guide_default_params(mc_buddhabrot_guide_params* out);
+int mc_buddhabrot_render_guided(mc_context* ctx, const mc_buddhabrot_params* p, const mc_buddhabrot_guide_params* guide,
+                                uint32_t* out_plane, mc_buddhabrot_stats* out_stats_or_NULL, mc_buddhabrot_guide_info* out_info_or_NULL);
 /* Tone mapping, deliberately small: a density d becomes map[min(d, L)] / L through a table of L + 1 entries, L = levels in 1 .. 2^20.
  *  - mc_buddhabrot_sqrt_map (host only): map[j] = (uint32_t)((double)L * sqrt((double)j / (double)L)), clamped to L.
  *  - mc_buddhabrot_tonemap (host) and mc_buddhabrot_tonemap_device_async: per pixel and channel c the output is

@@ -35,6 +35,7 @@ MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalise
 
 
 BUDDHA_KERNEL_PLAIN = 1    # MC_BUDDHA_KERNEL_PLAIN: measurement bit, the device call's plain form (one sample per lane, classify then replay)
+BUDDHA_CELLS_COMPLEMENT = 1   # MC_BUDDHA_CELLS_COMPLEMENT: mc_buddhabrot_importance_cells lists the cells NOT in the set
 BUDDHA_KERNEL_POOLED = 2   # MC_BUDDHA_KERNEL_POOLED: measurement bit, the pooled form (a wave owns a run of samples, one loop body for both phases)
 
 
@@ -119,6 +120,17 @@ class BuddhabrotStats(C.Structure):
 
     def as_tuple(self):
         return (self.samples, self.skipped, self.contributing, self.points, self.added)
+
+
+class BuddhabrotGuideParams(C.Structure):
+    """mc_buddhabrot_guide_params (include/mc_compute.h): the grid, the pilot, the list's threshold and dilation, the complement's weight."""
+    _fields_ = [("grid_log2", C.c_uint32), ("dilate", C.c_uint32), ("pilot_samples", C.c_uint64), ("threshold", C.c_uint32),
+                ("complement_weight", C.c_uint32)]
+
+
+class BuddhabrotGuideInfo(C.Structure):
+    """mc_buddhabrot_guide_info (include/mc_compute.h): what mc_buddhabrot_render_guided reports beside the render's statistics."""
+    _fields_ = [("n_cells", C.c_uint32), ("n_complement", C.c_uint32), ("pilot", BuddhabrotStats), ("complement", BuddhabrotStats)]
 
 
 def declared_symbols():
@@ -311,6 +323,15 @@ def lib():
             L.mc_buddhabrot_sqrt_map.argtypes = [u32, vp]
             L.mc_buddhabrot_tonemap.argtypes = [u32, u32, vp, vp, vp, u32, vp, vp, vp, vp]
             L.mc_buddhabrot_tonemap_device_async.argtypes = [vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        if hasattr(L, "mc_buddhabrot_importance"):   # its importance map and guided sampling
+            bp, sp, gp = C.POINTER(BuddhabrotParams), C.POINTER(BuddhabrotStats), C.POINTER(BuddhabrotGuideParams)
+            L.mc_buddhabrot_importance.argtypes = [bp, u32, vp, vp, sp]
+            L.mc_buddhabrot_importance_device_async.argtypes = [vp, bp, u32, vp, vp, vp, vp]
+            L.mc_buddhabrot_importance_cells.argtypes = [u32, vp, u32, u32, u32, vp, C.POINTER(u32)]
+            L.mc_buddhabrot_density_guided.argtypes = [bp, vp, u32, u32, u32, vp, sp]
+            L.mc_buddhabrot_density_guided_device_async.argtypes = [vp, bp, vp, u32, u32, u32, vp, vp, vp]
+            L.mc_buddhabrot_guide_default_params.argtypes = [gp]
+            L.mc_buddhabrot_render_guided.argtypes = [vp, bp, gp, vp, sp, C.POINTER(BuddhabrotGuideInfo)]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -471,6 +492,66 @@ def buddhabrot_density(p, plane=None, stats=None):
         stats = BuddhabrotStats()
     _check(lib().mc_buddhabrot_density(C.byref(p), _ptr(plane), C.byref(stats)), "mc_buddhabrot_density")
     return plane, stats
+
+
+def buddhabrot_importance(p, grid_log2, map=None, plane=None, stats=None, want_plane=True):
+    """mc_buddhabrot_importance (host only): ADDS p's samples to map (uint32[G * G], G = 2^grid_log2; a zeroed one when None), to plane
+    (a zeroed one when None; no plane at all when want_plane is false) and to stats.  Returns (map, plane or None, stats)."""
+    if map is None:
+        map = np.zeros(1 << (2 * grid_log2), np.uint32)
+    if map.dtype != np.uint32 or not map.flags["C_CONTIGUOUS"] or map.size != 1 << (2 * grid_log2):
+        raise ValueError("buddhabrot_importance: map must be a C-contiguous uint32 array of G * G words")
+    if want_plane and plane is None:
+        plane = np.zeros((p.height, p.width), np.uint32)
+    if want_plane and (plane.dtype != np.uint32 or not plane.flags["C_CONTIGUOUS"] or plane.size != p.width * p.height):
+        raise ValueError("buddhabrot_importance: plane must be a C-contiguous uint32 array of height x width")
+    if stats is None:
+        stats = BuddhabrotStats()
+    _check(lib().mc_buddhabrot_importance(C.byref(p), grid_log2, _ptr(map), _ptr(plane) if want_plane else None, C.byref(stats)),
+           "mc_buddhabrot_importance")
+    return map, (plane if want_plane else None), stats
+
+
+def buddhabrot_importance_cells(grid_log2, map, threshold=1, dilate=0, flags=0):
+    """mc_buddhabrot_importance_cells (host only): the ascending uint32 list of the cells with map >= threshold, grown by `dilate` rings;
+    BUDDHA_CELLS_COMPLEMENT in flags: the cells not in that set."""
+    m = np.ascontiguousarray(map, np.uint32).reshape(-1)
+    if 1 <= grid_log2 <= 12 and m.size != 1 << (2 * grid_log2):
+        raise ValueError(f"buddhabrot_importance_cells: the map has {m.size} words, G * G = {1 << (2 * grid_log2)} expected")
+    n = C.c_uint32(0)
+    _check(lib().mc_buddhabrot_importance_cells(grid_log2, _ptr(m), threshold, dilate, flags, None, C.byref(n)),
+           "mc_buddhabrot_importance_cells")
+    out = np.empty(n.value, np.uint32)
+    _check(lib().mc_buddhabrot_importance_cells(grid_log2, _ptr(m), threshold, dilate, flags, _ptr(out), C.byref(n)),
+           "mc_buddhabrot_importance_cells")
+    return out
+
+
+def buddhabrot_density_guided(p, cells, grid_log2, weight=1, plane=None, stats=None):
+    """mc_buddhabrot_density_guided (host only): sample k in cell cells[k mod len(cells)], `weight` per plotted point.  ADDS to plane (a
+    zeroed one when None) and to stats.  Returns (plane, stats)."""
+    cells = np.ascontiguousarray(cells, np.uint32).reshape(-1)
+    if plane is None:
+        plane = np.zeros((p.height, p.width), np.uint32)
+    if plane.dtype != np.uint32 or not plane.flags["C_CONTIGUOUS"] or plane.size != p.width * p.height:
+        raise ValueError("buddhabrot_density_guided: plane must be a C-contiguous uint32 array of height x width")
+    if stats is None:
+        stats = BuddhabrotStats()
+    _check(lib().mc_buddhabrot_density_guided(C.byref(p), _ptr(cells), cells.size, grid_log2, weight, _ptr(plane), C.byref(stats)),
+           "mc_buddhabrot_density_guided")
+    return plane, stats
+
+
+def buddhabrot_guide_params(**overrides):
+    """mc_buddhabrot_guide_default_params (g = 8, pilot 2^24 samples, threshold 1, dilate 1, no complement pass), then the overrides by
+    field name."""
+    g = BuddhabrotGuideParams()
+    _check(lib().mc_buddhabrot_guide_default_params(C.byref(g)), "mc_buddhabrot_guide_default_params")
+    for k, v in overrides.items():
+        if k not in dict(BuddhabrotGuideParams._fields_):
+            raise ValueError(f"buddhabrot_guide_params: no field {k}")
+        setattr(g, k, v)
+    return g
 
 
 def buddhabrot_sqrt_map(levels):
@@ -1236,7 +1317,28 @@ class Context:
         _check(lib().mc_buddhabrot_render(self._h, C.byref(p), _ptr(plane), C.byref(stats)), "mc_buddhabrot_render")
         return plane, stats
 
+    def buddhabrot_guided(self, p, guide):
+        """mc_buddhabrot_render_guided: (plane uint32 (height, width), BuddhabrotStats of the guided render, BuddhabrotGuideInfo) of the
+        chain pilot -> map -> cell list -> guided render [-> complement pass]."""
+        plane = np.empty((p.height, p.width), np.uint32)
+        stats, info = BuddhabrotStats(), BuddhabrotGuideInfo()
+        _check(lib().mc_buddhabrot_render_guided(self._h, C.byref(p), C.byref(guide), _ptr(plane), C.byref(stats), C.byref(info)),
+               "mc_buddhabrot_render_guided")
+        return plane, stats, info
+
     # ---- device-buffer forms (pointers are ints, e.g. torch.Tensor.data_ptr()) ------------------------
+    def buddhabrot_importance_device(self, p, grid_log2, d_map, d_plane=0, d_stats=0, stream=0):
+        """mc_buddhabrot_importance_device_async: ADDS to the device map uint32[G * G], to d_plane (0: no plane add is issued) and to
+        d_stats (uint64[5]; 0: none)."""
+        _check(lib().mc_buddhabrot_importance_device_async(self._h, C.byref(p), grid_log2, d_map or None, d_plane or None, d_stats or None,
+                                                           stream or None), "mc_buddhabrot_importance_device_async")
+
+    def buddhabrot_guided_device(self, p, d_cells, n_cells, grid_log2, weight, d_plane, d_stats=0, stream=0):
+        """mc_buddhabrot_density_guided_device_async: d_cells is a DEVICE list of n_cells uint32 cell indices below G * G."""
+        _check(lib().mc_buddhabrot_density_guided_device_async(self._h, C.byref(p), d_cells or None, n_cells, grid_log2, weight,
+                                                               d_plane or None, d_stats or None, stream or None),
+               "mc_buddhabrot_density_guided_device_async")
+
     def buddhabrot_device(self, p, d_plane, d_stats=0, stream=0):
         """mc_buddhabrot_density_device_async: ADDS p's samples to the device plane uint32[height][width] and to d_stats (uint64[5]; 0: none)."""
         _check(lib().mc_buddhabrot_density_device_async(self._h, C.byref(p), d_plane or None, d_stats or None, stream or None),

@@ -13,6 +13,7 @@
 //    a sample.  The default form: 2.7 and 5.5 times the plain form's rate on the two gate configurations.
 //  * the add is a relaxed, agent-scope atomic whose result is unused (global_atomic_add_u32 without return); integer adds commute, so the
 //    plane is bit-reproducible whatever the schedule.  Statistics are reduced per wave, then per block in LDS, and added once per block.
+//  * the importance map and the guided samples are template parameters of the two forms, not further kernels.
 //  Vector atomics and vector stores only.
 #include <cstring>
 
@@ -36,8 +37,38 @@ constexpr uint64_t kPoolMinRun = 512;      // samples a pooled wave owns at leas
 #endif
 constexpr uint32_t kPoolRefillLanes = MC_BUDDHA_REFILL_LANES;
 
-__device__ __forceinline__ void plane_add(uint32_t* plane, uint32_t bin) {
-    (void)__hip_atomic_fetch_add(plane + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ void plane_add(uint32_t* plane, uint32_t bin, uint32_t v) {
+    (void)__hip_atomic_fetch_add(plane + bin, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The three things a launch can be, as template parameters of both forms: kMap, the importance call, adds a sample's
+// added count to its cell's map word at the end of its plot phase; kPlane false, the pilot's normal use, issues no plane add and still
+// counts `added`; kGuided takes the sample's cell from the list and adds gd.weight per point.  <false, true, false> is the uniform call,
+// whose instructions are what they were before the parameters existed.
+
+// (base + off) mod n for base < n and off <= 64: a guided wave's k mod n_cells moves by increments, never by a 64-bit division.
+__device__ __forceinline__ uint32_t add_mod(uint32_t base, uint32_t off, uint32_t n) {
+    const uint64_t t = (uint64_t)base + off;
+    if (n > 64u) return (uint32_t)(t >= n ? t - n : t);
+    return (uint32_t)t % n;   // t < 128
+}
+// Sample k's c (and, for the map, its cell): the uniform hash, or the hash's high bits inside cell cells[j] of the list.  A list entry
+// beyond the grid is the caller's broken precondition; it is clamped, so the words stay what a cell of the grid gives.
+template <bool kMap, bool kGuided>
+__device__ __forceinline__ void take_sample(const Args& a, const buddha::Guide& gd, uint64_t k, uint32_t j, double& cx, double& cy,
+                                            uint32_t& cell) {
+    if constexpr (!kMap && !kGuided) {
+        buddha::sample_c(a, k, cx, cy);
+    } else {
+        uint32_t ux, uy;
+        buddha::hash_words(a.seed, k, ux, uy);
+        if constexpr (kGuided) {
+            const uint32_t top = (1u << (2u * gd.g)) - 1u, c = gd.cells[j];
+            buddha::guided_words(c > top ? top : c, gd.g, ux, uy);
+        }
+        if constexpr (kMap) cell = buddha::cell_of(ux, uy, gd.g);
+        buddha::c_of_words(a, ux, uy, cx, cy);
+    }
 }
 
 // The five per-lane counts of a block into d_stats: a wave sum by shuffles, the block's in LDS, one global add per field and block.
@@ -57,14 +88,27 @@ __device__ __forceinline__ void stats_flush(uint64_t* __restrict__ d_stats, uint
         atomicAdd(reinterpret_cast<unsigned long long*>(d_stats) + threadIdx.x, block_sum[threadIdx.x]);
 }
 
-__global__ void __launch_bounds__(kBlock) buddhabrot_plain_kernel(Args a, uint32_t* __restrict__ plane, uint64_t* __restrict__ d_stats) {
+template <bool kMap, bool kPlane, bool kGuided>
+__global__ void __launch_bounds__(kBlock) buddhabrot_plain_kernel(Args a, buddha::Guide gd, uint32_t* __restrict__ plane,
+                                                                  uint64_t* __restrict__ d_stats) {
     uint64_t st[buddha::kStats] = {0, 0, 0, 0, 0};
     const uint64_t samples = a.end - a.begin, stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t at = (uint64_t)blockIdx.x * kBlock + threadIdx.x; at < samples; at += stride) {   // (at < 2^40: no wrap near k = 2^64)
+    const uint64_t first = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    // guided: j = k mod n_cells by one 64-bit division per lane, then steps of stride mod n_cells
+    uint32_t j = 0, j_step = 0, cell = 0;
+    if constexpr (kGuided) {
+        j = (uint32_t)((a.begin + first) % gd.n_cells);
+        j_step = (uint32_t)(stride % gd.n_cells);
+    }
+    for (uint64_t at = first; at < samples; at += stride) {   // (at < 2^40: no wrap near k = 2^64)
         const uint64_t k = a.begin + at;
         st[buddha::kSamples]++;
         double cx, cy;
-        buddha::sample_c(a, k, cx, cy);
+        take_sample<kMap, kGuided>(a, gd, k, j, cx, cy, cell);
+        if constexpr (kGuided) {
+            const uint64_t t = (uint64_t)j + j_step;
+            j = (uint32_t)(t >= gd.n_cells ? t - gd.n_cells : t);
+        }
         if (buddha::interior(cx, cy)) {
             st[buddha::kSkipped]++;
             continue;
@@ -86,17 +130,22 @@ __global__ void __launch_bounds__(kBlock) buddhabrot_plain_kernel(Args a, uint32
             o.advance(cx, cy);
             uint32_t bin;
             if (buddha::bin_of(a, o.zx, o.zy, bin)) {
-                plane_add(plane, bin);
+                if constexpr (kPlane) plane_add(plane, bin, kGuided ? gd.weight : 1u);
                 added++;
             }
         }
         st[buddha::kAdded] += added;
+        if constexpr (kMap)
+            if (added) plane_add(gd.map, cell, added);
     }
     stats_flush(d_stats, st);
 }
 
 // run: the samples each wave owns (the last waves' runs end at a.end, or are empty).
-__global__ void __launch_bounds__(kBlock) buddhabrot_pooled_kernel(Args a, uint64_t run, uint32_t* __restrict__ plane,
+// The importance and guided instantiations ask for 8 waves per SIMD: left alone they take 65 and 66 VGPRs, one wave fewer than the
+// uniform call's 63; asked, the allocator gives 46 to 52 without scratch.  The uniform instantiation is not asked and keeps its code.
+template <bool kMap, bool kPlane, bool kGuided>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kMap || kGuided) ? 8 : 1, 8))) buddhabrot_pooled_kernel(Args a, buddha::Guide gd, uint64_t run, uint32_t* __restrict__ plane,
                                                                    uint64_t* __restrict__ d_stats) {
     enum : uint32_t { kIdle = 0, kClassify = 1, kPlot = 2 };
     uint64_t st[buddha::kStats] = {0, 0, 0, 0, 0};
@@ -112,6 +161,10 @@ __global__ void __launch_bounds__(kBlock) buddhabrot_pooled_kernel(Args a, uint6
     buddha::Orbit o;
     o.reset();
     uint32_t phase = kIdle, i = 0, n = 0, added = 0;
+    // importance: the lane keeps its sample's cell (not k) across the orbit.  guided: next_j = (a.begin + next) mod n_cells, wave-uniform,
+    // one 64-bit division per run; a run is contiguous in k, so every refill moves it by the lanes taken
+    uint32_t cell = 0, next_j = 0;
+    if constexpr (kGuided) next_j = (uint32_t)((a.begin + next) % gd.n_cells);
     for (;;) {
         // refill, once kPoolRefillLanes lanes are idle (or all of them): every idle lane takes the run's next index, in lane order,
         // until no lane is idle or the run is used up
@@ -119,10 +172,11 @@ __global__ void __launch_bounds__(kBlock) buddhabrot_pooled_kernel(Args a, uint6
             const unsigned long long idle = __ballot(phase == kIdle);
             if (!idle || next >= last) break;                                                            // wave-uniform, as the next
             if (!started && (uint32_t)__popcll(idle) < kPoolRefillLanes && idle != ~0ull) break;
-            const uint64_t at = next + (uint64_t)__popcll(idle & below);
+            const uint32_t ahead = (uint32_t)__popcll(idle & below);
+            const uint64_t at = next + (uint64_t)ahead;
             if (phase == kIdle && at < last) {
                 st[buddha::kSamples]++;
-                buddha::sample_c(a, a.begin + at, cx, cy);
+                take_sample<kMap, kGuided>(a, gd, a.begin + at, kGuided ? add_mod(next_j, ahead, gd.n_cells) : 0u, cx, cy, cell);
                 if (buddha::interior(cx, cy)) {
                     st[buddha::kSkipped]++;
                 } else {
@@ -133,6 +187,7 @@ __global__ void __launch_bounds__(kBlock) buddhabrot_pooled_kernel(Args a, uint6
             }
             const uint64_t take = (uint64_t)__popcll(idle);
             next = last - next < take ? last : next + take;
+            if constexpr (kGuided) next_j = add_mod(next_j, (uint32_t)take, gd.n_cells);
         }
         if (!__ballot(phase != kIdle)) break;   // the run is used up and every lane has finished: wave-uniform
         if (phase != kIdle) {
@@ -158,11 +213,13 @@ __global__ void __launch_bounds__(kBlock) buddhabrot_pooled_kernel(Args a, uint6
             } else {   // z is z_(i+1) of the n points
                 uint32_t bin;
                 if (buddha::bin_of(a, o.zx, o.zy, bin)) {
-                    plane_add(plane, bin);
+                    if constexpr (kPlane) plane_add(plane, bin, kGuided ? gd.weight : 1u);
                     added++;
                 }
                 if (++i == n) {
                     st[buddha::kAdded] += added;
+                    if constexpr (kMap)
+                        if (added) plane_add(gd.map, cell, added);
                     phase = kIdle;
                 }
             }
@@ -190,6 +247,7 @@ struct BuddhaState {
     DeviceBuffer table;                 // the tone map's quotients, 3 (levels + 1) floats: a cached device table like the colour LUT
     std::vector<uint32_t> table_maps;   // what `table` was formed from: m0 | m1 | m2
     uint32_t table_levels = 0;
+    DeviceBuffer map, cells, guide_stats;   // mc_buddhabrot_render_guided's map, cell lists and the statistics of its three passes
 };
 SideRecords<BuddhaState> g_buddha_states;
 
@@ -200,20 +258,17 @@ void buddhabrot_release(mc_context* ctx) {
         st.plane.release();
         st.stats.release();
         st.table.release();
+        st.map.release();
+        st.cells.release();
+        st.guide_stats.release();
     });
 }
 
-int buddhabrot_launch(mc_context* ctx, const mc_buddhabrot_params* p, void* d_plane, void* d_stats, hipStream_t s) {
-    const char* who = "mc_buddhabrot_density_device_async";
-    if (int rc = buddhabrot_check(p, who)) return rc;
-    if (!ctx || !d_plane) {
-        set_error_detail(std::string(who) + ": ctx or d_plane is NULL");
-        return MC_ERR_INVALID_ARGUMENT;
-    }
-    if (reinterpret_cast<uintptr_t>(d_plane) % 4u || reinterpret_cast<uintptr_t>(d_stats) % 8u) {
-        set_error_detail(std::string(who) + ": d_plane must be 4-byte aligned, d_stats 8-byte aligned");
-        return MC_ERR_INVALID_ARGUMENT;
-    }
+namespace {
+
+// One launch of either form in one of its instantiations; the grid is the uniform call's whatever the instantiation.
+template <bool kMap, bool kPlane, bool kGuided>
+int launch_as(mc_context* ctx, const mc_buddhabrot_params* p, const buddha::Guide& gd, void* d_plane, void* d_stats, hipStream_t s) {
     const Args a = buddha::make_args(p);
     const uint64_t samples = a.end - a.begin;
     if (!samples) return MC_OK;
@@ -222,17 +277,87 @@ int buddhabrot_launch(mc_context* ctx, const mc_buddhabrot_params* p, void* d_pl
     if (plain) {
         uint64_t blocks = (samples + kBlock - 1u) / kBlock;
         if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(buddhabrot_plain_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, (uint32_t*)d_plane, (uint64_t*)d_stats);
+        hipLaunchKernelGGL((buddhabrot_plain_kernel<kMap, kPlane, kGuided>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, gd,
+                           (uint32_t*)d_plane, (uint64_t*)d_stats);
     } else {
         const uint64_t per_block = kPoolMinRun * kWavesPerBlock;
         uint64_t blocks = (samples + per_block - 1u) / per_block;
         if (blocks > cap) blocks = cap;
         const uint64_t waves = blocks * kWavesPerBlock;
         const uint64_t run = (samples + waves - 1u) / waves;
-        hipLaunchKernelGGL(buddhabrot_pooled_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, run, (uint32_t*)d_plane,
-                           (uint64_t*)d_stats);
+        hipLaunchKernelGGL((buddhabrot_pooled_kernel<kMap, kPlane, kGuided>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, a, gd, run,
+                           (uint32_t*)d_plane, (uint64_t*)d_stats);
     }
     MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
+// What every device form checks of its pointers: a plane (when required or given) and the statistics, aligned.
+int check_device_pointers(mc_context* ctx, void* d_plane, bool plane_required, void* d_stats, const char* who) {
+    if (!ctx || (plane_required && !d_plane)) {
+        set_error_detail(std::string(who) + ": ctx or d_plane is NULL");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (reinterpret_cast<uintptr_t>(d_plane) % 4u || reinterpret_cast<uintptr_t>(d_stats) % 8u) {
+        set_error_detail(std::string(who) + ": d_plane must be 4-byte aligned, d_stats 8-byte aligned");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    return MC_OK;
+}
+
+}  // namespace
+
+int buddhabrot_launch(mc_context* ctx, const mc_buddhabrot_params* p, void* d_plane, void* d_stats, hipStream_t s) {
+    const char* who = "mc_buddhabrot_density_device_async";
+    if (int rc = buddhabrot_check(p, who)) return rc;
+    if (int rc = check_device_pointers(ctx, d_plane, true, d_stats, who)) return rc;
+    return launch_as<false, true, false>(ctx, p, buddha::Guide{}, d_plane, d_stats, s);
+}
+
+int buddhabrot_importance_launch(mc_context* ctx, const mc_buddhabrot_params* p, uint32_t grid_log2, void* d_map, void* d_plane,
+                                 void* d_stats, hipStream_t s) {
+    const char* who = "mc_buddhabrot_importance_device_async";
+    if (int rc = buddhabrot_check(p, who)) return rc;
+    if (int rc = buddhabrot_check_grid(grid_log2, who)) return rc;
+    if (int rc = check_device_pointers(ctx, d_plane, false, d_stats, who)) return rc;
+    if (!d_map || reinterpret_cast<uintptr_t>(d_map) % 4u) {
+        set_error_detail(std::string(who) + ": d_map is NULL or not 4-byte aligned");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    buddha::Guide gd{};
+    gd.map = (uint32_t*)d_map;
+    gd.g = grid_log2;
+    return d_plane ? launch_as<true, true, false>(ctx, p, gd, d_plane, d_stats, s)
+                   : launch_as<true, false, false>(ctx, p, gd, nullptr, d_stats, s);
+}
+
+int buddhabrot_guided_launch(mc_context* ctx, const mc_buddhabrot_params* p, const void* d_cells, uint32_t n_cells, uint32_t grid_log2,
+                             uint32_t weight, void* d_plane, void* d_stats, hipStream_t s) {
+    const char* who = "mc_buddhabrot_density_guided_device_async";
+    if (int rc = buddhabrot_check(p, who)) return rc;
+    if (int rc = buddhabrot_check_cell_list((const uint32_t*)d_cells, n_cells, grid_log2, weight, false, who)) return rc;
+    if (int rc = check_device_pointers(ctx, d_plane, true, d_stats, who)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_cells) % 4u) {
+        set_error_detail(std::string(who) + ": d_cells must be 4-byte aligned");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    buddha::Guide gd{};
+    gd.cells = (const uint32_t*)d_cells;
+    gd.n_cells = n_cells;
+    gd.g = grid_log2;
+    gd.weight = weight;
+    return launch_as<false, true, true>(ctx, p, gd, d_plane, d_stats, s);
+}
+
+int buddhabrot_guide_buffers(mc_context* ctx, uint32_t grid_log2, void** d_map, void** d_cells, void** d_stats3) {
+    BuddhaState* st = g_buddha_states.get(ctx);
+    const size_t words = (size_t)1 << (2u * grid_log2);
+    int rc;
+    if ((rc = st->map.reserve(words * 4)) || (rc = st->cells.reserve(words * 4)) || (rc = st->guide_stats.reserve(3 * buddha::kStats * 8)))
+        return rc;
+    *d_map = st->map.ptr;
+    *d_cells = st->cells.ptr;
+    *d_stats3 = st->guide_stats.ptr;
     return MC_OK;
 }
 
@@ -301,6 +426,26 @@ int mc_buddhabrot_density_device_async(mc_context* ctx, const mc_buddhabrot_para
     }
     MC_HIP_TRY(hipSetDevice(ctx->device));
     return buddhabrot_launch(ctx, p, d_plane, d_stats, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int mc_buddhabrot_importance_device_async(mc_context* ctx, const mc_buddhabrot_params* p, uint32_t grid_log2, void* d_map, void* d_plane,
+                                          void* d_stats, void* stream) {
+    if (!ctx) {
+        set_error_detail("mc_buddhabrot_importance_device_async: ctx is NULL");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    return buddhabrot_importance_launch(ctx, p, grid_log2, d_map, d_plane, d_stats, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int mc_buddhabrot_density_guided_device_async(mc_context* ctx, const mc_buddhabrot_params* p, const void* d_cells, uint32_t n_cells,
+                                              uint32_t grid_log2, uint32_t weight, void* d_plane, void* d_stats, void* stream) {
+    if (!ctx) {
+        set_error_detail("mc_buddhabrot_density_guided_device_async: ctx is NULL");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    return buddhabrot_guided_launch(ctx, p, d_cells, n_cells, grid_log2, weight, d_plane, d_stats, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int mc_buddhabrot_tonemap_device_async(mc_context* ctx, uint32_t width, uint32_t height, const void* d0, const void* d1, const void* d2,

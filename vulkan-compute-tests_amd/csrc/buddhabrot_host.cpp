@@ -1,9 +1,10 @@
 // Buddhabrot, host side: the checks every mc_buddhabrot_* call shares and the host-only entry points (mc_buddhabrot_default_params,
-// _density, _sqrt_map, _tonemap).
+// _density, _importance, _importance_cells, _density_guided, _guide_default_params, _sqrt_map, _tonemap).
 // Plain C++17, no HIP header; built with the library's floating-point flags (-ffp-contract=off), since the plane is a result.  The
 // arithmetic of a sample is buddhabrot.h's, the text the kernels compile too.
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "buddhabrot.h"
 
@@ -41,6 +42,90 @@ int buddhabrot_check(const mc_buddhabrot_params* p, const char* who) {
         return refuse(who, "flags names both MC_BUDDHA_KERNEL_PLAIN and MC_BUDDHA_KERNEL_POOLED");
     return MC_OK;
 }
+
+int buddhabrot_check_grid(uint32_t grid_log2, const char* who) {
+    if (!grid_log2 || grid_log2 > buddha::kMaxGridLog2) return refuse(who, "grid_log2 is outside 1 .. 12");
+    return MC_OK;
+}
+
+// read_list: `cells` is a host list, every entry is checked against the grid (the async device form cannot: its caller's precondition).
+int buddhabrot_check_cell_list(const uint32_t* cells, uint32_t n_cells, uint32_t grid_log2, uint32_t weight, bool read_list,
+                               const char* who) {
+    if (int rc = buddhabrot_check_grid(grid_log2, who)) return rc;
+    if (!cells) return refuse(who, "cells is NULL");
+    if (!n_cells) return refuse(who, "n_cells is 0");
+    if (!weight) return refuse(who, "weight is 0");
+    if (read_list) {
+        const uint32_t count = 1u << (2u * grid_log2);
+        for (uint32_t j = 0; j < n_cells; j++)
+            if (cells[j] >= count) return refuse(who, "a cell index is outside the grid (at least G * G)");
+    }
+    return MC_OK;
+}
+
+int buddhabrot_check_guide(const mc_buddhabrot_guide_params* guide, const char* who) {
+    if (!guide) return refuse(who, "guide is NULL");
+    if (int rc = buddhabrot_check_grid(guide->grid_log2, who)) return rc;
+    if (guide->pilot_samples > buddha::kMaxSamples) return refuse(who, "pilot_samples exceeds 2^40");
+    if (!guide->threshold) return refuse(who, "threshold is 0");
+    if (guide->dilate > buddha::kMaxDilate) return refuse(who, "dilate exceeds 8");
+    return MC_OK;
+}
+
+namespace {
+
+// The host calls' one body: the samples of a's range, uniform or (gd.cells) guided, into plane (unless null) at gd.weight per point,
+// into the map (unless null) and into st.
+void host_samples(const buddha::Args& a, const buddha::Guide& gd, uint32_t* plane, uint64_t (&st)[buddha::kStats]) {
+    for (uint64_t k = a.begin; k < a.end; k++) {
+        st[buddha::kSamples]++;
+        uint32_t ux, uy;
+        buddha::hash_words(a.seed, k, ux, uy);
+        if (gd.cells) buddha::guided_words(gd.cells[k % gd.n_cells], gd.g, ux, uy);
+        double cx, cy;
+        buddha::c_of_words(a, ux, uy, cx, cy);
+        if (buddha::interior(cx, cy)) {
+            st[buddha::kSkipped]++;
+            continue;
+        }
+        buddha::Orbit o;
+        o.reset();
+        uint32_t n = 0;
+        bool escaped = false;
+        for (uint32_t i = 0; i < a.max_iter; i++)
+            if (o.advance(cx, cy) > 4.0) {
+                n = i;
+                escaped = true;
+                break;
+            }
+        if (!escaped || n < a.min_iter) continue;
+        st[buddha::kContributing]++;
+        st[buddha::kPoints] += n;
+        o.reset();
+        uint32_t added = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            o.advance(cx, cy);
+            uint32_t bin;
+            if (buddha::bin_of(a, o.zx, o.zy, bin)) {
+                if (plane) plane[bin] += gd.weight;   // (wraps modulo 2^32)
+                added++;
+            }
+        }
+        st[buddha::kAdded] += added;
+        if (gd.map && added) gd.map[buddha::cell_of(ux, uy, gd.g)] += added;   // (wraps too)
+    }
+}
+
+void add_stats(mc_buddhabrot_stats* stats, const uint64_t (&st)[buddha::kStats]) {
+    if (!stats) return;
+    stats->samples += st[buddha::kSamples];
+    stats->skipped += st[buddha::kSkipped];
+    stats->contributing += st[buddha::kContributing];
+    stats->points += st[buddha::kPoints];
+    stats->added += st[buddha::kAdded];
+}
+
+}  // namespace
 
 int buddhabrot_check_levels(uint32_t levels, const char* who) {
     if (!levels || levels > buddha::kMaxLevels) return refuse(who, "levels is outside 1 .. 2^20");
@@ -96,46 +181,87 @@ int mc_buddhabrot_density(const mc_buddhabrot_params* p, uint32_t* plane, mc_bud
         set_error_detail(std::string(who) + ": plane is NULL");
         return MC_ERR_INVALID_ARGUMENT;
     }
-    const buddha::Args a = buddha::make_args(p);
+    buddha::Guide gd{};
+    gd.weight = 1u;
     uint64_t st[buddha::kStats] = {0, 0, 0, 0, 0};
-    for (uint64_t k = a.begin; k < a.end; k++) {
-        st[buddha::kSamples]++;
-        double cx, cy;
-        buddha::sample_c(a, k, cx, cy);
-        if (buddha::interior(cx, cy)) {
-            st[buddha::kSkipped]++;
-            continue;
-        }
-        buddha::Orbit o;
-        o.reset();
-        uint32_t n = 0;
-        bool escaped = false;
-        for (uint32_t i = 0; i < a.max_iter; i++)
-            if (o.advance(cx, cy) > 4.0) {
-                n = i;
-                escaped = true;
-                break;
-            }
-        if (!escaped || n < a.min_iter) continue;
-        st[buddha::kContributing]++;
-        st[buddha::kPoints] += n;
-        o.reset();
-        for (uint32_t i = 0; i < n; i++) {
-            o.advance(cx, cy);
-            uint32_t bin;
-            if (buddha::bin_of(a, o.zx, o.zy, bin)) {
-                plane[bin] += 1u;   // (wraps modulo 2^32)
-                st[buddha::kAdded]++;
-            }
-        }
+    host_samples(buddha::make_args(p), gd, plane, st);
+    add_stats(stats, st);
+    return MC_OK;
+}
+
+int mc_buddhabrot_importance(const mc_buddhabrot_params* p, uint32_t grid_log2, uint32_t* map, uint32_t* plane,
+                             mc_buddhabrot_stats* stats) {
+    const char* who = "mc_buddhabrot_importance";
+    if (int rc = buddhabrot_check(p, who)) return rc;
+    if (int rc = buddhabrot_check_grid(grid_log2, who)) return rc;
+    if (!map) return refuse(who, "map is NULL");
+    buddha::Guide gd{};
+    gd.map = map;
+    gd.g = grid_log2;
+    gd.weight = 1u;
+    uint64_t st[buddha::kStats] = {0, 0, 0, 0, 0};
+    host_samples(buddha::make_args(p), gd, plane, st);
+    add_stats(stats, st);
+    return MC_OK;
+}
+
+int mc_buddhabrot_importance_cells(uint32_t grid_log2, const uint32_t* map, uint32_t threshold, uint32_t dilate, uint32_t flags,
+                                   uint32_t* cells_out, uint32_t* n_cells) {
+    const char* who = "mc_buddhabrot_importance_cells";
+    if (int rc = buddhabrot_check_grid(grid_log2, who)) return rc;
+    if (!map) return refuse(who, "map is NULL");
+    if (!n_cells) return refuse(who, "n_cells is NULL");
+    if (!threshold) return refuse(who, "threshold is 0");
+    if (dilate > buddha::kMaxDilate) return refuse(who, "dilate exceeds 8");
+    if (flags & ~(uint32_t)MC_BUDDHA_CELLS_COMPLEMENT) return refuse(who, "flags has unknown bits");
+    const size_t G = (size_t)1 << grid_log2;
+    std::vector<uint8_t> in(G * G), row(G * G);
+    for (size_t c = 0; c < G * G; c++) in[c] = map[c] >= threshold;
+    // one ring of the 8-neighbourhood = the 3-wide maximum along the rows, then along the columns, clipped at the edges
+    for (uint32_t ring = 0; ring < dilate; ring++) {
+        for (size_t y = 0; y < G; y++)
+            for (size_t x = 0; x < G; x++)
+                row[y * G + x] = in[y * G + x] | (x ? in[y * G + x - 1] : 0) | (x + 1 < G ? in[y * G + x + 1] : 0);
+        for (size_t y = 0; y < G; y++)
+            for (size_t x = 0; x < G; x++)
+                in[y * G + x] = row[y * G + x] | (y ? row[(y - 1) * G + x] : 0) | (y + 1 < G ? row[(y + 1) * G + x] : 0);
     }
-    if (stats) {
-        stats->samples += st[buddha::kSamples];
-        stats->skipped += st[buddha::kSkipped];
-        stats->contributing += st[buddha::kContributing];
-        stats->points += st[buddha::kPoints];
-        stats->added += st[buddha::kAdded];
-    }
+    const uint8_t want = (flags & MC_BUDDHA_CELLS_COMPLEMENT) ? 0 : 1;
+    uint32_t n = 0;
+    for (size_t c = 0; c < G * G; c++)
+        if (in[c] == want) {
+            if (cells_out) cells_out[n] = (uint32_t)c;
+            n++;
+        }
+    *n_cells = n;
+    return MC_OK;
+}
+
+int mc_buddhabrot_density_guided(const mc_buddhabrot_params* p, const uint32_t* cells, uint32_t n_cells, uint32_t grid_log2,
+                                 uint32_t weight, uint32_t* plane, mc_buddhabrot_stats* stats) {
+    const char* who = "mc_buddhabrot_density_guided";
+    if (int rc = buddhabrot_check(p, who)) return rc;
+    if (int rc = buddhabrot_check_cell_list(cells, n_cells, grid_log2, weight, true, who)) return rc;
+    if (!plane) return refuse(who, "plane is NULL");
+    buddha::Guide gd{};
+    gd.cells = cells;
+    gd.n_cells = n_cells;
+    gd.g = grid_log2;
+    gd.weight = weight;
+    uint64_t st[buddha::kStats] = {0, 0, 0, 0, 0};
+    host_samples(buddha::make_args(p), gd, plane, st);
+    add_stats(stats, st);
+    return MC_OK;
+}
+
+int mc_buddhabrot_guide_default_params(mc_buddhabrot_guide_params* out) {
+    if (!out) return refuse("mc_buddhabrot_guide_default_params", "out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    out->grid_log2 = 8;
+    out->pilot_samples = 1ull << 24;
+    out->threshold = 1;
+    out->dilate = 1;
+    out->complement_weight = 0;
     return MC_OK;
 }
 

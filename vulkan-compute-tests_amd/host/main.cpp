@@ -14,7 +14,9 @@
 // library's view (-0.5, 0, 3, 3 H / W) and max_iter 1000), with --min-iter m, --seed s, --sample-window CX CY SX SY (where c is drawn
 // from; default -0.5 0 4 4), --nebula MR MG MB (three renders of those max_iter, one per colour channel), --tone sqrt|equalised
 // (default sqrt) and --white PCT (default 99.9: the white level L is the density not exceeded by PCT % of the non-empty bins, read from
-// one histogram capped at 2^20 - 1 — the app's policy, not the library's); --help prints this list,
+// one histogram capped at 2^20 - 1 — the app's policy, not the library's), and for zoomed views --guided[=G] with --pilot P, --dilate D,
+// --unbiased B (mc_buddhabrot_render_guided, DESIGN.md §3.27: a pilot's importance map over the 2^G x 2^G cells of the sample window,
+// the samples drawn from the cells whose orbits reach the view); --help prints this list,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -84,6 +86,9 @@ int main(int argc, char* argv[]) {
     bool buddhaSet = false, buddhaOptions = false, buddhaWindowSet = false, buddhaNebula = false, buddhaEqualised = false, maxIterSet = false;
     double buddhaWindow[4] = {-0.5, 0.0, 4.0, 4.0}, buddhaWhite = 99.9;
     unsigned long long buddhaNebulaIter[3] = {0, 0, 0};
+    // --guided[=G] with --pilot, --dilate, --unbiased (mc_buddhabrot_render_guided)
+    bool guidedSet = false, guidedOptions = false, pilotSet = false, dilateSet = false;
+    unsigned long long guidedLog2 = 0, guidedPilot = 0, guidedDilate = 0, guidedUnbiased = 0;
     // a whole non-negative number up to `most`, or the run ends
     auto count = [](const std::string& opt, const char* v, unsigned long long most) -> unsigned long long {
         char* end = nullptr;
@@ -130,7 +135,12 @@ int main(int argc, char* argv[]) {
                    "    --nebula MR MG MB       three renders of those max_iter, one per colour channel\n"
                    "    --tone sqrt|equalised   the map from density to brightness (default sqrt)\n"
                    "    --white PCT             the white level: the density not exceeded by PCT %% of the non-empty bins, read from one\n"
-                   "                            histogram capped at 2^20 - 1 (default 99.9)\n");
+                   "                            histogram capped at 2^20 - 1 (default 99.9)\n"
+                   "    --guided[=G]            for zoomed views: a pilot finds the cells of the 2^G x 2^G grid over the sample window (G in\n"
+                   "                            1 .. 12, default 8) whose orbits reach the view; the SAMPLES are drawn from those cells only\n"
+                   "      --pilot P             the pilot's uniform samples (default 2^24)\n"
+                   "      --dilate D            rings of neighbouring cells added to the list, 0 .. 8 (default 1)\n"
+                   "      --unbiased B          a second pass over all the other cells with 1 / B of the samples per cell at weight B\n");
             return EXIT_SUCCESS;
         }
         else if (a == "--buddhabrot") { need(1); buddhaSamples = count(a, argv[++i], 1ull << 40); buddhaSet = true; }
@@ -147,6 +157,15 @@ int main(int argc, char* argv[]) {
             if (end == v || *end || !(buddhaWhite > 0.0) || !(buddhaWhite <= 100.0)) { printf("--white %s: a percentage above 0, at most 100\n", v); exit(EXIT_FAILURE); }
             buddhaOptions = true;
         }
+        else if (a == "--guided") guidedSet = true;
+        else if (a.rfind("--guided=", 0) == 0) {
+            guidedLog2 = count("--guided=", a.c_str() + 9, 12);
+            if (!guidedLog2) { printf("%s: G is 1 to 12\n", a.c_str()); exit(EXIT_FAILURE); }
+            guidedSet = true;
+        }
+        else if (a == "--pilot") { need(1); guidedPilot = count(a, argv[++i], 1ull << 40); pilotSet = guidedOptions = true; }
+        else if (a == "--dilate") { need(1); guidedDilate = count(a, argv[++i], 8); dilateSet = guidedOptions = true; }
+        else if (a == "--unbiased") { need(1); guidedUnbiased = count(a, argv[++i], 0xffffffffull); guidedOptions = true; }
         else if (a == "--centre") { need(2); cxText = argv[++i]; cyText = argv[++i]; cx = atof(cxText); cy = atof(cyText); viewSet = centreSet = true; }
         else if (a == "--scale") { need(2); sxText = argv[++i]; syText = argv[++i]; sx = atof(sxText); sy = atof(syText); viewSet = scaleSet = true; }
         else if (a == "--precision") { need(1); precision = choice(argv[++i], {{"f32", MC_PRECISION_F32}, {"ds", MC_PRECISION_DS}, {"f64", MC_PRECISION_F64}, {"perturb", MC_PRECISION_PERTURB}, {"perturb-bla", MC_PRECISION_PERTURB_BLA}, {"perturb-bla-deep", MC_PRECISION_PERTURB_BLA_DEEP}}); }
@@ -305,6 +324,8 @@ int main(int argc, char* argv[]) {
         else pos.push_back(argv[i]);
     }
     if (buddhaOptions && !buddhaSet) { printf("--min-iter / --seed / --sample-window / --nebula / --tone / --white: only with --buddhabrot SAMPLES\n"); exit(EXIT_FAILURE); }
+    if ((guidedSet || guidedOptions) && !buddhaSet) { printf("--guided / --pilot / --dilate / --unbiased: only with --buddhabrot SAMPLES\n"); exit(EXIT_FAILURE); }
+    if (guidedOptions && !guidedSet) { printf("--pilot / --dilate / --unbiased: only with --guided\n"); exit(EXIT_FAILURE); }
     if (buddhaSet) {
         const char* why = !buddhaSamples                    ? "SAMPLES is at least 1"
                           : maxIterSet && !maxIter          ? "--max-iter is at least 1"
@@ -321,6 +342,7 @@ int main(int argc, char* argv[]) {
     if (buddhaSet) { printf("--buddhabrot: a Mandelbrot option\n"); exit(EXIT_FAILURE); }
 #endif
     (void)maxIterSet; (void)centreSet; (void)scaleSet; (void)buddhaMinIter; (void)buddhaSeed; (void)buddhaWindowSet; (void)buddhaNebula; (void)buddhaEqualised; (void)buddhaWindow; (void)buddhaWhite; (void)buddhaNebulaIter;
+    (void)guidedSet; (void)pilotSet; (void)dilateSet; (void)guidedLog2; (void)guidedPilot; (void)guidedDilate; (void)guidedUnbiased;
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
     if (supersampleSmooth) {
         const char* why = supersample <= 1u ? "needs --supersample 2 | 4 | 8"
@@ -389,6 +411,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 3; k++) b.nebulaIter[k] = (uint32_t)buddhaNebulaIter[k];
         b.equalised = buddhaEqualised;
         b.whitePct = buddhaWhite;
+        b.guided = guidedSet;
+        b.guideLog2 = (uint32_t)guidedLog2;
+        b.pilotSet = pilotSet; b.pilot = guidedPilot;
+        b.dilateSet = dilateSet; b.dilate = (uint32_t)guidedDilate;
+        b.unbiased = (uint32_t)guidedUnbiased;
         app.setBuddhabrot(b);
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --buddhabrot renders whole planes; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;

@@ -67,6 +67,11 @@ struct MandelbrotApp : public ComputeApp {
         double view[4] = {0, 0, 0, 0}, window[4] = {0, 0, 0, 0};
         uint32_t nebulaIter[3] = {0, 0, 0};
         double whitePct = 99.9;
+        // --guided[=G]: every channel through mc_buddhabrot_render_guided, one pilot per channel; 0 / unset: the
+        // library's defaults (mc_buddhabrot_guide_default_params)
+        bool guided = false, pilotSet = false, dilateSet = false;
+        uint32_t guideLog2 = 0, dilate = 0, unbiased = 0;
+        uint64_t pilot = 0;
     };
     void setBuddhabrot(const Buddhabrot& b) { buddha = b; }
     ~MandelbrotApp() { if (orbit) mc_mandelbrot_orbit_destroy(orbit); }
@@ -264,12 +269,34 @@ private:
             bp.max_iter = buddha.nebula ? buddha.nebulaIter[c] : (buddha.maxIter ? buddha.maxIter : bp.max_iter);
             planes[c].resize(npix);
             mc_buddhabrot_stats st;
-            check(mc_buddhabrot_render(ctx, &bp, planes[c].data(), &st), "mc_buddhabrot_render");
+            mc_buddhabrot_guide_info info;
+            uint32_t grid = 0;
+            if (buddha.guided) {
+                mc_buddhabrot_guide_params gp;
+                check(mc_buddhabrot_guide_default_params(&gp), "mc_buddhabrot_guide_default_params");
+                if (buddha.guideLog2) gp.grid_log2 = buddha.guideLog2;
+                if (buddha.pilotSet) gp.pilot_samples = buddha.pilot;
+                if (buddha.dilateSet) gp.dilate = buddha.dilate;
+                gp.complement_weight = buddha.unbiased;
+                grid = gp.grid_log2;
+                check(mc_buddhabrot_render_guided(ctx, &bp, &gp, planes[c].data(), &st, &info), "mc_buddhabrot_render_guided");
+            } else {
+                check(mc_buddhabrot_render(ctx, &bp, planes[c].data(), &st), "mc_buddhabrot_render");
+            }
             double kernel = 0.0;
             (void)mc_context_last_timing(ctx, &kernel, nullptr);
             printf("buddhabrot: max_iter %u, min_iter %u, seed %u: samples %llu, skipped %llu, contributing %llu, points %llu, added %llu (kernel %.3f ms)\n",
                    bp.max_iter, bp.min_iter, bp.seed, (unsigned long long)st.samples, (unsigned long long)st.skipped,
                    (unsigned long long)st.contributing, (unsigned long long)st.points, (unsigned long long)st.added, kernel);
+            if (buddha.guided) {
+                const unsigned long long all = 1ull << (2u * grid);
+                printf("guided: %u of %llu cells (%.2f %%), pilot added %llu of %llu samples", info.n_cells, all,
+                       100.0 * (double)info.n_cells / (double)all, (unsigned long long)info.pilot.added, (unsigned long long)info.pilot.samples);
+                if (info.complement.samples)
+                    printf(", complement %u cells: samples %llu, added %llu at weight %u", info.n_complement,
+                           (unsigned long long)info.complement.samples, (unsigned long long)info.complement.added, buddha.unbiased);
+                printf("\n");
+            }
         }
         constexpr uint32_t kCap = (1u << 20) - 1u;
         std::vector<uint64_t> hist((size_t)kCap + 1, 0);
