@@ -339,8 +339,11 @@ enum {
     /* bits 8-11: MC_MANDEL_SUPERSAMPLE(s) below */
     MC_MANDEL_COLOUR_SMOOTH_EQUALISED = 1u << 12,/* the smooth count ranked among a WHOLE image's escaped pixels (the contract is  */
                                   /* below, at mc_mandelbrot_render_smooth_equalised); set WITHOUT MC_MANDEL_COLOUR_SMOOTH     */
-    MC_MANDEL_SUPERSAMPLE_SMOOTH = 1u << 13 /* with MC_MANDEL_SUPERSAMPLE(s) and ONE of the two smooth colourings: the s x s samples  */
+    MC_MANDEL_SUPERSAMPLE_SMOOTH = 1u << 13,/* with MC_MANDEL_SUPERSAMPLE(s) and ONE of the two smooth colourings: the s x s samples  */
                                   /* are smooth counts (the contract is below, at mc_mandelbrot_resolve_smooth_device_async)   */
+    MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE = 1u << 14 /* with MC_MANDEL_SUPERSAMPLE(s) and ONE of the two smooth colourings, WITHOUT  */
+                                  /* bits 5 and 13: only pixels whose smooth count is further than a threshold from a          */
+                                  /* neighbour's get their s x s smooth samples (below, at mc_mandelbrot_render_adaptive_smooth) */
 };
 /* s x s supersampling, resolved on the device: bits 8-11 of flags hold s.  0 and 1: off (every call behaves as without the bits);
  * 2, 4, 8: valid; 3, 5, 6, 7, 9 .. 15: MC_ERR_INVALID_ARGUMENT.  The contract is below, at mc_mandelbrot_resolve_device_async. */
@@ -716,6 +719,56 @@ int mc_mandelbrot_resolve_smooth_device_async(mc_context* ctx, const mc_mandelbr
                                               const uint32_t* qmap /* HOST, max_iter + 1, or NULL */, void* d_rgba_f32, void* stream);
 int mc_mandelbrot_resolve_smooth(uint32_t max_iter, const float k_color[4], uint32_t s, uint32_t width, uint32_t rows, const uint32_t* q,
                                  const uint32_t* qmap /* max_iter + 1, or NULL */, float* out_rgba_f32);
+
+/* ---- adaptive smooth supersampling: refine by a count threshold (the project's own addition, additions within ABI 3; what
+ *      tests/mandel_adaptive_smooth_ref.py restates).  MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE in flags, valid only together with
+ *      MC_MANDEL_SUPERSAMPLE(s), s = 2, 4 or 8, and EXACTLY ONE of MC_MANDEL_COLOUR_SMOOTH and MC_MANDEL_COLOUR_SMOOTH_EQUALISED, on a
+ *      WHOLE image (row_begin = 0, row_end = height, no interleave), width * height <= 2^32 - 1, max_iter <= 2^24 - 1.  It is set WITHOUT
+ *      MC_MANDEL_SUPERSAMPLE_ADAPTIVE (bit 5) and MC_MANDEL_SUPERSAMPLE_SMOOTH (bit 13).  It defines no new floating-point expression.
+ *  - anchor: the anchor plane A is the plain smooth W x H render's q plane (uint32_t, 256 M = interior, M = max_iter), and
+ *    a(y, x) = min(A(y, x), 256 M).  q of grid sample (s*y, s*x) IS A(y, x), bit for bit, in every precision (the argument of the
+ *    adaptive section above, applied to the smooth count: a sample's q is a function of the same quotient).
+ *  - refined: pixel (y, x) is refined iff |a(y, x) - a(y', x')| > tau for one of its up to eight neighbours (y', x') inside the image.
+ *    The difference is formed without wrap (a > b ? a - b : b - a); tau is a uint32_t in units of 1/256 iteration.  tau = 0 is "differs
+ *    at all"; tau >= 256 M refines nothing; an interior neighbour is just the value 256 M (there is no separate interior clause).
+ *  - colour of a refined pixel: its s*s samples are the pixels (s*y + i, s*x + j) of the plain smooth s*W x s*H render (the smooth
+ *    supersampling section's samples), each coloured by that section's sample colour, summed by the supersampling section's tree
+ *    (adjacent pairs over the flattened index i*s + j) and multiplied once by 1.0f / (s*s); alpha is exactly 1.0f.  With
+ *    MC_MANDEL_COLOUR_SMOOTH that is the full MC_MANDEL_SUPERSAMPLE_SMOOTH image's pixel, bit for bit.
+ *  - colour of an unrefined pixel: the plain image's pixel, bit for bit (mc_mandelbrot_render with the colouring alone).
+ *  - ranked form (MC_MANDEL_COLOUR_SMOOTH_EQUALISED): the histogram and the knot map are the ANCHOR plane's (W*H values: the plain
+ *    smooth-equalised image's map, as the adaptive section does for MC_MANDEL_COLOUR_EQUALISED); unrefined pixels are that image's
+ *    pixels and refined pixels send every sample through the same map.  This is NOT the full ranked MC_MANDEL_SUPERSAMPLE_SMOOTH call's
+ *    map, which ranks all s*s*W*H samples: the two ranked images differ on refined pixels too.
+ *  - the image does not depend on the order of the list or on how entries are grouped onto waves, and is the same bits from run to run.
+ * MC_ERR_INVALID_ARGUMENT, mc_last_error_detail naming MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE and what it needs: the bit together with bit 5
+ * or bit 13; with MC_MANDEL_COLOUR_EQUALISED, MC_MANDEL_COLOUR_DISTANCE, MC_MANDEL_ITERS_U16 or the measurement switch MC_MANDEL_FMA; the
+ * bit alone, with s <= 1, or with neither or both colourings; a tile or band.  (Bits 5 and 13 together, without this bit, stay refused as
+ * before.)
+ * mc_mandelbrot_render (out_rgba_f32; out_iters refused as for every s >= 2) and mc_mandelbrot_render_rgba8 honour the bit in all six
+ * precisions with the default tau = MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD = 256: one iteration.  The chain: the plain smooth W x H render
+ * (anchor plane, and the plain colours), [the anchor plane's smooth histogram, the table's round trip, the knot map and the plain ranked
+ * colours,] a device list of the refined pixels, 4 bytes back to the host (the list's length), and a render of the list's samples that
+ * resolves each pixel between the lanes that computed its samples.  No s*s-sized plane exists: the scratch is 4 bytes of anchor and 4
+ * bytes of list per pixel beside the image.  mc_context_last_timing spans the chain; mc_context_last_refined reports the list's length
+ * and width * height.  mc_context_warmup_mandelbrot accepts the bit and makes the refine and list kernels resident;
+ * mc_mandelbrot_zoom_push renders through mc_mandelbrot_render and so accepts it.  mc_mandelbrot_supersample_params with the bit set clears
+ * it, keeps MC_MANDEL_COLOUR_SMOOTH and replaces MC_MANDEL_COLOUR_SMOOTH_EQUALISED by it, exactly as for MC_MANDEL_SUPERSAMPLE_SMOOTH.
+ * EVERY OTHER call that takes mc_mandelbrot_params refuses the bit by name with MC_ERR_INVALID_ARGUMENT: the calls listed for
+ * MC_MANDEL_SUPERSAMPLE_SMOOTH above and mc_mandelbrot_resolve_smooth_device_async; mc_multi_* answer MC_ERR_UNSUPPORTED.
+ * It pays where the picture has interior or slowly varying exterior and costs where nearly every pixel is refined (the plain pass comes on
+ * top): see the use / do-not-use line of DESIGN.md section 3.28.
+ *
+ * mc_mandelbrot_render_adaptive_smooth: the same chain with the caller's tau.  p must carry the bit; at least one output must be given
+ * (out_rgba_f32: width * height vec4; out_rgba8: width * height RGBA8, the conversion of mc_mandelbrot_render_rgba8).
+ * mc_mandelbrot_refine_smooth (host only, no device): the rule on a caller's plane q of width * height smooth counts (values above
+ * 256 max_iter are clamped, as the kernel clamps them).  mask: width * height bytes of 0 / 1, or NULL; refined: the number of refined
+ * pixels, or NULL; not both NULL.  A zero size, max_iter = 0 or above 2^24 - 1, or a NULL q: MC_ERR_INVALID_ARGUMENT. */
+#define MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD 256u
+int mc_mandelbrot_render_adaptive_smooth(mc_context* ctx, const mc_mandelbrot_params* p, uint32_t threshold,
+                                         float* out_rgba_f32 /* or NULL */, uint8_t* out_rgba8 /* or NULL */);
+int mc_mandelbrot_refine_smooth(uint32_t width, uint32_t height, uint32_t max_iter, const uint32_t* q, uint32_t threshold,
+                                uint8_t* mask_or_NULL, uint64_t* refined_or_NULL);
 
 /* ---- zoom sequences (the project's own addition: the reference renders one still; what tests/mandel_zoom_ref.py
  *      restates).  A zoom renders one KEYFRAME per octave (the scale halves from one to the next, the centre stays) and composes every

@@ -30,6 +30,8 @@ MANDEL_COLOUR_DISTANCE = 128    # MC_MANDEL_COLOUR_DISTANCE: the smooth colour s
 ZOOM_FILTER_BILINEAR = 0   # MC_MANDEL_ZOOM_FILTER_BILINEAR: the filtered zoom calls return what their unfiltered namesakes return
 ZOOM_FILTER_AREA = 1       # MC_MANDEL_ZOOM_FILTER_AREA: a box over the pixel's footprint in the minified deep keyframe
 MANDEL_COLOUR_SMOOTH_EQUALISED = 4096   # MC_MANDEL_COLOUR_SMOOTH_EQUALISED: the smooth count ranked among a whole image's escaped pixels; set without MANDEL_COLOUR_SMOOTH
+MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE = 16384   # MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE: with MANDEL_SUPERSAMPLE(s) and one smooth colouring, only pixels whose smooth count is further than a threshold from a neighbour's get their s x s smooth samples
+MANDEL_ADAPTIVE_SMOOTH_THRESHOLD = 256   # MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD: the default threshold, one iteration in units of 1/256
 MANDEL_SUPERSAMPLE_SMOOTH = 8192   # MC_MANDEL_SUPERSAMPLE_SMOOTH: with MANDEL_SUPERSAMPLE(s) and one smooth colouring, the s x s samples are smooth counts
 MANDEL_COLOUR_EQUALISED = 16    # MC_MANDEL_COLOUR_EQUALISED: histogram-equalised colouring of a whole image (include/mc_compute.h)
 
@@ -242,6 +244,9 @@ def lib():
         if hasattr(L, "mc_mandelbrot_resolve_smooth"):   # MC_MANDEL_SUPERSAMPLE_SMOOTH
             L.mc_mandelbrot_resolve_smooth_device_async.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp, vp, vp]
             L.mc_mandelbrot_resolve_smooth.argtypes = [u32, C.POINTER(f32), u32, u32, u32, vp, vp, vp]
+        if hasattr(L, "mc_mandelbrot_refine_smooth"):   # MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE
+            L.mc_mandelbrot_render_adaptive_smooth.argtypes = [vp, C.POINTER(MandelbrotParams), u32, vp, vp]
+            L.mc_mandelbrot_refine_smooth.argtypes = [u32, u32, u32, vp, u32, vp, C.POINTER(C.c_uint64)]
         if hasattr(L, "mc_mandelbrot_zoom_compose"):   # zoom sequences
             dbl = C.c_double
             L.mc_mandelbrot_zoom_ratio.argtypes = [u32, u32, C.POINTER(dbl)]
@@ -421,14 +426,17 @@ def split_double(d):
 
 def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, centre=(-0.445, 0.0), scale=(2.34, 2.34),
                       k_color=(0.1, 0.7, 0.6, 0.0), row_begin=0, row_end=None, row_block=0, row_stride=0, flags=0, supersample=0,
-                      adaptive=False, smooth_samples=False):
+                      adaptive=False, smooth_samples=False, adaptive_smooth=False):
     """adaptive: MANDEL_SUPERSAMPLE_ADAPTIVE beside supersample= (only pixels whose count differs from a neighbour's are sampled s x s).
     smooth_samples: MANDEL_SUPERSAMPLE_SMOOTH beside supersample= and one of MANDEL_COLOUR_SMOOTH / MANDEL_COLOUR_SMOOTH_EQUALISED in
-    flags= (the samples are smooth counts, resolved over fractional counts)."""
+    flags= (the samples are smooth counts, resolved over fractional counts).
+    adaptive_smooth: MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE beside supersample= and one of the two smooth colourings in flags=, without the
+    other two (only pixels whose smooth count is further than a threshold from a neighbour's get their s x s smooth samples)."""
     p = MandelbrotParams()
     _check(lib().mc_mandelbrot_default_params(width, height, C.byref(p)), "mc_mandelbrot_default_params")
     p.max_iter, p.precision, p.flags = max_iter, precision, flags | MANDEL_SUPERSAMPLE(supersample) | (MANDEL_SUPERSAMPLE_ADAPTIVE if adaptive else 0)
     p.flags |= MANDEL_SUPERSAMPLE_SMOOTH if smooth_samples else 0
+    p.flags |= MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE if adaptive_smooth else 0
     p.centre_x_hi, p.centre_x_lo = split_double(centre[0])
     p.centre_y_hi, p.centre_y_lo = split_double(centre[1])
     p.scale_x_hi, p.scale_x_lo = split_double(scale[0])
@@ -443,7 +451,7 @@ def mandelbrot_params(width, height, max_iter=128, precision=PRECISION_F32, cent
 def supersample_params(p):
     """mc_mandelbrot_supersample_params (host only): the plain-render params of p's sample grid (s times the width, height and rows; the
     supersample bits, MANDEL_COLOUR_EQUALISED and MANDEL_SUPERSAMPLE_ADAPTIVE cleared; with MANDEL_SUPERSAMPLE_SMOOTH that bit cleared too and
-    the colouring MANDEL_COLOUR_SMOOTH: the params of the grid's smooth render)."""
+    the colouring MANDEL_COLOUR_SMOOTH: the params of the grid's smooth render; MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE likewise)."""
     q = MandelbrotParams()
     _check(lib().mc_mandelbrot_supersample_params(C.byref(p), C.byref(q)), "mc_mandelbrot_supersample_params")
     return q
@@ -621,6 +629,20 @@ def resolve_smooth(max_iter, s, q, qmap=None, k_color=(0.1, 0.7, 0.6, 0.0)):
     out = np.empty((rows, width, 4), np.float32)
     _check(lib().mc_mandelbrot_resolve_smooth(max_iter, k, s, width, rows, _ptr(qa), _ptr(m), _ptr(out)), "mc_mandelbrot_resolve_smooth")
     return out
+
+
+def refine_smooth(q, max_iter, threshold=MANDEL_ADAPTIVE_SMOOTH_THRESHOLD):
+    """mc_mandelbrot_refine_smooth (host only): the refine rule of MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE on the smooth plane q, uint32
+    (height, width).  Returns (mask bool (height, width), refined): a pixel is refined iff its count, clamped to 256 * max_iter, is further
+    than threshold (units of 1/256 iteration) from one of its up to eight neighbours'."""
+    qa = np.ascontiguousarray(q, np.uint32)
+    if qa.ndim != 2:
+        raise ValueError("refine_smooth: q is a (height, width) plane")
+    mask = np.empty(qa.shape, np.uint8)
+    n = C.c_uint64(0)
+    _check(lib().mc_mandelbrot_refine_smooth(qa.shape[1], qa.shape[0], max_iter, _ptr(qa), threshold, _ptr(mask), C.byref(n)),
+           "mc_mandelbrot_refine_smooth")
+    return mask.astype(bool), n.value
 
 
 def smooth_count(n, max_iter, zx, zy, cx, cy):
@@ -1359,6 +1381,15 @@ class Context:
         """mc_mandelbrot_render_smooth_device_async: the device form of mandelbrot_smooth (d_smooth: a uint32 plane)."""
         _check(lib().mc_mandelbrot_render_smooth_device_async(self._h, C.byref(p), d_rgba or None, d_iters or None, d_smooth or None,
                                                               stream or None), "mc_mandelbrot_render_smooth_device_async")
+
+    def mandelbrot_adaptive_smooth(self, p, threshold=MANDEL_ADAPTIVE_SMOOTH_THRESHOLD, rgba8=False):
+        """mc_mandelbrot_render_adaptive_smooth (p carries MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE, a whole image): the adaptive smooth image
+        with the caller's threshold, float32 (height, width, 4) or, with rgba8=True, uint8 (height, width, 4).  Context.last_refined()
+        reports the refined share."""
+        out = np.empty((p.height, p.width, 4), np.uint8 if rgba8 else np.float32)
+        _check(lib().mc_mandelbrot_render_adaptive_smooth(self._h, C.byref(p), threshold, None if rgba8 else _ptr(out),
+                                                          _ptr(out) if rgba8 else None), "mc_mandelbrot_render_adaptive_smooth")
+        return out
 
     def mandelbrot_rgba8(self, p):
         """mc_mandelbrot_render_rgba8: the rows [row_begin, row_end) rendered and converted on the device; only RGBA8 leaves the GPU."""

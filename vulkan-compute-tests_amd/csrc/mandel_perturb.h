@@ -7,12 +7,15 @@
 
 namespace mc {
 
+struct SmoothSampleList;   // mandel_adaptive_smooth.h: the smooth list render (null everywhere below: not that render)
+
 // launch_impl (mandelbrot.hip) hands precision 3 over after its common checks: orbit / view / max_iter checks, the colour and dc tables,
 // the launch.  warm = the cold-start warm-up's one-tile launch (mc_context_warmup_mandelbrot).
 // list: the list render of mandel_adaptive.h (p is the sample grid), or nullptr.
 // d_smooth: the q plane of MC_MANDEL_COLOUR_SMOOTH, or nullptr; the flag in p selects the smooth instantiation of whichever kernel runs.
+// slist: the smooth list render of mandel_adaptive_smooth.h (p is the sample grid and carries MC_MANDEL_COLOUR_SMOOTH; list is null).
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                   const SampleList* list = nullptr, void* d_smooth = nullptr);
+                   const SampleList* list = nullptr, void* d_smooth = nullptr, const SmoothSampleList* slist = nullptr);
 // What the four launchers below take for MC_MANDEL_COLOUR_SMOOTH: on = the smooth instantiation (no list), q = its plane (may be null).
 struct SmoothOut {
     bool on = false;
@@ -31,7 +34,8 @@ struct PerturbDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E
     uint32_t has_zero;               // some Z_j = 0 exactly, 1 <= j < L (centres such as 0 and -1)
 };
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {},
+                        const SmoothSampleList* slist = nullptr);
 
 // The per-lane audit of the fast block (mandel_block_audit.h; mc_hook_mandel_block_audit and mc_hook_mandel_perturb_block_audit of
 // libmc_compute_test.so).  d_out: four uint32_t per pixel / lane (n, accepted blocks, raised blocks, first bad block).
@@ -51,7 +55,8 @@ struct PerturbBlaArgs {
     const double* bla;               // the BLA table (null when it has no entry: L < 3)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS: write the loop-trip count in place of n
 };
-int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {},
+                       const SmoothSampleList* slist = nullptr);
 
 // MC_PRECISION_PERTURB_BLA_DEEP (mandel_perturb_bla_deep.hip): the rescaled loop of the deep kernel with bilinear skips, for every orbit.
 // The table (mc_mandelbrot_orbit_bla_deep) has precision 4's level layout; each entry is one BlaDeepRec (mandel_orbit.h).
@@ -61,7 +66,8 @@ struct PerturbBlaDeepArgs {
     int32_t exp2;                    // E: the pixel's offset is u * 2^E (0 for an orbit of the old scale)
     uint32_t count_trips;            // MC_MANDEL_BLA_COUNT_TRIPS
 };
-int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {});
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {},
+                            const SmoothSampleList* slist = nullptr);
 
 // mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): orbit_create's iteration loop (mandel_orbit.h) on the context's device.
 // A launch runs at most orbit_launch_iters(k) = kOrbitLaunchWork / (k + 1)^2 iterations, clamped to [1, 65536].  3.2e7 gives 1864

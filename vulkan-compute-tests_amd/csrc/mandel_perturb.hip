@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "mandel_adaptive_smooth.h"
 #include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
@@ -181,6 +182,21 @@ __global__ void __launch_bounds__(64) mandel_perturb_block_audit_kernel(PerturbA
     block_audit<StatePerturb, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
 }
 
+// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid).
+// (After every existing kernel, which keep their listings.)
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_list_smooth_kernel(PerturbArgs a, SmoothSampleList l) {
+    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const SampleLane ln = sample_lane(l.l);
+    StatePerturb st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    EscapeCapture cap;
+    const uint32_t n = escape_time<StatePerturb, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
+    double cx, cy;
+    st.escape_c(cx, cy);
+    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, cap.zx, cap.zy, cx, cy), a.t.max_iter);
+}
+
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
 // by (W, H, precision, the bind generation): the params' view words are all zero for this precision.
 int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Binding& b, hipStream_t s) {
@@ -203,11 +219,14 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
     return MC_OK;
 }
 
+// (defined after the audit launcher: the smooth list kernel is instantiated after every existing kernel, whose listings stay as they were)
+void perturb_list_smooth_dispatch(const PerturbArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
+
 }  // namespace
 
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                   const SampleList* list, void* d_smooth) {
-    const SmoothOut smooth = {(p->flags & MC_MANDEL_COLOUR_SMOOTH) != 0u && !list, (uint32_t*)d_smooth};
+                   const SampleList* list, void* d_smooth, const SmoothSampleList* slist) {
+    const SmoothOut smooth = {(p->flags & MC_MANDEL_COLOUR_SMOOTH) != 0u && !list && !slist, (uint32_t*)d_smooth};
     const bool bla = p->precision == MC_PRECISION_PERTURB_BLA;
     const bool bla_deep = p->precision == MC_PRECISION_PERTURB_BLA_DEEP;
     const std::string name = bla ? "MC_PRECISION_PERTURB_BLA" : bla_deep ? "MC_PRECISION_PERTURB_BLA_DEEP" : "MC_PRECISION_PERTURB";
@@ -230,8 +249,10 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     MandelTarget t;
     dim3 grid, block(64);
     SampleList l{};
-    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, list, &t, &grid, &l)) return rc;   // mandel_target.h
+    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, slist ? &slist->l : list, &t, &grid, &l)) return rc;   // mandel_target.h
     if (list) list = &l;
+    const SmoothSampleList sl = {l, slist ? slist->pairs : nullptr};
+    if (slist) slist = &sl;
     if (bla && b->deep) {
         set_error_detail(name + ": the bound orbit is deep (min |scale| < 2^-960); BLA covers the plain loop only");
         return MC_ERR_UNSUPPORTED;
@@ -256,22 +277,23 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
     if (bla) {   // mandel_perturb_bla.hip
         const PerturbBlaArgs d = {t, b->bla_entries ? (const double*)b->bla.ptr : nullptr,
                                   (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_launch(d, grid, s, list, smooth))) return rc;
+        if ((rc = perturb_bla_launch(d, grid, s, list, smooth, slist))) return rc;
         return ctx->note_launch(s);
     }
     if (bla_deep) {   // mandel_perturb_bla_deep.hip
         const PerturbBlaDeepArgs d = {t, b->bla_deep_entries ? (const BlaDeepRec*)b->bla_deep.ptr : nullptr, b->scale_exp2,
                                       (p->flags & MC_MANDEL_BLA_COUNT_TRIPS) ? 1u : 0u};
-        if ((rc = perturb_bla_deep_launch(d, grid, s, list, smooth))) return rc;
+        if ((rc = perturb_bla_deep_launch(d, grid, s, list, smooth, slist))) return rc;
         return ctx->note_launch(s);
     }
     if (b->deep || (p->flags & MC_MANDEL_PERTURB_FORCE_DEEP)) {   // below 2^-960 (or forced by a test): mandel_perturb_deep.hip
         const PerturbDeepArgs d = {t, b->scale_exp2, b->has_zero ? 1u : 0u};
-        if ((rc = perturb_deep_launch(d, grid, s, list, smooth))) return rc;
+        if ((rc = perturb_deep_launch(d, grid, s, list, smooth, slist))) return rc;
         return ctx->note_launch(s);
     }
     const PerturbArgs a = {t};
-    if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
+    if (slist) perturb_list_smooth_dispatch(a, sl, grid, s);
+    else if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
     else if (list) hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
     else hipLaunchKernelGGL((mandel_perturb_smooth_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, smooth.q);
     MC_HIP_TRY(hipGetLastError());
@@ -295,6 +317,12 @@ int perturb_block_audit_launch(const double2* d_orbit, uint32_t L, bool deep, in
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }
+
+namespace {
+void perturb_list_smooth_dispatch(const PerturbArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((mandel_perturb_list_smooth_kernel<StatePerturb::kBlock>), grid, dim3(64), 0, s, a, sl);
+}
+}  // namespace
 
 void perturb_release(mc_context* ctx) {
     g_bindings.erase(ctx, [](Binding& b) {

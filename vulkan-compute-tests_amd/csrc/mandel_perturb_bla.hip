@@ -11,6 +11,7 @@
 //    the other, so the restatement's per-pixel loop is exactly what each lane computes.  Before any rebase and while every lane takes
 //    the same level, a wave shares m and every table read is wave-uniform (one cache line per probe).
 //  * IEEE double in source order (-ffp-contract=off), fp64 denormals kept.
+#include "mandel_adaptive_smooth.h"
 #include "mandel_perturb.h"
 #include "mandel_smooth.h"
 #include "mc_internal.h"
@@ -54,12 +55,27 @@ __global__ void __launch_bounds__(64) mandel_perturb_bla_smooth_kernel(PerturbBl
     const double2 c1 = Z[1];
     smooth_tile_store(a.t, ln, out_smooth, n, a.count_trips ? trips : n, ezx, ezy, c1.x + dcx, c1.y + dcy);
 }
+
+// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid);
+// q is of n, as the smooth plane's is.  (After every existing kernel, which keep their listings.)
+__global__ void __launch_bounds__(64) mandel_perturb_bla_list_smooth_kernel(PerturbBlaArgs a, SmoothSampleList l) {
+    const SampleLane ln = sample_lane(l.l);
+    const uint32_t gx = ln.gx, gy = ln.gy;
+    const bool valid = ln.valid;
+    double ezx = 0.0, ezy = 0.0;
+#include "mandel_perturb_bla_loop.h"
+    (void)trips;
+    const double2 c1 = Z[1];
+    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, ezx, ezy, c1.x + dcx, c1.y + dcy), a.t.max_iter);
+}
 #undef MC_BLA_ON_ESCAPE
 
 }  // namespace
 
-int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
-    if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
+int perturb_bla_launch(const PerturbBlaArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth,
+                       const SmoothSampleList* slist) {
+    if (slist) hipLaunchKernelGGL(mandel_perturb_bla_list_smooth_kernel, grid, dim3(64), 0, s, a, *slist);
+    else if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
     else if (!list) hipLaunchKernelGGL(mandel_perturb_bla_kernel, grid, dim3(64), 0, s, a);
     else hipLaunchKernelGGL(mandel_perturb_bla_list_kernel, grid, dim3(64), 0, s, a, *list);
     MC_HIP_TRY(hipGetLastError());

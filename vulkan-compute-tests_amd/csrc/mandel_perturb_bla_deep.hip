@@ -11,6 +11,7 @@
 //    exponent (delta' = 0: w = 0, S = E, as at the start).
 //  * a table entry is one 64-byte record (5 mantissas, 3 exponents), so a probe is one record read.
 //  * IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
+#include "mandel_adaptive_smooth.h"
 #include "mandel_perturb.h"
 #include "mandel_smooth.h"
 #include "mc_internal.h"
@@ -62,12 +63,27 @@ __global__ void __launch_bounds__(64) mandel_perturb_bla_deep_smooth_kernel(Pert
     const double2 c1 = Z[1];
     smooth_tile_store(a.t, ln, out_smooth, n, a.count_trips ? trips : n, ezx, ezy, c1.x + ldexp2(ux, E), c1.y + ldexp2(uy, E));
 }
+
+// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid);
+// q is of n, as the smooth plane's is.  (After every existing kernel, which keep their listings.)
+__global__ void __launch_bounds__(64) mandel_perturb_bla_deep_list_smooth_kernel(PerturbBlaDeepArgs a, SmoothSampleList l) {
+    const SampleLane ln = sample_lane(l.l);
+    const uint32_t gx = ln.gx, gy = ln.gy;
+    const bool valid = ln.valid;
+    double ezx = 0.0, ezy = 0.0;
+#include "mandel_perturb_bla_deep_loop.h"
+    (void)trips;
+    const double2 c1 = Z[1];
+    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, ezx, ezy, c1.x + ldexp2(ux, E), c1.y + ldexp2(uy, E)), a.t.max_iter);
+}
 #undef MC_BLA_ON_ESCAPE
 
 }  // namespace
 
-int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
-    if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_deep_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
+int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth,
+                            const SmoothSampleList* slist) {
+    if (slist) hipLaunchKernelGGL(mandel_perturb_bla_deep_list_smooth_kernel, grid, dim3(64), 0, s, a, *slist);
+    else if (smooth.on) hipLaunchKernelGGL(mandel_perturb_bla_deep_smooth_kernel, grid, dim3(64), 0, s, a, smooth.q);
     else if (!list) hipLaunchKernelGGL(mandel_perturb_bla_deep_kernel, grid, dim3(64), 0, s, a);
     else hipLaunchKernelGGL(mandel_perturb_bla_deep_list_kernel, grid, dim3(64), 0, s, a, *list);
     MC_HIP_TRY(hipGetLastError());

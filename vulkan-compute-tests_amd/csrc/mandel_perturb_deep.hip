@@ -11,6 +11,7 @@
 // IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
 #include "mandel_block_audit.h"
 #include "mandel_escape.h"
+#include "mandel_adaptive_smooth.h"
 #include "mandel_perturb.h"
 #include "mandel_smooth.h"
 #include "mc_internal.h"
@@ -222,10 +223,30 @@ __global__ void __launch_bounds__(64) mandel_perturb_deep_block_audit_kernel(Per
     block_audit<StateDeep, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
 }
 
+// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid).
+// (After every existing kernel, which keep their listings.)
+template <int U>
+__global__ void __launch_bounds__(64) mandel_perturb_deep_list_smooth_kernel(PerturbDeepArgs a, SmoothSampleList l) {
+    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
+    const SampleLane ln = sample_lane(l.l);
+    StateDeep st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    EscapeCapture cap;
+    const uint32_t n = escape_time<StateDeep, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
+    double cx, cy;
+    st.escape_c(cx, cy);
+    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, cap.zx, cap.zy, cx, cy), a.t.max_iter);
+}
+
+// (defined after the audit launcher: the smooth list kernel is instantiated after every existing kernel, whose listings stay as they were)
+void perturb_deep_list_smooth_dispatch(const PerturbDeepArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
+
 }  // namespace
 
-int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth) {
-    if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
+int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth,
+                        const SmoothSampleList* slist) {
+    if (slist) perturb_deep_list_smooth_dispatch(a, *slist, grid, s);
+    else if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
     else if (list) hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
     else hipLaunchKernelGGL((mandel_perturb_deep_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, smooth.q);
     MC_HIP_TRY(hipGetLastError());
@@ -239,5 +260,11 @@ int perturb_deep_block_audit_launch(const PerturbDeepArgs& a, dim3 grid, bool sa
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }
+
+namespace {
+void perturb_deep_list_smooth_dispatch(const PerturbDeepArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((mandel_perturb_deep_list_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, sl);
+}
+}  // namespace
 
 }  // namespace mc

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "mandel_adaptive.h"
+#include "mandel_adaptive_smooth_host.h"
 #include "mandel_equalise.h"
 #include "mandel_side_record.h"
 
@@ -71,6 +72,14 @@ void plain_params(const mc_mandelbrot_params* p, uint32_t iters_bytes, mc_mandel
 }
 
 }  // namespace
+
+// What mc_context_last_refined reports: either adaptive chain's last successful render (mandel_refine_smooth.hip calls this too).
+void adaptive_report(mc_context* ctx, uint64_t refined, uint64_t pixels) {
+    AdaptiveState* st = g_ad_states.get(ctx);
+    st->refined = refined;
+    st->pixels = pixels;
+    st->reported = true;
+}
 
 void adaptive_release(mc_context* ctx) {
     g_ad_states.erase(ctx, [](AdaptiveState& st) {
@@ -175,9 +184,7 @@ int mandelbrot_adaptive_launch(mc_context* ctx, const mc_mandelbrot_params* p, h
                               (float4*)ctx->scratch_rgba.ptr};
         if ((rc = mandelbrot_list_launch(ctx, &grid, l, s, false))) return rc;
     }
-    st->refined = count;
-    st->pixels = npix;
-    st->reported = true;
+    adaptive_report(ctx, count, npix);
     return MC_OK;
 }
 

@@ -165,6 +165,11 @@ int mandelbrot_supersample_params(const mc_mandelbrot_params* p, mc_mandelbrot_p
             out.flags = (out.flags & ~(uint32_t)MC_MANDEL_COLOUR_SMOOTH_EQUALISED) | (uint32_t)MC_MANDEL_COLOUR_SMOOTH;
         out.flags &= ~(uint32_t)MC_MANDEL_SUPERSAMPLE_SMOOTH;
     }
+    if (out.flags & MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE) {   // likewise: the list render's samples are the grid's smooth counts (mandel_refine_smooth.hip)
+        if (out.flags & MC_MANDEL_COLOUR_SMOOTH_EQUALISED)
+            out.flags = (out.flags & ~(uint32_t)MC_MANDEL_COLOUR_SMOOTH_EQUALISED) | (uint32_t)MC_MANDEL_COLOUR_SMOOTH;
+        out.flags &= ~(uint32_t)MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE;
+    }
     *q = out;
     return MC_OK;
 }

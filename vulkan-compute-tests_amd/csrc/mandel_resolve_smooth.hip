@@ -162,6 +162,7 @@ void resolve_smooth_launch(uint32_t f, const void* d_smooth, const void* pairs, 
 int mandelbrot_resolve_smooth_launch(mc_context* ctx, const mc_mandelbrot_params* p, const void* d_smooth, const uint32_t* qmap, void* d_rgba,
                                      const char* who, hipStream_t s) {
     if (!ctx || !p || !d_smooth || !d_rgba || !p->max_iter || !rows_ok(p)) return MC_ERR_INVALID_ARGUMENT;
+    if (int rc = adaptive_smooth_refuse_flag(p, who)) return rc;   // (this stage resolves a FULL sample plane)
     if (!smooth_samples_flag(p)) {
         set_error_detail(std::string(who) + ": the params must carry MC_MANDEL_SUPERSAMPLE_SMOOTH");
         return MC_ERR_INVALID_ARGUMENT;

@@ -3,6 +3,7 @@
 #pragma once
 #include <string>
 
+#include "mandel_adaptive_smooth_host.h"
 #include "mandel_smooth_equalise_host.h"
 
 namespace mc {
@@ -15,8 +16,10 @@ int mandelbrot_resolve_smooth_launch(mc_context* ctx, const mc_mandelbrot_params
 
 inline bool smooth_samples_flag(const mc_mandelbrot_params* p) { return p && (p->flags & MC_MANDEL_SUPERSAMPLE_SMOOTH) != 0u; }
 
-// From every call that does not honour the bit:
+// From every call that does not honour the bit.  The same calls do not honour MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE either, and refuse it
+// here by its own name (mandel_adaptive_smooth_host.h).
 inline int smooth_samples_refuse_flag(const mc_mandelbrot_params* p, const char* who) {
+    if (int rc = adaptive_smooth_refuse_flag(p, who)) return rc;
     if (!smooth_samples_flag(p)) return MC_OK;
     set_error_detail(std::string(who) + ": MC_MANDEL_SUPERSAMPLE_SMOOTH (supersampling resolved over smooth counts) is honoured by "
                      "mc_mandelbrot_render, mc_mandelbrot_render_rgba8 and mc_mandelbrot_resolve_smooth_device_async; by hand: "

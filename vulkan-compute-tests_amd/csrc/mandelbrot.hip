@@ -26,6 +26,7 @@
 
 #include "ds_arith.h"
 #include "mandel_adaptive.h"
+#include "mandel_adaptive_smooth.h"
 #include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
@@ -252,6 +253,21 @@ __global__ void __launch_bounds__(64) mandelbrot_block_audit_kernel(MandelArgs a
     block_audit<State, U, Sabotage>(st, a.max_iter, out + 4u * ((size_t)ln.ty * a.W + ln.gx));
 }
 
+// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping.  A lane is one
+// smooth sample of a refined pixel; its q never leaves the kernel, the pixel's colour is resolved between the lanes.  (After every
+// existing kernel, which keep their listings.)
+template <class State, int U>
+__global__ void __launch_bounds__(64) mandelbrot_list_smooth_kernel(MandelArgs a, SmoothSampleList l) {
+    const SampleLane ln = sample_lane(l.l);
+    State st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    double cx, cy;
+    st.escape_c(cx, cy);
+    EscapeCapture cap;
+    const uint32_t n = escape_time<State, U, EscapeCapture>(st, a.max_iter, ln.valid, &cap);
+    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.max_iter, cap.zx, cap.zy, cx, cy), a.max_iter);
+}
+
 }  // namespace
 
 // colour(n) = d + e*cos(6.28318*(f*t+g)), t = n/M — mandelbrot.comp:50-56, evaluated in fp32 in source
@@ -345,12 +361,17 @@ int mandelbrot_lut_device(mc_context* ctx, const mc_mandelbrot_params* p, hipStr
 // tile is run for at most 32 iterations into d_iters — enough for the runtime to load this code object and create the kernel.
 // list = the list render of mandel_adaptive.h (p is the sample grid, d_rgba the image the list's pixels are written to, d_iters unused).
 // d_smooth: the q plane of MC_MANDEL_COLOUR_SMOOTH (null: not wanted); the flag selects the smooth instantiation of every tile kernel.
+// slist = the smooth list render of mandel_adaptive_smooth.h (p is the sample grid and carries MC_MANDEL_COLOUR_SMOOTH; list is null).
+// (defined last in this file: the smooth list kernels are instantiated after every existing kernel, whose listings stay as they were)
+static void list_smooth_dispatch(uint32_t precision, const MandelArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
+
 static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
-                       const SampleList* list = nullptr, void* d_smooth = nullptr) {
+                       const SampleList* list = nullptr, void* d_smooth = nullptr, const SmoothSampleList* slist = nullptr) {
     if (!ctx || !p || (!d_rgba && !d_iters && !d_smooth)) return MC_ERR_INVALID_ARGUMENT;
     const bool smooth = (p->flags & MC_MANDEL_COLOUR_SMOOTH) != 0u;
     if (d_smooth && !smooth) return MC_ERR_INVALID_ARGUMENT;
-    if (smooth && list) return MC_ERR_INVALID_ARGUMENT;   // (the list kernels have no smooth instantiation: the entry points refuse the pair)
+    if (smooth && list) return MC_ERR_INVALID_ARGUMENT;   // (the integer list kernels colour counts: the entry points refuse the pair)
+    if (slist && (!smooth || list || d_smooth || (p->flags & MC_MANDEL_FMA))) return MC_ERR_INVALID_ARGUMENT;
     if (int rc = smooth_refuse_combination(p, "MC_MANDEL_COLOUR_SMOOTH")) return rc;
     if (!p->width || !p->height || !p->max_iter || p->row_end > p->height || p->row_begin >= p->row_end)
         return MC_ERR_INVALID_ARGUMENT;
@@ -361,7 +382,7 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     if (p->row_stride && (!p->row_block || p->row_block > p->row_stride)) return MC_ERR_INVALID_ARGUMENT;
     if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
         p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
-        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm, list, d_smooth);   // mandel_perturb.hip
+        return perturb_launch(ctx, p, d_rgba, d_iters, s, warm, list, d_smooth, slist);   // mandel_perturb.hip
     if (d_rgba || warm) {
         int rc = ensure_lut(ctx, p, s);
         if (rc) return rc;
@@ -373,12 +394,14 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
     MandelArgs a;
     dim3 grid, block(64);
     SampleList l{};
-    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, list, &a, &grid, &l)) return rc;   // mandel_target.h
+    if (int rc = launch_geometry(p, d_rgba, d_iters, warm, slist ? &slist->l : list, &a, &grid, &l)) return rc;   // mandel_target.h
     a.c_tab = (const float*)ctx->ctab.ptr;
     a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
     a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
     a.lut = a.out_rgba ? (const float4*)ctx->lut.ptr : nullptr;
-    if (!list && !smooth) {
+    if (slist) {
+        list_smooth_dispatch(p->precision, a, {l, slist->pairs}, grid, s);
+    } else if (!list && !smooth) {
         if (p->precision == MC_PRECISION_DS) {
             hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
         } else if (p->precision == MC_PRECISION_F64) {
@@ -417,6 +440,12 @@ int mandelbrot_list_launch(mc_context* ctx, const mc_mandelbrot_params* grid, co
     return launch_impl(ctx, grid, l.out_rgba, nullptr, s, warm, &l);
 }
 
+int mandelbrot_list_smooth_launch(mc_context* ctx, const mc_mandelbrot_params* grid, const SmoothSampleList& sl, hipStream_t s, bool warm) {
+    const SampleList& l = sl.l;
+    if (!l.list || !l.count || !l.img_w || !l.table || !l.out_rgba || l.log2s < 1u || l.log2s > 3u) return MC_ERR_INVALID_ARGUMENT;
+    return launch_impl(ctx, grid, l.out_rgba, nullptr, s, warm, nullptr, nullptr, &sl);
+}
+
 int mandelbrot_warmup(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters_scratch, hipStream_t s) {
     return launch_impl(ctx, p, nullptr, d_iters_scratch, s, true);
 }
@@ -452,6 +481,13 @@ int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p
 #undef MC_AUDIT_LAUNCH
     MC_HIP_TRY(hipGetLastError());
     return ctx->note_launch(s);
+}
+
+static void list_smooth_dispatch(uint32_t precision, const MandelArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
+    const dim3 block(64);
+    if (precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateDS, 4>), grid, block, 0, s, a, sl);
+    else if (precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateF64, 8>), grid, block, 0, s, a, sl);
+    else hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateF32<false>, 8>), grid, block, 0, s, a, sl);
 }
 
 }  // namespace mc

@@ -228,6 +228,10 @@ static int multi_mandelbrot(mc_multi* m, const mc_mandelbrot_params* p, float* o
     if (p->precision == MC_PRECISION_PERTURB || p->precision == MC_PRECISION_PERTURB_BLA ||
         p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
         return MC_ERR_UNSUPPORTED;   // single-device only (include/mc_compute.h)
+    if (p->flags & MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE) {   // a device sees a tile, and a tile cannot see its neighbours' counts
+        set_error_detail("mc_multi_*: MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE is single-device only");
+        return MC_ERR_UNSUPPORTED;
+    }
     if (p->flags & MC_MANDEL_SUPERSAMPLE_SMOOTH) {   // the resolve over smooth counts runs on the device that holds the samples
         set_error_detail("mc_multi_*: MC_MANDEL_SUPERSAMPLE_SMOOTH is single-device only");
         return MC_ERR_UNSUPPORTED;

@@ -20,6 +20,7 @@
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cmath>
@@ -54,6 +55,8 @@ int main(int argc, char* argv[]) {
     uint32_t colour = 0;   // --colour reference | equalised (MC_MANDEL_COLOUR_EQUALISED) | smooth (MC_MANDEL_COLOUR_SMOOTH) | distance (MC_MANDEL_COLOUR_DISTANCE) | smooth-equalised (MC_MANDEL_COLOUR_SMOOTH_EQUALISED)
     uint32_t supersample = 1;   // --supersample 1 | 2 | 4 | 8 (MC_MANDEL_SUPERSAMPLE)
     bool adaptive = false;      // --adaptive (MC_MANDEL_SUPERSAMPLE_ADAPTIVE): valid with --supersample 2 | 4 | 8 only
+    bool adaptiveSmooth = false;      // --adaptive-smooth[=Q] (MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE): with --supersample 2 | 4 | 8 and --colour smooth | smooth-equalised
+    uint32_t adaptiveSmoothQ = MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD;   // Q: the threshold in units of 1/256 iteration
     bool supersampleSmooth = false;   // --supersample-smooth (MC_MANDEL_SUPERSAMPLE_SMOOTH): with --supersample 2 | 4 | 8 and --colour smooth | smooth-equalised
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
     uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
@@ -124,7 +127,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--help") {
             printf("options: --gpus N, --out FILE, --quiet, --gpu-postprocess, --png-threads T, --timing-json, --width W, --height H, --max-iter M,\n"
                    "  --centre X Y, --scale SX SY, --precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep,\n"
-                   "  --colour reference|equalised|smooth|distance|smooth-equalised, --supersample 1|2|4|8, --adaptive, --supersample-smooth,\n"
+                   "  --colour reference|equalised|smooth|distance|smooth-equalised, --supersample 1|2|4|8, --adaptive, --supersample-smooth, --adaptive-smooth[=Q],\n"
                    "  --orbit host|device|auto, --zoom K F, --zoom-keyframes colours|counts, --zoom-filter bilinear|area,\n"
                    "  --math strict|fast|careful, --denoise [P], --noise-guided [K], --budget [L], --noise-target T, --scene FILE, --accel linear|bvh,\n"
                    "  --buddhabrot SAMPLES  the orbit-density plane of SAMPLES pseudo-random c (the Mandelbrot app); --centre / --scale default to\n"
@@ -194,6 +197,24 @@ int main(int argc, char* argv[]) {
             printf("--adaptive: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
 #endif
+        }
+        else if (a == "--adaptive-smooth" || a.rfind("--adaptive-smooth=", 0) == 0) {   // smooth samples only where the smooth count moves by more than Q
+            adaptiveSmooth = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--adaptive-smooth: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+            if (a.size() > 17) {
+                const std::string v = a.substr(18);
+                char* end = nullptr;
+                errno = 0;
+                const unsigned long long q = strtoull(v.c_str(), &end, 10);
+                if (v.empty() || v[0] < '0' || v[0] > '9' || *end || errno || q > 0xffffffffull) {
+                    printf("--adaptive-smooth=Q: Q is a decimal number of 1/256 iterations, 0 .. 4294967295; got '%s'\n", v.c_str());
+                    exit(EXIT_FAILURE);
+                }
+                adaptiveSmoothQ = (uint32_t)q;
+            }
         }
         else if (a == "--supersample-smooth") {   // the samples are smooth counts: the resolve over fractional counts
             supersampleSmooth = true;
@@ -343,6 +364,18 @@ int main(int argc, char* argv[]) {
 #endif
     (void)maxIterSet; (void)centreSet; (void)scaleSet; (void)buddhaMinIter; (void)buddhaSeed; (void)buddhaWindowSet; (void)buddhaNebula; (void)buddhaEqualised; (void)buddhaWindow; (void)buddhaWhite; (void)buddhaNebulaIter;
     (void)guidedSet; (void)pilotSet; (void)dilateSet; (void)guidedLog2; (void)guidedPilot; (void)guidedDilate; (void)guidedUnbiased;
+    if (adaptiveSmooth) {   // (before the two options it does not combine with word their own refusals)
+        const char* why = adaptive            ? "not with --adaptive (that option compares integer counts; this one is given without it)"
+                          : supersampleSmooth ? "not with --supersample-smooth (that option is the full resolve; this one is given without it)"
+                          : supersample <= 1u ? "needs --supersample 2 | 4 | 8"
+                          : colour != MC_MANDEL_COLOUR_SMOOTH && colour != MC_MANDEL_COLOUR_SMOOTH_EQUALISED ? "needs --colour smooth | smooth-equalised"
+                          : gpus > 1          ? "one GPU (a device's tile cannot see its neighbours' counts)"
+                          : buddhaSet         ? "not with --buddhabrot"
+                          : zoomCounts        ? "not with --zoom-keyframes counts (a supersampled pixel has no single count; use --zoom-keyframes colours)"
+                          : zoomSet && adaptiveSmoothQ != MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD ? "with --zoom the threshold is the default 256 (keyframes render through mc_mandelbrot_zoom_push)"
+                                              : nullptr;
+        if (why) { printf("--adaptive-smooth: %s\n", why); exit(EXIT_FAILURE); }
+    }
     if (adaptive && supersample <= 1u) { printf("--adaptive: needs --supersample 2 | 4 | 8\n"); exit(EXIT_FAILURE); }
     if (supersampleSmooth) {
         const char* why = supersample <= 1u ? "needs --supersample 2 | 4 | 8"
@@ -387,7 +420,7 @@ int main(int argc, char* argv[]) {
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
     (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
-    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
+    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)adaptiveSmooth; (void)adaptiveSmoothQ; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
@@ -421,7 +454,7 @@ int main(int argc, char* argv[]) {
         streamedSave = ComputeApp::kStreamOff;
     }
     if (colour == MC_MANDEL_COLOUR_SMOOTH) {   // a per-pixel function: the normal banded, streamed save
-        if (supersample > 1u && !supersampleSmooth) {
+        if (supersample > 1u && !supersampleSmooth && !adaptiveSmooth) {
             printf("--colour smooth: does not combine with --supersample yet (a resolve over fractional counts) unless --supersample-smooth asks for it\n");
             return EXIT_FAILURE;
         }
@@ -432,7 +465,7 @@ int main(int argc, char* argv[]) {
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --colour distance renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     } else if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED) {   // the rank over the whole image's smooth plane: the whole-image calls, as equalised
-        if (supersample > 1u && !supersampleSmooth) {
+        if (supersample > 1u && !supersampleSmooth && !adaptiveSmooth) {
             printf("--colour smooth-equalised: does not combine with --supersample (a resolve over fractional counts) unless --supersample-smooth asks for it\n");
             return EXIT_FAILURE;
         }
@@ -448,6 +481,10 @@ int main(int argc, char* argv[]) {
         app.setSupersample(supersample);
         if (adaptive) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_ADAPTIVE);   // (whole-image calls as well: the save is never streamed)
         if (supersampleSmooth) app.setColourFlags(MC_MANDEL_SUPERSAMPLE_SMOOTH);
+        if (adaptiveSmooth) {
+            app.setColourFlags(MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE);
+            app.setAdaptiveSmoothThreshold(adaptiveSmoothQ);
+        }
         if (streamedSave == ComputeApp::kStreamOn) printf("note: --supersample renders the whole image in one call; --streamed-save has no effect\n");
         streamedSave = ComputeApp::kStreamOff;
     }
@@ -605,8 +642,9 @@ int main(int argc, char* argv[]) {
         app.run();
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
+        if (adaptiveSmooth) app.printRefinedSmooth();   // "refined R of P pixels (threshold Q)"
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
-        if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1 && !supersampleSmooth) app.printSmoothEqualisedStats();
+        if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1 && !supersampleSmooth && !adaptiveSmooth) app.printSmoothEqualisedStats();
 #endif
 #if defined(PATHTRACER_MODE)
         if (budgetSet) app.printBudget();

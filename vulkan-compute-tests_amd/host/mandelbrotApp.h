@@ -29,6 +29,8 @@ struct MandelbrotApp : public ComputeApp {
         split(sy, params.scale_y_hi, params.scale_y_lo);
     }
     void setColourFlags(uint32_t flags) { params.flags |= flags; }   // MC_MANDEL_COLOUR_EQUALISED, _SMOOTH, _DISTANCE, _SMOOTH_EQUALISED (main.cpp --colour)
+    // --adaptive-smooth[=Q]: run() renders through mc_mandelbrot_render_adaptive_smooth with this threshold
+    void setAdaptiveSmoothThreshold(uint32_t q) { adaptiveSmoothQ = q; }
     void setSupersample(uint32_t s) { params.flags |= MC_MANDEL_SUPERSAMPLE(s); }   // 2, 4 or 8 (main.cpp --supersample)
     void setPrecision(uint32_t precision) { params.precision = precision; }   // MC_PRECISION_F32 / _DS / _F64 (setView packs the same words)
     // MC_PRECISION_PERTURB / _BLA / _BLA_DEEP: the view is this orbit's (the app owns it; for the BLA precisions main() has built the
@@ -108,6 +110,11 @@ struct MandelbrotApp : public ComputeApp {
     virtual void runCommandBuffer() override {
         if (buddha.samples) { runBuddhabrot(); return; }
         if (streaming()) { runStreamed(); return; }
+        if (!multi && (params.flags & MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE)) {   // the caller's threshold: the call that takes one
+            check(mc_mandelbrot_render_adaptive_smooth(ctx, &params, adaptiveSmoothQ, gpuPostprocess ? nullptr : buffer.data(),
+                                                       gpuPostprocess ? rgba8.bytes() : nullptr), "mc_mandelbrot_render_adaptive_smooth");
+            return;
+        }
         if (gpuPostprocess) {   // render + float->u8 on the device: 4 B/pixel cross PCIe instead of 16
             if (multi) check(mc_multi_mandelbrot_render_rgba8(multi, &params, rgba8.bytes()), "mc_multi_mandelbrot_render_rgba8");
             else check(mc_mandelbrot_render_rgba8(ctx, &params, rgba8.bytes()), "mc_mandelbrot_render_rgba8");
@@ -216,6 +223,13 @@ struct MandelbrotApp : public ComputeApp {
         uint64_t refined = 0, pixels = 0;
         check(mc_context_last_refined(ctx, &refined, &pixels), "mc_context_last_refined");
         printf("refined %llu of %llu pixels\n", (unsigned long long)refined, (unsigned long long)pixels);
+    }
+
+    // --adaptive-smooth: the same report with the threshold the render used
+    void printRefinedSmooth() {
+        uint64_t refined = 0, pixels = 0;
+        check(mc_context_last_refined(ctx, &refined, &pixels), "mc_context_last_refined");
+        printf("refined %llu of %llu pixels (threshold %u)\n", (unsigned long long)refined, (unsigned long long)pixels, adaptiveSmoothQ);
     }
 
     // --colour distance: the share of pixels whose distance estimate is below one pixel, the ones the shading darkens.  D came with the
@@ -365,6 +379,7 @@ private:
     std::function<std::string(mc_context*)> orbitFactory;
     uint32_t zoomK = 0, zoomF = 0;   // --zoom K F; 0: a still
     bool zoomCounts = false;         // --zoom-keyframes counts
+    uint32_t adaptiveSmoothQ = MC_MANDEL_ADAPTIVE_SMOOTH_THRESHOLD;   // --adaptive-smooth[=Q]
     uint32_t zoomFilter = MC_MANDEL_ZOOM_FILTER_BILINEAR;   // --zoom-filter
     double zoomCx = 0.0, zoomCy = 0.0, zoomSx = 0.0, zoomSy = 0.0;
     std::function<std::string(mc_context*, int)> zoomOrbit;
