@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import mandel_adaptive_ref as A
+import mandel_block_audit_cases as K
 import mandel_equalise_ref as E
+import mandel_perturb_ref as R
 import mandel_supersample_ref as S
 from test_gpu_mandel_supersample import ZERO, bits, bound_view, run_app, same, sample_plane, six_views, upload
 
@@ -133,6 +135,42 @@ def test_equalised_whole_image(ctx, B, which):
             # and it is not the fully supersampled equalised image's map (that one's histogram is of all samples)
             not_eq, _ = ctx.mandelbrot(B.mandelbrot_params(W, H, supersample=s, adaptive=True, **kw), want_iters=False)
             assert not np.array_equal(bits(not_eq), bits(rgba))
+
+
+# ---- the two engines of the list mapping that the six views do not reach (DESIGN.md §3.29's table) ---------------------------------
+# 24 x 20 pixels: partial tiles on both axes; s = 2 and s = 8: sixteen pixels per wave and one pixel per wave.
+@pytest.mark.parametrize("s", [2, 8])
+def test_list_render_of_the_contracted_fp32_loop(ctx, B, s):
+    """MC_MANDEL_FMA (StateF32<true>): the sample grid's plane by the tile kernel against the contracted loop restated on the host, the
+    adaptive image by the list kernel against the restatement over that plane."""
+    W, H, M = 24, 20, 256
+    p = B.mandelbrot_params(W, H, max_iter=M, supersample=s, adaptive=True, flags=B.MANDEL_FMA)
+    q, plane = sample_plane(ctx, B, p)
+    assert q.flags & B.MANDEL_FMA
+    assert np.array_equal(plane, K.fma_iters(s * W, s * H, M, (-0.445, 0.0), (2.34, 2.34)))
+    want, mask = A.image(plane, s, M, B.colour_lut(M))
+    assert 0 < mask.sum() < W * H
+    rgba, _ = ctx.mandelbrot(p, want_iters=False)
+    same(rgba, want, s)
+    assert ctx.last_refined() == (int(mask.sum()), W * H)
+
+
+@pytest.mark.parametrize("s", [2, 8])
+def test_list_render_by_the_forced_deep_kernel(ctx, B, s):
+    """MC_PRECISION_PERTURB under MC_MANDEL_PERTURB_FORCE_DEEP (StateDeep) on a short shallow orbit: the sample grid's plane by the tile
+    kernel against PERTURB's loop restated on the host, the adaptive image by the list kernel against the restatement over that plane."""
+    W, H, M = 24, 20, 200
+    kw = dict(max_iter=M, precision=B.PRECISION_PERTURB, flags=B.MANDEL_PERTURB_FORCE_DEEP, **ZERO)
+    with bound_view(B, ctx, kw, lambda: B.Orbit("-0.75", "0.1", 0.75, 0.5, M)) as v:
+        p = B.mandelbrot_params(W, H, supersample=s, adaptive=True, **kw)
+        q, plane = sample_plane(ctx, B, p)
+        assert q.flags & B.MANDEL_PERTURB_FORCE_DEEP
+        assert np.array_equal(plane, R.plane(v.o.table(), v.o.length, s * W, s * H, M, v.o.scale))
+        want, mask = A.image(plane, s, M, B.colour_lut(M))
+        assert 0 < mask.sum() < W * H
+        rgba, _ = ctx.mandelbrot(p, want_iters=False)
+        same(rgba, want, s)
+        assert ctx.last_refined() == (int(mask.sum()), W * H)
 
 
 def test_all_interior_view_launches_nothing(ctx, B):

@@ -11,7 +11,7 @@
 namespace mc {
 
 // MC_PRECISION_PERTURB_BLA_DEEP: one entry of the table of mc_mandelbrot_orbit_bla_deep, mantissas and exponents together in one 64-byte
-// record, so that a probe reads a single record.  The kernel reads this layout (mandel_perturb_bla_deep_loop.h).
+// record, so that a probe reads a single record.  The kernel reads this layout (mandel_perturb_bla_deep.hip).
 struct BlaDeepRec {
     double ax, ay, bx, by, r;        // the mantissas: A = (ax, ay) * 2^ea, B = (bx, by) * 2^eb, R = r * 2^er
     int32_t ea, eb, er, pad[3];

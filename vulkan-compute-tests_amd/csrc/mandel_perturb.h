@@ -16,7 +16,8 @@ struct SmoothSampleList;   // mandel_adaptive_smooth.h: the smooth list render (
 // slist: the smooth list render of mandel_adaptive_smooth.h (p is the sample grid and carries MC_MANDEL_COLOUR_SMOOTH; list is null).
 int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
                    const SampleList* list = nullptr, void* d_smooth = nullptr, const SmoothSampleList* slist = nullptr);
-// What the four launchers below take for MC_MANDEL_COLOUR_SMOOTH: on = the smooth instantiation (no list), q = its plane (may be null).
+// What the launchers below and launch_mapping (mandel_kernels.h) take for MC_MANDEL_COLOUR_SMOOTH: on = the smooth tile mapping (no
+// list), q = its plane (may be null).
 struct SmoothOut {
     bool on = false;
     uint32_t* q = nullptr;
@@ -39,8 +40,9 @@ int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, cons
 
 // The per-lane audit of the fast block (mandel_block_audit.h; mc_hook_mandel_block_audit and mc_hook_mandel_perturb_block_audit of
 // libmc_compute_test.so).  d_out: four uint32_t per pixel / lane (n, accepted blocks, raised blocks, first bad block).
-// mandelbrot.hip: F32 (MC_MANDEL_FMA honoured), DS, F64 on p's whole image or contiguous rows.  mandel_perturb.hip: StatePerturb, or
-// (deep) StateDeep with E = exp2, on a device orbit table of L + 1 entries and d_table = [ux[n_lanes] | uy[n_lanes]].
+// mandelbrot.hip: F32 (MC_MANDEL_FMA honoured), DS, F64 on p's whole image or contiguous rows (mandelbrot_block_audit_kernel of
+// mandel_kernels.h).  mandel_perturb.hip: StatePerturb, or (deep) StateDeep with E = exp2, on a device orbit table of L + 1 entries and
+// d_table = [ux[n_lanes] | uy[n_lanes]] (mandelbrot_lane_audit_kernel).
 int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p, bool sabotage, uint32_t* d_out, hipStream_t s);
 int perturb_block_audit_launch(const double2* d_orbit, uint32_t L, bool deep, int32_t exp2, bool has_zero, const double* d_table,
                                uint32_t n_lanes, uint32_t max_iter, bool sabotage, uint32_t* d_out, hipStream_t s);

@@ -11,12 +11,9 @@
 #include <string>
 #include <vector>
 
-#include "mandel_adaptive_smooth.h"
-#include "mandel_block_audit.h"
-#include "mandel_escape.h"
+#include "mandel_kernels.h"
 #include "mandel_perturb.h"
 #include "mandel_side_record.h"
-#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -53,7 +50,9 @@ struct PerturbArgs {
 // One pixel's offset from the reference orbit (the loop of include/mc_compute.h, MC_PRECISION_PERTURB).  Per iteration 20 fp64 ops
 // (2 + 2 for a, 4 + 4 for the new offset, 2 for z, 3 for |z|^2, 3 for |d|^2) against F64's 8.
 struct StatePerturb {
+    using Args = PerturbArgs;
     static constexpr int kBlock = 8;        // the escape-time block length U: the fast block prefetches this many orbit entries
+    static constexpr bool kEscapeCBeforeLoop = false;   // c needs a load of Z_1: the smooth kernels form it after the loop
     const double2* __restrict__ Z;
     uint32_t L;
     double dcx, dcy, dx, dy, zmx, zmy;      // zm = Z[m]
@@ -137,66 +136,6 @@ struct StatePerturb {
     }
 };
 
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_kernel(PerturbArgs a) {
-    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const TileLane ln = tile_lane(a.t);
-    StatePerturb st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    tile_store(a.t, ln, escape_time<StatePerturb, U>(st, a.t.max_iter, ln.valid));
-}
-
-// The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_list_kernel(PerturbArgs a, SampleList l) {
-    const SampleLane ln = sample_lane(l);
-    StatePerturb st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    const uint32_t n = escape_time<StatePerturb, U>(st, a.t.max_iter, ln.valid);
-    sample_resolve(l, ln, n, a.t.max_iter);
-}
-
-// MC_MANDEL_COLOUR_SMOOTH: the escape z latched in the exact steps, then the shared epilogue (mandel_smooth.h).
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_smooth_kernel(PerturbArgs a, uint32_t* __restrict__ out_smooth) {
-    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const TileLane ln = tile_lane(a.t);
-    StatePerturb st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    EscapeCapture cap;
-    const uint32_t n = escape_time<StatePerturb, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
-    double cx, cy;
-    st.escape_c(cx, cy);
-    smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
-}
-
-// The per-lane audit of the fast block (mandel_block_audit.h) over a caller's lanes: lane k reads table[k] and table[W + k] (W = the
-// number of lanes), one thread per lane and nothing shared between them.  (After the kernels above, which keep their listings.)
-template <int U, bool Sabotage>
-__global__ void __launch_bounds__(64) mandel_perturb_block_audit_kernel(PerturbArgs a, uint32_t* __restrict__ out) {
-    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
-    if (k >= a.t.W) return;
-    StatePerturb st;
-    st.init(k, k, a);
-    block_audit<StatePerturb, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
-}
-
-// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid).
-// (After every existing kernel, which keep their listings.)
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_list_smooth_kernel(PerturbArgs a, SmoothSampleList l) {
-    static_assert(U == StatePerturb::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const SampleLane ln = sample_lane(l.l);
-    StatePerturb st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    EscapeCapture cap;
-    const uint32_t n = escape_time<StatePerturb, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
-    double cx, cy;
-    st.escape_c(cx, cy);
-    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, cap.zx, cap.zy, cx, cy), a.t.max_iter);
-}
-
 // dcx[g] = ((double)g / (double)W - 0.5) * sx, dcy likewise: F64's c table without the centre.  In the context's c-table slot, keyed
 // by (W, H, precision, the bind generation): the params' view words are all zero for this precision.
 int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Binding& b, hipStream_t s) {
@@ -218,9 +157,6 @@ int ensure_dc_table(mc_context* ctx, const mc_mandelbrot_params* p, const Bindin
     ctx->ctab_key = key;
     return MC_OK;
 }
-
-// (defined after the audit launcher: the smooth list kernel is instantiated after every existing kernel, whose listings stay as they were)
-void perturb_list_smooth_dispatch(const PerturbArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
 
 }  // namespace
 
@@ -247,7 +183,7 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         return MC_ERR_INVALID_ARGUMENT;
     }
     MandelTarget t;
-    dim3 grid, block(64);
+    dim3 grid;
     SampleList l{};
     if (int rc = launch_geometry(p, d_rgba, d_iters, warm, slist ? &slist->l : list, &t, &grid, &l)) return rc;   // mandel_target.h
     if (list) list = &l;
@@ -292,11 +228,7 @@ int perturb_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba,
         return ctx->note_launch(s);
     }
     const PerturbArgs a = {t};
-    if (slist) perturb_list_smooth_dispatch(a, sl, grid, s);
-    else if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_kernel<StatePerturb::kBlock>), grid, block, 0, s, a);
-    else if (list) hipLaunchKernelGGL((mandel_perturb_list_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, l);
-    else hipLaunchKernelGGL((mandel_perturb_smooth_kernel<StatePerturb::kBlock>), grid, block, 0, s, a, smooth.q);
-    MC_HIP_TRY(hipGetLastError());
+    if ((rc = launch_state<StatePerturb>(a, grid, s, list, smooth, slist))) return rc;
     return ctx->note_launch(s);
 }
 
@@ -311,18 +243,8 @@ int perturb_block_audit_launch(const double2* d_orbit, uint32_t L, bool deep, in
     t.orbit = d_orbit;
     const dim3 grid((n_lanes + 63u) / 64u);
     if (deep) return perturb_deep_block_audit_launch({t, exp2, has_zero ? 1u : 0u}, grid, sabotage, d_out, s);   // mandel_perturb_deep.hip
-    const PerturbArgs a = {t};
-    if (sabotage) hipLaunchKernelGGL((mandel_perturb_block_audit_kernel<StatePerturb::kBlock, true>), grid, dim3(64), 0, s, a, d_out);
-    else hipLaunchKernelGGL((mandel_perturb_block_audit_kernel<StatePerturb::kBlock, false>), grid, dim3(64), 0, s, a, d_out);
-    MC_HIP_TRY(hipGetLastError());
-    return MC_OK;
+    return launch_block_audit<StatePerturb, true>({t}, grid, s, sabotage, d_out);
 }
-
-namespace {
-void perturb_list_smooth_dispatch(const PerturbArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((mandel_perturb_list_smooth_kernel<StatePerturb::kBlock>), grid, dim3(64), 0, s, a, sl);
-}
-}  // namespace
 
 void perturb_release(mc_context* ctx) {
     g_bindings.erase(ctx, [](Binding& b) {

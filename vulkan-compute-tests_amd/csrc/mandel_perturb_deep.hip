@@ -9,11 +9,8 @@
 // The fast block runs U = 8 steps of the general formula with S fixed and the block's orbit entries fetched at its start; a lane that
 // would renormalise, change phase, rebase, meet a Z = 0 step or escape raises needs_exact, and the block is replayed by step().
 // IEEE double in source order (-ffp-contract=off), fp64 denormals kept; ldexp = v_ldexp_f64, the exponent = v_frexp_exp_i32_f64.
-#include "mandel_block_audit.h"
-#include "mandel_escape.h"
-#include "mandel_adaptive_smooth.h"
+#include "mandel_kernels.h"
 #include "mandel_perturb.h"
-#include "mandel_smooth.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -30,7 +27,9 @@ __device__ __forceinline__ int frexp_exp(double x) { return __builtin_amdgcn_fre
 __device__ __forceinline__ uint32_t hi_word(double x) { return (uint32_t)((uint64_t)__double_as_longlong(x) >> 32); }
 
 struct StateDeep {
-    static constexpr int kBlock = 8;
+    using Args = PerturbDeepArgs;
+    static constexpr int kBlock = 8;        // the escape-time block length U: the fast block prefetches this many orbit entries
+    static constexpr bool kEscapeCBeforeLoop = false;   // as StatePerturb: c needs a load of Z_1
     const double2* __restrict__ Z;
     uint32_t L;
     int32_t E;
@@ -178,93 +177,15 @@ struct StateDeep {
     }
 };
 
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_deep_kernel(PerturbDeepArgs a) {
-    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const TileLane ln = tile_lane(a.t);
-    StateDeep st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    tile_store(a.t, ln, escape_time<StateDeep, U>(st, a.t.max_iter, ln.valid));
-}
-
-// The same state under the list mapping of mandel_adaptive.h (a: the sample grid).
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_deep_list_kernel(PerturbDeepArgs a, SampleList l) {
-    const SampleLane ln = sample_lane(l);
-    StateDeep st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    const uint32_t n = escape_time<StateDeep, U>(st, a.t.max_iter, ln.valid);
-    sample_resolve(l, ln, n, a.t.max_iter);
-}
-
-// MC_MANDEL_COLOUR_SMOOTH: the escape z latched in the exact steps, then the shared epilogue (mandel_smooth.h).
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_deep_smooth_kernel(PerturbDeepArgs a, uint32_t* __restrict__ out_smooth) {
-    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const TileLane ln = tile_lane(a.t);
-    StateDeep st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    EscapeCapture cap;
-    const uint32_t n = escape_time<StateDeep, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
-    double cx, cy;
-    st.escape_c(cx, cy);
-    smooth_tile_store(a.t, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
-}
-
-// The per-lane audit of the fast block (mandel_block_audit.h) over a caller's lanes: lane k reads table[k] and table[W + k] (W = the
-// number of lanes).  (After the kernels above, which keep their listings.)
-template <int U, bool Sabotage>
-__global__ void __launch_bounds__(64) mandel_perturb_deep_block_audit_kernel(PerturbDeepArgs a, uint32_t* __restrict__ out) {
-    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
-    if (k >= a.t.W) return;
-    StateDeep st;
-    st.init(k, k, a);
-    block_audit<StateDeep, U, Sabotage>(st, a.t.max_iter, out + 4u * (size_t)k);
-}
-
-// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping (a: the sample grid).
-// (After every existing kernel, which keep their listings.)
-template <int U>
-__global__ void __launch_bounds__(64) mandel_perturb_deep_list_smooth_kernel(PerturbDeepArgs a, SmoothSampleList l) {
-    static_assert(U == StateDeep::kBlock, "the fast block prefetches exactly one block of orbit entries");
-    const SampleLane ln = sample_lane(l.l);
-    StateDeep st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    EscapeCapture cap;
-    const uint32_t n = escape_time<StateDeep, U, EscapeCapture>(st, a.t.max_iter, ln.valid, &cap);
-    double cx, cy;
-    st.escape_c(cx, cy);
-    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.t.max_iter, cap.zx, cap.zy, cx, cy), a.t.max_iter);
-}
-
-// (defined after the audit launcher: the smooth list kernel is instantiated after every existing kernel, whose listings stay as they were)
-void perturb_deep_list_smooth_dispatch(const PerturbDeepArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
-
 }  // namespace
 
 int perturb_deep_launch(const PerturbDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list, SmoothOut smooth,
                         const SmoothSampleList* slist) {
-    if (slist) perturb_deep_list_smooth_dispatch(a, *slist, grid, s);
-    else if (!list && !smooth.on) hipLaunchKernelGGL((mandel_perturb_deep_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a);
-    else if (list) hipLaunchKernelGGL((mandel_perturb_deep_list_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, *list);
-    else hipLaunchKernelGGL((mandel_perturb_deep_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, smooth.q);
-    MC_HIP_TRY(hipGetLastError());
-    return MC_OK;
+    return launch_state<StateDeep>(a, grid, s, list, smooth, slist);
 }
 
-// (after perturb_deep_launch: the audit kernels are instantiated last, so the kernels above keep their place in the listing)
 int perturb_deep_block_audit_launch(const PerturbDeepArgs& a, dim3 grid, bool sabotage, uint32_t* d_out, hipStream_t s) {
-    if (sabotage) hipLaunchKernelGGL((mandel_perturb_deep_block_audit_kernel<StateDeep::kBlock, true>), grid, dim3(64), 0, s, a, d_out);
-    else hipLaunchKernelGGL((mandel_perturb_deep_block_audit_kernel<StateDeep::kBlock, false>), grid, dim3(64), 0, s, a, d_out);
-    MC_HIP_TRY(hipGetLastError());
-    return MC_OK;
+    return launch_block_audit<StateDeep, true>(a, grid, s, sabotage, d_out);
 }
-
-namespace {
-void perturb_deep_list_smooth_dispatch(const PerturbDeepArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((mandel_perturb_deep_list_smooth_kernel<StateDeep::kBlock>), grid, dim3(64), 0, s, a, sl);
-}
-}  // namespace
 
 }  // namespace mc

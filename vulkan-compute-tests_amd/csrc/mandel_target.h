@@ -1,5 +1,6 @@
-// What the Mandelbrot tile kernels share (mandelbrot.hip and the four mandel_perturb*.hip): the target block of their arguments, the 8x8
-// tile mapping, the store epilogue, and the launch geometry their two host launchers (launch_impl, perturb_launch) compute from a request.
+// What the Mandelbrot render kernels address (the mapping templates of mandel_kernels.h and the two BLA kernels): the target block of their
+// arguments, the 8x8 tile mapping, the store epilogue, and the launch geometry the two host launchers (launch_impl of mandelbrot.hip,
+// perturb_launch of mandel_perturb.hip) compute from a request.
 #pragma once
 #include "mandel_adaptive.h"
 #include "mc_internal.h"
@@ -7,7 +8,8 @@
 namespace mc {
 
 // The first member of every perturbation kernel's argument struct: the image, the tile's rows, the outputs and the two tables every
-// one of them reads.  (MandelArgs of mandelbrot.hip keeps its own layout; the helpers below take either.)
+// one of them reads.  (MandelArgs of mandelbrot.hip keeps its own layout; the helpers below take either, and target_of of
+// mandel_kernels.h names the one a kernel's arguments hold.)
 struct MandelTarget {
     uint32_t W, H, max_iter, L;      // L: the orbit's length
     uint32_t row_begin, row_end, row_block, row_stride;

@@ -25,14 +25,8 @@
 #include <cstring>
 
 #include "ds_arith.h"
-#include "mandel_adaptive.h"
-#include "mandel_adaptive_smooth.h"
-#include "mandel_block_audit.h"
-#include "mandel_escape.h"
-#include "mandel_perturb.h"
-#include "mandel_smooth.h"
+#include "mandel_kernels.h"
 #include "mandel_smooth_host.h"
-#include "mandel_target.h"
 #include "mc_internal.h"
 
 namespace mc {
@@ -54,10 +48,15 @@ struct MandelArgs {
     // Replaces two IEEE divisions (~50 instructions) per pixel; exterior tiles only run a handful of iterations.
     const float* __restrict__ c_tab;
 };
+// MandelArgs keeps its own layout: it is its own target block (mandel_kernels.h)
+__host__ __device__ __forceinline__ const MandelArgs& target_of(const MandelArgs& a) { return a; }
 
 // ---- per-pixel state machines: step() advances one iteration and reports "escaped now" ----------
 template <bool FMA>
 struct StateF32 {
+    using Args = MandelArgs;
+    static constexpr int kBlock = 8;                   // the escape-time block length U
+    static constexpr bool kEscapeCBeforeLoop = true;   // c sits in registers: the smooth kernels convert it before the loop
     float cx, cy, zx, zy, sx, sy;   // sx = zx*zx, sy = zy*zy of the current z
     __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const MandelArgs& a) {
         cx = a.c_tab[gx];                          // mandelbrot.comp:30,38 (host-evaluated, see build_c_table)
@@ -102,6 +101,9 @@ struct StateF32 {
 };
 
 struct StateDS {
+    using Args = MandelArgs;
+    static constexpr int kBlock = 4;                   // the escape-time block length U
+    static constexpr bool kEscapeCBeforeLoop = true;   // c sits in registers: the smooth kernels convert it before the loop
     ds2 cx, cy, zx, zy, sx, sy;
     __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const MandelArgs& a) {
         const float2* tab = reinterpret_cast<const float2*>(a.c_tab);
@@ -172,6 +174,9 @@ struct StateDS {
 // stay enabled (the gfx9 default; the kernel descriptor's FLOAT_DENORM_MODE_16_64 is 3), so orbits that pass near 0
 // round as IEEE does.
 struct StateF64 {
+    using Args = MandelArgs;
+    static constexpr int kBlock = 8;                   // the escape-time block length U
+    static constexpr bool kEscapeCBeforeLoop = true;   // c sits in registers: the smooth kernels convert it before the loop
     double cx, cy, zx, zy, sx, sy;   // sx = zx*zx, sy = zy*zy of the current z
     __device__ __forceinline__ void init(uint32_t gx, uint32_t gy, const MandelArgs& a) {
         const double* tab = reinterpret_cast<const double*>(a.c_tab);
@@ -205,68 +210,6 @@ struct StateF64 {
                same_bits(sy, o.sy);
     }
 };
-
-template <class State, int U>
-__global__ void __launch_bounds__(64) mandelbrot_kernel(MandelArgs a) {
-    // workgroup = one wave = one 8x8 pixel tile, lane = (lx, ly) inside the tile.  Tiles finish anywhere between 1 and
-    // max_iter iterations apart, so the unit the hardware schedules is the tile itself: a 4-wave block would keep its
-    // place on the CU until its slowest tile is through (K1: 0.208 -> 0.200 ms).
-    const TileLane ln = tile_lane(a);
-    State st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    tile_store(a, ln, escape_time<State, U>(st, a.max_iter, ln.valid));
-}
-
-// The same per-lane state under the list mapping of mandel_adaptive.h: `a` describes the sample grid, a lane is one sample of a refined
-// pixel, and the pixel's colour is resolved between the lanes (no count leaves the kernel).
-template <class State, int U>
-__global__ void __launch_bounds__(64) mandelbrot_list_kernel(MandelArgs a, SampleList l) {
-    const SampleLane ln = sample_lane(l);
-    State st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    const uint32_t n = escape_time<State, U>(st, a.max_iter, ln.valid);
-    sample_resolve(l, ln, n, a.max_iter);
-}
-
-// MC_MANDEL_COLOUR_SMOOTH (mandel_smooth.h): the same loop with the z of each lane's first escape latched, then the shared epilogue —
-// c as the state read it from the table, the fp64 continuation to radius 256, q and the interpolated colour.
-template <class State, int U>
-__global__ void __launch_bounds__(64) mandelbrot_smooth_kernel(MandelArgs a, uint32_t* __restrict__ out_smooth) {
-    const TileLane ln = tile_lane(a);
-    State st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    double cx, cy;
-    st.escape_c(cx, cy);   // (before the loop: the state's c never changes, and the loop's registers are free again after it)
-    EscapeCapture cap;
-    const uint32_t n = escape_time<State, U, EscapeCapture>(st, a.max_iter, ln.valid, &cap);
-    smooth_tile_store(a, ln, out_smooth, n, n, cap.zx, cap.zy, cx, cy);
-}
-
-// The per-lane audit of the fast block (mandel_block_audit.h): the tile mapping of mandelbrot_kernel, one thread per pixel and nothing
-// shared between them; four words per pixel, tile-local.  (Last: the kernels above keep their listings.)
-template <class State, int U, bool Sabotage>
-__global__ void __launch_bounds__(64) mandelbrot_block_audit_kernel(MandelArgs a, uint32_t* __restrict__ out) {
-    const TileLane ln = tile_lane(a);
-    if (!ln.valid) return;
-    State st;
-    st.init(ln.gx, ln.gy, a);
-    block_audit<State, U, Sabotage>(st, a.max_iter, out + 4u * ((size_t)ln.ty * a.W + ln.gx));
-}
-
-// MC_MANDEL_SUPERSAMPLE_SMOOTH_ADAPTIVE (mandel_adaptive_smooth.h): the smooth kernel's lane under the list mapping.  A lane is one
-// smooth sample of a refined pixel; its q never leaves the kernel, the pixel's colour is resolved between the lanes.  (After every
-// existing kernel, which keep their listings.)
-template <class State, int U>
-__global__ void __launch_bounds__(64) mandelbrot_list_smooth_kernel(MandelArgs a, SmoothSampleList l) {
-    const SampleLane ln = sample_lane(l.l);
-    State st;
-    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
-    double cx, cy;
-    st.escape_c(cx, cy);
-    EscapeCapture cap;
-    const uint32_t n = escape_time<State, U, EscapeCapture>(st, a.max_iter, ln.valid, &cap);
-    smooth_sample_resolve(l, ln, smooth::smooth_count(n, a.max_iter, cap.zx, cap.zy, cx, cy), a.max_iter);
-}
 
 }  // namespace
 
@@ -357,14 +300,27 @@ int mandelbrot_lut_device(mc_context* ctx, const mc_mandelbrot_params* p, hipStr
     return MC_OK;
 }
 
+// The state of a request: (precision, MC_MANDEL_FMA) chosen in this one place, for the render and for the audit.  f is called with a
+// StateTag of the state; smooth says whether the state has the smooth kernels (StateF32<true> has none: MC_MANDEL_FMA with
+// MC_MANDEL_COLOUR_SMOOTH is refused before any launch).
+template <class State, bool Smooth = true>
+struct StateTag {
+    using type = State;
+    static constexpr bool smooth = Smooth;
+};
+template <class F>
+static int with_state(const mc_mandelbrot_params* p, F&& f) {
+    if (p->precision == MC_PRECISION_DS) return f(StateTag<StateDS>{});
+    if (p->precision == MC_PRECISION_F64) return f(StateTag<StateF64>{});
+    if (p->flags & MC_MANDEL_FMA) return f(StateTag<StateF32<true>, false>{});
+    return f(StateTag<StateF32<false>>{});
+}
+
 // warm = the cold-start warm-up (mc_context_warmup_mandelbrot): the tables of the REAL request are built and uploaded, then ONE 8 x 8
 // tile is run for at most 32 iterations into d_iters — enough for the runtime to load this code object and create the kernel.
 // list = the list render of mandel_adaptive.h (p is the sample grid, d_rgba the image the list's pixels are written to, d_iters unused).
 // d_smooth: the q plane of MC_MANDEL_COLOUR_SMOOTH (null: not wanted); the flag selects the smooth instantiation of every tile kernel.
 // slist = the smooth list render of mandel_adaptive_smooth.h (p is the sample grid and carries MC_MANDEL_COLOUR_SMOOTH; list is null).
-// (defined last in this file: the smooth list kernels are instantiated after every existing kernel, whose listings stay as they were)
-static void list_smooth_dispatch(uint32_t precision, const MandelArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s);
-
 static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_rgba, void* d_iters, hipStream_t s, bool warm,
                        const SampleList* list = nullptr, void* d_smooth = nullptr, const SmoothSampleList* slist = nullptr) {
     if (!ctx || !p || (!d_rgba && !d_iters && !d_smooth)) return MC_ERR_INVALID_ARGUMENT;
@@ -392,37 +348,19 @@ static int launch_impl(mc_context* ctx, const mc_mandelbrot_params* p, void* d_r
         if (rc) return rc;
     }
     MandelArgs a;
-    dim3 grid, block(64);
+    dim3 grid;
     SampleList l{};
     if (int rc = launch_geometry(p, d_rgba, d_iters, warm, slist ? &slist->l : list, &a, &grid, &l)) return rc;   // mandel_target.h
     a.c_tab = (const float*)ctx->ctab.ptr;
     a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
     a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
     a.lut = a.out_rgba ? (const float4*)ctx->lut.ptr : nullptr;
-    if (slist) {
-        list_smooth_dispatch(p->precision, a, {l, slist->pairs}, grid, s);
-    } else if (!list && !smooth) {
-        if (p->precision == MC_PRECISION_DS) {
-            hipLaunchKernelGGL((mandelbrot_kernel<StateDS, 4>), grid, block, 0, s, a);
-        } else if (p->precision == MC_PRECISION_F64) {
-            hipLaunchKernelGGL((mandelbrot_kernel<StateF64, 8>), grid, block, 0, s, a);
-        } else if (p->flags & MC_MANDEL_FMA) {
-            hipLaunchKernelGGL((mandelbrot_kernel<StateF32<true>, 8>), grid, block, 0, s, a);
-        } else {
-            hipLaunchKernelGGL((mandelbrot_kernel<StateF32<false>, 8>), grid, block, 0, s, a);
-        }
-    } else if (list) {
-        if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_kernel<StateDS, 4>), grid, block, 0, s, a, l);
-        else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF64, 8>), grid, block, 0, s, a, l);
-        else if (p->flags & MC_MANDEL_FMA) hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<true>, 8>), grid, block, 0, s, a, l);
-        else hipLaunchKernelGGL((mandelbrot_list_kernel<StateF32<false>, 8>), grid, block, 0, s, a, l);
-    } else {   // (last: the smooth kernels are instantiated after the existing ones, whose listings stay as they were)
-        uint32_t* q = (uint32_t*)d_smooth;
-        if (p->precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateDS, 4>), grid, block, 0, s, a, q);
-        else if (p->precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateF64, 8>), grid, block, 0, s, a, q);
-        else hipLaunchKernelGGL((mandelbrot_smooth_kernel<StateF32<false>, 8>), grid, block, 0, s, a, q);
-    }
-    MC_HIP_TRY(hipGetLastError());
+    const SmoothSampleList sl = {l, slist ? slist->pairs : nullptr};
+    const int rc = with_state(p, [&](auto tag) {
+        using Tag = decltype(tag);
+        return launch_state<typename Tag::type, Tag::smooth>(a, grid, s, list ? &l : nullptr, {smooth, (uint32_t*)d_smooth}, slist ? &sl : nullptr);
+    });
+    if (rc) return rc;
     return ctx->note_launch(s);
 }
 
@@ -468,26 +406,9 @@ int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p
     a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
     a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
     a.lut = nullptr;
-    const dim3 block(64);
-#define MC_AUDIT_LAUNCH(State, U)                                                                                      \
-    do {                                                                                                               \
-        if (sabotage) hipLaunchKernelGGL((mandelbrot_block_audit_kernel<State, U, true>), grid, block, 0, s, a, d_out); \
-        else hipLaunchKernelGGL((mandelbrot_block_audit_kernel<State, U, false>), grid, block, 0, s, a, d_out);         \
-    } while (0)
-    if (p->precision == MC_PRECISION_DS) MC_AUDIT_LAUNCH(StateDS, 4);
-    else if (p->precision == MC_PRECISION_F64) MC_AUDIT_LAUNCH(StateF64, 8);
-    else if (fma) MC_AUDIT_LAUNCH(StateF32<true>, 8);
-    else MC_AUDIT_LAUNCH(StateF32<false>, 8);
-#undef MC_AUDIT_LAUNCH
-    MC_HIP_TRY(hipGetLastError());
+    const int rc = with_state(p, [&](auto tag) { return launch_block_audit<typename decltype(tag)::type, false>(a, grid, s, sabotage, d_out); });
+    if (rc) return rc;
     return ctx->note_launch(s);
-}
-
-static void list_smooth_dispatch(uint32_t precision, const MandelArgs& a, const SmoothSampleList& sl, dim3 grid, hipStream_t s) {
-    const dim3 block(64);
-    if (precision == MC_PRECISION_DS) hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateDS, 4>), grid, block, 0, s, a, sl);
-    else if (precision == MC_PRECISION_F64) hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateF64, 8>), grid, block, 0, s, a, sl);
-    else hipLaunchKernelGGL((mandelbrot_list_smooth_kernel<StateF32<false>, 8>), grid, block, 0, s, a, sl);
 }
 
 }  // namespace mc
