@@ -52,7 +52,8 @@ extern "C" {
  * mc_buddhabrot_params and mc_buddhabrot_stats with mc_buddhabrot_default_params, _density, _density_device_async, _render, _sqrt_map,
  * _tonemap and _tonemap_device_async; then its importance map and guided sampling: mc_buddhabrot_guide_params and _guide_info with
  * mc_buddhabrot_importance, _importance_device_async, _importance_cells, _density_guided, _density_guided_device_async,
- * _guide_default_params and _render_guided.
+ * _guide_default_params and _render_guided; then dives: mc_mandelbrot_orbit_rescale, and BLA tables built on the device with
+ * mc_context_bind_mandelbrot_orbit_tables, mc_context_last_table_timing, mc_context_bound_bla_copy and mc_context_bound_bla_deep_copy.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -234,6 +235,24 @@ int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o);
 int mc_mandelbrot_orbit_info(const mc_mandelbrot_orbit* o, uint32_t* length, uint32_t* max_iter, uint32_t* bits);
 int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z /* (length+1)*2: re, im */);
 int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o);   /* NULL unbinds */
+/* mc_mandelbrot_orbit_rescale: a new orbit object that carries o's table Z_0 .. Z_L, length, max_iter and bits unchanged under another
+ * scale of the same centre, (scale_x * 2^scale_exp2, scale_y * 2^scale_exp2): what a dive needs, whose keyframes share one centre, so
+ * that the orbit is computed once, for the deepest keyframe.  Host only.  The scale fields of the new object (the doubles, or the
+ * mantissas with their exponent, and whether it is deep) are the ones mc_mandelbrot_orbit_create_deep stores for that scale, the folding
+ * into plain doubles when min |scale| >= 2^-960 included.  It carries no BLA table; o is untouched and may be destroyed afterwards.
+ *  - refusals of the scale are mc_mandelbrot_orbit_create_deep's, with the same status and the same text after the function's name:
+ *    mantissas finite and nonzero (MC_ERR_INVALID_ARGUMENT), min |scale| < 2^-8192 and a plain scale above the double range
+ *    (MC_ERR_UNSUPPORTED).  NULL o or out: MC_ERR_INVALID_ARGUMENT.
+ *  - one more, MC_ERR_UNSUPPORTED: the bits formula above applied to the new scale gives more than o's bits: o was computed for a
+ *    shallower view and has too few bits for this one.  (So a deep object never comes from a plain one: the formula steps at 2^-960.)
+ *  - accuracy: the table is the source's.  The fixed point is carried in whole 64-bit limbs, ceil(bits / 64) of them, so whenever both
+ *    scales need the same number of limbs the table is bit for bit the one a fresh constructor makes for the new scale.  Across limb
+ *    counts it is the table of the deeper, more precise orbit: each entry is the exact orbit's value rounded after a smaller
+ *    accumulated error, and individual doubles may differ from the fresh constructor's in the last place (and L may differ where
+ *    |Z_j|^2 sits within that error of 2).  Every kernel's contract is stated over the bound table, so renders stay exact
+ *    restatements of it either way. */
+int mc_mandelbrot_orbit_rescale(const mc_mandelbrot_orbit* o, double scale_x, double scale_y, int32_t scale_exp2,
+                                mc_mandelbrot_orbit** out);
 
 /* MC_PRECISION_PERTURB_BLA (4): MC_PRECISION_PERTURB with bilinear approximation (BLA): one step stands in for 2^k iterations while the
  * offset is small enough for the linear terms to dominate (what tests/mandel_bla_ref.py restates).
@@ -323,6 +342,34 @@ int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out /* en
 #define MC_PRECISION_PERTURB_BLA_DEEP 5u
 int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries);
 int mc_mandelbrot_orbit_bla_deep_copy(const mc_mandelbrot_orbit* o, double* mant /* entries * 5 */, int32_t* exps /* entries * 3 */);
+/* BLA tables built on the device.
+ * mc_context_bind_mandelbrot_orbit_tables is mc_context_bind_mandelbrot_orbit (drain the context's launch streams, upload Z, set the
+ * binding, synchronise before returning) plus one thing: each table named in device_tables is computed on the context's device, from
+ * the Z just uploaded and the orbit's scale, straight into the binding.  No host table is read, made, or stored in o.  A table not
+ * named behaves as in the plain bind: uploaded if o holds it, released otherwise; device_tables = 0 IS the plain bind.
+ * MC_ORBIT_TABLE_BLA on a deep orbit is MC_ERR_UNSUPPORTED (mc_mandelbrot_orbit_bla's text), unknown bits are
+ * MC_ERR_INVALID_ARGUMENT, and every refusal comes before the current binding is touched.  L < 3 binds "a table with no entry", as
+ * the host builders make it.
+ *  - contract: the tables are the ones mc_mandelbrot_orbit_bla / mc_mandelbrot_orbit_bla_deep build from the same object, every field
+ *    the same bits (one text of the arithmetic, compiled for both sides), with one exception: where the host's value is a NaN the
+ *    device's is a NaN too, of any sign and payload (the two processors generate different default NaNs; PERTURB_BLA's table does
+ *    produce inf - inf in A or B at high levels of a bounded orbit).  Such an entry has R = 0, the kernels never read A or B of an entry
+ *    whose R is 0, so renders are bit-identical regardless.  R is never a NaN.
+ *  - the build: one lane per entry; a workgroup carries 1024 adjacent entries of a level up through the ten levels above them with a
+ *    block barrier between levels, so a launch builds eleven levels and every level of at most 1024 entries, with all above it, runs in
+ *    a single workgroup.  No atomics.
+ * mc_context_last_table_timing: the last such bind of the context that named a table: device_ms = first build launch to the end of the
+ * last (HIP events), and the number of launches (0 and 0.0 for a table with no entry).  Either pointer may be NULL;
+ * MC_ERR_INVALID_ARGUMENT before the first such bind.
+ * mc_context_bound_bla_copy / mc_context_bound_bla_deep_copy read the context's bound tables back in exactly the layout of
+ * mc_mandelbrot_orbit_bla_copy / mc_mandelbrot_orbit_bla_deep_copy, wherever the tables came from; *levels / *entries receive the
+ * shape.  Any output pointer may be NULL (all NULL: query the shape).  MC_ERR_INVALID_ARGUMENT when nothing of that kind is bound. */
+enum { MC_ORBIT_TABLE_BLA = 1u << 0, MC_ORBIT_TABLE_BLA_DEEP = 1u << 1 };
+int mc_context_bind_mandelbrot_orbit_tables(mc_context* ctx, const mc_mandelbrot_orbit* o, uint32_t device_tables);
+int mc_context_last_table_timing(mc_context* ctx, double* device_ms, uint32_t* launches);
+int mc_context_bound_bla_copy(mc_context* ctx, double* out /* entries * 5 */, uint32_t* levels, uint64_t* entries);
+int mc_context_bound_bla_deep_copy(mc_context* ctx, double* mant /* entries * 5 */, int32_t* exps /* entries * 3 */, uint32_t* levels,
+                                   uint64_t* entries);
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1,/* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */

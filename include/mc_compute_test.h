@@ -94,6 +94,11 @@ int mc_hook_mandel_perturb_block_audit(mc_context* ctx, const double* orbit_xy, 
  *   `limbs` with sign `neg`, on the CPU.
  * mc_hook_orbit_create_lanes_host: mc_mandelbrot_orbit_create_deep with the iteration loop replaced by the kernel's phases as lane loops
  *   on the CPU (no device): the whole device algorithm, checkable on a box without a GPU. */
+/* The BLA tables built on the device (mc_context_bind_mandelbrot_orbit_tables, csrc/mandel_bla_table.hip): a workgroup carries this many
+ * adjacent entries of a level up through the levels above them, so a level of at most this many entries, and every level above it, is
+ * built by a single workgroup, and a launch builds log2(this) + 1 levels.  A power of two.  The tests read it here, to place their table
+ * shapes on either side of it. */
+#define MC_BLA_TABLE_GROUP_ENTRIES 1024u
 int mc_hook_orbit_mul_host(int k, const uint64_t* a_limbs, const uint64_t* b_limbs, uint64_t* out_limbs);
 int mc_hook_orbit_mul_device(mc_context* ctx, int k, const uint64_t* a_limbs, const uint64_t* b_limbs, uint64_t* out_limbs);
 int mc_hook_orbit_to_double_host(int k, const uint64_t* limbs, int neg, double* out);

@@ -3,7 +3,8 @@
 //       tools/orbit_host_check.cpp vulkan-compute-tests_amd/csrc/mandel_orbit.cpp -o orbit_host_check && ./orbit_host_check
 // (tests/test_mandel_orbit_sanitized.py does exactly that).  The cases are the smallest that reach each bound of that code: the limb
 // counts 1, 3, 17 and 130 (at 130 both fixed arrays of FixOps are full), every refusal, the parser's length and exponent limits, the
-// rounding to double at zero, below 2^-1022 and below 2^-1074, and both BLA tables at the lengths where a level is empty, single or odd.
+// rounding to double at zero, below 2^-1022 and below 2^-1074, both BLA tables at the lengths where a level is empty, single or odd,
+// and mc_mandelbrot_orbit_rescale at the same limb-count edges with both builders run on its result.
 // A failed check prints its line and exits 1; the last line of a clean run is "orbit_host_check: <n> cases OK".
 #include <cmath>
 #include <cstdio>
@@ -268,6 +269,48 @@ int main() {
         a.read();
         CHECK(a.L == 2);
         check_tables(a, false);
+    }
+    // ---- mc_mandelbrot_orbit_rescale: the copy of the table at each limb-count edge, the scale fields, both builders (the shared header,
+    //      csrc/mandel_bla_table.h) on the result, every refusal, the source destroyed before the result is read
+    {
+        struct Case { const char *cx, *cy; int32_t src, dst; uint32_t M, bits; bool deep; };
+        const Case cases[] = {{esc_x, esc_y, -30, 20, 300, 127, false},      // k = 2 source at a scale that asks for one limb
+                              {in_x, in_y, -140, -100, 300, 237, false},     // the same four limbs
+                              {in_x, in_y, -1100, -900, 300, 1197, false},   // deep -> plain: folded into doubles
+                              {in_x, in_y, -1100, -1090, 300, 1197, true},   // deep -> deep
+                              {in_x, in_y, -8191, -8191, 40, 8288, true}};   // k = 130
+        for (const Case& c : cases) {
+            Orbit r;
+            std::vector<double> want;
+            {
+                Orbit s;
+                CHECK(mc_mandelbrot_orbit_create_deep(c.cx, c.cy, 1.0, 0.75, c.src, c.M, &s.o) == MC_OK);
+                s.read();
+                want = s.z;
+                CHECK(mc_mandelbrot_orbit_bla_deep(s.o, nullptr, nullptr) == MC_OK);   // a table in the source: not carried over
+                CHECK(mc_mandelbrot_orbit_rescale(s.o, 1.0, 0.75, c.dst, &r.o) == MC_OK);
+                CHECK(s.o->scale_exp2 == (s.o->deep ? c.src : 0) && s.o->has_bla_deep && s.o->z == want);
+            }
+            r.read();
+            CHECK(r.z == want && r.bits == c.bits && r.M == c.M && r.o->deep == c.deep && !r.o->has_bla && !r.o->has_bla_deep);
+            if (c.deep) CHECK(r.o->scale_x == 1.0 && r.o->scale_y == 0.75 && r.o->scale_exp2 == c.dst);
+            else CHECK(r.o->scale_x == std::ldexp(1.0, c.dst) && r.o->scale_y == std::ldexp(0.75, c.dst) && r.o->scale_exp2 == 0);
+            check_tables(r, c.deep);
+        }
+        Orbit s;
+        CHECK(mc_mandelbrot_orbit_create_deep(in_x, in_y, 1.0, 0.75, -100, 50, &s.o) == MC_OK);
+        const char* fn = "mc_mandelbrot_orbit_rescale: ";
+        auto refused = [&](int rc, int status, const char* text) { check_refusal(rc, o, status, (std::string(fn) + text).c_str()); };
+        refused(mc_mandelbrot_orbit_rescale(s.o, 1.0, 0.75, -101, &o), MC_ERR_UNSUPPORTED, "the orbit was computed for a shallower view");
+        refused(mc_mandelbrot_orbit_rescale(s.o, 1.0, 0.75, INT32_MIN, &o), MC_ERR_UNSUPPORTED, "scale below 2^-8192");
+        refused(mc_mandelbrot_orbit_rescale(s.o, 1.0, 0.75, INT32_MAX, &o), MC_ERR_UNSUPPORTED, "scale above the double range");
+        refused(mc_mandelbrot_orbit_rescale(s.o, 1.5, 1.0, 1024, &o), MC_ERR_UNSUPPORTED, "scale above the double range");
+        refused(mc_mandelbrot_orbit_rescale(nullptr, 1.0, 0.75, -100, &o), MC_ERR_INVALID_ARGUMENT, "NULL argument");
+        CHECK(mc_mandelbrot_orbit_rescale(s.o, 1.0, 0.75, -100, nullptr) == MC_ERR_INVALID_ARGUMENT);
+        for (double b : bad) {
+            refused(mc_mandelbrot_orbit_rescale(s.o, b, 0.75, -100, &o), MC_ERR_INVALID_ARGUMENT, "scale_x and scale_y must be finite and nonzero");
+            refused(mc_mandelbrot_orbit_rescale(s.o, 1.0, b, -100, &o), MC_ERR_INVALID_ARGUMENT, "scale_x and scale_y must be finite and nonzero");
+        }
     }
     std::printf("orbit_host_check: %d cases OK\n", g_cases);
     return 0;

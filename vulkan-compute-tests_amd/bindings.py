@@ -216,6 +216,12 @@ def lib():
         if hasattr(L, "mc_mandelbrot_orbit_bla_deep"):   # MC_PRECISION_PERTURB_BLA_DEEP
             L.mc_mandelbrot_orbit_bla_deep.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
             L.mc_mandelbrot_orbit_bla_deep_copy.argtypes = [vp, vp, vp]
+        if hasattr(L, "mc_mandelbrot_orbit_rescale"):   # dives: one shared orbit, BLA tables built on the device
+            L.mc_mandelbrot_orbit_rescale.argtypes = [vp, C.c_double, C.c_double, C.c_int32, C.POINTER(vp)]
+            L.mc_context_bind_mandelbrot_orbit_tables.argtypes = [vp, vp, u32]
+            L.mc_context_last_table_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u32)]
+            L.mc_context_bound_bla_copy.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
+            L.mc_context_bound_bla_deep_copy.argtypes = [vp, vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
         if hasattr(L, "mc_mandelbrot_equalise_map"):   # MC_MANDEL_COLOUR_EQUALISED
             L.mc_mandelbrot_histogram_device_async.argtypes = [vp, vp, u32, C.c_uint64, u32, vp, vp]
             L.mc_mandelbrot_equalise_map.argtypes = [u32, vp, vp]
@@ -1082,6 +1088,15 @@ def scale_from_text(text):
     return (-m if v < 0 else m), e
 
 
+ORBIT_TABLE_BLA = 1 << 0        # mc_context_bind_mandelbrot_orbit_tables: the tables to build on the device
+ORBIT_TABLE_BLA_DEEP = 1 << 1
+
+
+def bla_table_group_entries():
+    """MC_BLA_TABLE_GROUP_ENTRIES of include/mc_compute_test.h: the device table build's single-workgroup threshold."""
+    return int(re.search(r"#define\s+MC_BLA_TABLE_GROUP_ENTRIES\s+(\d+)u", open(TEST_HEADER_PATH).read()).group(1))
+
+
 class Orbit:
     """mc_mandelbrot_orbit: the reference orbit of MC_PRECISION_PERTURB, computed on the host (no device needed) from the centre as
     decimal text (str, taken verbatim) and the scale as doubles.  A context manager; Context.bind_mandelbrot_orbit copies it to a device.
@@ -1109,16 +1124,36 @@ class Orbit:
             else:
                 _check(lib().mc_mandelbrot_orbit_create_deep(enc(centre_x), enc(centre_y), float(scale_x), float(scale_y), E,
                                                              int(max_iter), C.byref(self._h)), "mc_mandelbrot_orbit_create_deep")
-            emin = min(math.frexp(abs(float(scale_x))), math.frexp(abs(float(scale_y))), key=lambda fe: (fe[1], fe[0]))[1] + E
-            self.deep = emin < -959
-            if self.deep:
-                self.scale = (float(scale_x), float(scale_y))
-            else:
-                self.scale, E = (math.ldexp(float(scale_x), E), math.ldexp(float(scale_y), E)), 0
+            self._set_scale(scale_x, scale_y, E)
+            E = self.scale_exp2
         self.scale_exp2 = None if scale_exp2 is None else E
+        self._read_info()
+
+    def _set_scale(self, scale_x, scale_y, E):
+        """The attributes of an object made for (scale_x, scale_y) * 2^E, as the deep constructor stores the scale."""
+        emin = min(math.frexp(abs(float(scale_x))), math.frexp(abs(float(scale_y))), key=lambda fe: (fe[1], fe[0]))[1] + E
+        self.deep = emin < -959
+        if self.deep:
+            self.scale, self.scale_exp2 = (float(scale_x), float(scale_y)), E
+        else:
+            self.scale, self.scale_exp2 = (math.ldexp(float(scale_x), E), math.ldexp(float(scale_y), E)), 0
+
+    def _read_info(self):
         n, m, b = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().mc_mandelbrot_orbit_info(self._h, C.byref(n), C.byref(m), C.byref(b)), "mc_mandelbrot_orbit_info")
         self.length, self.max_iter, self.bits = n.value, m.value, b.value
+
+    def rescale(self, scale_x, scale_y, scale_exp2=0):
+        """mc_mandelbrot_orbit_rescale: a new Orbit with this one's table under the scale (scale_x, scale_y) * 2^scale_exp2 of the same
+        centre (no BLA table; this object is untouched).  Refused when the new scale asks for more bits than this orbit carries."""
+        h = C.c_void_p()
+        _check(lib().mc_mandelbrot_orbit_rescale(self._h, float(scale_x), float(scale_y), int(scale_exp2), C.byref(h)),
+               "mc_mandelbrot_orbit_rescale")
+        o = Orbit.__new__(Orbit)
+        o._h = h
+        o._set_scale(scale_x, scale_y, int(scale_exp2))
+        o._read_info()
+        return o
 
     def table(self):
         """Z_0 .. Z_L as an (L + 1, 2) float64 array (re, im)."""
@@ -1242,12 +1277,41 @@ class Context:
         _check(lib().mc_context_last_refined(self._h, C.byref(r), C.byref(n)), "mc_context_last_refined")
         return r.value, n.value
 
-    def bind_mandelbrot_orbit(self, orbit):
-        """mc_context_bind_mandelbrot_orbit: the view of MC_PRECISION_PERTURB renders on this context (None unbinds)."""
+    def bind_mandelbrot_orbit(self, orbit, device_tables=None):
+        """mc_context_bind_mandelbrot_orbit: the view of MC_PRECISION_PERTURB renders on this context (None unbinds).
+        device_tables (an OR of ORBIT_TABLE_BLA / ORBIT_TABLE_BLA_DEEP, or 0): mc_context_bind_mandelbrot_orbit_tables, which builds the
+        named BLA tables on this context's device instead of taking them from the orbit; last_table_timing() then reports the build."""
         if orbit is not None and not orbit._h:   # a closed orbit's handle is NULL, which the C call reads as "unbind"
             raise ValueError("Context.bind_mandelbrot_orbit: the orbit is closed")
-        _check(lib().mc_context_bind_mandelbrot_orbit(self._h, orbit._h if orbit is not None else None),
-               "mc_context_bind_mandelbrot_orbit")
+        h = orbit._h if orbit is not None else None
+        if device_tables is None:
+            _check(lib().mc_context_bind_mandelbrot_orbit(self._h, h), "mc_context_bind_mandelbrot_orbit")
+        else:
+            _check(lib().mc_context_bind_mandelbrot_orbit_tables(self._h, h, int(device_tables)),
+                   "mc_context_bind_mandelbrot_orbit_tables")
+
+    def last_table_timing(self):
+        """(device_ms, launches) of the last bind_mandelbrot_orbit(..., device_tables=nonzero) (mc_context_last_table_timing)."""
+        ms, n = C.c_double(0), C.c_uint32(0)
+        _check(lib().mc_context_last_table_timing(self._h, C.byref(ms), C.byref(n)), "mc_context_last_table_timing")
+        return ms.value, n.value
+
+    def bound_bla_table(self):
+        """mc_context_bound_bla_copy: (table (entries, 5) float64 in Orbit.bla_table()'s layout, levels) of the bound BLA table."""
+        lv, n = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().mc_context_bound_bla_copy(self._h, None, C.byref(lv), C.byref(n)), "mc_context_bound_bla_copy")
+        out = np.empty((n.value, 5), np.float64)
+        _check(lib().mc_context_bound_bla_copy(self._h, _ptr(out), None, None), "mc_context_bound_bla_copy")
+        return out, lv.value
+
+    def bound_bla_deep_table(self):
+        """mc_context_bound_bla_deep_copy: (mantissas (entries, 5) float64, exponents (entries, 3) int32, levels) of the bound floatexp
+        table, in Orbit.bla_deep_table()'s layout."""
+        lv, n = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().mc_context_bound_bla_deep_copy(self._h, None, None, C.byref(lv), C.byref(n)), "mc_context_bound_bla_deep_copy")
+        mant, exps = np.empty((n.value, 5), np.float64), np.empty((n.value, 3), np.int32)
+        _check(lib().mc_context_bound_bla_deep_copy(self._h, _ptr(mant), _ptr(exps), None, None), "mc_context_bound_bla_deep_copy")
+        return mant, exps, lv.value
 
     # ---- host-buffer forms -------------------------------------------------------------------------
     def mandelbrot(self, p, want_rgba=True, want_iters=True, out=None):

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "mandel_bla_table.h"
 #include "mandel_orbit.h"
 
 // ---- multi-limb fixed point -----------------------------------------------------------------------------------------------------
@@ -237,6 +238,11 @@ int host_loop(const FixOps& ops, const Fix& cx, const Fix& cy, uint32_t max_iter
     return MC_OK;
 }
 
+const char* below_floor_text(bool deep) {
+    return deep ? "scale below 2^-8192 (the orbit's fixed point would need more than 130 limbs)"
+                : "scale below 2^-960 (pixel offsets would leave the normal doubles)";
+}
+
 // The orbit of every constructor.  bits and the refusal of scales below the floor are decided by the caller; deep = the tiny-entry
 // refusal of include/mc_compute.h applies.  `fn` names the entry point in the error detail.  An empty loop: host_loop.
 int make_orbit(const char* fn, const mc::OrbitLoop& loop, const char* centre_x, const char* centre_y, int64_t bits, bool below_floor,
@@ -248,9 +254,7 @@ int make_orbit(const char* fn, const mc::OrbitLoop& loop, const char* centre_x, 
         return refuse(fn, "centre_x is not a decimal of at most 4096 characters with |value| <= 4");
     if (!parse_decimal(centre_y, ops, cy))
         return refuse(fn, "centre_y is not a decimal of at most 4096 characters with |value| <= 4");
-    if (below_floor)
-        return refuse(fn, deep ? "scale below 2^-8192 (the orbit's fixed point would need more than 130 limbs)"
-                               : "scale below 2^-960 (pixel offsets would leave the normal doubles)", MC_ERR_UNSUPPORTED);
+    if (below_floor) return refuse(fn, below_floor_text(deep), MC_ERR_UNSUPPORTED);
     mc_mandelbrot_orbit* o = new (std::nothrow) mc_mandelbrot_orbit();
     if (!o) return MC_ERR_OUT_OF_MEMORY;
     uint32_t tiny_j = 0;
@@ -287,26 +291,29 @@ int check_arguments(const char* fn, const char* centre_x, const char* centre_y, 
     return MC_OK;
 }
 
-// mc_mandelbrot_orbit_create under the name `fn`, past check_arguments.
-int create_plain(const char* fn, const mc::OrbitLoop& loop, const char* centre_x, const char* centre_y, double scale_x, double scale_y,
-                 uint32_t max_iter, mc_mandelbrot_orbit** out) {
+// What an orbit object stores for a view's scale, and what the scale asks of the fixed point: the one text of it, for every constructor
+// and for mc_mandelbrot_orbit_rescale.  deep: (x, y) are the mantissas and exp2 the exponent; otherwise (x, y) is the scale and exp2 is 0.
+struct OrbitScale {
+    double x, y;
+    int32_t exp2;
+    bool deep;
+    int64_t bits;       // the header's formula
+    bool below_floor;   // refused (after the centre strings are checked): below_floor_text(deep)
+};
+
+// mc_mandelbrot_orbit_create's scale: finite nonzero doubles.
+OrbitScale plain_scale(double scale_x, double scale_y) {
     const double smin = std::fmin(std::fabs(scale_x), std::fabs(scale_y));
     int e = 0;
     (void)std::frexp(smin, &e);                      // smin = f * 2^e, f in [0.5, 1): ceil(-log2 smin) = 1 - e exactly
     int64_t bits = (int64_t)1 - e + 96;
     if (bits < 64) bits = 64;
-    const int rc = make_orbit(fn, loop, centre_x, centre_y, bits, smin < std::ldexp(1.0, -960), false, max_iter, out);
-    if (rc) return rc;
-    (*out)->scale_x = scale_x;
-    (*out)->scale_y = scale_y;
-    return MC_OK;
+    return {scale_x, scale_y, 0, false, bits, smin < std::ldexp(1.0, -960)};
 }
 
-}  // namespace
-
-int mc::orbit_create(const char* fn, const char* fn_plain, const OrbitLoop& loop, const char* centre_x, const char* centre_y,
-                     double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out) {
-    if (int rc = check_arguments(fn, centre_x, centre_y, scale_x, scale_y, max_iter, out)) return rc;
+// mc_mandelbrot_orbit_create_deep's scale (scale_x, scale_y) * 2^scale_exp2, finite nonzero mantissas: folded into plain doubles when
+// min |scale| >= 2^-960 (the orbit is mc_mandelbrot_orbit_create's), kept as mantissas and exponent below.
+int normalise_scale(const char* fn, double scale_x, double scale_y, int32_t scale_exp2, OrbitScale* s) {
     // min |scale| = f * 2^emin, f in [0.5, 1), from the mantissas' frexp exponents plus scale_exp2 (64-bit: no overflow)
     int ex = 0, ey = 0;
     const double fx = std::frexp(std::fabs(scale_x), &ex), fy = std::frexp(std::fabs(scale_y), &ey);
@@ -317,14 +324,37 @@ int mc::orbit_create(const char* fn, const char* fn_plain, const OrbitLoop& loop
         const double sx = std::ldexp(scale_x, scale_exp2);   // exact: both results are normal doubles
         const double sy = std::ldexp(scale_y, scale_exp2);
         if (!std::isfinite(sx) || !std::isfinite(sy)) return refuse(fn, "scale above the double range", MC_ERR_UNSUPPORTED);
-        return create_plain(fn_plain, loop, centre_x, centre_y, sx, sy, max_iter, out);
+        *s = plain_scale(sx, sy);
+        return MC_OK;
     }
-    const int rc = make_orbit(fn, loop, centre_x, centre_y, 1 - emin + 96, emin < -8191, true, max_iter, out);   // bits > 1056
-    if (rc) return rc;
-    (*out)->scale_x = scale_x;
-    (*out)->scale_y = scale_y;
-    (*out)->scale_exp2 = scale_exp2;
+    *s = {scale_x, scale_y, scale_exp2, true, 1 - emin + 96, emin < -8191};   // bits > 1056
     return MC_OK;
+}
+
+void store_scale(mc_mandelbrot_orbit* o, const OrbitScale& s) {
+    o->scale_x = s.x;
+    o->scale_y = s.y;
+    o->scale_exp2 = s.exp2;
+    o->deep = s.deep;
+}
+
+// The orbit for a normalised scale, past check_arguments; `fn` names the entry point in the error detail.
+int create_scaled(const char* fn, const mc::OrbitLoop& loop, const char* centre_x, const char* centre_y, const OrbitScale& s,
+                  uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    const int rc = make_orbit(fn, loop, centre_x, centre_y, s.bits, s.below_floor, s.deep, max_iter, out);
+    if (rc) return rc;
+    store_scale(*out, s);
+    return MC_OK;
+}
+
+}  // namespace
+
+int mc::orbit_create(const char* fn, const char* fn_plain, const OrbitLoop& loop, const char* centre_x, const char* centre_y,
+                     double scale_x, double scale_y, int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out) {
+    if (int rc = check_arguments(fn, centre_x, centre_y, scale_x, scale_y, max_iter, out)) return rc;
+    OrbitScale s;
+    if (int rc = normalise_scale(fn, scale_x, scale_y, scale_exp2, &s)) return rc;
+    return create_scaled(s.deep ? fn : fn_plain, loop, centre_x, centre_y, s, max_iter, out);
 }
 
 extern "C" {
@@ -333,13 +363,43 @@ int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, doubl
                                mc_mandelbrot_orbit** out) {
     const char* fn = "mc_mandelbrot_orbit_create";
     if (int rc = check_arguments(fn, centre_x, centre_y, scale_x, scale_y, max_iter, out)) return rc;
-    return create_plain(fn, {}, centre_x, centre_y, scale_x, scale_y, max_iter, out);
+    return create_scaled(fn, {}, centre_x, centre_y, plain_scale(scale_x, scale_y), max_iter, out);
 }
 
 int mc_mandelbrot_orbit_create_deep(const char* centre_x, const char* centre_y, double scale_x, double scale_y, int32_t scale_exp2,
                                     uint32_t max_iter, mc_mandelbrot_orbit** out) {
     return mc::orbit_create("mc_mandelbrot_orbit_create_deep", "mc_mandelbrot_orbit_create", {}, centre_x, centre_y, scale_x, scale_y,
                             scale_exp2, max_iter, out);
+}
+
+// The table of `o` under another scale of the same centre (include/mc_compute.h).
+int mc_mandelbrot_orbit_rescale(const mc_mandelbrot_orbit* o, double scale_x, double scale_y, int32_t scale_exp2,
+                                mc_mandelbrot_orbit** out) {
+    const char* fn = "mc_mandelbrot_orbit_rescale";
+    if (!out || !o) return refuse(fn, "NULL argument");
+    *out = nullptr;
+    if (!std::isfinite(scale_x) || !std::isfinite(scale_y) || scale_x == 0.0 || scale_y == 0.0)
+        return refuse(fn, "scale_x and scale_y must be finite and nonzero");
+    OrbitScale s;
+    if (int rc = normalise_scale(fn, scale_x, scale_y, scale_exp2, &s)) return rc;
+    if (s.below_floor) return refuse(fn, below_floor_text(s.deep), MC_ERR_UNSUPPORTED);
+    if (s.bits > (int64_t)o->bits)
+        return refuse(fn, "the orbit was computed for a shallower view (it carries " + std::to_string(o->bits) +
+                              " fractional bits, this scale asks for " + std::to_string(s.bits) + ")", MC_ERR_UNSUPPORTED);
+    mc_mandelbrot_orbit* r = new (std::nothrow) mc_mandelbrot_orbit();
+    if (!r) return MC_ERR_OUT_OF_MEMORY;
+    try {
+        r->z = o->z;
+    } catch (const std::bad_alloc&) {
+        delete r;
+        return MC_ERR_OUT_OF_MEMORY;
+    }
+    r->length = o->length;
+    r->max_iter = o->max_iter;
+    r->bits = o->bits;
+    store_scale(r, s);
+    *out = r;
+    return MC_OK;
 }
 
 int mc_mandelbrot_orbit_destroy(mc_mandelbrot_orbit* o) {
@@ -361,25 +421,6 @@ int mc_mandelbrot_orbit_copy(const mc_mandelbrot_orbit* o, double* out_z) {
     return MC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// Both BLA tables over an orbit of length L: level 0 holds steps 1 .. L-2, level k (L-2) >> k entries, while that is at least one.
-struct BlaShape {
-    uint64_t n0, total;
-    uint32_t levels;
-};
-BlaShape bla_shape(uint32_t length) {
-    BlaShape sh{length >= 3 ? (uint64_t)length - 2 : 0, 0, 0};
-    for (; (sh.n0 >> sh.levels) >= 1; sh.levels++) sh.total += sh.n0 >> sh.levels;
-    return sh;
-}
-
-}  // namespace
-
-extern "C" {
-
 // The BLA table of include/mc_compute.h (MC_PRECISION_PERTURB_BLA), operation by operation.
 int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries) {
     if (!o) return refuse("mc_mandelbrot_orbit_bla", "NULL orbit");
@@ -387,7 +428,7 @@ int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* 
         return refuse("mc_mandelbrot_orbit_bla", "a deep orbit (min |scale| < 2^-960) renders by the rescaled loop, which has no BLA",
                       MC_ERR_UNSUPPORTED);
     if (!o->has_bla) {
-        const BlaShape sh = bla_shape(o->length);
+        const mc::blatab::Shape sh = mc::blatab::shape(o->length);
         const uint64_t n0 = sh.n0, total = sh.total;
         const uint32_t nlev = sh.levels;
         std::vector<double> t;
@@ -396,35 +437,13 @@ int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* 
         } catch (const std::bad_alloc&) {
             return refuse("mc_mandelbrot_orbit_bla", "the table does not fit in host memory", MC_ERR_OUT_OF_MEMORY);
         }
-        const double eps = std::ldexp(1.0, -53);
-        const double cm = 0.5 * (std::fabs(o->scale_x) + std::fabs(o->scale_y));
-        for (uint64_t j = 1; j <= n0; j++) {
-            double* e = &t[5 * (j - 1)];
-            const double zx = o->z[2 * j], zy = o->z[2 * j + 1];
-            e[0] = zx + zx;
-            e[1] = zy + zy;
-            e[2] = 1.0;
-            e[3] = 0.0;
-            e[4] = eps * std::fmax(std::fabs(e[0]), std::fabs(e[1]));
-        }
+        const double cm = mc::blatab::plain_cm(o->scale_x, o->scale_y);
+        for (uint64_t j = 1; j <= n0; j++) mc::blatab::plain_level0(o->z[2 * j], o->z[2 * j + 1], &t[5 * (j - 1)]);
         uint64_t prev = 0, off = n0;   // level k-1 starts at prev, level k at off
         for (uint32_t k = 1; k < nlev; k++) {
             const uint64_t cnt = n0 >> k;
-            for (uint64_t q = 0; q < cnt; q++) {
-                const double* x = &t[5 * (prev + 2 * q)];       // (k-1, m), m = 1 + q 2^k
-                const double* y = &t[5 * (prev + 2 * q + 1)];   // (k-1, m + 2^(k-1))
-                double* e = &t[5 * (off + q)];
-                e[0] = (y[0] * x[0]) - (y[1] * x[1]);
-                e[1] = (y[0] * x[1]) + (y[1] * x[0]);
-                e[2] = ((y[0] * x[2]) - (y[1] * x[3])) + y[2];
-                e[3] = ((y[0] * x[3]) + (y[1] * x[2])) + y[3];
-                const double na = std::fabs(x[0]) + std::fabs(x[1]);
-                const double nb = std::fabs(x[2]) + std::fabs(x[3]);
-                const double q_ = (y[4] - (nb * cm)) / na;
-                const bool ok = std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2]) && std::isfinite(e[3]) &&
-                                std::isfinite(q_) && na > 0.0 && q_ > 0.0;
-                e[4] = ok ? std::fmin(x[4], q_) : 0.0;
-            }
+            for (uint64_t q = 0; q < cnt; q++)   // x = (k-1, m), m = 1 + q 2^k, then y = (k-1, m + 2^(k-1))
+                mc::blatab::plain_merge(&t[5 * (prev + 2 * q)], &t[5 * (prev + 2 * q + 1)], cm, &t[5 * (off + q)]);
             prev = off;
             off += cnt;
         }
@@ -438,48 +457,11 @@ int mc_mandelbrot_orbit_bla(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* 
     return MC_OK;
 }
 
-namespace {
-
-// Floatexp values of MC_PRECISION_PERTURB_BLA_DEEP (include/mc_compute.h): (x, y) * 2^e, normalised (max(|x|, |y|) in [0.5, 1), or
-// x = y = 0 with e = 0).  Exponents are formed in 64 bits here; the table's bound keeps every stored one within +-2^20.
-struct Fx {
-    double x, y;
-    int64_t e;
-};
-Fx fx_norm(double x, double y, int64_t e) {
-    const double a = std::fmax(std::fabs(x), std::fabs(y));
-    if (a == 0.0) return {0.0, 0.0, 0};
-    int k = 0;
-    (void)std::frexp(a, &k);
-    return {std::ldexp(x, -k), std::ldexp(y, -k), e + k};
-}
-// p + q for mantissas in any range: a zero operand yields the other, normalised; otherwise both are aligned with ldexp at the larger of
-// their frexp exponents, added, and the sum normalised.
-Fx fx_add(const Fx& p, const Fx& q) {
-    if (p.x == 0.0 && p.y == 0.0) return fx_norm(q.x, q.y, q.e);
-    if (q.x == 0.0 && q.y == 0.0) return fx_norm(p.x, p.y, p.e);
-    int kp = 0, kq = 0;
-    (void)std::frexp(std::fmax(std::fabs(p.x), std::fabs(p.y)), &kp);
-    (void)std::frexp(std::fmax(std::fabs(q.x), std::fabs(q.y)), &kq);
-    const int64_t e = p.e + kp > q.e + kq ? p.e + kp : q.e + kq;
-    return fx_norm(std::ldexp(p.x, (int)(p.e - e)) + std::ldexp(q.x, (int)(q.e - e)),
-                   std::ldexp(p.y, (int)(p.e - e)) + std::ldexp(q.y, (int)(q.e - e)), e);
-}
-// a < b for normalised nonnegative reals (zero below every positive value)
-bool fx_less(const Fx& a, const Fx& b) {
-    if (b.x == 0.0) return false;
-    if (a.x == 0.0) return true;
-    return a.e < b.e || (a.e == b.e && a.x < b.x);
-}
-constexpr int64_t kFxBound = int64_t(1) << 20;   // an entry with an exponent beyond +-2^20 is stored as zero (R = 0)
-
-}  // namespace
-
 // The floatexp BLA table of include/mc_compute.h (MC_PRECISION_PERTURB_BLA_DEEP), operation by operation.
 int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint64_t* entries) {
     if (!o) return refuse("mc_mandelbrot_orbit_bla_deep", "NULL orbit");
     if (!o->has_bla_deep) {
-        const BlaShape sh = bla_shape(o->length);
+        const mc::blatab::Shape sh = mc::blatab::shape(o->length);
         const uint64_t n0 = sh.n0, total = sh.total;
         const uint32_t nlev = sh.levels;
         std::vector<mc::BlaDeepRec> t;
@@ -488,45 +470,13 @@ int mc_mandelbrot_orbit_bla_deep(mc_mandelbrot_orbit* o, uint32_t* levels, uint6
         } catch (const std::bad_alloc&) {
             return refuse("mc_mandelbrot_orbit_bla_deep", "the table does not fit in host memory", MC_ERR_OUT_OF_MEMORY);
         }
-        auto put = [](mc::BlaDeepRec& r, const Fx& A, const Fx& B, const Fx& R) {
-            const bool out = A.e < -kFxBound || A.e > kFxBound || B.e < -kFxBound || B.e > kFxBound || R.e < -kFxBound || R.e > kFxBound;
-            const Fx z{0.0, 0.0, 0};
-            const Fx& a = out ? z : A;
-            const Fx& b = out ? z : B;
-            const Fx& q = out ? z : R;
-            r.ax = a.x; r.ay = a.y; r.bx = b.x; r.by = b.y; r.r = q.x;
-            r.ea = (int32_t)a.e; r.eb = (int32_t)b.e; r.er = (int32_t)q.e;
-            r.pad[0] = r.pad[1] = r.pad[2] = 0;
-        };
-        auto get = [](const mc::BlaDeepRec& r, Fx& A, Fx& B, Fx& R) {
-            A = {r.ax, r.ay, r.ea}; B = {r.bx, r.by, r.eb}; R = {r.r, 0.0, r.er};
-        };
-        const Fx cm = fx_norm(0.5 * (std::fabs(o->scale_x) + std::fabs(o->scale_y)), 0.0, o->deep ? o->scale_exp2 : 0);
-        for (uint64_t j = 1; j <= n0; j++) {
-            const double zx = o->z[2 * j], zy = o->z[2 * j + 1];
-            const Fx A = fx_norm(zx + zx, zy + zy, 0);
-            const Fx R = A.x == 0.0 && A.y == 0.0 ? Fx{0.0, 0.0, 0} : Fx{std::fmax(std::fabs(A.x), std::fabs(A.y)), 0.0, A.e - 53};
-            put(t[j - 1], A, Fx{0.5, 0.0, 1}, R);
-        }
+        const mc::blatab::Fx cm = mc::blatab::deep_cm(o->scale_x, o->scale_y, o->deep, o->scale_exp2);
+        for (uint64_t j = 1; j <= n0; j++) mc::blatab::deep_level0(o->z[2 * j], o->z[2 * j + 1], t[j - 1]);
         uint64_t prev = 0, off = n0;   // level k-1 starts at prev, level k at off
         for (uint32_t k = 1; k < nlev; k++) {
             const uint64_t cnt = n0 >> k;
-            for (uint64_t q = 0; q < cnt; q++) {
-                Fx xa, xb, xr, ya, yb, yr;
-                get(t[prev + 2 * q], xa, xb, xr);       // (k-1, m), m = 1 + q 2^k
-                get(t[prev + 2 * q + 1], ya, yb, yr);   // (k-1, m + 2^(k-1))
-                const Fx A = fx_norm((ya.x * xa.x) - (ya.y * xa.y), (ya.x * xa.y) + (ya.y * xa.x), ya.e + xa.e);
-                const Fx B = fx_add(Fx{(ya.x * xb.x) - (ya.y * xb.y), (ya.x * xb.y) + (ya.y * xb.x), ya.e + xb.e}, yb);
-                const double na = std::fabs(xa.x) + std::fabs(xa.y);
-                const double nb = std::fabs(xb.x) + std::fabs(xb.y);
-                const Fx diff = fx_add(yr, Fx{-(nb * cm.x), 0.0, xb.e + cm.e});   // Ry - N1(Bx) cm
-                Fx R{0.0, 0.0, 0};
-                if (na > 0.0 && diff.x > 0.0) {
-                    const Fx qv = fx_norm(diff.x / na, 0.0, diff.e - xa.e);
-                    R = fx_less(qv, xr) ? qv : xr;                                 // min(Rx, q); Rx = 0 gives 0
-                }
-                put(t[off + q], A, B, R);
-            }
+            for (uint64_t q = 0; q < cnt; q++)   // x = (k-1, m), m = 1 + q 2^k, then y = (k-1, m + 2^(k-1))
+                mc::blatab::deep_merge(t[prev + 2 * q], t[prev + 2 * q + 1], cm, t[off + q]);
             prev = off;
             off += cnt;
         }

@@ -71,6 +71,16 @@ struct PerturbBlaDeepArgs {
 int perturb_bla_deep_launch(const PerturbBlaDeepArgs& a, dim3 grid, hipStream_t s, const SampleList* list = nullptr, SmoothOut smooth = {},
                             const SmoothSampleList* slist = nullptr);
 
+// mc_context_bind_mandelbrot_orbit_tables (mandel_bla_table.hip): the tables named in `tables` (MC_ORBIT_TABLE_*) built on the context's
+// device from the orbit table d_orbit (Z_0 .. Z_length, already on the stream) and the orbit's scale fields, into d_bla / d_bla_deep
+// (bla_table_bytes each; untouched when the table has no entry).  Blocking: returns with the stream idle and the timing of
+// mc_context_last_table_timing recorded.
+size_t bla_table_bytes(uint32_t table, uint32_t length);
+int bla_table_build(mc_context* ctx, uint32_t tables, const void* d_orbit, uint32_t length, double scale_x, double scale_y, bool deep,
+                    int32_t scale_exp2, void* d_bla, void* d_bla_deep, hipStream_t s);
+// mc_context_destroy: the context's table-timing events are freed.
+void bla_table_release(mc_context* ctx);
+
 // mc_mandelbrot_orbit_create_device (mandel_orbit_device.hip): orbit_create's iteration loop (mandel_orbit.h) on the context's device.
 // A launch runs at most orbit_launch_iters(k) = kOrbitLaunchWork / (k + 1)^2 iterations, clamped to [1, 65536].  3.2e7 gives 1864
 // iterations at k = 130: 49 ms at the 26.3 us per iteration measured there (which also lists what the rule gives at the

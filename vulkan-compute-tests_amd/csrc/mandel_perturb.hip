@@ -8,9 +8,11 @@
 //  * IEEE double in source order: this TU is built with -ffp-contract=off like every other; fp64 denormals stay enabled.
 #include <atomic>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
+#include "mandel_bla_table.h"
 #include "mandel_kernels.h"
 #include "mandel_perturb.h"
 #include "mandel_side_record.h"
@@ -29,7 +31,8 @@ struct Binding {
     bool deep = false;                 // rendered by the deep kernel (mandel_perturb_deep.hip)
     bool has_zero = false;             // some Z_j = 0 exactly, 1 <= j < L
     uint32_t generation = 0;           // a new value per bind, part of the dc table's cache key
-    // MC_PRECISION_PERTURB_BLA: the orbit's BLA table when it had one at the bind (mc_mandelbrot_orbit_bla).  The per-level offsets
+    // MC_PRECISION_PERTURB_BLA: the orbit's BLA table when it had one at the bind (mc_mandelbrot_orbit_bla), or the one the bind built
+    // on the device (mc_context_bind_mandelbrot_orbit_tables).  The per-level offsets
     // follow from L (mandel_perturb.h); levels / entries are its shape.  An orbit without a table leaves bla unallocated.
     DeviceBuffer bla;
     uint32_t bla_levels = 0;
@@ -37,6 +40,7 @@ struct Binding {
     bool has_bla = false;
     // MC_PRECISION_PERTURB_BLA_DEEP: the orbit's floatexp table when it had one at the bind (mc_mandelbrot_orbit_bla_deep), likewise
     DeviceBuffer bla_deep;
+    uint32_t bla_deep_levels = 0;
     uint64_t bla_deep_entries = 0;
     bool has_bla_deep = false;
 };
@@ -265,45 +269,69 @@ bool perturb_bound_scale(mc_context* ctx, double* scale_x, double* scale_y, int3
 
 }  // namespace mc
 
-extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o) {
+namespace mc {
+namespace {
+
+// mc_context_bind_mandelbrot_orbit (device_tables = 0) and mc_context_bind_mandelbrot_orbit_tables.  A table named in device_tables is
+// built on the device from the Z uploaded here; any other is uploaded when the orbit holds it and released otherwise.
+int bind_orbit(const char* fn, mc_context* ctx, const mc_mandelbrot_orbit* o, uint32_t device_tables) {
     if (!ctx) return MC_ERR_INVALID_ARGUMENT;
+    if (device_tables & ~(uint32_t)(MC_ORBIT_TABLE_BLA | MC_ORBIT_TABLE_BLA_DEEP)) {
+        set_error_detail(std::string(fn) + ": unknown bits in device_tables");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (o && o->deep && (device_tables & MC_ORBIT_TABLE_BLA)) {
+        set_error_detail(std::string(fn) + ": a deep orbit (min |scale| < 2^-960) renders by the rescaled loop, which has no BLA");
+        return MC_ERR_UNSUPPORTED;
+    }
     MC_HIP_TRY(hipSetDevice(ctx->device));
     // a running launch of this context may read the current table (or the dc table keyed by its generation): wait for the context's
     // launch streams — not the whole device — before replacing it, as the colour table does
     int rc = ctx->drain_launch_streams();
     if (rc) return rc;
     if (!o) {
-        mc::perturb_release(ctx);
+        perturb_release(ctx);
         return MC_OK;
     }
-    mc::Binding* b = mc::g_bindings.get(ctx);
-    b->generation = ++mc::g_generation;
+    const bool dev_bla = (device_tables & MC_ORBIT_TABLE_BLA) != 0u, dev_deep = (device_tables & MC_ORBIT_TABLE_BLA_DEEP) != 0u;
+    const blatab::Shape sh = blatab::shape(o->length);
+    Binding* b = g_bindings.get(ctx);
+    b->generation = ++g_generation;
     b->length = 0;                   // unusable until the copy below has completed
     b->has_bla = false;
     b->has_bla_deep = false;
     const size_t bytes = o->z.size() * sizeof(double);
     if ((rc = b->orbit.reserve(bytes))) return rc;
     MC_HIP_TRY(hipMemcpyAsync(b->orbit.ptr, o->z.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (o->has_bla && !o->bla.empty()) {   // MC_PRECISION_PERTURB_BLA's table; an orbit without one binds exactly as before
+    if (dev_bla && sh.total) {   // built below, in place
+        if ((rc = b->bla.reserve(bla_table_bytes(MC_ORBIT_TABLE_BLA, o->length)))) return rc;
+    } else if (!dev_bla && o->has_bla && !o->bla.empty()) {   // MC_PRECISION_PERTURB_BLA's table; an orbit without one binds exactly as before
         const size_t tbytes = o->bla.size() * sizeof(double);
         if ((rc = b->bla.reserve(tbytes))) return rc;
         MC_HIP_TRY(hipMemcpyAsync(b->bla.ptr, o->bla.data(), tbytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
         b->bla.release();   // (a table left by an earlier bind)
     }
-    if (o->has_bla_deep && !o->bla_deep.empty()) {   // MC_PRECISION_PERTURB_BLA_DEEP's table, likewise
-        const size_t tbytes = o->bla_deep.size() * sizeof(mc::BlaDeepRec);
+    if (dev_deep && sh.total) {
+        if ((rc = b->bla_deep.reserve(bla_table_bytes(MC_ORBIT_TABLE_BLA_DEEP, o->length)))) return rc;
+    } else if (!dev_deep && o->has_bla_deep && !o->bla_deep.empty()) {   // MC_PRECISION_PERTURB_BLA_DEEP's table, likewise
+        const size_t tbytes = o->bla_deep.size() * sizeof(BlaDeepRec);
         if ((rc = b->bla_deep.reserve(tbytes))) return rc;
         MC_HIP_TRY(hipMemcpyAsync(b->bla_deep.ptr, o->bla_deep.data(), tbytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
         b->bla_deep.release();
     }
+    if (device_tables &&
+        (rc = bla_table_build(ctx, device_tables, b->orbit.ptr, o->length, o->scale_x, o->scale_y, o->deep, o->scale_exp2, b->bla.ptr,
+                              b->bla_deep.ptr, ctx->stream)))
+        return rc;
     MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    b->has_bla = o->has_bla;
-    b->bla_levels = o->bla_levels;
-    b->bla_entries = o->bla_entries;
-    b->has_bla_deep = o->has_bla_deep;
-    b->bla_deep_entries = o->bla_deep_entries;
+    b->has_bla = dev_bla || o->has_bla;
+    b->bla_levels = dev_bla ? sh.levels : o->bla_levels;
+    b->bla_entries = dev_bla ? sh.total : o->bla_entries;
+    b->has_bla_deep = dev_deep || o->has_bla_deep;
+    b->bla_deep_levels = dev_deep ? sh.levels : o->bla_deep_levels;
+    b->bla_deep_entries = dev_deep ? sh.total : o->bla_deep_entries;
     b->length = o->length;
     b->max_iter = o->max_iter;
     b->scale_x = o->scale_x;
@@ -313,5 +341,66 @@ extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandel
     b->has_zero = false;
     for (uint32_t j = 1; j < o->length; j++)
         if (o->z[2 * j] == 0.0 && o->z[2 * j + 1] == 0.0) { b->has_zero = true; break; }
+    return MC_OK;
+}
+
+// The binding whose table of one kind is to be read back; a refusal when nothing of the kind is bound.
+int bound_table(const char* fn, mc_context* ctx, bool deep_kind, const Binding** out) {
+    *out = nullptr;
+    if (!ctx) return MC_ERR_INVALID_ARGUMENT;
+    const Binding* b = g_bindings.find(ctx);
+    if (!b || !b->length || !(deep_kind ? b->has_bla_deep : b->has_bla)) {
+        set_error_detail(std::string(fn) + ": no such table is bound to the context");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    MC_HIP_TRY(hipSetDevice(ctx->device));
+    *out = b;
+    return MC_OK;
+}
+
+}  // namespace
+}  // namespace mc
+
+extern "C" int mc_context_bind_mandelbrot_orbit(mc_context* ctx, const mc_mandelbrot_orbit* o) {
+    return mc::bind_orbit("mc_context_bind_mandelbrot_orbit", ctx, o, 0u);
+}
+
+extern "C" int mc_context_bind_mandelbrot_orbit_tables(mc_context* ctx, const mc_mandelbrot_orbit* o, uint32_t device_tables) {
+    return mc::bind_orbit("mc_context_bind_mandelbrot_orbit_tables", ctx, o, device_tables);
+}
+
+extern "C" int mc_context_bound_bla_copy(mc_context* ctx, double* out, uint32_t* levels, uint64_t* entries) {
+    const mc::Binding* b;
+    if (int rc = mc::bound_table("mc_context_bound_bla_copy", ctx, false, &b)) return rc;
+    if (out && b->bla_entries) {
+        MC_HIP_TRY(hipMemcpyAsync(out, b->bla.ptr, (size_t)b->bla_entries * mc::blatab::kPlainDoubles * sizeof(double),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+        MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (levels) *levels = b->bla_levels;
+    if (entries) *entries = b->bla_entries;
+    return MC_OK;
+}
+
+extern "C" int mc_context_bound_bla_deep_copy(mc_context* ctx, double* mant, int32_t* exps, uint32_t* levels, uint64_t* entries) {
+    const mc::Binding* b;
+    if (int rc = mc::bound_table("mc_context_bound_bla_deep_copy", ctx, true, &b)) return rc;
+    if ((mant || exps) && b->bla_deep_entries) {
+        std::vector<mc::BlaDeepRec> t;
+        try {
+            t.resize((size_t)b->bla_deep_entries);
+        } catch (const std::bad_alloc&) {
+            return MC_ERR_OUT_OF_MEMORY;
+        }
+        MC_HIP_TRY(hipMemcpyAsync(t.data(), b->bla_deep.ptr, t.size() * sizeof(mc::BlaDeepRec), hipMemcpyDeviceToHost, ctx->stream));
+        MC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t j = 0; j < t.size(); j++) {
+            const mc::BlaDeepRec& r = t[j];
+            if (mant) { mant[5 * j] = r.ax; mant[5 * j + 1] = r.ay; mant[5 * j + 2] = r.bx; mant[5 * j + 3] = r.by; mant[5 * j + 4] = r.r; }
+            if (exps) { exps[3 * j] = r.ea; exps[3 * j + 1] = r.eb; exps[3 * j + 2] = r.er; }
+        }
+    }
+    if (levels) *levels = b->bla_deep_levels;
+    if (entries) *entries = b->bla_deep_entries;
     return MC_OK;
 }

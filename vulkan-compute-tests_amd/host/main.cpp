@@ -29,6 +29,7 @@
 #include <utility>
 #include <cstring>
 #include <stdexcept>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -63,6 +64,8 @@ int main(int argc, char* argv[]) {
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
+    bool blaDevice = false, blaTableSet = false;       // --bla-table host | device: where the BLA precisions' table is built
+    bool zoomOrbitShared = false, zoomOrbitSet = false;   // --zoom-orbit keyframe | shared: one orbit per keyframe, or the deepest one's for all
     uint32_t zoomFilter = MC_MANDEL_ZOOM_FILTER_BILINEAR;   // --zoom-filter bilinear | area: the area filter of the minified deep keyframe
     bool zoomFilterSet = false;
     bool zoomCounts = false;            // --zoom-keyframes colours | counts: count keyframes, one rank map per frame
@@ -250,6 +253,24 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--bla-table") {   // where perturb-bla / perturb-bla-deep build their table: on the host, or on the device at the bind
+            need(1);
+            blaDevice = choice(argv[++i], {{"host", 0u}, {"device", 1u}}) != 0u;
+            blaTableSet = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--bla-table: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
+        else if (a == "--zoom-orbit") {   // --zoom with a perturbation precision: an orbit per keyframe, or the deepest keyframe's rescaled for each
+            need(1);
+            zoomOrbitShared = choice(argv[++i], {{"keyframe", 0u}, {"shared", 1u}}) != 0u;
+            zoomOrbitSet = true;
+#if !defined(MANDELBROT_MODE)
+            printf("--zoom-orbit: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
         else if (a == "--zoom-filter") {   // how --zoom's frames read the minified deep keyframe: one bilinear tap, or a box over the pixel's footprint
             need(1);
             zoomFilter = choice(argv[++i], {{"bilinear", (uint32_t)MC_MANDEL_ZOOM_FILTER_BILINEAR}, {"area", (uint32_t)MC_MANDEL_ZOOM_FILTER_AREA}});
@@ -391,6 +412,18 @@ int main(int argc, char* argv[]) {
     }
     if (zoomSet && gpus > 1) { printf("--zoom: one GPU (the keyframes stay on the context's device)\n"); exit(EXIT_FAILURE); }
     if (zoomFilterSet && !zoomSet) { printf("--zoom-filter: needs --zoom K F (it chooses how a zoom sequence's frames read the deep keyframe)\n"); exit(EXIT_FAILURE); }
+    {
+        const bool orbitView = precision == MC_PRECISION_PERTURB || precision == MC_PRECISION_PERTURB_BLA || precision == MC_PRECISION_PERTURB_BLA_DEEP;
+        if (zoomOrbitSet && !(zoomSet && orbitView)) {
+            printf("--zoom-orbit: needs --zoom K F and --precision perturb | perturb-bla | perturb-bla-deep (it chooses how a dive's keyframes get their reference orbit)\n");
+            exit(EXIT_FAILURE);
+        }
+        if (blaTableSet && !(precision == MC_PRECISION_PERTURB_BLA || precision == MC_PRECISION_PERTURB_BLA_DEEP)) {
+            printf("--bla-table: needs --precision perturb-bla | perturb-bla-deep (it chooses where their table is built)\n");
+            exit(EXIT_FAILURE);
+        }
+        if (blaDevice && gpus > 1) { printf("--bla-table device: one GPU (the table is built into the context's binding)\n"); exit(EXIT_FAILURE); }
+    }
     if (zoomCounts) {   // count keyframes carry one count per pixel: the colourings and resolves that need more stay with --zoom-keyframes colours
         const char* why = !zoomSet                                ? "needs --zoom K F (it chooses what a zoom sequence keeps of a keyframe)"
                           : colour == MC_MANDEL_COLOUR_DISTANCE   ? "not with --colour distance (a stencil over a whole smooth plane; use --zoom-keyframes colours)"
@@ -420,7 +453,7 @@ int main(int argc, char* argv[]) {
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
     (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
-    (void)orbitWhere; (void)orbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)adaptiveSmooth; (void)adaptiveSmoothQ; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
+    (void)orbitWhere; (void)orbitSet; (void)blaDevice; (void)blaTableSet; (void)zoomOrbitShared; (void)zoomOrbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)adaptiveSmooth; (void)adaptiveSmoothQ; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
     MandelbrotApp app = MandelbrotApp(width, height);   // reference: 2000 x 2000 (main.cpp:20)
@@ -531,48 +564,85 @@ int main(int argc, char* argv[]) {
                                             (orbitWhere == kOrbitAuto && kOrbitAutoLimbs > 0 && lmin != 0.0L && (bits + 63) / 64 + 1 >= kOrbitAutoLimbs));
         // the orbit and its tables on ctx's device (or the host: ctx == nullptr); the message the run ends with, or "" after setOrbit()
         // shift: --zoom's keyframes, the scale's exponent raised by that much (0: the view itself)
-        auto makeOrbit = [=, &app](mc_context* ctx, int shift) -> std::string {
-            auto message = [](const char* fmt, auto... args) {
-                char buf[8192];
-                snprintf(buf, sizeof buf, fmt, args...);
-                return std::string(buf);
-            };
-            mc_mandelbrot_orbit* made = nullptr;
+        auto message = [](const char* fmt, auto... args) {
+            char buf[8192];
+            snprintf(buf, sizeof buf, fmt, args...);
+            return std::string(buf);
+        };
+        // (mantissa, exponent): exact at any depth and under any shift.  EVERY keyframe of a zoom takes this form, the last one
+        // (shift 0) too: mc_mandelbrot_zoom_push compares successive scales exactly, and the plain constructor's strtod of the text
+        // need not be the double this mantissa gives
+        const bool expForm = deepScale || zoomSet;
+        const double mantX = (double)ldexpl(lx, -e), mantY = (double)ldexpl(ly, -e);
+        // the orbit on ctx's device (or the host: ctx == nullptr): the message the run ends with, or "" and the object
+        auto createOrbit = [=](mc_context* ctx, int shift, mc_mandelbrot_orbit** made) -> std::string {
             const auto t0 = std::chrono::steady_clock::now();
             int rc;
-            // (mantissa, exponent): exact at any depth and under any shift.  EVERY keyframe of a zoom takes this form, the last one
-            // (shift 0) too: mc_mandelbrot_zoom_push compares successive scales exactly, and the plain constructor's strtod of the text
-            // need not be the double this mantissa gives
-            const bool expForm = deepScale || zoomSet;
             if (ctx) {
-                if (expForm) rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e + shift, maxIter, &made);
-                else rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, sx, sy, 0, maxIter, &made);
+                if (expForm) rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, mantX, mantY, e + shift, maxIter, made);
+                else rc = mc_mandelbrot_orbit_create_device(ctx, cxText, cyText, sx, sy, 0, maxIter, made);
             } else if (expForm) {
-                rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, (double)ldexpl(lx, -e), (double)ldexpl(ly, -e), e + shift, maxIter, &made);
+                rc = mc_mandelbrot_orbit_create_deep(cxText, cyText, mantX, mantY, e + shift, maxIter, made);
             } else {
-                rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, &made);
+                rc = mc_mandelbrot_orbit_create(cxText, cyText, sx, sy, maxIter, made);
             }
             const double orbitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (rc != MC_OK)
                 return message("--centre %s %s / --scale %s %s: %s (%s)", cxText, cyText, sxText, syText, mc_error_string(rc), mc_last_error_detail());
-            if (orbitSet) {
+            if (orbitSet || zoomOrbitShared) {
                 uint32_t obits = 0, launches = 0;
-                mc_mandelbrot_orbit_info(made, nullptr, nullptr, &obits);
+                mc_mandelbrot_orbit_info(*made, nullptr, nullptr, &obits);
                 if (ctx) mc_context_last_orbit_timing(ctx, nullptr, &launches, nullptr);
-                printf("orbit: %.3f ms (%s, %u bits, %u launches)\n", orbitMs, ctx ? "device" : "host", obits, launches);
+                if (zoomOrbitShared)   // the dive's one orbit: its limb count is what every keyframe's table is read with
+                    printf("orbit: %.3f ms (%s, %u bits, %u fractional limbs, %u launches), shared by %d keyframes\n", orbitMs,
+                           ctx ? "device" : "host", obits, (obits + 63u) / 64u, launches, zoomK + 1);
+                else printf("orbit: %.3f ms (%s, %u bits, %u launches)\n", orbitMs, ctx ? "device" : "host", obits, launches);
             }
-            if (precision == MC_PRECISION_PERTURB_BLA && (rc = mc_mandelbrot_orbit_bla(made, nullptr, nullptr)) != MC_OK) {   // the table, on the host
+            return std::string();
+        };
+        // the orbit's table (on the host, unless --bla-table device leaves it to the bind), then the app owns the orbit
+        auto adoptOrbit = [=, &app](mc_mandelbrot_orbit* made) -> std::string {
+            const auto t0 = std::chrono::steady_clock::now();
+            int rc;
+            if (!blaDevice && precision == MC_PRECISION_PERTURB_BLA && (rc = mc_mandelbrot_orbit_bla(made, nullptr, nullptr)) != MC_OK) {   // the table, on the host
                 mc_mandelbrot_orbit_destroy(made);
                 return message("mc_mandelbrot_orbit_bla: %s (%s)", mc_error_string(rc), mc_last_error_detail());
             }
-            if (precision == MC_PRECISION_PERTURB_BLA_DEEP && (rc = mc_mandelbrot_orbit_bla_deep(made, nullptr, nullptr)) != MC_OK) {
+            if (!blaDevice && precision == MC_PRECISION_PERTURB_BLA_DEEP && (rc = mc_mandelbrot_orbit_bla_deep(made, nullptr, nullptr)) != MC_OK) {
                 mc_mandelbrot_orbit_destroy(made);
                 return message("mc_mandelbrot_orbit_bla_deep: %s (%s)", mc_error_string(rc), mc_last_error_detail());
             }
+            if (!blaDevice && (blaTableSet || zoomOrbitShared) && (precision == MC_PRECISION_PERTURB_BLA || precision == MC_PRECISION_PERTURB_BLA_DEEP))
+                printf("table: %.3f ms (host; uploaded by the bind)\n",
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             app.setOrbit(made);   // bound to the context by init(), before the warm-up thread starts
             return std::string();
         };
-        if (zoomSet) {   // one orbit per keyframe, made by runZoom() as the keyframes come
+        // shift: --zoom's keyframes, the scale's exponent raised by that much (0: the view itself)
+        auto makeOrbit = [=](mc_context* ctx, int shift) -> std::string {
+            mc_mandelbrot_orbit* made = nullptr;
+            const std::string err = createOrbit(ctx, shift, &made);
+            return err.empty() ? adoptOrbit(made) : err;
+        };
+        if (blaDevice)
+            app.setDeviceTables(precision == MC_PRECISION_PERTURB_BLA ? (uint32_t)MC_ORBIT_TABLE_BLA : (uint32_t)MC_ORBIT_TABLE_BLA_DEEP);
+        if (zoomSet && zoomOrbitShared) {   // the deepest keyframe's orbit, made with the first keyframe; keyframe j takes its table under its own scale
+            std::shared_ptr<mc_mandelbrot_orbit*> deepest(new mc_mandelbrot_orbit*(nullptr), [](mc_mandelbrot_orbit** p) {
+                if (*p) mc_mandelbrot_orbit_destroy(*p);
+                delete p;
+            });
+            app.setZoom((uint32_t)zoomK, (uint32_t)zoomF, cx, cy, sx, sy,
+                        [=](mc_context* c, int shift) -> std::string {
+                            if (!*deepest) {
+                                const std::string err = createOrbit(onDevice ? c : nullptr, 0, deepest.get());
+                                if (!err.empty()) return err;
+                            }
+                            mc_mandelbrot_orbit* made = nullptr;
+                            const int rc = mc_mandelbrot_orbit_rescale(*deepest, mantX, mantY, e + shift, &made);
+                            if (rc != MC_OK) return message("mc_mandelbrot_orbit_rescale: %s (%s)", mc_error_string(rc), mc_last_error_detail());
+                            return adoptOrbit(made);
+                        });
+        } else if (zoomSet) {   // one orbit per keyframe, made by runZoom() as the keyframes come
             app.setZoom((uint32_t)zoomK, (uint32_t)zoomF, cx, cy, sx, sy,
                         [makeOrbit, onDevice](mc_context* c, int shift) { return makeOrbit(onDevice ? c : nullptr, shift); });
         } else if (onDevice) {

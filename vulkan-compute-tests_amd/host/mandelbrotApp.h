@@ -40,6 +40,9 @@ struct MandelbrotApp : public ComputeApp {
         orbit = o;
         setView(0.0, 0.0, 0.0, 0.0);
     }
+    // --bla-table device: the orbit carries no table; every bind builds the named ones (MC_ORBIT_TABLE_*) on the device
+    // and prints how long that took.  0 (the default): the plain bind of the table main() built.
+    void setDeviceTables(uint32_t tables) { deviceTables = tables; }
     // --orbit device | auto: the orbit is made on the context's device (mc_mandelbrot_orbit_create_device), so only once the context
     // exists: contextCreated() calls the factory before the bind and before the warm-up helper starts.  It calls setOrbit(), or
     // returns the message the run ends with.
@@ -85,6 +88,18 @@ struct MandelbrotApp : public ComputeApp {
         createBuffer(bufferSize);   // output buffer
     }
 
+    void bindOrbit() {
+        if (!deviceTables) {
+            check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
+            return;
+        }
+        check(mc_context_bind_mandelbrot_orbit_tables(ctx, orbit, deviceTables), "mc_context_bind_mandelbrot_orbit_tables");
+        double tableMs = 0.0;
+        uint32_t launches = 0;
+        check(mc_context_last_table_timing(ctx, &tableMs, &launches), "mc_context_last_table_timing");
+        printf("table: %.3f ms (device, %u launches; built by the bind)\n", tableMs, launches);
+    }
+
     // The request run() makes: push constant kColor (mandelbrotApp.h:139-141) and ONE dispatch over the whole image (:146)
     mc_mandelbrot_params request() const {
         mc_mandelbrot_params q = params;
@@ -99,7 +114,7 @@ struct MandelbrotApp : public ComputeApp {
             const std::string err = orbitFactory(ctx);
             if (!err.empty()) throw std::runtime_error(err);
         }
-        if (orbit) check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
+        if (orbit) bindOrbit();
     }
 
     virtual std::function<int()> warmupCall() const override {   // tables + code object of that request (bit 1: the banded render's second stream)
@@ -197,7 +212,7 @@ struct MandelbrotApp : public ComputeApp {
             if (zoomOrbit) {
                 const std::string err = zoomOrbit(ctx, shift);
                 if (!err.empty()) throw std::runtime_error(err);
-                check(mc_context_bind_mandelbrot_orbit(ctx, orbit), "mc_context_bind_mandelbrot_orbit");
+                bindOrbit();
             } else {
                 setView(zoomCx, zoomCy, std::ldexp(zoomSx, shift), std::ldexp(zoomSy, shift));
             }
@@ -383,6 +398,7 @@ private:
     uint32_t zoomFilter = MC_MANDEL_ZOOM_FILTER_BILINEAR;   // --zoom-filter
     double zoomCx = 0.0, zoomCy = 0.0, zoomSx = 0.0, zoomSy = 0.0;
     std::function<std::string(mc_context*, int)> zoomOrbit;
+    uint32_t deviceTables = 0;       // --bla-table device: MC_ORBIT_TABLE_*
 };
 
 #endif  // MANDELBROTAPP_H_
