@@ -53,7 +53,9 @@ extern "C" {
  * _tonemap and _tonemap_device_async; then its importance map and guided sampling: mc_buddhabrot_guide_params and _guide_info with
  * mc_buddhabrot_importance, _importance_device_async, _importance_cells, _density_guided, _density_guided_device_async,
  * _guide_default_params and _render_guided; then dives: mc_mandelbrot_orbit_rescale, and BLA tables built on the device with
- * mc_context_bind_mandelbrot_orbit_tables, mc_context_last_table_timing, mc_context_bound_bla_copy and mc_context_bound_bla_deep_copy.
+ * mc_context_bind_mandelbrot_orbit_tables, mc_context_last_table_timing, mc_context_bound_bla_copy and mc_context_bound_bla_deep_copy;
+ * then exact counts of sampled pixels: mc_mandelbrot_exact_pixel_offsets, mc_mandelbrot_exact_counts, mc_mandelbrot_exact_counts_device
+ * and mc_context_last_exact_timing.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -370,6 +372,58 @@ int mc_context_last_table_timing(mc_context* ctx, double* device_ms, uint32_t* l
 int mc_context_bound_bla_copy(mc_context* ctx, double* out /* entries * 5 */, uint32_t* levels, uint64_t* entries);
 int mc_context_bound_bla_deep_copy(mc_context* ctx, double* mant /* entries * 5 */, int32_t* exps /* entries * 3 */, uint32_t* levels,
                                    uint64_t* entries);
+
+/* ---- exact counts of sampled pixels (the project's own addition, additions within ABI 3; what
+ *      tests/mandel_exact_ref.py restates on Python integers).  Every deep mode returns ITS OWN loop's count; these calls iterate a
+ *      pixel's c directly in the orbit's multi-limb fixed point and return the count that arithmetic gives, so a caller can spot-check
+ *      a render, or find out whether its reference sits on the hair.
+ *  - of the orbit object o three things are used: its centre c_ref AS THE FIXED-POINT NUMBER THE CONSTRUCTOR PARSED (sign, magnitude,
+ *    round to odd: above), its `bits` and, for the offsets, its scale.  Never its table, length or max_iter.  An object of
+ *    mc_mandelbrot_orbit_rescale carries its source's c_ref and bits.
+ *  - limbs: k = ceil(bits / 64); n = k + 1 + extra_limbs 64-bit limbs are in use, F = 64 (n - 1) of their bits fractional; n > 131 is
+ *    MC_ERR_UNSUPPORTED.  c_ref's limbs are extended by extra_limbs zero limbs at the low end: the same value.
+ *  - per pixel: c = c_ref + (dcx, dcy) * 2^dc_exp2, dcx and dcy finite doubles (MC_ERR_INVALID_ARGUMENT otherwise), the sum EXACT: the
+ *    offset times 2^F must be an integer.  If a bit of it would drop: MC_ERR_UNSUPPORTED, and mc_last_error_detail names the pixel's
+ *    index (raise extra_limbs); nothing is ever truncated.  Either part of |c| above 4: MC_ERR_UNSUPPORTED, the index named likewise.
+ *  - iteration, on integers scaled by 2^F, sign and magnitude: mul(a, b) = sign(a) sign(b) ((|a| |b| + 2^(F-1)) >> F), +0 when the
+ *    magnitude is 0.
+ *      zx = zy = sx = sy = 0; for j in [0, M):
+ *        t = 2 mul(zx, zy);  zy' = t + cy;  zx' = (sx - sy) + cx;  sx = mul(zx', zx');  sy = mul(zy', zy');
+ *        if (sx + sy > 2) { n = j; stop }
+ *    n = M when the loop runs out: the counting of every render mode.  This is the orbit constructor's own loop without its doubles:
+ *    for c = c_ref (offset 0), extra_limbs = 0 and M = the orbit's max_iter, n = L - 1 when the orbit escaped and M otherwise.
+ *  - 1 <= n_pixels <= 2^20, 1 <= max_iter <= 2^32 - 2, no NULL pointer: MC_ERR_INVALID_ARGUMENT otherwise.  The offsets are the
+ *    caller's: an F32 / DS / F64 render is checked with an orbit at centre "0", "0" of the view's scale and each pixel's double c as
+ *    its offset.
+ * mc_mandelbrot_exact_pixel_offsets (host only) writes the offsets THE PERTURBATION KERNELS USE for pixels (gx[i], gy[i]) of the
+ * width x height view of o, the same expressions in source order: PERTURB's dc with *dc_exp2 = 0 for an orbit of the plain loop,
+ * the rescaled loop's u with *dc_exp2 = E for a deep one.  gx[i] >= width or gy[i] >= height, width or height outside [1, 2^20],
+ * n_pixels outside [1, 2^20], a NULL pointer: MC_ERR_INVALID_ARGUMENT.  Within that bound the 96 guard bits of the `bits` formula make
+ * the conversion above exact with extra_limbs = 0: (g / W - 0.5) is a multiple of 2^-55 no smaller than 2^-22 when nonzero, so an offset's
+ * last bit lies no lower than 2^-76 times the scale.
+ * mc_mandelbrot_exact_counts: host, serial, no device: usable without a GPU; the reference form.
+ * mc_mandelbrot_exact_counts_device: the same integers from ctx's device; blocking, on the context's stream; every refusal (the host
+ * form's, with the same status and the same text after the function's name; ctx == NULL is MC_ERR_INVALID_ARGUMENT) comes before
+ * anything is launched; neither the context's bound orbit nor its render scratch is touched.  The host builds every c and uploads the
+ * limbs.  n <= 16: one pixel per WAVE (MC_EXACT_KERNEL_WAVE: a product's 4n <= 64 columns are the wave's lanes, its carries one ballot
+ * word); n >= 17: one pixel per workgroup of 1024 threads, the device orbit's phases (MC_EXACT_KERNEL_WORKGROUP).  Iterations run in
+ * slices of iters_per_launch, sized so that a launch stays near the device orbit's 50 ms; a pixel's state lives in device memory
+ * between launches; the host reads one status / count word per pixel after each launch and stops when none is running.  That state
+ * is 928 bytes per pixel for n <= 16 and 7424 bytes per pixel for n >= 17 whatever n is, once in host memory and once on the device
+ * (2^20 pixels: 0.9 GiB and 7.3 GiB); MC_ERR_OUT_OF_MEMORY when either does not fit, before anything is launched.
+ * mc_context_last_exact_timing: the last successful device call of the context (a call that fails leaves the record of the one
+ * before): device_ms = first launch to the end of the last kernel
+ * (HIP events; the reads between launches included), the launches, n, the slice length and which kernel ran.  Any pointer may be NULL;
+ * MC_ERR_INVALID_ARGUMENT before the first such call. */
+enum { MC_EXACT_KERNEL_WAVE = 1u, MC_EXACT_KERNEL_WORKGROUP = 2u };
+int mc_mandelbrot_exact_pixel_offsets(const mc_mandelbrot_orbit* o, uint32_t width, uint32_t height, uint64_t n_pixels,
+                                      const uint32_t* gx, const uint32_t* gy, double* dcx, double* dcy, int32_t* dc_exp2);
+int mc_mandelbrot_exact_counts(const mc_mandelbrot_orbit* o, uint32_t max_iter, uint32_t extra_limbs, uint64_t n_pixels,
+                               const double* dcx, const double* dcy, int32_t dc_exp2, uint32_t* out_n);
+int mc_mandelbrot_exact_counts_device(mc_context* ctx, const mc_mandelbrot_orbit* o, uint32_t max_iter, uint32_t extra_limbs,
+                                      uint64_t n_pixels, const double* dcx, const double* dcy, int32_t dc_exp2, uint32_t* out_n);
+int mc_context_last_exact_timing(mc_context* ctx, double* device_ms, uint32_t* launches, uint32_t* limbs, uint32_t* iters_per_launch,
+                                 uint32_t* kernel);
 enum {
     /* bit 0 is a measurement switch of this repository (include/mc_compute_test.h), never set by a binding */
     MC_MANDEL_ITERS_U16 = 1u << 1,/* device form: d_iters is a uint16_t plane (max_iter <= 65535) — the multi-GPU exchange  */

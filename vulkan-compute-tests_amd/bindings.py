@@ -222,6 +222,12 @@ def lib():
             L.mc_context_last_table_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u32)]
             L.mc_context_bound_bla_copy.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
             L.mc_context_bound_bla_deep_copy.argtypes = [vp, vp, vp, C.POINTER(u32), C.POINTER(C.c_uint64)]
+        if hasattr(L, "mc_mandelbrot_exact_counts"):   # exact counts of sampled pixels
+            L.mc_mandelbrot_exact_pixel_offsets.argtypes = [vp, u32, u32, C.c_uint64, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+            L.mc_mandelbrot_exact_counts.argtypes = [vp, u32, u32, C.c_uint64, vp, vp, C.c_int32, vp]
+            L.mc_mandelbrot_exact_counts_device.argtypes = [vp, vp, u32, u32, C.c_uint64, vp, vp, C.c_int32, vp]
+            L.mc_context_last_exact_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
+                                                       C.POINTER(u32)]
         if hasattr(L, "mc_mandelbrot_equalise_map"):   # MC_MANDEL_COLOUR_EQUALISED
             L.mc_mandelbrot_histogram_device_async.argtypes = [vp, vp, u32, C.c_uint64, u32, vp, vp]
             L.mc_mandelbrot_equalise_map.argtypes = [u32, vp, vp]
@@ -1195,6 +1201,31 @@ class Orbit:
         _check(lib().mc_mandelbrot_orbit_bla_deep_copy(self._h, _ptr(mant), _ptr(exps)), "mc_mandelbrot_orbit_bla_deep_copy")
         return mant, exps
 
+    def exact_pixel_offsets(self, width, height, pixels):
+        """mc_mandelbrot_exact_pixel_offsets: (dcx, dcy, dc_exp2) of the pixels ((gx, gy) pairs, an (N, 2) array) of the width x height
+        view of this orbit: the offsets the perturbation kernels use, two float64 arrays and the exponent they share."""
+        px = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)
+        gx, gy = np.ascontiguousarray(px[:, 0]), np.ascontiguousarray(px[:, 1])
+        dcx, dcy, e = np.empty(len(px), np.float64), np.empty(len(px), np.float64), C.c_int32(0)
+        _check(lib().mc_mandelbrot_exact_pixel_offsets(self._h, int(width), int(height), len(px), _ptr(gx), _ptr(gy), _ptr(dcx), _ptr(dcy),
+                                                       C.byref(e)), "mc_mandelbrot_exact_pixel_offsets")
+        return dcx, dcy, e.value
+
+    def exact_counts(self, max_iter, dcx, dcy, dc_exp2=0, extra_limbs=0, device=None):
+        """mc_mandelbrot_exact_counts: the exact count of c = c_ref + (dcx[i], dcy[i]) * 2^dc_exp2 for every i, a uint32 array; on the
+        host, serially, or (device=ctx) mc_mandelbrot_exact_counts_device, the same integers from that context's device."""
+        dcx, dcy = np.ascontiguousarray(dcx, np.float64).ravel(), np.ascontiguousarray(dcy, np.float64).ravel()
+        if dcx.size != dcy.size:
+            raise ValueError("Orbit.exact_counts: dcx and dcy differ in length")
+        out = np.empty(dcx.size, np.uint32)
+        if device is None:
+            _check(lib().mc_mandelbrot_exact_counts(self._h, int(max_iter), int(extra_limbs), dcx.size, _ptr(dcx), _ptr(dcy), int(dc_exp2),
+                                                    _ptr(out)), "mc_mandelbrot_exact_counts")
+        else:
+            _check(lib().mc_mandelbrot_exact_counts_device(device._h, self._h, int(max_iter), int(extra_limbs), dcx.size, _ptr(dcx),
+                                                           _ptr(dcy), int(dc_exp2), _ptr(out)), "mc_mandelbrot_exact_counts_device")
+        return out
+
     def close(self):
         if self._h:
             lib().mc_mandelbrot_orbit_destroy(self._h)
@@ -1270,6 +1301,23 @@ class Context:
         ms, n, k1 = C.c_double(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().mc_context_last_orbit_timing(self._h, C.byref(ms), C.byref(n), C.byref(k1)), "mc_context_last_orbit_timing")
         return ms.value, n.value, k1.value
+
+    def exact_counts(self, orbit, width, height, pixels, max_iter, extra_limbs=0, device=True):
+        """The exact counts of the pixels ((gx, gy) pairs) of the width x height view of `orbit` (uint32, one per pixel): the offsets of
+        mc_mandelbrot_exact_pixel_offsets iterated by mc_mandelbrot_exact_counts_device on this context, or (device=False) by the
+        serial host call."""
+        dcx, dcy, e = orbit.exact_pixel_offsets(width, height, pixels)
+        return orbit.exact_counts(max_iter, dcx, dcy, e, extra_limbs, device=self if device else None)
+
+    EXACT_KERNEL_WAVE, EXACT_KERNEL_WORKGROUP = 1, 2
+
+    def last_exact_timing(self):
+        """(device_ms, launches, limbs, iters_per_launch, kernel) of the last successful device exact-count call of this context
+        (mc_context_last_exact_timing); kernel is EXACT_KERNEL_WAVE or EXACT_KERNEL_WORKGROUP."""
+        ms, n, k1, it, kind = C.c_double(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().mc_context_last_exact_timing(self._h, C.byref(ms), C.byref(n), C.byref(k1), C.byref(it), C.byref(kind)),
+               "mc_context_last_exact_timing")
+        return ms.value, n.value, k1.value, it.value, kind.value
 
     def last_refined(self):
         """(refined, pixels) of the last successful adaptive render on this context (mc_context_last_refined)."""

@@ -276,6 +276,15 @@ int make_orbit(const char* fn, const mc::OrbitLoop& loop, const char* centre_x, 
     o->max_iter = max_iter;
     o->bits = (uint32_t)bits;
     o->deep = deep;
+    try {
+        o->cx.assign(cx.m, cx.m + ops.n());
+        o->cy.assign(cy.m, cy.m + ops.n());
+    } catch (const std::bad_alloc&) {
+        delete o;
+        return MC_ERR_OUT_OF_MEMORY;
+    }
+    o->cx_neg = cx.neg;
+    o->cy_neg = cy.neg;
     *out = o;
     return MC_OK;
 }
@@ -357,6 +366,114 @@ int mc::orbit_create(const char* fn, const char* fn_plain, const OrbitLoop& loop
     return create_scaled(s.deep ? fn : fn_plain, loop, centre_x, centre_y, s, max_iter, out);
 }
 
+// ---- exact counts of sampled pixels (include/mc_compute.h: "exact counts") ----------------------------------------------------------
+namespace {
+
+// v * 2^exp2 as a Fix.  1: a bit would fall below the last fractional bit; 2: it does not fit under the integer limb's top bits.
+int offset_fix(const FixOps& ops, double v, int64_t exp2, Fix& out) {
+    ops.zero(out);
+    if (v == 0.0) return 0;
+    int e = 0;
+    const double f = std::frexp(std::fabs(v), &e);          // f in [0.5, 1), subnormals included
+    uint64_t m = (uint64_t)std::ldexp(f, 53);               // an integer below 2^53, exactly
+    int64_t s = (int64_t)e - 53 + exp2 + 64 * (int64_t)ops.k;   // |v| 2^exp2 2^F = m 2^s
+    const int tz = __builtin_ctzll(m);
+    m >>= tz;
+    s += tz;
+    if (s < 0) return 1;
+    const int len = 64 - __builtin_clzll(m);
+    if (s + len > 64 * (int64_t)ops.k + 8) return 2;        // 256 or more: |c| > 4 whatever c_ref is
+    const int limb = (int)(s >> 6), r = (int)(s & 63);
+    out.m[limb] |= m << r;
+    if (r && limb + 1 < ops.n()) out.m[limb + 1] |= m >> (64 - r);
+    out.neg = v < 0.0;
+    return 0;
+}
+
+bool above_four(const FixOps& ops, const Fix& a) {
+    if (a.m[ops.k] != 4) return a.m[ops.k] > 4;
+    for (int i = 0; i < ops.k; i++) if (a.m[i]) return true;
+    return false;
+}
+
+}  // namespace
+
+int mc::exact_prepare(const char* fn, const mc_mandelbrot_orbit* o, uint32_t max_iter, uint32_t extra_limbs, uint64_t n_pixels,
+                      const double* dcx, const double* dcy, int32_t dc_exp2, const uint32_t* out_n, ExactPixels* px) {
+    if (!o || !dcx || !dcy || !out_n) return refuse(fn, "NULL argument");
+    if (n_pixels == 0 || n_pixels > (1u << 20)) return refuse(fn, "n_pixels must be in [1, 2^20]");
+    if (max_iter == 0 || max_iter == 0xffffffffu) return refuse(fn, "max_iter must be in [1, 2^32 - 2]");
+    const int k0 = (int)((o->bits + 63) / 64);
+    if ((int)o->cx.size() != k0 + 1 || (int)o->cy.size() != k0 + 1) return refuse(fn, "the orbit object carries no centre");
+    if (extra_limbs > 131u || k0 + 1 + (int)extra_limbs > kMaxFrac + 1)
+        return refuse(fn, "more than 131 limbs (" + std::to_string(k0 + 1) + " of the orbit plus " + std::to_string(extra_limbs) + " extra)",
+                      MC_ERR_UNSUPPORTED);
+    const FixOps ops{k0 + (int)extra_limbs};
+    const int n = ops.n();
+    Fix rx, ry, off, c;
+    ops.zero(rx); ops.zero(ry);
+    for (int i = 0; i <= k0; i++) { rx.m[i + extra_limbs] = o->cx[i]; ry.m[i + extra_limbs] = o->cy[i]; }
+    rx.neg = o->cx_neg; ry.neg = o->cy_neg;
+    try {
+        px->n = n;
+        px->cx.assign((size_t)n_pixels * n, 0u);
+        px->cy.assign((size_t)n_pixels * n, 0u);
+        px->cx_neg.assign(n_pixels, 0u);
+        px->cy_neg.assign(n_pixels, 0u);
+    } catch (const std::bad_alloc&) {
+        return MC_ERR_OUT_OF_MEMORY;
+    }
+    for (uint64_t p = 0; p < n_pixels; p++) {
+        for (int axis = 0; axis < 2; axis++) {
+            const double v = axis ? dcy[p] : dcx[p];
+            const std::string who = std::string("pixel ") + std::to_string(p) + (axis ? ": dcy" : ": dcx");
+            if (!std::isfinite(v)) return refuse(fn, who + " is not finite");
+            const int bad = offset_fix(ops, v, dc_exp2, off);
+            if (bad == 1)
+                return refuse(fn, who + " * 2^dc_exp2 has bits below 2^-" + std::to_string(64 * ops.k) + ", the last fractional bit of " +
+                                      std::to_string(n) + " limbs (never truncated: raise extra_limbs)", MC_ERR_UNSUPPORTED);
+            if (bad == 0) ops.add(axis ? ry : rx, off, c);
+            if (bad == 2 || above_four(ops, c)) return refuse(fn, who + ": |c| above 4", MC_ERR_UNSUPPORTED);
+            std::memcpy((axis ? px->cy.data() : px->cx.data()) + (size_t)p * n, c.m, (size_t)n * sizeof(uint64_t));
+            (axis ? px->cy_neg : px->cx_neg)[p] = c.neg;
+        }
+    }
+    return MC_OK;
+}
+
+void mc::fix_mul_round(int n, const uint64_t* a, const uint64_t* b, uint64_t* r) {
+    const FixOps ops{n - 1};
+    Fix fa, fb, fr;
+    ops.zero(fa); ops.zero(fb);
+    std::memcpy(fa.m, a, (size_t)n * sizeof(uint64_t));
+    std::memcpy(fb.m, b, (size_t)n * sizeof(uint64_t));
+    ops.mul(fa, fb, fr);
+    std::memcpy(r, fr.m, (size_t)n * sizeof(uint64_t));
+}
+
+// host_loop without the doubles.
+uint32_t mc::exact_count_host(int n, const uint64_t* cxm, const uint64_t* cym, bool cx_neg, bool cy_neg, uint32_t max_iter) {
+    const FixOps ops{n - 1};
+    Fix cx, cy, zx, zy, sx, sy, t;
+    ops.zero(cx); ops.zero(cy);
+    std::memcpy(cx.m, cxm, (size_t)n * sizeof(uint64_t));
+    std::memcpy(cy.m, cym, (size_t)n * sizeof(uint64_t));
+    cx.neg = cx_neg; cy.neg = cy_neg;
+    ops.zero(zx); ops.zero(zy); ops.zero(sx); ops.zero(sy);
+    for (uint32_t j = 0; j < max_iter; j++) {
+        ops.mul(zx, zy, t);
+        ops.twice(t);
+        ops.add(t, cy, zy);
+        ops.sub(sx, sy, t);
+        ops.add(t, cx, zx);
+        ops.mul(zx, zx, sx);
+        ops.mul(zy, zy, sy);
+        ops.add(sx, sy, t);
+        if (ops.above_two(t)) return j;
+    }
+    return max_iter;
+}
+
 extern "C" {
 
 int mc_mandelbrot_orbit_create(const char* centre_x, const char* centre_y, double scale_x, double scale_y, uint32_t max_iter,
@@ -390,6 +507,8 @@ int mc_mandelbrot_orbit_rescale(const mc_mandelbrot_orbit* o, double scale_x, do
     if (!r) return MC_ERR_OUT_OF_MEMORY;
     try {
         r->z = o->z;
+        r->cx = o->cx;
+        r->cy = o->cy;
     } catch (const std::bad_alloc&) {
         delete r;
         return MC_ERR_OUT_OF_MEMORY;
@@ -397,6 +516,8 @@ int mc_mandelbrot_orbit_rescale(const mc_mandelbrot_orbit* o, double scale_x, do
     r->length = o->length;
     r->max_iter = o->max_iter;
     r->bits = o->bits;
+    r->cx_neg = o->cx_neg;
+    r->cy_neg = o->cy_neg;
     store_scale(r, s);
     *out = r;
     return MC_OK;
@@ -505,6 +626,33 @@ int mc_mandelbrot_orbit_bla_copy(const mc_mandelbrot_orbit* o, double* out) {
     if (!o || !out || !o->has_bla)
         return refuse("mc_mandelbrot_orbit_bla_copy", "NULL argument, or no table (mc_mandelbrot_orbit_bla builds it)");
     if (!o->bla.empty()) std::memcpy(out, o->bla.data(), o->bla.size() * sizeof(double));
+    return MC_OK;
+}
+
+// The offsets the perturbation kernels use (mandel_perturb.hip: ensure_dc_table), in source order.
+int mc_mandelbrot_exact_pixel_offsets(const mc_mandelbrot_orbit* o, uint32_t width, uint32_t height, uint64_t n_pixels, const uint32_t* gx,
+                                      const uint32_t* gy, double* dcx, double* dcy, int32_t* dc_exp2) {
+    const char* fn = "mc_mandelbrot_exact_pixel_offsets";
+    if (!o || !gx || !gy || !dcx || !dcy || !dc_exp2) return refuse(fn, "NULL argument");
+    if (width == 0 || height == 0 || width > (1u << 20) || height > (1u << 20)) return refuse(fn, "width and height must be in [1, 2^20]");
+    if (n_pixels == 0 || n_pixels > (1u << 20)) return refuse(fn, "n_pixels must be in [1, 2^20]");
+    for (uint64_t p = 0; p < n_pixels; p++)
+        if (gx[p] >= width || gy[p] >= height) return refuse(fn, "pixel " + std::to_string(p) + " lies outside the view");
+    for (uint64_t p = 0; p < n_pixels; p++) {
+        dcx[p] = ((double)gx[p] / (double)width - 0.5) * o->scale_x;
+        dcy[p] = ((double)gy[p] / (double)height - 0.5) * o->scale_y;
+    }
+    *dc_exp2 = o->deep ? o->scale_exp2 : 0;
+    return MC_OK;
+}
+
+int mc_mandelbrot_exact_counts(const mc_mandelbrot_orbit* o, uint32_t max_iter, uint32_t extra_limbs, uint64_t n_pixels, const double* dcx,
+                               const double* dcy, int32_t dc_exp2, uint32_t* out_n) {
+    mc::ExactPixels px;
+    if (int rc = mc::exact_prepare("mc_mandelbrot_exact_counts", o, max_iter, extra_limbs, n_pixels, dcx, dcy, dc_exp2, out_n, &px)) return rc;
+    for (uint64_t p = 0; p < n_pixels; p++)
+        out_n[p] = mc::exact_count_host(px.n, &px.cx[(size_t)p * px.n], &px.cy[(size_t)p * px.n], px.cx_neg[p] != 0, px.cy_neg[p] != 0,
+                                        max_iter);
     return MC_OK;
 }
 

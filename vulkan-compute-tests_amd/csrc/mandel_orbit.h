@@ -36,6 +36,10 @@ struct mc_mandelbrot_orbit {
     uint32_t bla_deep_levels = 0;
     uint64_t bla_deep_entries = 0;
     bool has_bla_deep = false;
+    // The centre as the constructor parsed it: ceil(bits / 64) + 1 limbs each, least significant first (the last is the integer limb),
+    // sign and magnitude.  What mc_mandelbrot_exact_counts iterates from; mc_mandelbrot_orbit_rescale copies it.
+    std::vector<uint64_t> cx, cy;
+    bool cx_neg = false, cy_neg = false;
 };
 
 namespace mc {
@@ -53,5 +57,20 @@ using OrbitLoop = std::function<int(int k, const uint64_t* cx, const uint64_t* c
 // mc_mandelbrot_orbit_create under the name `fn_plain`.  An empty loop runs the host's own (FixOps).
 int orbit_create(const char* fn, const char* fn_plain, const OrbitLoop& loop, const char* centre_x, const char* centre_y, double scale_x,
                  double scale_y, int32_t scale_exp2, uint32_t max_iter, mc_mandelbrot_orbit** out);
+
+// mc_mandelbrot_exact_counts (include/mc_compute.h): every check of the arguments and every pixel's c = c_ref + offset, added exactly.
+// n limbs per number; cx / cy hold pixel p's magnitude at [p * n, (p + 1) * n), least significant limb first.  `fn` names the entry point
+// in the error detail.  The device form (mandel_exact.hip) uploads these; the host form iterates them with FixOps.
+struct ExactPixels {
+    int n = 0;
+    std::vector<uint64_t> cx, cy;
+    std::vector<uint8_t> cx_neg, cy_neg;
+};
+int exact_prepare(const char* fn, const mc_mandelbrot_orbit* o, uint32_t max_iter, uint32_t extra_limbs, uint64_t n_pixels,
+                  const double* dcx, const double* dcy, int32_t dc_exp2, const uint32_t* out_n, ExactPixels* px);
+// FixOps::mul on magnitudes of n limbs (n - 1 fractional): r = (a b + 2^(F - 1)) >> F.  For tools/mandel_exact_host_check.cpp.
+void fix_mul_round(int n, const uint64_t* a, const uint64_t* b, uint64_t* r);
+// The contract's loop on FixOps for one c of n limbs: the count in [0, max_iter].
+uint32_t exact_count_host(int n, const uint64_t* cx, const uint64_t* cy, bool cx_neg, bool cy_neg, uint32_t max_iter);
 
 }  // namespace mc

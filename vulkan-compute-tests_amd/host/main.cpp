@@ -62,6 +62,8 @@ int main(int argc, char* argv[]) {
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
     uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
+    unsigned long long exactCheck = 0, exactExtraLimbs = 0;   // --exact-check N [--exact-extra-limbs E]: N pixels iterated exactly after the render
+    bool exactExtraSet = false;
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
     bool zoomSet = false;
     bool blaDevice = false, blaTableSet = false;       // --bla-table host | device: where the BLA precisions' table is built
@@ -131,6 +133,7 @@ int main(int argc, char* argv[]) {
             printf("options: --gpus N, --out FILE, --quiet, --gpu-postprocess, --png-threads T, --timing-json, --width W, --height H, --max-iter M,\n"
                    "  --centre X Y, --scale SX SY, --precision f32|ds|f64|perturb|perturb-bla|perturb-bla-deep,\n"
                    "  --colour reference|equalised|smooth|distance|smooth-equalised, --supersample 1|2|4|8, --adaptive, --supersample-smooth, --adaptive-smooth[=Q],\n"
+                   "  --exact-check N [--exact-extra-limbs E]  (the perturbation precisions) N sampled pixels iterated exactly on the device,\n"
                    "  --orbit host|device|auto, --zoom K F, --zoom-keyframes colours|counts, --zoom-filter bilinear|area,\n"
                    "  --math strict|fast|careful, --denoise [P], --noise-guided [K], --budget [L], --noise-target T, --scene FILE, --accel linear|bvh,\n"
                    "  --buddhabrot SAMPLES  the orbit-density plane of SAMPLES pseudo-random c (the Mandelbrot app); --centre / --scale default to\n"
@@ -235,6 +238,8 @@ int main(int argc, char* argv[]) {
             exit(EXIT_FAILURE);
 #endif
         }
+        else if (a == "--exact-check") { need(1); exactCheck = count(a, argv[++i], 1ull << 20); }   // 0: off
+        else if (a == "--exact-extra-limbs") { need(1); exactExtraLimbs = count(a, argv[++i], 128); exactExtraSet = true; }
         else if (a == "--zoom") {   // a zoom sequence: K + 1 keyframes, K * F + 1 frames composed from them
             need(2);
             zoomK = atoi(argv[++i]);
@@ -422,6 +427,14 @@ int main(int argc, char* argv[]) {
             printf("--bla-table: needs --precision perturb-bla | perturb-bla-deep (it chooses where their table is built)\n");
             exit(EXIT_FAILURE);
         }
+        if (exactCheck || exactExtraSet) {
+            const char* why = !exactCheck   ? "--exact-extra-limbs: needs --exact-check N"
+                              : !orbitView  ? "--exact-check: needs --precision perturb | perturb-bla | perturb-bla-deep (the check iterates c_ref + the pixel's offset)"
+                              : zoomSet     ? "--exact-check: not with --zoom (it checks one still)"
+                              : gpus > 1    ? "--exact-check: one GPU"
+                                            : nullptr;
+            if (why) { printf("%s\n", why); exit(EXIT_FAILURE); }
+        }
         if (blaDevice && gpus > 1) { printf("--bla-table device: one GPU (the table is built into the context's binding)\n"); exit(EXIT_FAILURE); }
     }
     if (zoomCounts) {   // count keyframes carry one count per pixel: the colourings and resolves that need more stay with --zoom-keyframes colours
@@ -453,6 +466,7 @@ int main(int argc, char* argv[]) {
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
     (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
+    (void)exactCheck; (void)exactExtraLimbs; (void)exactExtraSet;
     (void)orbitWhere; (void)orbitSet; (void)blaDevice; (void)blaTableSet; (void)zoomOrbitShared; (void)zoomOrbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)adaptiveSmooth; (void)adaptiveSmoothQ; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -712,6 +726,7 @@ int main(int argc, char* argv[]) {
         app.run();
 #if defined(MANDELBROT_MODE)
         if (adaptive) app.printRefined();   // "refined R of P pixels" (mc_context_last_refined)
+        if (exactCheck) app.printExactCheck((uint32_t)exactCheck, (uint32_t)exactExtraLimbs);   // "exact check: A of N equal (limbs n, T ms)"
         if (adaptiveSmooth) app.printRefinedSmooth();   // "refined R of P pixels (threshold Q)"
         if (colour == MC_MANDEL_COLOUR_DISTANCE && gpus <= 1) app.printDistanceShare();
         if (colour == MC_MANDEL_COLOUR_SMOOTH_EQUALISED && gpus <= 1 && !supersampleSmooth && !adaptiveSmooth) app.printSmoothEqualisedStats();

@@ -247,6 +247,45 @@ struct MandelbrotApp : public ComputeApp {
         printf("refined %llu of %llu pixels (threshold %u)\n", (unsigned long long)refined, (unsigned long long)pixels, adaptiveSmoothQ);
     }
 
+    // --exact-check N: N pixels of the view, the centre pixel and a fixed lattice of N - 1, iterated exactly on the
+    // device (mc_mandelbrot_exact_counts_device) and compared with the render's counts.  The save keeps colours only: the count plane is
+    // rendered once more, without the colouring and sampling flags.
+    void printExactCheck(uint32_t n, uint32_t extraLimbs) {
+        std::vector<uint32_t> gx(n), gy(n), exact(n);
+        std::vector<double> dcx(n), dcy(n);
+        gx[0] = resx / 2; gy[0] = resy / 2;
+        uint32_t cols = 1;
+        while ((uint64_t)cols * cols < n - 1u) cols++;
+        const uint32_t rows = n > 1 ? (n - 1u + cols - 1u) / cols : 1u;
+        for (uint32_t i = 1; i < n; i++) {
+            gx[i] = (uint32_t)(((uint64_t)(2u * ((i - 1u) % cols) + 1u) * resx) / (2u * cols));
+            gy[i] = (uint32_t)(((uint64_t)(2u * ((i - 1u) / cols) + 1u) * resy) / (2u * rows));
+        }
+        mc_mandelbrot_params q = params;
+        q.flags = 0;
+        std::vector<uint32_t> plane((size_t)resx * resy);
+        check(mc_mandelbrot_render(ctx, &q, nullptr, plane.data()), "mc_mandelbrot_render");
+        int32_t e = 0;
+        check(mc_mandelbrot_exact_pixel_offsets(orbit, resx, resy, n, gx.data(), gy.data(), dcx.data(), dcy.data(), &e),
+              "mc_mandelbrot_exact_pixel_offsets");
+        check(mc_mandelbrot_exact_counts_device(ctx, orbit, params.max_iter, extraLimbs, n, dcx.data(), dcy.data(), e, exact.data()),
+              "mc_mandelbrot_exact_counts_device");
+        double ms = 0.0;
+        uint32_t limbs = 0;
+        check(mc_context_last_exact_timing(ctx, &ms, nullptr, &limbs, nullptr, nullptr), "mc_context_last_exact_timing");
+        uint32_t equal = 0;
+        for (uint32_t i = 0; i < n; i++) equal += plane[(size_t)gy[i] * resx + gx[i]] == exact[i] ? 1u : 0u;
+        printf("exact check: %u of %u equal (limbs %u, %.3f ms)\n", equal, n, limbs, ms);
+        uint32_t shown = 0;
+        for (uint32_t i = 0; i < n && shown < 8u; i++) {
+            const uint32_t r = plane[(size_t)gy[i] * resx + gx[i]];
+            if (r != exact[i]) {
+                printf("  pixel (%u, %u): render %u, exact %u\n", gx[i], gy[i], r, exact[i]);
+                shown++;
+            }
+        }
+    }
+
     // --colour distance: the share of pixels whose distance estimate is below one pixel, the ones the shading darkens.  D came with the
     // colours where the storage buffer was rendered; the RGBA8 route (--gpu-postprocess) left none behind and renders the plane once more.
     void printDistanceShare() {
