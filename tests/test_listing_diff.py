@@ -45,6 +45,22 @@ def test_kernel_names_come_from_the_symbol():
     assert LD.kernel_name("plain_c_kernel") == ("plain_c_kernel",)
 
 
+def test_a_bla_template_that_names_its_policy_is_not_renamed_again():
+    """The BLA units' tile kernel had the name its template has now.  The old kernels go to their policies; a first directory that already
+    holds the template compares with itself."""
+    old_tile = "_ZN2mc12_GLOBAL__N_125mandel_perturb_bla_kernelENS_14PerturbBlaArgsE"
+    old_list = "_ZN2mc12_GLOBAL__N_130mandel_perturb_bla_list_kernelENS_14PerturbBlaArgsENS_10SampleListE"
+    new_tile = "_ZN2mc12_GLOBAL__N_125mandel_perturb_bla_kernelINS0_7MapTileEJEEEvNS_14PerturbBlaArgsEDpT0_"
+    new_list = "_ZN2mc12_GLOBAL__N_125mandel_perturb_bla_kernelINS0_7MapListEJNS_10SampleListEEEEvNS_14PerturbBlaArgsEDpT0_"
+    assert LD.renamed(LD.kernel_name(old_tile)) == LD.kernel_name(new_tile) == ("mandel_perturb_bla_kernel", "MapTile")
+    assert LD.renamed(LD.kernel_name(old_list)) == LD.kernel_name(new_list) == ("mandel_perturb_bla_kernel", "MapList")
+    for symbol in (new_tile, new_list):
+        assert LD.renamed(LD.kernel_name(symbol)) == LD.kernel_name(symbol)
+    both = listing(new_tile, 0) + listing(new_list, 1)
+    lines, bad = LD.compare(both, both)
+    assert bad == 0 and lines == ["mandel_perturb_bla_kernel<MapList>: identical", "mandel_perturb_bla_kernel<MapTile>: identical"]
+
+
 def test_label_renumbering_and_rename_compare_equal():
     lines, bad = LD.compare(listing(OLD_SYMBOL, 0, cuid="aaaa"), listing(NEW_SYMBOL, 3, cuid="bbbb"))
     assert bad == 0 and lines == ["mandelbrot_kernel<StatePerturb, 8>: identical"]

@@ -59,7 +59,9 @@ def kernel_name(symbol):
 
 
 def renamed(name):
-    if name[0] in RENAMES:
+    """An old per-engine kernel under its template's name.  (A BLA unit's tile kernel had the name its template has now: a first
+    directory that already holds the template, which names its mapping policy, is left as it is.)"""
+    if name[0] in RENAMES and not any(isinstance(t, str) and t.startswith("Map") for t in name[1:]):
         template, state = RENAMES[name[0]]
         return (template, state) + name[1:]
     return name
