@@ -55,7 +55,9 @@ extern "C" {
  * _guide_default_params and _render_guided; then dives: mc_mandelbrot_orbit_rescale, and BLA tables built on the device with
  * mc_context_bind_mandelbrot_orbit_tables, mc_context_last_table_timing, mc_context_bound_bla_copy and mc_context_bound_bla_deep_copy;
  * then exact counts of sampled pixels: mc_mandelbrot_exact_pixel_offsets, mc_mandelbrot_exact_counts, mc_mandelbrot_exact_counts_device
- * and mc_context_last_exact_timing.
+ * and mc_context_last_exact_timing; then atom domains: mc_mandelbrot_render_atom, mc_mandelbrot_render_atom_device_async,
+ * mc_mandelbrot_atom_scan, mc_mandelbrot_atom_domains, mc_mandelbrot_atom_domains_device_async, mc_mandelbrot_nucleus_refine and
+ * mc_mandelbrot_orbit_offset_text.
  * 3 (end of round 6): + mc_mandelbrot_render_banded, row bands in mc_mandelbrot_render_rgba8, scene-class bit 32 (MC_PT_SCENE_SPECULAR),
  * bit 1 of mc_context_warmup_mandelbrot's last argument.
  * 2 (round 6): + mc_assemble_rgba8_device_async, mc_context_warmup_*; since 1 (round 5 additions, un-bumped then): mc_build_id,
@@ -1079,6 +1081,89 @@ int mc_mandelbrot_zoom_compose_counts_filtered_device_async(mc_context* ctx, con
 int mc_mandelbrot_zoom_frame_filtered(mc_mandelbrot_zoom* z, double r, uint32_t filter, float* out_rgba_f32, uint8_t* out_rgba8);
 int mc_mandelbrot_zoom_counts_frame_filtered(mc_mandelbrot_zoom_counts* z, uint32_t step, uint32_t steps_per_octave, uint32_t filter,
                                              float* out_rgba_f32, uint8_t* out_rgba8);
+
+/* ---- atom domains: locating minibrots (the project's own addition, additions within ABI 3; what
+ *      tests/mandel_atom_ref.py restates).  Every deep call needs a centre written to about as many digits as its depth; these calls find
+ *      one.  The ATOM-DOMAIN PERIOD of a pixel is the iteration index at which |z| is smallest: atom domains surround every nucleus
+ *      (the centre of a minibrot, where z_p(c) = 0) and are far larger than the minibrot itself, so a coarse render finds them; Newton's
+ *      method on z_p(c) = 0 from the domain's best pixel lands on the nucleus; the nucleus written as text is the centre of the dive.
+ *      New entry points only: no flag bit selects any of this and mc_mandelbrot_params.flags must be 0 here.
+ *
+ * THE PERIOD PLANE.  mc_mandelbrot_render_atom (blocking, on the context's stream) and mc_mandelbrot_render_atom_device_async render p's
+ * whole image into up to three row-major planes (any may be NULL, not all): the counts n (uint32_t), the periods (uint32_t) and amin (double).
+ *  - the per-precision loop is unchanged; n is the count every render returns, and the n plane is bit for bit the plain render's.
+ *  - z_m (m = 1 .. n) is the z that the m-th iteration formed and whose escape test failed, handed over as two doubles exactly as the
+ *    smooth kernels' escape z is: exact conversions of the two floats for F32, the doubles themselves for F64, and for PERTURB
+ *    Z[m] + d with the loop's m and d after the iteration's rebase decision, d itself after a rebase (m = 0: Z_0 = 0 is not added).
+ *  - a_m = max(|x_m|, |y_m|) in double: exact, two abs and one max.  The max-norm and not x^2 + y^2 on purpose: at a scale of 1e-280 the
+ *    |z|^2 of a pixel near a nucleus underflows double, the max-norm does not.
+ *  - period = the smallest m in [1, n] with a_m < a_j for all j < m and a_m <= a_j for all j: start from best = +inf, period = 0 and
+ *    take (a_m, m) when a_m < best, strictly, for m = 1 .. n in order.  A z_m with a NaN part never updates.  amin = that a_m.
+ *    n = 0 (or nothing but NaNs) gives period 0 and amin = +inf.  Interior pixels use n = max_iter.
+ *  - F32 and F64 keep their cycle exit: a lane found to cycle has already seen every value its orbit will ever take, and the update is
+ *    strict, so the planes are those of the loop run to max_iter (DESIGN.md section 3.33 gives the argument, a test holds it).
+ *  - precisions: MC_PRECISION_F32, MC_PRECISION_F64, and MC_PRECISION_PERTURB with a bound orbit of the plain loop (min |scale| >= 2^-960;
+ *    PERTURB's rules for the view words, the binding and max_iter: MC_ERR_INVALID_ARGUMENT).  MC_ERR_UNSUPPORTED, named in
+ *    mc_last_error_detail: MC_PRECISION_DS; a deep bound orbit (its z leaves the double range; a floatexp amin is a follow-up);
+ *    MC_PRECISION_PERTURB_BLA and MC_PRECISION_PERTURB_BLA_DEEP (a skip does not visit its iterations).
+ *  - MC_ERR_INVALID_ARGUMENT: any nonzero flags; rows other than the whole image (row_begin = 0, row_end = height, no interleave); all
+ *    three outputs NULL; a zero width, height or max_iter.
+ *  - every iteration of these kernels is an exact step (the plain kernels' fast blocks are not used: a block that carries the minimum
+ *    through its accumulator is an optimisation left out), so the period plane costs more than a frame of the same size: render it
+ *    coarse.  Atom domains are large.
+ * mc_mandelbrot_atom_scan (host only) runs the same update, the one source the kernels compile, over a caller's sequence
+ * z_1 .. z_n (n x 2 doubles: re, im); z may be NULL when n = 0.
+ * Inside a hyperbolic component the minimum can fall on a MULTIPLE of the component's period (pixels of the period-2 disc report 4, and
+ * Newton with p = 4 goes to the same nucleus, -1): the plane is as defined above; sorting out multiples is the caller's policy. */
+int mc_mandelbrot_render_atom(mc_context* ctx, const mc_mandelbrot_params* p, uint32_t* out_iters, uint32_t* out_period, double* out_amin);
+int mc_mandelbrot_render_atom_device_async(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters, void* d_period, void* d_amin,
+                                           void* stream);
+int mc_mandelbrot_atom_scan(const double* z /* n x 2 */, uint32_t n, uint32_t* period, double* amin);
+/* THE DOMAINS OF A PLANE: for each period v in [0, max_iter], over the n_pixels < 2^32 pixels of a period plane and its amin plane,
+ *    count[v] = the number of pixels with period == v;
+ *    amin[v]  = the smallest amin among those pixels, +inf when there is none;
+ *    pixel[v] = the lowest linear index among the pixels attaining it, 0xffffffff when there is none.
+ * amin values are ordered by their bit patterns as uint64_t, which for the values the atom render writes (non-negative, or +inf) is their
+ * numeric order; a value whose pattern lies above +inf's (a negative, a NaN) is counted but takes no part in amin[v] or pixel[v].
+ * mc_mandelbrot_atom_domains: host planes into host tables of max_iter + 1 entries each; a period above max_iter is
+ * MC_ERR_INVALID_ARGUMENT (the pixel is named).  mc_mandelbrot_atom_domains_device_async: device planes into device tables, which it
+ * initialises itself, in stream order: count is mc_mandelbrot_histogram_device_async's histogram of the period plane (so a period above
+ * max_iter is counted in count[max_iter], that call's clamp) and is IGNORED by amin and pixel; max_iter >= 1; planes and tables aligned
+ * to their element sizes.  Min and add commute: the three tables do not depend on the schedule. */
+int mc_mandelbrot_atom_domains(const uint32_t* period, const double* amin, uint64_t n_pixels, uint32_t max_iter, uint32_t* count,
+                               double* amin_table, uint32_t* pixel);
+int mc_mandelbrot_atom_domains_device_async(mc_context* ctx, const void* d_period, const void* d_amin, uint64_t n_pixels, uint32_t max_iter,
+                                            void* d_count, void* d_amin_table, void* d_pixel, void* stream);
+/* NEWTON IN PERTURBATION SPACE (host only).  mc_mandelbrot_nucleus_refine refines offset = (ox, oy), the position of c relative to the
+ * orbit's centre in PERTURB's dc units (c = c_ref + offset), toward a zero of z_p(c), p = period.  IEEE double throughout, one operation
+ * at a time in the order written, no contraction.  Per Newton step:
+ *    d = 0, m = 0, D = 0;  for k = 0 .. p - 1:
+ *      z_k = Z[m] + d, or d when m = 0 (z_0 = 0);  t = z_k + z_k;
+ *      D = (((t.x * D.x) - (t.y * D.y)) + 1, (t.x * D.y) + (t.y * D.x))                   (both parts from the old D)
+ *      one iteration of PERTURB's loop above with dc = offset, operation for operation, the rebase rule with its m == L case included
+ *      (no escape test: the orbit table's last entry stands in for every index past it, as in the kernels);
+ *    z_p = Z[m] + d, or d when m = 0;  q = z_p / D by Smith's division (|D|^2 overflows at 1e-150 and below):
+ *      |D.x| >= |D.y|:  r = D.y / D.x;  den = D.x + (D.y * r);  q = ((z.x + (z.y * r)) / den, (z.y - (z.x * r)) / den)
+ *      otherwise:       r = D.x / D.y;  den = D.y + (D.x * r);  q = (((z.x * r) + z.y) / den, ((z.y * r) - z.x) / den)
+ *    offset = offset - q.
+ * It stops after the step whose max(|q.x|, |q.y|) <= 2^-52 * max(|ox|, |oy|) (the new offset), or after max_steps, and returns MC_OK
+ * either way: *steps is the number of steps taken and last_step the last q, which tell the two apart.  A non-finite D, q or offset is
+ * MC_ERR_UNSUPPORTED with the step named in mc_last_error_detail (offset then holds the last finite value).  MC_ERR_INVALID_ARGUMENT: a
+ * deep orbit, period = 0, period > the orbit's max_iter, max_steps = 0, a non-finite start, a NULL pointer.
+ * A shallow (F32 / F64) view uses an orbit at centre "0", "0" and the pixel's own c as the offset, as mc_mandelbrot_exact_counts does.
+ * An offset carries 53 bits: to go deeper, recentre on the text below and refine again from offset 0, about 40 bits per round. */
+int mc_mandelbrot_nucleus_refine(const mc_mandelbrot_orbit* o, uint32_t period, uint32_t max_steps,
+                                 double offset[2] /* in: start, out: refined */, uint32_t* steps, double last_step[2]);
+/* THE CENTRE AS TEXT (host only).  mc_mandelbrot_orbit_offset_text writes c = c_ref + (ox, oy) as two decimals a constructor accepts:
+ * c_ref is the fixed-point number the constructor parsed (as for mc_mandelbrot_exact_counts), the sum is EXACT, made on the centre's stored
+ * limbs extended at the low end by as many zero limbs as the offset's lowest bit needs (nothing is refused for depth, nothing dropped),
+ * and each part is written as [-]digits.digits with frac_digits fractional digits (frac_digits = 0: no point), truncated toward zero; a
+ * zero value has no sign.  For a deep orbit (ox, oy) are in units of 2^scale_exp2, the rescaled loop's u: c = c_ref + (ox, oy) *
+ * 2^scale_exp2; otherwise they are PERTURB's dc.  Both strings are NUL-terminated and need max(len) + 1 bytes each: a smaller capacity
+ * is MC_ERR_INVALID_ARGUMENT with the needed size in mc_last_error_detail, and nothing is written.  MC_ERR_INVALID_ARGUMENT also for a
+ * non-finite offset, a NULL pointer, frac_digits above 1 000 000. */
+int mc_mandelbrot_orbit_offset_text(const mc_mandelbrot_orbit* o, double ox, double oy, uint32_t frac_digits, char* out_x, char* out_y,
+                                    size_t capacity);
 
 /* ---- Buddhabrot: the orbit-density plane of the same iteration (the project's own addition: the reference has no counterpart and no
  *      picture to match; additions within ABI 3; what tests/buddhabrot_ref.py restates).  Every point of every

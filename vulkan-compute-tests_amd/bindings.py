@@ -349,6 +349,15 @@ def lib():
             L.mc_buddhabrot_density_guided_device_async.argtypes = [vp, bp, vp, u32, u32, u32, vp, vp, vp]
             L.mc_buddhabrot_guide_default_params.argtypes = [gp]
             L.mc_buddhabrot_render_guided.argtypes = [vp, bp, gp, vp, sp, C.POINTER(BuddhabrotGuideInfo)]
+        if hasattr(L, "mc_mandelbrot_render_atom"):   # atom domains: the period plane, its domains, Newton's method, the centre as text
+            mp, u64, f64 = C.POINTER(MandelbrotParams), C.c_uint64, C.c_double
+            L.mc_mandelbrot_render_atom.argtypes = [vp, mp, vp, vp, vp]
+            L.mc_mandelbrot_render_atom_device_async.argtypes = [vp, mp, vp, vp, vp, vp]
+            L.mc_mandelbrot_atom_scan.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(f64)]
+            L.mc_mandelbrot_atom_domains.argtypes = [vp, vp, u64, u32, vp, vp, vp]
+            L.mc_mandelbrot_atom_domains_device_async.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp]
+            L.mc_mandelbrot_nucleus_refine.argtypes = [vp, u32, u32, vp, C.POINTER(u32), vp]
+            L.mc_mandelbrot_orbit_offset_text.argtypes = [vp, f64, f64, u32, C.c_char_p, C.c_char_p, C.c_size_t]
         L.mc_multi_create.argtypes = [i32, C.POINTER(vp)]
         L.mc_multi_destroy.argtypes = [vp]
         L.mc_multi_mandelbrot_render.argtypes = [vp, C.POINTER(MandelbrotParams), vp, vp]
@@ -1098,6 +1107,28 @@ ORBIT_TABLE_BLA = 1 << 0        # mc_context_bind_mandelbrot_orbit_tables: the t
 ORBIT_TABLE_BLA_DEEP = 1 << 1
 
 
+def atom_scan(z):
+    """mc_mandelbrot_atom_scan: (period, amin) of the sequence z_1 .. z_n, an (n, 2) float64 array (re, im), by the update the atom
+    kernels compile.  Host only."""
+    z = np.ascontiguousarray(z, np.float64).reshape(-1, 2)
+    per, best = C.c_uint32(0), C.c_double(0.0)
+    _check(lib().mc_mandelbrot_atom_scan(_ptr(z) if len(z) else None, len(z), C.byref(per), C.byref(best)), "mc_mandelbrot_atom_scan")
+    return per.value, best.value
+
+
+def atom_domains(period, amin, max_iter):
+    """mc_mandelbrot_atom_domains: (count uint32, amin float64, pixel uint32), max_iter + 1 entries each, of a period plane and its amin
+    plane (any shape, the linear index is the flattened one).  Host only."""
+    period, amin = np.ascontiguousarray(period, np.uint32).ravel(), np.ascontiguousarray(amin, np.float64).ravel()
+    if period.size != amin.size:
+        raise ValueError("atom_domains: the two planes differ in size")
+    n = int(max_iter) + 1
+    count, tab, pixel = np.empty(n, np.uint32), np.empty(n, np.float64), np.empty(n, np.uint32)
+    _check(lib().mc_mandelbrot_atom_domains(_ptr(period) if period.size else _ptr(count), _ptr(amin) if amin.size else _ptr(tab), period.size,
+                                            int(max_iter), _ptr(count), _ptr(tab), _ptr(pixel)), "mc_mandelbrot_atom_domains")
+    return count, tab, pixel
+
+
 def bla_table_group_entries():
     """MC_BLA_TABLE_GROUP_ENTRIES of include/mc_compute_test.h: the device table build's single-workgroup threshold."""
     return int(re.search(r"#define\s+MC_BLA_TABLE_GROUP_ENTRIES\s+(\d+)u", open(TEST_HEADER_PATH).read()).group(1))
@@ -1225,6 +1256,23 @@ class Orbit:
             _check(lib().mc_mandelbrot_exact_counts_device(device._h, self._h, int(max_iter), int(extra_limbs), dcx.size, _ptr(dcx),
                                                            _ptr(dcy), int(dc_exp2), _ptr(out)), "mc_mandelbrot_exact_counts_device")
         return out
+
+    def nucleus_refine(self, period, offset, max_steps=64):
+        """mc_mandelbrot_nucleus_refine: Newton's method on z_period(c_ref + offset) = 0 from offset = (ox, oy), in PERTURB's dc units.
+        Returns ((ox, oy) refined, steps taken, (qx, qy) the last step)."""
+        off, last, steps = np.array(offset, np.float64).reshape(2), np.zeros(2, np.float64), C.c_uint32(0)
+        _check(lib().mc_mandelbrot_nucleus_refine(self._h, int(period), int(max_steps), _ptr(off), C.byref(steps), _ptr(last)),
+               "mc_mandelbrot_nucleus_refine")
+        return (float(off[0]), float(off[1])), steps.value, (float(last[0]), float(last[1]))
+
+    def offset_text(self, ox, oy, frac_digits, capacity=None):
+        """mc_mandelbrot_orbit_offset_text: c_ref + (ox, oy) (a deep orbit: (ox, oy) * 2^scale_exp2), summed exactly, as two decimal strings
+        with frac_digits fractional digits, truncated toward zero.  capacity=None: large enough."""
+        cap = int(frac_digits) + 32 if capacity is None else int(capacity)
+        bx, by = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1))
+        _check(lib().mc_mandelbrot_orbit_offset_text(self._h, float(ox), float(oy), int(frac_digits), bx, by, cap),
+               "mc_mandelbrot_orbit_offset_text")
+        return bx.value.decode(), by.value.decode()
 
     def close(self):
         if self._h:
@@ -1372,6 +1420,27 @@ class Context:
         iters = np.empty((rows, p.width), np.uint32) if want_iters else None
         _check(lib().mc_mandelbrot_render(self._h, C.byref(p), _ptr(rgba), _ptr(iters)), "mc_mandelbrot_render")
         return rgba, iters
+
+    def mandelbrot_atom(self, p, want_iters=True, want_period=True, want_amin=True):
+        """mc_mandelbrot_render_atom: (n uint32, period uint32, amin float64) planes of p's whole image, None where not wanted."""
+        shape = (p.height, p.width)
+        iters = np.empty(shape, np.uint32) if want_iters else None
+        period = np.empty(shape, np.uint32) if want_period else None
+        amin = np.empty(shape, np.float64) if want_amin else None
+        _check(lib().mc_mandelbrot_render_atom(self._h, C.byref(p), _ptr(iters), _ptr(period), _ptr(amin)), "mc_mandelbrot_render_atom")
+        return iters, period, amin
+
+    def mandelbrot_atom_device(self, p, d_iters=0, d_period=0, d_amin=0, stream=0):
+        """mc_mandelbrot_render_atom_device_async into device planes (0: not wanted)."""
+        _check(lib().mc_mandelbrot_render_atom_device_async(self._h, C.byref(p), d_iters or None, d_period or None, d_amin or None,
+                                                            stream or None), "mc_mandelbrot_render_atom_device_async")
+
+    def mandelbrot_atom_domains_device(self, d_period, d_amin, n_pixels, max_iter, d_count, d_amin_table, d_pixel, stream=0):
+        """mc_mandelbrot_atom_domains_device_async: device planes into device tables of max_iter + 1 entries (count uint32, amin float64,
+        pixel uint32), which the call initialises itself."""
+        _check(lib().mc_mandelbrot_atom_domains_device_async(self._h, d_period or None, d_amin or None, int(n_pixels), int(max_iter),
+                                                             d_count or None, d_amin_table or None, d_pixel or None, stream or None),
+               "mc_mandelbrot_atom_domains_device_async")
 
     def mandelbrot_smooth(self, p, want_rgba=True, want_iters=True, want_smooth=True):
         """mc_mandelbrot_render_smooth (p carries MANDEL_COLOUR_SMOOTH): (rgba float32, n uint32, q uint32) of p's tile, None where not

@@ -13,6 +13,7 @@
 #pragma once
 #include "mandel_adaptive.h"
 #include "mandel_adaptive_smooth.h"
+#include "mandel_atom.h"
 #include "mandel_block_audit.h"
 #include "mandel_escape.h"
 #include "mandel_perturb.h"
@@ -218,6 +219,33 @@ int launch_block_audit(const typename State::Args& a, dim3 grid, hipStream_t s, 
     if constexpr (LaneMapped) k = sabotage ? mandelbrot_lane_audit_kernel<State, U, true> : mandelbrot_lane_audit_kernel<State, U, false>;
     else k = sabotage ? mandelbrot_block_audit_kernel<State, U, true> : mandelbrot_block_audit_kernel<State, U, false>;
     hipLaunchKernelGGL(k, grid, dim3(64), 0, s, a, d_out);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
+// atom (mc_mandelbrot_render_atom, mandel_atom.h): the tile kernel's lane with the state's exact steps only and the (period, amin) capture
+// latched after each; n goes where the tile kernel puts it (out_iters alone: no flag is accepted), period and amin into their own planes.
+// Whole images only, so the tile-local row is the storage row.  Vector stores, no atomics.
+template <class State, int U>
+__global__ void __launch_bounds__(64) mandelbrot_atom_kernel(typename State::Args a, AtomOut o) {
+    require_block_length<State, U>();
+    const auto& t = target_of(a);
+    const TileLane ln = tile_lane(t);
+    ExactSteps<State> st;
+    st.init(ln.valid ? ln.gx : 0u, ln.valid ? ln.gy : 0u, a);
+    AtomCapture cap;
+    const uint32_t n = escape_time<ExactSteps<State>, U, AtomCapture>(st, t.max_iter, ln.valid, &cap);
+    tile_store(t, ln, n);
+    if (ln.valid) {
+        const size_t idx = (size_t)ln.ty * t.W + ln.gx;
+        if (o.period) o.period[idx] = cap.period;
+        if (o.amin) o.amin[idx] = cap.best;
+    }
+}
+
+template <class State>
+int launch_atom(const typename State::Args& a, dim3 grid, hipStream_t s, const AtomOut& o) {
+    hipLaunchKernelGGL((mandelbrot_atom_kernel<State, State::kBlock>), grid, dim3(64), 0, s, a, o);
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }

@@ -258,6 +258,44 @@ void perturb_release(mc_context* ctx) {
     });
 }
 
+// mc_mandelbrot_render_atom, MC_PRECISION_PERTURB (mandel_atom.h): perturb_launch's checks of the binding and the view, the refusal of a
+// deep orbit (its z leaves the double range), the dc table, the launch.  p is a whole image with no flag (mandelbrot_atom_launch).
+int perturb_atom_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters, const AtomOut& o, hipStream_t s) {
+    const std::string name = "mc_mandelbrot_render_atom: MC_PRECISION_PERTURB";
+    const Binding* b = g_bindings.find(ctx);
+    if (!b || !b->orbit.ptr || !b->length) {
+        set_error_detail(name + ": no orbit bound to the context (mc_context_bind_mandelbrot_orbit)");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    const float words[8] = {p->centre_x_hi, p->centre_x_lo, p->centre_y_hi, p->centre_y_lo,
+                            p->scale_x_hi, p->scale_x_lo, p->scale_y_hi, p->scale_y_lo};
+    for (float w : words)
+        if (w != 0.0f) {
+            set_error_detail(name + ": the view is the bound orbit's; the params' eight view words must be zero");
+            return MC_ERR_INVALID_ARGUMENT;
+        }
+    if (p->max_iter > b->max_iter) {
+        set_error_detail(name + ": max_iter above the bound orbit's");
+        return MC_ERR_INVALID_ARGUMENT;
+    }
+    if (b->deep) {
+        set_error_detail(name + ": the bound orbit is deep (min |scale| < 2^-960): its z leaves the double range, a floatexp amin is not built");
+        return MC_ERR_UNSUPPORTED;
+    }
+    MandelTarget t;
+    dim3 grid;
+    SampleList l{};
+    if (int rc = launch_geometry(p, nullptr, d_iters, false, nullptr, &t, &grid, &l)) return rc;
+    if (int rc = ensure_dc_table(ctx, p, *b, s)) return rc;
+    t.L = b->length;
+    t.lut = nullptr;
+    t.table = (const double*)ctx->ctab.ptr;
+    t.orbit = (const double2*)b->orbit.ptr;
+    const PerturbArgs a = {t};
+    if (int rc = launch_atom<StatePerturb>(a, grid, s, o)) return rc;
+    return ctx->note_launch(s);
+}
+
 bool perturb_bound_scale(mc_context* ctx, double* scale_x, double* scale_y, int32_t* scale_exp2) {
     const Binding* b = g_bindings.find(ctx);
     if (!b || !b->length) return false;

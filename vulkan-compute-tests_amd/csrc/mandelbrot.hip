@@ -411,4 +411,39 @@ int mandelbrot_block_audit_launch(mc_context* ctx, const mc_mandelbrot_params* p
     return ctx->note_launch(s);
 }
 
+// mc_mandelbrot_render_atom / _device_async (include/mc_compute.h: "atom domains").  The refusals in the header's order; F32 and F64 launch
+// here with the render's own c table, PERTURB in mandel_perturb.hip.
+int mandelbrot_atom_launch(mc_context* ctx, const mc_mandelbrot_params* p, void* d_iters, void* d_period, void* d_amin, hipStream_t s) {
+    const std::string fn = "mc_mandelbrot_render_atom";
+    auto refuse = [&](const std::string& why, int status) {
+        set_error_detail(fn + ": " + why);
+        return status;
+    };
+    if (!ctx || !p) return MC_ERR_INVALID_ARGUMENT;
+    if (!d_iters && !d_period && !d_amin) return refuse("all three outputs are NULL", MC_ERR_INVALID_ARGUMENT);
+    if (p->flags) return refuse("flags must be 0 (the period plane is built from entry points, not flag bits)", MC_ERR_INVALID_ARGUMENT);
+    if (!p->width || !p->height || !p->max_iter) return refuse("width, height and max_iter must be nonzero", MC_ERR_INVALID_ARGUMENT);
+    if (!whole_image(p) || p->row_block) return refuse("the whole image only (row_begin = 0, row_end = height, no interleave)", MC_ERR_INVALID_ARGUMENT);
+    if (p->precision == MC_PRECISION_DS) return refuse("MC_PRECISION_DS is not supported (F32, F64 and PERTURB are)", MC_ERR_UNSUPPORTED);
+    if (p->precision == MC_PRECISION_PERTURB_BLA)
+        return refuse("MC_PRECISION_PERTURB_BLA is not supported: a skip does not visit its iterations", MC_ERR_UNSUPPORTED);
+    if (p->precision == MC_PRECISION_PERTURB_BLA_DEEP)
+        return refuse("MC_PRECISION_PERTURB_BLA_DEEP is not supported: a skip does not visit its iterations", MC_ERR_UNSUPPORTED);
+    const AtomOut o = {(uint32_t*)d_period, (double*)d_amin};
+    if (p->precision == MC_PRECISION_PERTURB) return perturb_atom_launch(ctx, p, d_iters, o, s);
+    if (p->precision != MC_PRECISION_F32 && p->precision != MC_PRECISION_F64) return refuse("unknown precision", MC_ERR_INVALID_ARGUMENT);
+    if (int rc = ensure_c_table(ctx, p, s)) return rc;
+    MandelArgs a;
+    dim3 grid;
+    SampleList l{};
+    if (int rc = launch_geometry(p, nullptr, d_iters, false, nullptr, &a, &grid, &l)) return rc;
+    a.c_tab = (const float*)ctx->ctab.ptr;
+    a.cx_hi = p->centre_x_hi; a.cx_lo = p->centre_x_lo; a.cy_hi = p->centre_y_hi; a.cy_lo = p->centre_y_lo;
+    a.sx_hi = p->scale_x_hi; a.sx_lo = p->scale_x_lo; a.sy_hi = p->scale_y_hi; a.sy_lo = p->scale_y_lo;
+    a.lut = nullptr;
+    const int rc = p->precision == MC_PRECISION_F64 ? launch_atom<StateF64>(a, grid, s, o) : launch_atom<StateF32<false>>(a, grid, s, o);
+    if (rc) return rc;
+    return ctx->note_launch(s);
+}
+
 }  // namespace mc

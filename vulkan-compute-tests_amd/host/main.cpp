@@ -16,7 +16,9 @@
 // (default sqrt) and --white PCT (default 99.9: the white level L is the density not exceeded by PCT % of the non-empty bins, read from
 // one histogram capped at 2^20 - 1 — the app's policy, not the library's), and for zoomed views --guided[=G] with --pilot P, --dilate D,
 // --unbiased B (mc_buddhabrot_render_guided, DESIGN.md §3.27: a pilot's importance map over the 2^G x 2^G cells of the sample window,
-// the samples drawn from the cells whose orbits reach the view); --help prints this list,
+// the samples drawn from the cells whose orbits reach the view), --locate[=N] (the Mandelbrot app with --precision f32|f64|perturb: after
+// the save, the N largest atom domains of the view, their periods, the nucleus Newton's method finds from each one's best pixel and a
+// ready --centre X Y for the dive); --help prints this list,
 // --large-sphere-walls, --sphere-precision f32|fp64|ds|df64 (the reference's compile-time precision experiment);
 // --reference-png writes the file through the reference's own lodepng (a build with `make REFERENCE=<checkout>`): its bytes.
 // A value none of these lists name is an error (EXIT_FAILURE) — never a silent default.
@@ -62,6 +64,7 @@ int main(int argc, char* argv[]) {
     enum : uint32_t { kOrbitHost = 0, kOrbitDevice = 1, kOrbitAuto = 2 };
     uint32_t orbitWhere = kOrbitHost;   // --orbit host | device | auto (mc_mandelbrot_orbit_create_device)
     bool orbitSet = false;              // given at all: the run prints its "orbit:" line
+    uint32_t locate = 0;                // --locate[=N]: after the save, the N largest atom domains and their nuclei; 0: off
     unsigned long long exactCheck = 0, exactExtraLimbs = 0;   // --exact-check N [--exact-extra-limbs E]: N pixels iterated exactly after the render
     bool exactExtraSet = false;
     int zoomK = 0, zoomF = 0;           // --zoom K F: K octaves of F frames each (mc_mandelbrot_zoom_*)
@@ -135,6 +138,8 @@ int main(int argc, char* argv[]) {
                    "  --colour reference|equalised|smooth|distance|smooth-equalised, --supersample 1|2|4|8, --adaptive, --supersample-smooth, --adaptive-smooth[=Q],\n"
                    "  --exact-check N [--exact-extra-limbs E]  (the perturbation precisions) N sampled pixels iterated exactly on the device,\n"
                    "  --orbit host|device|auto, --zoom K F, --zoom-keyframes colours|counts, --zoom-filter bilinear|area,\n"
+                   "  --locate[=N]  (--precision f32|f64|perturb) after the save: the N (default 8) largest atom domains of the view, each with its\n"
+                   "      period, the nucleus Newton's method finds from its best pixel, and a ready --centre X Y,\n"
                    "  --math strict|fast|careful, --denoise [P], --noise-guided [K], --budget [L], --noise-target T, --scene FILE, --accel linear|bvh,\n"
                    "  --buddhabrot SAMPLES  the orbit-density plane of SAMPLES pseudo-random c (the Mandelbrot app); --centre / --scale default to\n"
                    "      the view -0.5 0 / 3 3H/W and --max-iter to 1000; with it:\n"
@@ -282,6 +287,21 @@ int main(int argc, char* argv[]) {
             zoomFilterSet = true;
 #if !defined(MANDELBROT_MODE)
             printf("--zoom-filter: a Mandelbrot option\n");
+            exit(EXIT_FAILURE);
+#endif
+        }
+        else if (a == "--locate" || a.rfind("--locate=", 0) == 0) {   // N is optional, as --denoise's P is (default 8)
+            const char* v = nullptr;
+            if (a.size() > 8) v = argv[i] + 9;
+            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') v = argv[++i];
+            const int n = v ? atoi(v) : 8;
+            if (n < 1 || n > 64 || (v && (!*v || std::strspn(v, "0123456789") != std::strlen(v)))) {
+                printf("--locate %s: the number of domains is 1 .. 64\n", v ? v : "");
+                exit(EXIT_FAILURE);
+            }
+            locate = (uint32_t)n;
+#if !defined(MANDELBROT_MODE)
+            printf("--locate: a Mandelbrot option\n");
             exit(EXIT_FAILURE);
 #endif
         }
@@ -435,6 +455,15 @@ int main(int argc, char* argv[]) {
                                             : nullptr;
             if (why) { printf("%s\n", why); exit(EXIT_FAILURE); }
         }
+        if (locate) {
+            const char* why = !(precision == MC_PRECISION_F32 || precision == MC_PRECISION_F64 || precision == MC_PRECISION_PERTURB)
+                                  ? "--locate: needs --precision f32 | f64 | perturb (the period plane is built for those: mc_mandelbrot_render_atom)"
+                              : zoomSet       ? "--locate: not with --zoom (it reads one still)"
+                              : buddhaSet     ? "--locate: not with --buddhabrot"
+                              : gpus > 1      ? "--locate: one GPU"
+                                              : nullptr;
+            if (why) { printf("%s\n", why); exit(EXIT_FAILURE); }
+        }
         if (blaDevice && gpus > 1) { printf("--bla-table device: one GPU (the table is built into the context's binding)\n"); exit(EXIT_FAILURE); }
     }
     if (zoomCounts) {   // count keyframes carry one count per pixel: the colourings and resolves that need more stay with --zoom-keyframes colours
@@ -466,7 +495,7 @@ int main(int argc, char* argv[]) {
     if (sceneFile || accel) { printf("--scene / --accel: path tracer options\n"); exit(EXIT_FAILURE); }
 #endif
     (void)budgetSet; (void)noiseTargetSet; (void)zoomSet; (void)zoomCounts; (void)zoomFilter; (void)zoomFilterSet; (void)denoise; (void)noiseGuided; (void)noiseGuidedSet; (void)sceneFile; (void)accel;
-    (void)exactCheck; (void)exactExtraLimbs; (void)exactExtraSet;
+    (void)exactCheck; (void)exactExtraLimbs; (void)exactExtraSet; (void)locate;
     (void)orbitWhere; (void)orbitSet; (void)blaDevice; (void)blaTableSet; (void)zoomOrbitShared; (void)zoomOrbitSet; (void)colour; (void)supersample; (void)supersampleSmooth; (void)adaptiveSmooth; (void)adaptiveSmoothQ; (void)width; (void)height; (void)maxIter; (void)precision; (void)mathMode; (void)cx; (void)cy; (void)sx; (void)sy; (void)viewSet; (void)largeSpheres; (void)spherePrec; (void)cxText; (void)cyText; (void)sxText; (void)syText; (void)sxText; (void)syText;
 
 #if defined(MANDELBROT_MODE)
@@ -743,6 +772,9 @@ int main(int argc, char* argv[]) {
         else app.saveRenderedImage();
         double saveMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (!quiet) printf("saveRenderedImage() finished in %.3f ms\n", saveMs);
+#if defined(MANDELBROT_MODE)
+        if (locate) app.printLocate(locate);   // "locate: ..." and one line per domain, each with a ready --centre X Y
+#endif
         if (timingJson) {   // init = context creation (HIP start-up); alloc = the pinned storage buffer; run = the blocking render call, of
                             // which kernel + copy are device time; convert = float -> u8 (+ rotation) on the host (0: done on the device);
                             // png = encode + write; total = process wall time up to here

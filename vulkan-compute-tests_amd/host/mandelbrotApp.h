@@ -286,6 +286,103 @@ struct MandelbrotApp : public ComputeApp {
         }
     }
 
+    // --locate[=N]: one atom render of the view (mc_mandelbrot_render_atom, at the image's own size), its domains
+    // (mc_mandelbrot_atom_domains), then for each of the N periods >= 1 with the most pixels (ties: the smaller period) Newton's method
+    // from the domain's best pixel (mc_mandelbrot_nucleus_refine) and the nucleus as text (mc_mandelbrot_orbit_offset_text).  F32 / F64:
+    // an orbit at centre "0", "0" of the view's scale with the pixel's own c as the offset; PERTURB: the view's orbit and the pixel's dc.
+    // An entry whose nucleus agrees with a smaller listed period's to 2^-40 of the scale is marked "= period q" (the minimum inside a
+    // component can fall on a multiple of its period): which to dive into is left to the reader.
+    void printLocate(uint32_t count) {
+        using clock = std::chrono::steady_clock;
+        auto ms = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+        const auto tStart = clock::now();
+        const uint32_t W = resx, H = resy, M = params.max_iter;
+        const bool perturb = params.precision == MC_PRECISION_PERTURB, f32 = params.precision == MC_PRECISION_F32;
+        mc_mandelbrot_params q = params;
+        q.flags = 0;
+        std::vector<uint32_t> period((size_t)W * H), cnt((size_t)M + 1), best((size_t)M + 1);
+        std::vector<double> amin((size_t)W * H), low((size_t)M + 1);
+        check(mc_mandelbrot_render_atom(ctx, &q, nullptr, period.data(), amin.data()), "mc_mandelbrot_render_atom");
+        const double renderMs = ms(tStart);
+        check(mc_mandelbrot_atom_domains(period.data(), amin.data(), (uint64_t)W * H, M, cnt.data(), low.data(), best.data()),
+              "mc_mandelbrot_atom_domains");
+        // the view as the kernels read it, and the orbit Newton runs on
+        double cx = 0.0, cy = 0.0, sx = 0.0, sy = 0.0;
+        mc_mandelbrot_orbit* zero = nullptr;
+        struct Guard {
+            mc_mandelbrot_orbit*& o;
+            ~Guard() { if (o) mc_mandelbrot_orbit_destroy(o); }
+        } guard{zero};
+        auto pixelOffset = [&](uint32_t gx, uint32_t gy, double off[2]) {
+            if (perturb) {
+                int32_t e = 0;
+                check(mc_mandelbrot_exact_pixel_offsets(orbit, W, H, 1, &gx, &gy, &off[0], &off[1], &e), "mc_mandelbrot_exact_pixel_offsets");
+            } else if (f32) {   // mandelbrot.comp:30-31,38 in fp32, then the exact conversion
+                off[0] = (double)(params.centre_x_hi + ((float)gx / (float)W - 0.5f) * params.scale_x_hi);
+                off[1] = (double)(params.centre_y_hi + ((float)gy / (float)H - 0.5f) * params.scale_y_hi);
+            } else {
+                off[0] = cx + ((double)gx / (double)W - 0.5) * sx;
+                off[1] = cy + ((double)gy / (double)H - 0.5) * sy;
+            }
+        };
+        if (perturb) {
+            double corner[2];
+            pixelOffset(0u, 0u, corner);   // (0 / n - 0.5) * scale, exactly
+            sx = -2.0 * corner[0];
+            sy = -2.0 * corner[1];
+        } else {
+            cx = f32 ? (double)params.centre_x_hi : (double)params.centre_x_hi + (double)params.centre_x_lo;
+            cy = f32 ? (double)params.centre_y_hi : (double)params.centre_y_hi + (double)params.centre_y_lo;
+            sx = f32 ? (double)params.scale_x_hi : (double)params.scale_x_hi + (double)params.scale_x_lo;
+            sy = f32 ? (double)params.scale_y_hi : (double)params.scale_y_hi + (double)params.scale_y_lo;
+            check(mc_mandelbrot_orbit_create("0", "0", sx, sy, M, &zero), "mc_mandelbrot_orbit_create");
+        }
+        const mc_mandelbrot_orbit* o = perturb ? orbit : zero;
+        std::vector<uint32_t> order;
+        for (uint32_t v = 1; v <= M; v++)
+            if (cnt[v]) order.push_back(v);
+        const size_t periods = order.size();
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cnt[a] > cnt[b]; });
+        if (order.size() > count) order.resize(count);
+        const double smin = std::fmin(std::fabs(sx), std::fabs(sy));
+        const uint32_t digits = (uint32_t)std::fmax(0.0, std::ceil(-std::log10(smin))) + 20u;
+        printf("locate: atom plane %u x %u, %zu periods, render %.3f ms; the %zu largest domains (centres with %u fractional digits):\n", W, H,
+               periods, renderMs, order.size(), digits);
+        struct Entry { uint32_t p; int rc; std::string why; double o[2]; uint32_t steps; double last[2]; };
+        std::vector<Entry> found;
+        for (uint32_t p : order) {   // every nucleus first: an entry is compared with all the others
+            Entry e{p, MC_OK, "", {0.0, 0.0}, 0u, {0.0, 0.0}};
+            pixelOffset(best[p] % W, best[p] / W, e.o);
+            e.rc = mc_mandelbrot_nucleus_refine(o, p, 64u, e.o, &e.steps, e.last);
+            if (e.rc != MC_OK) e.why = std::string(mc_error_string(e.rc)) + " (" + mc_last_error_detail() + ")";
+            found.push_back(e);
+        }
+        std::vector<char> tx((size_t)digits + 32), ty((size_t)digits + 32);
+        for (const Entry& e : found) {
+            const uint32_t p = e.p;
+            printf("  period %u: %u pixels, best pixel (%u, %u) amin %.6g, ", p, cnt[p], best[p] % W, best[p] / W, low[p]);
+            if (e.rc != MC_OK) {
+                printf("Newton failed: %s\n", e.why.c_str());
+                continue;
+            }
+            const double px = ((e.o[0] - cx) / sx + 0.5) * (double)W, py = ((e.o[1] - cy) / sy + 0.5) * (double)H;
+            const bool inside = px >= 0.0 && px < (double)W && py >= 0.0 && py < (double)H;
+            const bool converged = std::fmax(std::fabs(e.last[0]), std::fabs(e.last[1])) <=
+                                   std::ldexp(1.0, -52) * std::fmax(std::fabs(e.o[0]), std::fabs(e.o[1]));
+            check(mc_mandelbrot_orbit_offset_text(o, e.o[0], e.o[1], digits, tx.data(), ty.data(), tx.size()), "mc_mandelbrot_orbit_offset_text");
+            printf("Newton %u steps%s to pixel (%.2f, %.2f), %s", e.steps, converged ? "" : " (not converged)", px, py,
+                   inside ? "inside" : "outside view");
+            uint32_t same = 0;   // the smallest listed period with the same nucleus
+            for (const Entry& f : found)
+                if (f.rc == MC_OK && f.p < p && (same == 0u || f.p < same) && std::fabs(f.o[0] - e.o[0]) <= std::ldexp(std::fabs(sx), -40) &&
+                    std::fabs(f.o[1] - e.o[1]) <= std::ldexp(std::fabs(sy), -40))
+                    same = f.p;
+            if (same) printf(", = period %u", same);
+            printf(": --centre %s %s\n", tx.data(), ty.data());
+        }
+        printf("locate: %.3f ms in all\n", ms(tStart));
+    }
+
     // --colour distance: the share of pixels whose distance estimate is below one pixel, the ones the shading darkens.  D came with the
     // colours where the storage buffer was rendered; the RGBA8 route (--gpu-postprocess) left none behind and renders the plane once more.
     void printDistanceShare() {
